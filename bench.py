@@ -24,8 +24,15 @@ an error.
 
 Inputs are resident in HBM when the timed region starts (database shard + the query
 keyframes); only the 24-byte result leaves the device per step.  The timed block of `--steps`
-steps is repeated `--repeats` times (each bracketed by barrier + synchronize); the median
-repetition is reported, min / max beside it.
+steps is run `--repeats` times (each bracketed by barrier + synchronize; once by default, so
+that a plain run times exactly `--steps` steps); the median repetition is reported, min / max
+beside it.
+
+A plain run sets up, warms up, times the steps and prints the headline line.  `--full` adds
+what else the benchmark measures: five repetitions of the timed block by default, the
+secondary measurements (`secondary`), the CPU baselines (`cpu_baseline`) and the `summary`
+keys.  `--dump-outputs DIR` writes the winners of the timed path's last step (one per scan
+of the batch: keyframe index, ring shift, fp64 distance) as DIR/*.npy, float64.
 """
 import argparse
 import json
@@ -70,7 +77,14 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=128, help="timed steps; a step = one batch of --scans-per-launch incoming scans")
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=5, help="repetitions of the timed block of --steps steps (median reported)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="repetitions of the timed block of --steps steps (median reported; default 1, 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: five repetitions by default, the secondary measurements, the CPU "
+                         "baselines and the summary keys (a plain run does only what the headline needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the winners of the last step (keyframe index, ring shift, fp64 distance "
+                         "per scan) as DIR/winner_*.npy, float64")
     ap.add_argument("--keyframes", type=int, default=0, help="keyframes per GPU (0: 10 000 at N = 1, 12 500 at N > 1)")
     ap.add_argument("--pipeline", type=int, default=2, help="kernel launches enqueued ahead (1 = strictly one after another)")
     ap.add_argument("--merge-every", type=int, default=16, help="N > 1, --native-chunk 0: scans whose per-rank winners share one exchange")
@@ -88,11 +102,24 @@ def parse_args():
     ap.add_argument("--dry-run", action="store_true",
                     help="print the rank command line `--gpus N` / the device list `--front G` would use, check that the node shows that many "
                          "GPUs (torch.cuda.device_count(): does not initialise HIP) and exit -- 0 when the run could start, 3 otherwise")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[2] geometric-verification measurement")
-    ap.add_argument("--only-secondary", default="", help="comma-separated names: run only these secondary measurements (experiments)")
-    ap.add_argument("--cpu-pairs", type=int, default=0, help="pairs in the 1-thread CPU sample (0 = auto ~10 s)")
-    return ap.parse_args()
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary measurements")
+    ap.add_argument("--only-secondary", default="", help="--full: comma-separated names: run only these secondary measurements (experiments)")
+    ap.add_argument("--cpu-pairs", type=int, default=0, help="--full: pairs in the 1-thread CPU sample (0 = auto ~10 s)")
+    args = ap.parse_args()
+    if args.only_secondary and not args.full:
+        ap.error("--only-secondary selects among the measurements of --full; add --full")
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
+
+
+def dump_outputs(out_dir, nn, sh, dd):
+    """--dump-outputs: the winners of the last timed step as a caller of the path receives them, one entry per scan of the
+    step, in float64 (indices and shifts are exact in it)"""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("winner_index", nn), ("winner_shift", sh), ("winner_distance", dd)):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -830,7 +857,7 @@ def secondary_livox_stream(device, n0=1000, n_scans=600):
 # ------------------------------------------------------------------------------------------------
 # the C-ABI sharded front (one process, all GPUs of the node): SURVEY 8(e) through scl_create_sharded
 # ------------------------------------------------------------------------------------------------
-def bench_front(G, steps, spl):
+def bench_front(G, steps, spl, dump_dir=""):
     """BASELINE configs[3] through the C ABI: ONE engine over G shards (keyframe g on shard g % G; devices = the visible GPUs, round
     robin, so on a one-GPU box the shards share the card and the exchange is the host merge -- or, SCL_FRONT_EXCHANGE=2 with
     SCL_RCCL_LIB=tests/cpp/libmock_rccl.so, the tests' stand-in collective; with G distinct devices the two RCCL min all-reduces).  Stream form (per-shard streams + host merge of the
@@ -853,9 +880,11 @@ def bench_front(G, steps, spl):
     ts = []
     for _ in range(3):
         t0 = time.perf_counter()
-        eng.detect_full_stream(qs, 0, n_elig, spl, 2)
+        last = eng.detect_full_stream(qs, 0, n_elig, spl, 2)
         ts.append(time.perf_counter() - t0)
     dt = float(np.median(ts))
+    if dump_dir:
+        dump_outputs(dump_dir, *(a[-spl:] for a in last))
     lat = []
     for i in range(60):
         t0 = time.perf_counter()
@@ -878,7 +907,7 @@ def main():
     if args.dry_run:
         sys.exit(dry_run(args))
     if args.front > 0:
-        return bench_front(args.front, args.steps, max(1, args.scans_per_launch))
+        return bench_front(args.front, args.steps, max(1, args.scans_per_launch), args.dump_outputs)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     world_env = os.environ.get("WORLD_SIZE")
@@ -994,15 +1023,16 @@ def main():
         # outside the timed region: every planted revisit (query 4j = a rolled copy of one of rank 0's keyframes) must
         # have been found by the merged result, on every rank
         if timed_results and isinstance(timed_results[0][0], np.ndarray):      # the one-GPU form's arrays, call by call
-            flat = []
-            for dd_, nn_, sh_ in timed_results:
-                flat.extend(zip(dd_.tolist(), nn_.tolist(), sh_.tolist()))
-            timed_results = flat
-        for i, (d, g, sh) in enumerate(timed_results):
-            if os.environ.get("SCL_ABLATE"):             # diagnostic build with phases switched off: results are wrong on purpose
-                break
-            if ((warm_scans + i) % n_query) % 4 == 0:
-                assert d < 1e-6 and g >= 0 and g % world == 0, (i, d, g, sh)
+            dd_t, nn_t, sh_t = (np.concatenate([o[j] for o in timed_results]) for j in range(3))
+        else:                                                                   # FullScanStream: (distance, index, shift) per scan
+            rt = np.asarray(timed_results, dtype=np.float64).reshape(-1, 3)
+            dd_t, nn_t, sh_t = rt[:, 0], rt[:, 1].astype(np.int64), rt[:, 2].astype(np.int64)
+        if not os.environ.get("SCL_ABLATE"):             # diagnostic build with phases switched off: results are wrong on purpose
+            planted = ((warm_scans + np.arange(dd_t.size)) % n_query) % 4 == 0
+            bad = np.flatnonzero(planted & ~((dd_t < 1e-6) & (nn_t >= 0) & (nn_t % world == 0)))
+            assert bad.size == 0, (int(bad[0]), dd_t[bad[0]], nn_t[bad[0]], sh_t[bad[0]])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, nn_t[-spl:], sh_t[-spl:], dd_t[-spl:])
     eng.profile_enable(False)
     prof = eng.profile()
     al_pairs, al_fallbacks = eng.alignment_stats()
@@ -1103,7 +1133,7 @@ def main():
                                  "rccl_ranks": dist.get_world_size() if dist.get_backend() == "nccl" else 0,
                                  "library": "RCCL (torch.distributed 'nccl' on ROCm)" if dist.get_backend() == "nccl" else "gloo (CPU rehearsal: SCL_BENCH_SHARE_GPU=1)",
                                  "exchange": args.exchange, "devices_distinct": not share_gpu}
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             out["secondary"] = {}
             for name, fn in (("exact_all_pairs", lambda: secondary_exact_all_pairs(eng, n_elig, n_query)),
                              ("detect_full_blocking_us", lambda: secondary_blocking_scan(eng, n_elig, n_query)),
@@ -1124,7 +1154,7 @@ def main():
                     out["secondary"][name] = fn()
                 except Exception as ex:                      # never lose the headline line to a secondary measurement
                     out["secondary"][name] = {"error": repr(ex)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(shard, args.cpu_pairs)
             icp_gpu = out.get("secondary", {}).get("icp_verification")
             if isinstance(icp_gpu, dict) and "error" not in icp_gpu:        # the ICP half of the denominator, beside the GPU figures it belongs to
@@ -1137,39 +1167,40 @@ def main():
                     icp_gpu["cpu_baseline"] = icp_cpu
                 except Exception as ex:
                     icp_gpu["cpu_baseline"] = {"error": repr(ex)}
-        # the figures a reader needs first, once more as short keys at the END of the line (a driver that keeps only the tail of the
-        # line keeps these): every value is a copy of a field above
-        sec = out.get("secondary", {})
+        if args.full:
+            # the figures a reader needs first, once more as short keys at the END of the line (a driver that keeps only the tail of the
+            # line keeps these): every value is a copy of a field above
+            sec = out.get("secondary", {})
 
-        def pick(d, *path):
-            for k in path:
-                if not isinstance(d, dict) or k not in d:
-                    return None
-                d = d[k]
-            return d
-        out["summary"] = {
-            "value_pairs_per_s_batches_of_16": value, "roofline_frac": out["roofline"]["frac"],
-            "q1_blocking_scan_us_p50": pick(sec, "detect_full_blocking_us", "p50"),
-            "q1_pairs_per_s": pick(sec, "detect_full_blocking_us", "pairs_per_s_at_p50"),
-            "detect_intra_us_p50": pick(sec, "detect_full_blocking_us", "detect_intra_us", "p50"),
-            "exact_all_pairs_per_s": pick(sec, "exact_all_pairs", "value"),
-            "ringkey_topk_k3_device_us": pick(sec, "ringkey_topk", "k3", "device_us"),
-            "ingest_device_us_per_scan_64x120_120k": pick(sec, "ingest_per_scan", "64x120_120k_points", "device_us_per_scan_in_a_batch_of_16"),
-            "ingest_roofline_frac_64x120_120k": pick(sec, "ingest_per_scan", "64x120_120k_points", "roofline", "frac"),
-            "resident_points_pairs_per_s": pick(sec, "stream_from_resident_points", "value"),
-            "resident_points_us_per_scan": pick(sec, "stream_from_resident_points", "us_per_scan"),
-            "stream_from_points_scans_per_s": pick(sec, "stream_from_points", "scans_per_s"),
-            "stream_from_points_pairs_per_s": pick(sec, "stream_from_points", "value"),
-            "stream_from_points_over_pcie_floor": pick(sec, "stream_from_points", "pcie", "us_per_scan_over_floor"),
-            "sc_distance_80x180_pairs_per_s": pick(sec, "sc_distance_80x180", "value"),
-            "exact_all_pairs_80x180_per_s": pick(sec, "sc_distance_80x180", "exact_all_pairs", "value"),
-            "icp_p2plane_ms_per_query": pick(sec, "icp_verification", "point_to_plane", "from_store", "ms_per_query"),
-            "icp_p2p_ms_per_query": pick(sec, "icp_verification", "point_to_point", "from_store", "ms_per_query"),
-            "livox_stream_p50_ms": pick(sec, "livox_stream_80x180", "latency_ms", "p50"),
-            "livox_stream_dropped_frames": pick(sec, "livox_stream_80x180", "dropped_frames"),
-            "cpu_one_thread_pairs_per_s": pick(out, "cpu_baseline", "value"),
-            "cpu_all_core_pairs_per_s": pick(out, "cpu_baseline", "all_cores_reference_shaped", "value"),
-            "cpu_all_core_threads": pick(out, "cpu_baseline", "all_cores_reference_shaped", "cores")}
+            def pick(d, *path):
+                for k in path:
+                    if not isinstance(d, dict) or k not in d:
+                        return None
+                    d = d[k]
+                return d
+            out["summary"] = {
+                "value_pairs_per_s_batches_of_16": value, "roofline_frac": out["roofline"]["frac"],
+                "q1_blocking_scan_us_p50": pick(sec, "detect_full_blocking_us", "p50"),
+                "q1_pairs_per_s": pick(sec, "detect_full_blocking_us", "pairs_per_s_at_p50"),
+                "detect_intra_us_p50": pick(sec, "detect_full_blocking_us", "detect_intra_us", "p50"),
+                "exact_all_pairs_per_s": pick(sec, "exact_all_pairs", "value"),
+                "ringkey_topk_k3_device_us": pick(sec, "ringkey_topk", "k3", "device_us"),
+                "ingest_device_us_per_scan_64x120_120k": pick(sec, "ingest_per_scan", "64x120_120k_points", "device_us_per_scan_in_a_batch_of_16"),
+                "ingest_roofline_frac_64x120_120k": pick(sec, "ingest_per_scan", "64x120_120k_points", "roofline", "frac"),
+                "resident_points_pairs_per_s": pick(sec, "stream_from_resident_points", "value"),
+                "resident_points_us_per_scan": pick(sec, "stream_from_resident_points", "us_per_scan"),
+                "stream_from_points_scans_per_s": pick(sec, "stream_from_points", "scans_per_s"),
+                "stream_from_points_pairs_per_s": pick(sec, "stream_from_points", "value"),
+                "stream_from_points_over_pcie_floor": pick(sec, "stream_from_points", "pcie", "us_per_scan_over_floor"),
+                "sc_distance_80x180_pairs_per_s": pick(sec, "sc_distance_80x180", "value"),
+                "exact_all_pairs_80x180_per_s": pick(sec, "sc_distance_80x180", "exact_all_pairs", "value"),
+                "icp_p2plane_ms_per_query": pick(sec, "icp_verification", "point_to_plane", "from_store", "ms_per_query"),
+                "icp_p2p_ms_per_query": pick(sec, "icp_verification", "point_to_point", "from_store", "ms_per_query"),
+                "livox_stream_p50_ms": pick(sec, "livox_stream_80x180", "latency_ms", "p50"),
+                "livox_stream_dropped_frames": pick(sec, "livox_stream_80x180", "dropped_frames"),
+                "cpu_one_thread_pairs_per_s": pick(out, "cpu_baseline", "value"),
+                "cpu_all_core_pairs_per_s": pick(out, "cpu_baseline", "all_cores_reference_shaped", "value"),
+                "cpu_all_core_threads": pick(out, "cpu_baseline", "all_cores_reference_shaped", "cores")}
         print(json.dumps(out), flush=True)
     eng.close()
     if world > 1:

@@ -18,7 +18,7 @@ elif [ "$P" = "c" ]; then
 else
   O=gpurun_out/r05b; mkdir -p $O
   STEPS=128 scripts/profile_k1.sh && cp -r gpurun_out/prof_k1 $O/k1 && rm -rf $O/k1/trace $O/k1/p[0-9]*
-  timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench_driver_style.err; tail -c 600 $O/bench_driver_style.json
-  timeout -k 10 300 python3 bench.py > $O/bench_full.json 2> $O/bench_full.err
+  timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench_driver_style.err; tail -c 600 $O/bench_driver_style.json
+  timeout -k 10 300 python3 bench.py --full > $O/bench_full.json 2> $O/bench_full.err
   timeout -k 10 300 python3 scripts/soak_parity.py 240 > $O/soak_parity.txt 2>&1; tail -2 $O/soak_parity.txt
 fi
