@@ -1,0 +1,138 @@
+// m2dp_hip_descriptor.hpp -- header-only adapter that plugs the MI355X M2DP engine (scl_m2dp.h) into the reference's descriptor
+// plugin interface, beside scan_context_hip_descriptor.hpp and lidar_iris_hip_descriptor.hpp.
+//
+// Include it AFTER the reference's descriptor.h (it needs `class scan_descriptor`, descriptor.h:21-36, and
+// pcl::PointCloud<pcl::PointXYZI>).  The DescriptorType switch changes by one line:
+//
+//   distributedMapping.h:412   scanDescriptor = std::unique_ptr<scan_descriptor>(new m2dp_descriptor());
+//   becomes                    scanDescriptor = std::unique_ptr<scan_descriptor>(new m2dp_hip_descriptor(0.3, 30, numberOfRobots, id));
+//
+// What differs from the reference's class, on purpose (scl_m2dp.h has the details):
+//   * the detections work (the reference's have empty bodies, descriptor.h:1998-2006): 1-NN by squared L2 in nanoflann's float
+//     order, the newest numExcludeRecent keyframes of this robot kept out of intra detection, a loop when the distance is below
+//     distThres -- 0.3 is a PLACEHOLDER, not validated on real data; the second member of the pair is the distance;
+//   * saveDescriptorAndKey reads all 192 floats makeAndSaveDescriptorAndKey emits (the reference reads 128);
+//   * the PCA axes follow a sign rule (PCL's are unpinned), which makes the signature rotation invariant.
+// Errors are written to stderr and mapped to "no loop" / empty results, as the reference only logs.
+// Lifetime: as for scan_context_hip_descriptor -- scan_descriptor has no virtual destructor, call close() before
+// dropping the object if the host re-creates descriptors.
+#pragma once
+
+#include <cstdint>
+#include <cstdio>
+#include <utility>
+#include <vector>
+
+#include "scl_m2dp.h"
+
+class m2dp_hip_descriptor : public scan_descriptor
+{
+public:
+    m2dp_hip_descriptor(double distThres = 0.3, int numExcludeRecent = 30, int robotNum = 1, int thisID = 0, int device = 0)
+    {
+        scl_m2dp_config cfg;
+        scl_m2dp_default_config(&cfg);
+        cfg.dist_thres = distThres; cfg.num_exclude_recent = numExcludeRecent; cfg.robot_num = robotNum; cfg.this_id = thisID;
+        cfg.device = device;
+        const int rc = scl_m2dp_create(&cfg, &m2dp_);
+        if (rc != SCL_OK) {
+            std::fprintf(stderr, "[m2dp_hip_descriptor] engine creation failed: %s\n", scl_status_string(rc));
+            m2dp_ = nullptr;
+        }
+    }
+
+    ~m2dp_hip_descriptor() { close(); }
+    void close()
+    {
+        if (m2dp_) scl_m2dp_destroy(m2dp_);
+        m2dp_ = nullptr;
+    }
+    m2dp_hip_descriptor(const m2dp_hip_descriptor &) = delete;
+    m2dp_hip_descriptor &operator=(const m2dp_hip_descriptor &) = delete;
+
+    // descriptor.h:25 / 1820-1863: the 192 floats [u, v]
+    std::vector<float> makeAndSaveDescriptorAndKey(const pcl::PointCloud<pcl::PointXYZI> &scan,
+                                                   const int8_t robot, const int index) override
+    {
+        std::vector<float> v(SCL_M2DP_DIM, 0.0f);
+        report(scl_m2dp_make_and_save(m2dp_, scan.points.data(), static_cast<int>(scan.points.size()),
+                                      static_cast<int>(sizeof(pcl::PointXYZI)), robot, index, v.data()),
+               "makeAndSaveDescriptorAndKey");
+        return v;
+    }
+
+    // the batch form: scans[i] appended as (robots[i], indexs[i]); returns scans.size() * 192 floats
+    std::vector<float> makeAndSaveDescriptorsAndKeys(const std::vector<const pcl::PointCloud<pcl::PointXYZI> *> &scans,
+                                                     const std::vector<int8_t> &robots, const std::vector<int> &indexs)
+    {
+        std::vector<float> v(scans.size() * SCL_M2DP_DIM, 0.0f);
+        if (robots.size() != scans.size() || indexs.size() != scans.size()) {
+            std::fprintf(stderr, "[m2dp_hip_descriptor] makeAndSaveDescriptorsAndKeys: %zu scans, %zu robots, %zu indexs\n",
+                         scans.size(), robots.size(), indexs.size());
+            return v;
+        }
+        std::vector<const void *> ptrs(scans.size());
+        std::vector<int> counts(scans.size());
+        for (size_t i = 0; i < scans.size(); ++i) { ptrs[i] = scans[i]->points.data(); counts[i] = static_cast<int>(scans[i]->points.size()); }
+        report(scl_m2dp_make_and_save_many(m2dp_, ptrs.data(), counts.data(), static_cast<int>(sizeof(pcl::PointXYZI)), robots.data(),
+                                           indexs.data(), static_cast<int>(scans.size()), v.data()),
+               "makeAndSaveDescriptorsAndKeys");
+        return v;
+    }
+
+    // descriptor.h:27 / 1989-1995, all 192 floats
+    void saveDescriptorAndKey(const float *m2dpVec, const int8_t robot, const int index) override
+    {
+        report(scl_m2dp_save_from_wire(m2dp_, m2dpVec, robot, index), "saveDescriptorAndKey");
+    }
+
+    // descriptor.h:29 / 1998-2001 (empty there): {local index of the loop keyframe or -1, distance}
+    std::pair<int, float> detectIntraLoopClosureID(const int curPtr) override
+    {
+        int loop_id = -1; float dist = 0.0f;
+        if (!report(scl_m2dp_detect_intra(m2dp_, curPtr, &loop_id, &dist), "detectIntraLoopClosureID"))
+            return std::pair<int, float>(-1, 0.0f);
+        return std::pair<int, float>(loop_id, dist);
+    }
+
+    // descriptor.h:31 / 2003-2006 (empty there): {global key of the loop keyframe or -1, distance}
+    std::pair<int, float> detectInterLoopClosureID(const int curPtr) override
+    {
+        int loop_id = -1; float dist = 0.0f;
+        if (!report(scl_m2dp_detect_inter(m2dp_, curPtr, &loop_id, &dist), "detectInterLoopClosureID"))
+            return std::pair<int, float>(-1, 0.0f);
+        return std::pair<int, float>(loop_id, dist);
+    }
+
+    // descriptor.h:33 / 2008-2011
+    std::pair<int8_t, int> getIndex(const int key) override
+    {
+        int8_t robot = 0; int index = -1;
+        report(scl_m2dp_get_index(m2dp_, key, &robot, &index), "getIndex");
+        return std::pair<int8_t, int>(robot, index);
+    }
+
+    // descriptor.h:35 / 2013-2016
+    int getSize(const int idIn = -1) override
+    {
+        if (!m2dp_) return 0;
+        const int n = scl_m2dp_get_size_of(m2dp_, idIn);
+        return n < 0 ? 0 : n;
+    }
+
+    scl_m2dp *engine() { return m2dp_; }
+
+private:
+    bool report(int rc, const char *where) const
+    {
+        if (!m2dp_) {
+            std::fprintf(stderr, "[m2dp_hip_descriptor] %s: no engine (creation failed or close() was called)\n", where);
+            return false;
+        }
+        if (rc == SCL_OK) return true;
+        std::fprintf(stderr, "[m2dp_hip_descriptor] %s: %s (%s)\n", where, scl_status_string(rc), scl_m2dp_last_error(m2dp_));
+        return false;
+    }
+
+    scl_m2dp *m2dp_ = nullptr;
+};

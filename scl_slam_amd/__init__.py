@@ -10,8 +10,10 @@ from ._native import load_library, LIB_PATH, NativeLibraryError  # noqa: F401
 from .engine import (  # noqa: F401
     SclConfig, SclError, ScanContextEngine, ScanContextDescriptor, IcpParams, QUERY_STAGED,
 )
+from .m2dp import M2dpConfig, M2dpEngine, M2dpError  # noqa: F401
 
 __all__ = [
     "load_library", "LIB_PATH", "NativeLibraryError", "SclConfig", "SclError",
     "ScanContextEngine", "ScanContextDescriptor", "IcpParams", "QUERY_STAGED",
+    "M2dpConfig", "M2dpEngine", "M2dpError",
 ]
