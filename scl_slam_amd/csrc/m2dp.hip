@@ -32,6 +32,10 @@
 #include <string>
 #include <vector>
 
+#include "device_common.hpp"
+
+using scl::jacobi3;
+
 namespace {
 
 constexpr int kGroup = SCL_M2DP_MAX_GROUP;
@@ -120,40 +124,6 @@ __global__ __launch_bounds__(kThreads) void m2dp_moments_kernel(const unsigned c
     block_sum_fixed<9>(s, red);
     if (threadIdx.x == 0)
         for (int j = 0; j < 9; ++j) part[((size_t)blockIdx.y * kParts + blockIdx.x) * 9 + j] = red[j * kThreads];
-}
-
-// 3 x 3 symmetric eigen-decomposition, cyclic Jacobi in fp64 (columns of v = eigenvectors)
-__device__ void jacobi3(double a[3][3], double v[3][3])
-{
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) v[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 64; ++sweep) {
-        const double off = fabs(a[0][1]) + fabs(a[0][2]) + fabs(a[1][2]);
-        const double diag = fabs(a[0][0]) + fabs(a[1][1]) + fabs(a[2][2]);
-        if (off == 0.0 || off <= 1e-300 || off < 1e-18 * diag) break;
-        for (int p = 0; p < 2; ++p)
-            for (int q = p + 1; q < 3; ++q) {
-                const double apq = a[p][q];
-                if (apq == 0.0) continue;
-                const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
-                double t;
-                if (fabs(theta) > 1e150) t = 0.5 / theta;
-                else t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < 3; ++k) {                     // A <- A J
-                    const double akp = a[k][p], akq = a[k][q];
-                    a[k][p] = c * akp - s * akq; a[k][q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < 3; ++k) {                     // A <- J^T A
-                    const double apk = a[p][k], aqk = a[q][k];
-                    a[p][k] = c * apk - s * aqk; a[q][k] = s * apk + c * aqk;
-                }
-                for (int k = 0; k < 3; ++k) {
-                    const double vkp = v[k][p], vkq = v[k][q];
-                    v[k][p] = c * vkp - s * vkq; v[k][q] = s * vkp + c * vkq;
-                }
-            }
-    }
 }
 
 __global__ __launch_bounds__(64) void m2dp_frame_kernel(const M2Scan *scans, const double *part, float *framef)
