@@ -1,0 +1,173 @@
+"""The ctypes layer the descriptor plugin mirrors share (iris.py, m2dp.py, fpfh.py): signature binding, the error class, the
+handle life-cycle and the keyframe-registry calls; for the vector plugins (M2DP, FPFH) also the database, build and 1-NN calls."""
+from ctypes import POINTER, byref, c_char_p, c_float, c_int, c_int8, c_void_p
+
+import numpy as np
+
+_bound = set()
+
+
+def bind(lib, table):
+    """Set restype / argtypes of every function of `table` ({name: (restype, argtypes)}) on `lib`, once per table; returns lib."""
+    if id(table) not in _bound:
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name); fn.restype = res; fn.argtypes = args
+        _bound.add(id(table))
+    return lib
+
+
+def plugin_signatures(prefix, config):
+    """The calls every plugin header declares: life-cycle, save_from_wire and the keyframe registry."""
+    P, ip = c_void_p, POINTER(c_int)
+    return {
+        f"{prefix}_default_config": (c_int, [POINTER(config)]),
+        f"{prefix}_create": (c_int, [POINTER(config), POINTER(P)]),
+        f"{prefix}_destroy": (c_int, [P]),
+        f"{prefix}_last_error": (c_char_p, [P]),
+        f"{prefix}_save_from_wire": (c_int, [P, POINTER(c_float), c_int8, c_int]),
+        f"{prefix}_get_size": (c_int, [P]),
+        f"{prefix}_get_size_of": (c_int, [P, c_int]),
+        f"{prefix}_get_index": (c_int, [P, c_int, POINTER(c_int8), ip]),
+        f"{prefix}_local_to_global": (c_int, [P, c_int, c_int, ip]),
+    }
+
+
+def vector_signatures(prefix, config):
+    """plugin_signatures plus the float-descriptor calls of M2DP and FPFH."""
+    P, fp, ip = c_void_p, POINTER(c_float), POINTER(c_int)
+    sig = plugin_signatures(prefix, config)
+    sig.update({
+        f"{prefix}_make": (c_int, [P, P, c_int, c_int, fp]),
+        f"{prefix}_make_and_save": (c_int, [P, P, c_int, c_int, c_int8, c_int, fp]),
+        f"{prefix}_make_and_save_many": (c_int, [P, POINTER(c_void_p), ip, c_int, POINTER(c_int8), ip, c_int, fp]),
+        f"{prefix}_get_signature": (c_int, [P, c_int, fp]),
+        f"{prefix}_detect_intra": (c_int, [P, c_int, ip, fp]),
+        f"{prefix}_detect_inter": (c_int, [P, c_int, ip, fp]),
+    })
+    return sig
+
+
+class PluginError(RuntimeError):
+    def __init__(self, where, status, message=""):
+        super().__init__(f"{where}: status {status} ({message})")
+        self.status = status
+
+
+class PluginEngine:
+    """One plugin handle.  Subclasses set PREFIX (the C prefix, e.g. "scl_m2dp"), CONFIG (the ctypes config struct) and ERROR
+    (their PluginError subclass), and pass the bound library and the config fields to __init__ (None keeps the default)."""
+    PREFIX = None
+    CONFIG = None
+    ERROR = PluginError
+
+    def __init__(self, lib, **fields):
+        self.L = lib
+        cfg = self.CONFIG()
+        getattr(lib, f"{self.PREFIX}_default_config")(byref(cfg))
+        for name, value in fields.items():
+            if value is not None:
+                setattr(cfg, name, value)
+        self.cfg = cfg
+        self.h = c_void_p()
+        rc = getattr(lib, f"{self.PREFIX}_create")(byref(cfg), byref(self.h))
+        if rc != 0:
+            self.h = c_void_p()
+            raise self.ERROR(f"{self.PREFIX}_create", rc)
+
+    def _check(self, rc, where):
+        if rc != 0:
+            raise self.ERROR(where, rc, getattr(self.L, f"{self.PREFIX}_last_error")(self.h).decode())
+
+    def _call(self, name, *args):
+        """PREFIX_name(handle, *args), status checked"""
+        fn = f"{self.PREFIX}_{name}"
+        self._check(getattr(self.L, fn)(self.h, *args), fn)
+
+    def close(self):
+        if self.h and self.h.value:
+            getattr(self.L, f"{self.PREFIX}_destroy")(self.h); self.h = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def get_size(self, robot=-1):
+        n = getattr(self.L, f"{self.PREFIX}_get_size_of")(self.h, robot)
+        if n < 0:
+            self._check(n, f"{self.PREFIX}_get_size_of")
+        return n
+
+    def get_index(self, key):
+        r, i = c_int8(), c_int()
+        self._call("get_index", key, byref(r), byref(i))
+        return r.value, i.value
+
+    def local_to_global(self, robot, local):
+        k = c_int()
+        self._call("local_to_global", robot, local, byref(k))
+        return k.value
+
+
+class VectorPluginEngine(PluginEngine):
+    """A plugin whose descriptor is DIM floats (M2DP, FPFH): make, make_and_save(_many), save_from_wire, get_signature and the
+    1-NN detections."""
+    DIM = None
+
+    @staticmethod
+    def _cloud(points):
+        a = np.ascontiguousarray(points, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] < 3:
+            raise ValueError("points: (n, >= 3) float32 records")
+        return a, a.shape[0], a.shape[1] * 4
+
+    def make(self, points):
+        a, n, st = self._cloud(points)
+        out = np.empty(self.DIM, np.float32)
+        self._call("make", a.ctypes.data_as(c_void_p), n, st, out.ctypes.data_as(POINTER(c_float)))
+        return out
+
+    def make_and_save(self, points, robot=0, index=0):
+        a, n, st = self._cloud(points)
+        out = np.empty(self.DIM, np.float32)
+        self._call("make_and_save", a.ctypes.data_as(c_void_p), n, st, robot, index, out.ctypes.data_as(POINTER(c_float)))
+        return out
+
+    def make_and_save_many(self, clouds, robots=None, indexs=None, want_values=True):
+        """clouds: list of (n_i, k) float32 arrays with one record width k; returns (count, DIM) float32 (None if not wanted)"""
+        arrs = [self._cloud(c) for c in clouds]
+        count = len(arrs)
+        if count and len({st for _, _, st in arrs}) != 1:
+            raise ValueError("make_and_save_many: one stride for all clouds")
+        st = arrs[0][2] if count else 12
+        ptrs = (c_void_p * max(count, 1))(*[a.ctypes.data for a, _, _ in arrs])
+        ns = np.ascontiguousarray([n for _, n, _ in arrs], np.int32)
+        rb = np.ascontiguousarray(robots if robots is not None else np.zeros(count), np.int8)
+        ix = np.ascontiguousarray(indexs if indexs is not None else np.arange(count), np.int32)
+        out = np.empty((count, self.DIM), np.float32) if want_values else None
+        self._call("make_and_save_many", ptrs, ns.ctypes.data_as(POINTER(c_int)), st, rb.ctypes.data_as(POINTER(c_int8)),
+                   ix.ctypes.data_as(POINTER(c_int)), count, out.ctypes.data_as(POINTER(c_float)) if out is not None else None)
+        return out
+
+    def save_from_wire(self, values, robot=0, index=0):
+        v = np.ascontiguousarray(values, np.float32)
+        assert v.size == self.DIM
+        self._call("save_from_wire", v.ctypes.data_as(POINTER(c_float)), robot, index)
+
+    def get_signature(self, key):
+        out = np.empty(self.DIM, np.float32)
+        self._call("get_signature", key, out.ctypes.data_as(POINTER(c_float)))
+        return out
+
+    def detect_intra(self, cur):
+        """(loop local index or -1, float32 distance to the nearest)"""
+        loop, d = c_int(), c_float()
+        self._call("detect_intra", cur, byref(loop), byref(d))
+        return loop.value, np.float32(d.value)
+
+    def detect_inter(self, cur):
+        """(loop global key or -1, float32 distance to the nearest)"""
+        loop, d = c_int(), c_float()
+        self._call("detect_inter", cur, byref(loop), byref(d))
+        return loop.value, np.float32(d.value)

@@ -23,6 +23,7 @@
 #include "db_file.hpp"
 #include "engine_internal.hpp"
 #include "device_sort.hpp"
+#include "plugin_host.hpp"
 
 #ifdef SCL_DIAGNOSTICS
 namespace scl { void ingest_stamps_print(); void cand_stamps_print(); }   // make_sc.hip / sc_masked.hip: phase stamps (SCL_INGEST_STAMPS=1)
@@ -31,15 +32,6 @@ namespace scl { void ingest_stamps_print(); void cand_stamps_print(); }   // mak
 using namespace scl;
 
 namespace {
-
-#define SCL_HIP(e_, call)                                                              \
-    do {                                                                               \
-        hipError_t err__ = (call);                                                     \
-        if (err__ != hipSuccess) {                                                     \
-            (e_)->last_error = std::string(#call) + ": " + hipGetErrorString(err__);   \
-            return err__ == hipErrorOutOfMemory ? SCL_ERR_NOMEM : SCL_ERR_HIP;         \
-        }                                                                              \
-    } while (0)
 
 // one spin of a polling loop, on whatever the host is (the engine's host code also builds for aarch64 robots)
 inline void cpu_relax()
@@ -51,12 +43,6 @@ inline void cpu_relax()
 #else
     std::this_thread::yield();
 #endif
-}
-
-int fail(const scl_engine *e, int code, const char *msg)
-{
-    if (e) e->last_error = msg;
-    return code;
 }
 
 struct ProfScope {
@@ -130,15 +116,6 @@ int sync_short(scl_engine *e)
         if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(300)) { q = hipEventSynchronize(e->ev_call); break; }
     SCL_HIP(e, q);
     collect_profile(e);
-    return SCL_OK;
-}
-
-template <class T>
-int dev_alloc(scl_engine *e, T **p, size_t count)
-{
-    void *q = nullptr;
-    SCL_HIP(e, hipMalloc(&q, sizeof(T) * (count ? count : 1)));
-    *p = static_cast<T *>(q);
     return SCL_OK;
 }
 

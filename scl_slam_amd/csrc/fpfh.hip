@@ -12,8 +12,8 @@
 //                        normal in the same lane (fp64 scatter in (d2, index) order, jacobi3, PCL's float flip), written in input order;
 //   fpfh_spfh_kernel     the N - 2 pairs (last point, j): PCL's pair features in float, three bins, counted per wave by ballots
 //                        and popcounts, one global atomic per bin per workgroup;
-//   fpfh_finish_kernel   counts -> the floats of PCL's sequential `+=` (fpfh_values.hpp), straight into the database slot;
-//   fpfh_nn_kernel       detection: 33-D squared L2 in nanoflann's float order, (distance bits, position) keys, 64-bit atomic min.
+//   fpfh_finish_kernel   counts -> the floats of PCL's sequential `+=` (fpfh_values.hpp), straight into the database slot.
+// The database, the keyframe registry, make_and_save_many and the 1-NN detection (nn_l2_kernel<33>): plugin_host.hpp.
 #include "scl_fpfh.h"
 
 #include <hip/hip_runtime.h>
@@ -30,9 +30,9 @@
 #include "device_common.hpp"
 #include "device_sort.hpp"
 #include "fpfh_values.hpp"
+#include "plugin_host.hpp"
 
-using scl::iris_atan2f;
-using scl::jacobi3;
+using namespace scl;
 
 namespace {
 
@@ -392,31 +392,6 @@ __global__ __launch_bounds__(64) void fpfh_finish_kernel(const FpScan *scans, co
     db[(size_t)sc.slot * kDim + t] = scl::fpfh_value(counts[(size_t)blockIdx.x * kCounts + t], inc);
 }
 
-__global__ __launch_bounds__(kThreads) void fpfh_nn_kernel(const float *db, const int *list, int n, int qkey, unsigned long long *best)
-{
-    __shared__ float q[kDim];
-    for (int i = threadIdx.x; i < kDim; i += kThreads) q[i] = db[(size_t)qkey * kDim + i];
-    __syncthreads();
-    const int i = blockIdx.x * kThreads + threadIdx.x;
-    unsigned long long key = ~0ull;
-    if (i < n) {
-        const float *c = db + (size_t)(list ? list[i] : i) * kDim;
-        float s = 0.0f;
-        for (int k = 0; k < 32; k += 4) {                             // nanoflann's L2_Adaptor: groups of four, then the tail
-            const float d0 = q[k] - c[k], d1 = q[k + 1] - c[k + 1], d2 = q[k + 2] - c[k + 2], d3 = q[k + 3] - c[k + 3];
-            s += ((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3;
-        }
-        const float d32 = q[32] - c[32];
-        s += d32 * d32;
-        key = ((unsigned long long)__float_as_uint(s) << 32) | (unsigned int)i;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(key, off);
-        key = o < key ? o : key;
-    }
-    if ((threadIdx.x & 63) == 0 && key != ~0ull) atomicMin(best, key);
-}
-
 __device__ __forceinline__ unsigned long long mix64(unsigned long long z)
 {
     z += 0x9e3779b97f4a7c15ull;
@@ -450,10 +425,8 @@ struct scl_fpfh {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     mutable std::mutex mu;
     mutable std::string last_error;
-    int n = 0, cap = 0;
-    float *d_db = nullptr;
-    std::vector<int8_t> robots; std::vector<int> indexs;
-    std::vector<std::vector<int>> local2global;
+    scl::KeyframeRegistry reg;
+    scl::FloatRows<kDim> db;
     // the reference's inter detection state: the call counter and the snapshot [0, snap_n) taken at the last rebuild
     int tree_counter = 0, snap_n = 0;
     // the launch group's workspace (per point, per cell, per scan)
@@ -477,53 +450,12 @@ struct scl_fpfh {
 
 namespace {
 
-#define FP_HIP(h_, call)                                                               \
-    do {                                                                               \
-        hipError_t err__ = (call);                                                     \
-        if (err__ != hipSuccess) {                                                     \
-            (h_)->last_error = std::string(#call) + ": " + hipGetErrorString(err__);   \
-            return err__ == hipErrorOutOfMemory ? SCL_ERR_NOMEM : SCL_ERR_HIP;         \
-        }                                                                              \
-    } while (0)
-
-int ffail(const scl_fpfh *h, int code, const char *msg) { if (h) h->last_error = msg; return code; }
-
-template <class T> int malloc_dev(scl_fpfh *h, T **p, size_t count)
-{
-    void *q = nullptr;
-    FP_HIP(h, hipMalloc(&q, sizeof(T) * (count ? count : 1)));
-    *p = static_cast<T *>(q);
-    return SCL_OK;
-}
-
-template <class T> int regrow(scl_fpfh *h, T **p, size_t count)
-{
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    return malloc_dev(h, p, count);
-}
-
-int grow(scl_fpfh *h, int need)
-{
-    if (need <= h->cap) return SCL_OK;
-    int ncap = h->cap > 0 ? h->cap : 256;
-    while (ncap < need) ncap *= 2;
-    float *nd = nullptr;
-    int rc = malloc_dev(h, &nd, (size_t)ncap * kDim);
-    if (rc) return rc;
-    if (h->n > 0) FP_HIP(h, hipMemcpyAsync(nd, h->d_db, sizeof(float) * kDim * h->n, hipMemcpyDeviceToDevice, h->stream));
-    FP_HIP(h, hipStreamSynchronize(h->stream));
-    if (h->d_db) (void)hipFree(h->d_db);
-    h->d_db = nd; h->cap = ncap;
-    return SCL_OK;
-}
-
 int check_layout(scl_fpfh *h, const void *points, int n_points, int stride)
 {
-    if (stride < 12 || (stride & 3)) return ffail(h, SCL_ERR_INVALID_ARG, "bad point layout (stride_bytes >= 12, multiple of 4)");
-    if (n_points < 3) return ffail(h, SCL_ERR_INVALID_ARG, "FPFH needs at least 3 points (N - 2 pairs)");
-    if (n_points > (1 << 28)) return ffail(h, SCL_ERR_INVALID_ARG, "FPFH: more than 2^28 points in one cloud");
-    if (!points) return ffail(h, SCL_ERR_INVALID_ARG, "null point pointer");
+    if (stride < 12 || (stride & 3)) return fail(h, SCL_ERR_INVALID_ARG, "bad point layout (stride_bytes >= 12, multiple of 4)");
+    if (n_points < 3) return fail(h, SCL_ERR_INVALID_ARG, "FPFH needs at least 3 points (N - 2 pairs)");
+    if (n_points > (1 << 28)) return fail(h, SCL_ERR_INVALID_ARG, "FPFH: more than 2^28 points in one cloud");
+    if (!points) return fail(h, SCL_ERR_INVALID_ARG, "null point pointer");
     return SCL_OK;
 }
 
@@ -533,27 +465,27 @@ int reserve(scl_fpfh *h, size_t pts, size_t cells, size_t bytes)
     int rc;
     if (bytes > h->pts_cap) {
         const size_t c = bytes + bytes / 4 + 4096;
-        if ((rc = regrow(h, &h->d_pts, c))) return rc;
+        if ((rc = dev_regrow(h, &h->d_pts, c))) return rc;
         h->pts_cap = c;
     }
     if (pts > h->pt_cap) {
         const size_t c = pts + pts / 4 + 1024;
-        if ((rc = regrow(h, &h->d_pos, c)) || (rc = regrow(h, &h->d_sp, c)) || (rc = regrow(h, &h->d_normals, c)) ||
-            (rc = regrow(h, &h->d_keys0, c)) || (rc = regrow(h, &h->d_keys1, c)) || (rc = regrow(h, &h->d_vals0, c)) ||
-            (rc = regrow(h, &h->d_vals1, c)))
+        if ((rc = dev_regrow(h, &h->d_pos, c)) || (rc = dev_regrow(h, &h->d_sp, c)) || (rc = dev_regrow(h, &h->d_normals, c)) ||
+            (rc = dev_regrow(h, &h->d_keys0, c)) || (rc = dev_regrow(h, &h->d_keys1, c)) || (rc = dev_regrow(h, &h->d_vals0, c)) ||
+            (rc = dev_regrow(h, &h->d_vals1, c)))
             return rc;
         h->pt_cap = c;
     }
     const size_t sb = scl::sort_scratch_bytes(h->pt_cap, kGroup);
     if (sb > h->sort_cap) {
         unsigned char *p = nullptr;
-        if ((rc = malloc_dev(h, &p, sb))) return rc;
+        if ((rc = dev_alloc(h, &p, sb))) return rc;
         if (h->d_sort) (void)hipFree(h->d_sort);
         h->d_sort = p; h->sort_cap = sb;
     }
     if (cells > h->cell_cap) {
         const size_t c = cells + cells / 4 + 1024;
-        if ((rc = regrow(h, &h->d_starts, c))) return rc;
+        if ((rc = dev_regrow(h, &h->d_starts, c))) return rc;
         h->cell_cap = c;
     }
     return SCL_OK;
@@ -580,34 +512,34 @@ int run_group_locked(scl_fpfh *h, const void *const *clouds, const int *n_points
         max_n = std::max(max_n, n_points[g]); max_cap = std::max(max_cap, scans[g].cell_cap);
     }
     seg.off[G] = (int)pts;
-    if (pts > (size_t)1 << 30 || cells > (size_t)1 << 31) return ffail(h, SCL_ERR_INVALID_ARG, "FPFH: launch group too large");
+    if (pts > (size_t)1 << 30 || cells > (size_t)1 << 31) return fail(h, SCL_ERR_INVALID_ARG, "FPFH: launch group too large");
     int rc = reserve(h, pts, cells, bytes);
     if (rc) return rc;
     int bits = 1;
     while (bits < 40 && ((unsigned long long)1 << bits) <= (unsigned long long)max_cap) ++bits;
     for (int g = 0; g < G; ++g)
-        FP_HIP(h, hipMemcpyAsync(h->d_pts + scans[g].byte_off, clouds[g], (size_t)n_points[g] * stride, hipMemcpyHostToDevice, h->stream));
-    FP_HIP(h, hipMemcpyAsync(h->d_scans, scans, sizeof(FpScan) * G, hipMemcpyHostToDevice, h->stream));
-    FP_HIP(h, hipMemsetAsync(h->d_bad, 0, sizeof(int) * G, h->stream));
-    FP_HIP(h, hipMemsetAsync(h->d_counts, 0, sizeof(unsigned int) * kCounts * G, h->stream));
-    FP_HIP(h, hipEventRecord(h->ev0, h->stream));
+        SCL_HIP(h, hipMemcpyAsync(h->d_pts + scans[g].byte_off, clouds[g], (size_t)n_points[g] * stride, hipMemcpyHostToDevice, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(h->d_scans, scans, sizeof(FpScan) * G, hipMemcpyHostToDevice, h->stream));
+    SCL_HIP(h, hipMemsetAsync(h->d_bad, 0, sizeof(int) * G, h->stream));
+    SCL_HIP(h, hipMemsetAsync(h->d_counts, 0, sizeof(unsigned int) * kCounts * G, h->stream));
+    SCL_HIP(h, hipEventRecord(h->ev0, h->stream));
     const dim3 pgrid((unsigned)((max_n + kThreads - 1) / kThreads), (unsigned)G);
     hipLaunchKernelGGL(fpfh_grid_kernel, dim3(G), dim3(kGridThreads), 0, h->stream, h->d_pts, h->d_scans, stride, h->d_grids, h->d_bad);
     hipLaunchKernelGGL(fpfh_key_kernel, pgrid, dim3(kThreads), 0, h->stream, h->d_pts, h->d_scans, stride, h->d_grids, h->d_bad, h->d_keys0,
                        h->d_vals0, h->d_pos);
-    FP_HIP(h, scl::sort_pairs_u64_segmented(h->d_sort, h->d_keys0, h->d_keys1, h->d_vals0, h->d_vals1, seg, bits, h->stream));
+    SCL_HIP(h, scl::sort_pairs_u64_segmented(h->d_sort, h->d_keys0, h->d_keys1, h->d_vals0, h->d_vals1, seg, bits, h->stream));
     hipLaunchKernelGGL(fpfh_cells_kernel, pgrid, dim3(kThreads), 0, h->stream, h->d_scans, h->d_grids, h->d_keys1, h->d_vals1, h->d_pos,
                        h->d_starts, h->d_sp);
     hipLaunchKernelGGL(fpfh_knn_kernel, pgrid, dim3(kThreads), 0, h->stream, h->d_scans, h->d_grids, h->d_starts, h->d_sp, h->d_pos, h->d_bad,
                        h->d_normals, want_nbr ? h->d_nbr : nullptr, want_nbr ? h->d_nbr_d2 : nullptr, h->d_cand);
     hipLaunchKernelGGL(fpfh_spfh_kernel, dim3(kSpfhBlocks, G), dim3(kThreads), 0, h->stream, h->d_scans, h->d_pos, h->d_normals, h->d_bad,
                        h->d_counts);
-    hipLaunchKernelGGL(fpfh_finish_kernel, dim3(G), dim3(64), 0, h->stream, h->d_scans, h->d_bad, h->d_counts, h->d_db);
-    FP_HIP(h, hipGetLastError());
-    FP_HIP(h, hipEventRecord(h->ev1, h->stream));
+    hipLaunchKernelGGL(fpfh_finish_kernel, dim3(G), dim3(64), 0, h->stream, h->d_scans, h->d_bad, h->d_counts, h->db.d_db);
+    SCL_HIP(h, hipGetLastError());
+    SCL_HIP(h, hipEventRecord(h->ev1, h->stream));
     int bad[kGroup];
-    FP_HIP(h, hipMemcpyAsync(bad, h->d_bad, sizeof(int) * G, hipMemcpyDeviceToHost, h->stream));
-    FP_HIP(h, hipStreamSynchronize(h->stream));
+    SCL_HIP(h, hipMemcpyAsync(bad, h->d_bad, sizeof(int) * G, hipMemcpyDeviceToHost, h->stream));
+    SCL_HIP(h, hipStreamSynchronize(h->stream));
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) h->kernel_us += 1000.0 * (double)ms;
     *any_bad = 0;
@@ -618,45 +550,13 @@ int run_group_locked(scl_fpfh *h, const void *const *clouds, const int *n_points
     return SCL_OK;
 }
 
-void commit_locked(scl_fpfh *h, int8_t robot, int index)
-{
-    h->local2global[(size_t)robot].push_back(h->n);
-    h->robots.push_back(robot); h->indexs.push_back(index); h->n++;
-}
-
-// the nearest of `list` (global keys, ascending; nullptr: keys 0 .. n - 1) to key `q`: position (-1 if n == 0)
-int nearest_locked(scl_fpfh *h, int q, const int *list, int n, int *pos)
-{
-    *pos = -1;
-    if (n <= 0) return SCL_OK;
-    if (list && (size_t)n > h->list_cap) {
-        if (h->d_list) (void)hipFree(h->d_list);
-        h->d_list = nullptr; h->list_cap = 0;
-        const size_t c = (size_t)n + (size_t)n / 2 + 256;
-        int rc = malloc_dev(h, &h->d_list, c);
-        if (rc) return rc;
-        h->list_cap = c;
-    }
-    if (list) FP_HIP(h, hipMemcpyAsync(h->d_list, list, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    FP_HIP(h, hipMemsetAsync(h->d_best, 0xff, sizeof(unsigned long long), h->stream));
-    hipLaunchKernelGGL(fpfh_nn_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, h->d_db,
-                       list ? h->d_list : nullptr, n, q, h->d_best);
-    FP_HIP(h, hipGetLastError());
-    unsigned long long best = ~0ull;
-    FP_HIP(h, hipMemcpyAsync(&best, h->d_best, sizeof(best), hipMemcpyDeviceToHost, h->stream));
-    FP_HIP(h, hipStreamSynchronize(h->stream));
-    if (best == ~0ull) return ffail(h, SCL_ERR_HIP, "nearest neighbour: no key reduced");
-    *pos = (int)(best & 0xffffffffu);
-    return SCL_OK;
-}
-
 // the reported distance between keys a and b: sqrtf of the squared L2 over the first report_dims floats, nanoflann's order
 int report_distance_locked(scl_fpfh *h, int a, int b, float *dist)
 {
     float va[kDim], vb[kDim];
-    FP_HIP(h, hipMemcpyAsync(va, h->d_db + (size_t)a * kDim, sizeof va, hipMemcpyDeviceToHost, h->stream));
-    FP_HIP(h, hipMemcpyAsync(vb, h->d_db + (size_t)b * kDim, sizeof vb, hipMemcpyDeviceToHost, h->stream));
-    FP_HIP(h, hipStreamSynchronize(h->stream));
+    SCL_HIP(h, hipMemcpyAsync(va, h->db.row(a), sizeof va, hipMemcpyDeviceToHost, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(vb, h->db.row(b), sizeof vb, hipMemcpyDeviceToHost, h->stream));
+    SCL_HIP(h, hipStreamSynchronize(h->stream));
     const int D = h->cfg.report_dims;
     float s = 0.0f;
     int k = 0;
@@ -669,19 +569,19 @@ int report_distance_locked(scl_fpfh *h, int a, int b, float *dist)
     return SCL_OK;
 }
 
-// a single cloud through the chain (test hooks): rows slot h->n (scratch, not committed)
+// a single cloud through the chain (test hooks): rows slot h->reg.n (scratch, not committed)
 int run_single_locked(scl_fpfh *h, const void *points, int n_points, int stride, bool want_nbr)
 {
     int rc = check_layout(h, points, n_points, stride), bad = 0;
     if (rc) return rc;
-    if ((rc = grow(h, h->n + 1))) return rc;
+    if ((rc = h->db.grow(h, h->reg.n + 1))) return rc;
     if (want_nbr && (size_t)n_points * kK > h->nbr_cap) {
         const size_t c = (size_t)n_points * kK;
-        if ((rc = regrow(h, &h->d_nbr, c)) || (rc = regrow(h, &h->d_nbr_d2, c))) return rc;
+        if ((rc = dev_regrow(h, &h->d_nbr, c)) || (rc = dev_regrow(h, &h->d_nbr_d2, c))) return rc;
         h->nbr_cap = c;
     }
-    if ((rc = run_group_locked(h, &points, &n_points, stride, 1, h->n, &bad, want_nbr))) return rc;
-    if (bad) return ffail(h, SCL_ERR_INVALID_ARG, "non-finite coordinate");
+    if ((rc = run_group_locked(h, &points, &n_points, stride, 1, h->reg.n, &bad, want_nbr))) return rc;
+    if (bad) return fail(h, SCL_ERR_INVALID_ARG, "non-finite coordinate");
     return SCL_OK;
 }
 
@@ -713,17 +613,17 @@ int scl_fpfh_create(const scl_fpfh_config *cfg, scl_fpfh **out)
     scl_fpfh *h = new (std::nothrow) scl_fpfh();
     if (!h) return SCL_ERR_NOMEM;
     h->cfg = *cfg; h->device = cfg->device;
-    h->local2global.resize((size_t)cfg->robot_num);
+    h->reg.init(cfg->robot_num);
     auto bail = [&](int code) { scl_fpfh_destroy(h); return code; };
     if (hipSetDevice(h->device) != hipSuccess) return bail(SCL_ERR_HIP);
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(SCL_ERR_HIP);
     if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return bail(SCL_ERR_HIP);
     int rc;
-    if ((rc = malloc_dev(h, &h->d_scans, kGroup)) || (rc = malloc_dev(h, &h->d_grids, kGroup)) || (rc = malloc_dev(h, &h->d_bad, kGroup)) ||
-        (rc = malloc_dev(h, &h->d_counts, (size_t)kGroup * kCounts)) || (rc = malloc_dev(h, &h->d_cand, 1)) ||
-        (rc = malloc_dev(h, &h->d_best, 1)))
+    if ((rc = dev_alloc(h, &h->d_scans, kGroup)) || (rc = dev_alloc(h, &h->d_grids, kGroup)) || (rc = dev_alloc(h, &h->d_bad, kGroup)) ||
+        (rc = dev_alloc(h, &h->d_counts, (size_t)kGroup * kCounts)) || (rc = dev_alloc(h, &h->d_cand, 1)) ||
+        (rc = dev_alloc(h, &h->d_best, 1)))
         return bail(rc);
-    if ((rc = grow(h, 1))) return bail(rc);
+    if ((rc = h->db.grow(h, 1))) return bail(rc);
     if (hipMemset(h->d_cand, 0, sizeof(unsigned long long)) != hipSuccess) return bail(SCL_ERR_HIP);
     *out = h;
     return SCL_OK;
@@ -734,7 +634,7 @@ int scl_fpfh_destroy(scl_fpfh *h)
     if (!h) return SCL_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void *p : {(void *)h->d_db, (void *)h->d_pts, (void *)h->d_pos, (void *)h->d_sp, (void *)h->d_normals, (void *)h->d_keys0,
+    for (void *p : {(void *)h->db.d_db, (void *)h->d_pts, (void *)h->d_pos, (void *)h->d_sp, (void *)h->d_normals, (void *)h->d_keys0,
                     (void *)h->d_keys1, (void *)h->d_vals0, (void *)h->d_vals1, h->d_sort, (void *)h->d_starts, (void *)h->d_scans,
                     (void *)h->d_grids, (void *)h->d_bad, (void *)h->d_counts, (void *)h->d_cand, (void *)h->d_best, (void *)h->d_list,
                     (void *)h->d_nbr, (void *)h->d_nbr_d2})
@@ -753,9 +653,7 @@ int scl_fpfh_make(scl_fpfh *h, const void *points, int n_points, int stride_byte
     (void)hipSetDevice(h->device);
     int rc = run_single_locked(h, points, n_points, stride_bytes, false);
     if (rc) return rc;
-    FP_HIP(h, hipMemcpyAsync(out_values, h->d_db + (size_t)h->n * kDim, sizeof(float) * kDim, hipMemcpyDeviceToHost, h->stream));
-    FP_HIP(h, hipStreamSynchronize(h->stream));
-    return SCL_OK;
+    return h->db.read(h, h->reg.n, 1, out_values);
 }
 
 int scl_fpfh_make_and_save_many(scl_fpfh *h, const void *const *clouds, const int *n_points, int stride_bytes,
@@ -764,27 +662,8 @@ int scl_fpfh_make_and_save_many(scl_fpfh *h, const void *const *clouds, const in
     if (!h || count < 0 || (count > 0 && (!clouds || !n_points || !robots || !indexs))) return SCL_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     (void)hipSetDevice(h->device);
-    for (int i = 0; i < count; ++i) {
-        int rc = check_layout(h, clouds[i], n_points[i], stride_bytes);
-        if (rc) return rc;
-        if (robots[i] < 0 || robots[i] >= h->cfg.robot_num) return ffail(h, SCL_ERR_INVALID_ARG, "robot id outside [0, robot_num)");
-    }
-    if (count == 0) return SCL_OK;
-    int rc = grow(h, h->n + count);
-    if (rc) return rc;
-    for (int s = 0; s < count; s += kGroup) {
-        const int G = std::min(kGroup, count - s);
-        int bad = 0;
-        if ((rc = run_group_locked(h, clouds + s, n_points + s, stride_bytes, G, h->n + s, &bad))) return rc;
-        if (bad) return ffail(h, SCL_ERR_INVALID_ARG, "non-finite coordinate: nothing of the call was stored");
-    }
-    if (out_values) {
-        FP_HIP(h, hipMemcpyAsync(out_values, h->d_db + (size_t)h->n * kDim, sizeof(float) * kDim * (size_t)count, hipMemcpyDeviceToHost,
-                                 h->stream));
-        FP_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    for (int i = 0; i < count; ++i) commit_locked(h, robots[i], indexs[i]);
-    return SCL_OK;
+    auto run = [&](const void *const *c, const int *np, int G, int slot0, int *bad) { return run_group_locked(h, c, np, stride_bytes, G, slot0, bad); };
+    return make_and_save_many_locked(h, clouds, n_points, stride_bytes, robots, indexs, count, out_values, kGroup, check_layout, run);
 }
 
 int scl_fpfh_make_and_save(scl_fpfh *h, const void *points, int n_points, int stride_bytes, int8_t robot, int index, float *out_values)
@@ -797,60 +676,24 @@ int scl_fpfh_save_from_wire(scl_fpfh *h, const float *values, int8_t robot, int 
     if (!h || !values) return SCL_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     (void)hipSetDevice(h->device);
-    if (robot < 0 || robot >= h->cfg.robot_num) return ffail(h, SCL_ERR_INVALID_ARG, "robot id outside [0, robot_num)");
-    int rc = grow(h, h->n + 1);
-    if (rc) return rc;
-    FP_HIP(h, hipMemcpyAsync(h->d_db + (size_t)h->n * kDim, values, sizeof(float) * kDim, hipMemcpyHostToDevice, h->stream));
-    FP_HIP(h, hipStreamSynchronize(h->stream));
-    commit_locked(h, robot, index);
+    int rc;
+    if ((rc = check_robot(h, robot, SCL_ERR_INVALID_ARG)) || (rc = h->db.grow(h, h->reg.n + 1)) || (rc = h->db.write(h, h->reg.n, values))) return rc;
+    h->reg.commit(robot, index);
     return SCL_OK;
 }
 
-int scl_fpfh_get_size(const scl_fpfh *h)
-{
-    if (!h) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    return h->n;
-}
-
-int scl_fpfh_get_size_of(const scl_fpfh *h, int id)
-{
-    if (!h) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (id == -1) return h->n;
-    if (id < 0 || id >= h->cfg.robot_num) return ffail(h, SCL_ERR_OUT_OF_RANGE, "robot id outside [0, robot_num)");
-    return (int)h->local2global[(size_t)id].size();
-}
-
-int scl_fpfh_get_index(const scl_fpfh *h, int key, int8_t *robot, int *index)
-{
-    if (!h || !robot || !index) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (key < 0 || key >= h->n) return ffail(h, SCL_ERR_OUT_OF_RANGE, "key out of range");
-    *robot = h->robots[(size_t)key]; *index = h->indexs[(size_t)key];
-    return SCL_OK;
-}
-
-int scl_fpfh_local_to_global(const scl_fpfh *h, int robot, int local, int *key)
-{
-    if (!h || !key) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (robot < 0 || robot >= h->cfg.robot_num) return ffail(h, SCL_ERR_OUT_OF_RANGE, "robot id outside [0, robot_num)");
-    const std::vector<int> &l2g = h->local2global[(size_t)robot];
-    if (local < 0 || local >= (int)l2g.size()) return ffail(h, SCL_ERR_OUT_OF_RANGE, "local index out of range");
-    *key = l2g[(size_t)local];
-    return SCL_OK;
-}
+int scl_fpfh_get_size(const scl_fpfh *h) { return get_size(h); }
+int scl_fpfh_get_size_of(const scl_fpfh *h, int id) { return get_size_of(h, id); }
+int scl_fpfh_get_index(const scl_fpfh *h, int key, int8_t *robot, int *index) { return get_index(h, key, robot, index); }
+int scl_fpfh_local_to_global(const scl_fpfh *h, int robot, int local, int *key) { return local_to_global(h, robot, local, key); }
 
 int scl_fpfh_get_signature(scl_fpfh *h, int key, float *values)
 {
     if (!h || !values) return SCL_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     (void)hipSetDevice(h->device);
-    if (key < 0 || key >= h->n) return ffail(h, SCL_ERR_OUT_OF_RANGE, "key out of range");
-    FP_HIP(h, hipMemcpyAsync(values, h->d_db + (size_t)key * kDim, sizeof(float) * kDim, hipMemcpyDeviceToHost, h->stream));
-    FP_HIP(h, hipStreamSynchronize(h->stream));
-    return SCL_OK;
+    if (key < 0 || key >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "key out of range");
+    return h->db.read(h, key, 1, values);
 }
 
 int scl_fpfh_detect_intra(scl_fpfh *h, int cur, int *loop_id, float *dist)
@@ -860,12 +703,12 @@ int scl_fpfh_detect_intra(scl_fpfh *h, int cur, int *loop_id, float *dist)
     (void)hipSetDevice(h->device);
     *loop_id = -1;
     if (dist) *dist = INFINITY;
-    const std::vector<int> &mine = h->local2global[(size_t)h->cfg.this_id];
-    if (cur < 0 || cur >= (int)mine.size()) return ffail(h, SCL_ERR_OUT_OF_RANGE, "detect_intra: no such keyframe of this robot");
+    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
+    if (cur < 0 || cur >= (int)mine.size()) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_intra: no such keyframe of this robot");
     const int history = cur - h->cfg.num_exclude_recent;
     if (history <= 0) return SCL_OK;
-    int pos; float d;
-    int rc = nearest_locked(h, mine[(size_t)cur], mine.data(), history, &pos);     // ascending keys: position = local index
+    int pos; float d2, d;
+    int rc = nearest_locked(h, mine[(size_t)cur], mine.data(), history, &pos, &d2);     // ascending keys: position = local index
     if (rc) return rc;
     if ((rc = report_distance_locked(h, mine[(size_t)cur], mine[(size_t)pos], &d))) return rc;
     if (dist) *dist = d;
@@ -880,23 +723,18 @@ int scl_fpfh_detect_inter(scl_fpfh *h, int cur, int *loop_id, float *dist)
     (void)hipSetDevice(h->device);
     *loop_id = -1;
     if (dist) *dist = INFINITY;
-    if (cur < 0 || cur >= h->n) return ffail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter: key out of range");
+    if (cur < 0 || cur >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter: key out of range");
     int pos = -1, rc;
-    std::vector<int> list;
+    float d2;
     if (h->cfg.inter_mode == 0) {                                 // D.h:381-428
-        if (h->n < h->cfg.num_exclude_recent + 1) { if (dist) *dist = 0.0f; return SCL_OK; }
-        if (h->tree_counter % h->cfg.tree_making_period == 0) h->snap_n = h->n - h->cfg.num_exclude_recent;
+        if (h->reg.n < h->cfg.num_exclude_recent + 1) { if (dist) *dist = 0.0f; return SCL_OK; }
+        if (h->tree_counter % h->cfg.tree_making_period == 0) h->snap_n = h->reg.n - h->cfg.num_exclude_recent;
         h->tree_counter += 1;
-        if ((rc = nearest_locked(h, cur, nullptr, h->snap_n, &pos))) return rc;
+        if ((rc = nearest_locked(h, cur, nullptr, h->snap_n, &pos, &d2))) return rc;
     } else {
-        if (h->robots[(size_t)cur] == h->cfg.this_id) {
-            for (int i = 0; i < h->cfg.robot_num; ++i)
-                if (i != h->cfg.this_id) list.insert(list.end(), h->local2global[(size_t)i].begin(), h->local2global[(size_t)i].end());
-        } else {
-            list = h->local2global[(size_t)h->cfg.this_id];
-        }
+        std::vector<int> list = h->reg.inter_candidates(cur, h->cfg.this_id);
         std::sort(list.begin(), list.end());                      // ties go to the lowest key
-        if ((rc = nearest_locked(h, cur, list.data(), (int)list.size(), &pos))) return rc;
+        if ((rc = nearest_locked(h, cur, list.data(), (int)list.size(), &pos, &d2))) return rc;
         if (pos < 0) return SCL_OK;
         pos = list[(size_t)pos];
     }
@@ -915,9 +753,9 @@ int scl_fpfh_neighbors(scl_fpfh *h, const void *points, int n_points, int stride
     int rc = run_single_locked(h, points, n_points, stride_bytes, true);
     if (rc) return rc;
     const size_t cnt = (size_t)n_points * (size_t)std::min(n_points, kK);
-    if (idx) FP_HIP(h, hipMemcpyAsync(idx, h->d_nbr, sizeof(int) * cnt, hipMemcpyDeviceToHost, h->stream));
-    if (d2) FP_HIP(h, hipMemcpyAsync(d2, h->d_nbr_d2, sizeof(float) * cnt, hipMemcpyDeviceToHost, h->stream));
-    FP_HIP(h, hipStreamSynchronize(h->stream));
+    if (idx) SCL_HIP(h, hipMemcpyAsync(idx, h->d_nbr, sizeof(int) * cnt, hipMemcpyDeviceToHost, h->stream));
+    if (d2) SCL_HIP(h, hipMemcpyAsync(d2, h->d_nbr_d2, sizeof(float) * cnt, hipMemcpyDeviceToHost, h->stream));
+    SCL_HIP(h, hipStreamSynchronize(h->stream));
     return SCL_OK;
 }
 
@@ -930,8 +768,8 @@ int scl_fpfh_normals(scl_fpfh *h, const void *points, int n_points, int stride_b
     if (rc) return rc;
     if (normals) {
         std::vector<float4> nv((size_t)n_points);
-        FP_HIP(h, hipMemcpyAsync(nv.data(), h->d_normals, sizeof(float4) * (size_t)n_points, hipMemcpyDeviceToHost, h->stream));
-        FP_HIP(h, hipStreamSynchronize(h->stream));
+        SCL_HIP(h, hipMemcpyAsync(nv.data(), h->d_normals, sizeof(float4) * (size_t)n_points, hipMemcpyDeviceToHost, h->stream));
+        SCL_HIP(h, hipStreamSynchronize(h->stream));
         for (int i = 0; i < n_points; ++i) { normals[3 * i] = nv[(size_t)i].x; normals[3 * i + 1] = nv[(size_t)i].y; normals[3 * i + 2] = nv[(size_t)i].z; }
     }
     return SCL_OK;
@@ -945,8 +783,8 @@ int scl_fpfh_counts(scl_fpfh *h, const void *points, int n_points, int stride_by
     int rc = run_single_locked(h, points, n_points, stride_bytes, false);
     if (rc) return rc;
     uint32_t c[kCounts];
-    FP_HIP(h, hipMemcpyAsync(c, h->d_counts, sizeof c, hipMemcpyDeviceToHost, h->stream));
-    FP_HIP(h, hipStreamSynchronize(h->stream));
+    SCL_HIP(h, hipMemcpyAsync(c, h->d_counts, sizeof c, hipMemcpyDeviceToHost, h->stream));
+    SCL_HIP(h, hipStreamSynchronize(h->stream));
     if (counts) std::memcpy(counts, c, sizeof(uint32_t) * kDim);
     if (skipped) *skipped = c[kCounts - 1];
     return SCL_OK;
@@ -965,7 +803,7 @@ int scl_fpfh_acosf_blocks(scl_fpfh *h, int first_block, int n_blocks, uint64_t *
     std::lock_guard<std::mutex> lk(h->mu);
     (void)hipSetDevice(h->device);
     unsigned long long *d = nullptr;
-    int rc = malloc_dev(h, &d, (size_t)n_blocks);
+    int rc = dev_alloc(h, &d, (size_t)n_blocks);
     if (rc) return rc;
     hipError_t he = hipMemsetAsync(d, 0, sizeof(unsigned long long) * (size_t)n_blocks, h->stream);
     if (he == hipSuccess) {
@@ -976,7 +814,7 @@ int scl_fpfh_acosf_blocks(scl_fpfh *h, int first_block, int n_blocks, uint64_t *
     if (he == hipSuccess) he = hipMemcpyAsync(checksums, d, sizeof(uint64_t) * (size_t)n_blocks, hipMemcpyDeviceToHost, h->stream);
     if (he == hipSuccess) he = hipStreamSynchronize(h->stream);
     (void)hipFree(d);
-    FP_HIP(h, he);
+    SCL_HIP(h, he);
     return SCL_OK;
 }
 
@@ -986,7 +824,7 @@ int scl_fpfh_stats(const scl_fpfh *h, unsigned long long *points, unsigned long 
     std::lock_guard<std::mutex> lk(h->mu);
     (void)hipSetDevice(h->device);
     unsigned long long c = 0;
-    FP_HIP(h, hipMemcpy(&c, h->d_cand, sizeof(c), hipMemcpyDeviceToHost));
+    SCL_HIP(h, hipMemcpy(&c, h->d_cand, sizeof(c), hipMemcpyDeviceToHost));
     if (points) *points = h->points;
     if (candidates) *candidates = c;
     if (kernel_us) *kernel_us = h->kernel_us;

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "device_common.hpp"
+#include "plugin_host.hpp"
 
 using namespace scl;
 
@@ -304,16 +305,14 @@ struct scl_iris {
     hipStream_t stream = nullptr;
     mutable std::mutex mu;
     mutable std::string last_error;
-    int n = 0, cap = 0;
+    scl::KeyframeRegistry reg;
+    int cap = 0;                                               // rows of the image / row key / template store (reg.n live)
     int words = 0, trows = 0;
     unsigned char *d_images = nullptr; float *d_rowkeys = nullptr; unsigned int *d_T = nullptr, *d_M = nullptr;
     double2 *d_h = nullptr;
     unsigned int *d_cells = nullptr; int *d_zmax = nullptr; unsigned char *d_points = nullptr; size_t points_cap = 0;
     unsigned char *d_img1 = nullptr; float *d_key1 = nullptr; unsigned char *d_unpack = nullptr;
     int *d_cand = nullptr, *d_shifts = nullptr, *d_diff = nullptr, *d_total = nullptr; size_t job_cap = 0;
-    std::vector<int8_t> robots; std::vector<int> indexs;
-    // the plugin layer (D.h:1289-1292): per robot the global keys of its keyframes in arrival order
-    std::vector<std::vector<int>> local2global;
     int *d_list = nullptr; float *d_d2 = nullptr; size_t list_cap = 0;
     // FFT shift estimate (logPolarFFTTemplateMatch): tables made at creation, work buffers for fm_cap jobs
     double *d_wcR = nullptr, *d_wsR = nullptr, *d_wcC = nullptr, *d_wsC = nullptr; float *d_hp = nullptr; int2 *d_lpmap = nullptr; float log_base = 0.f;
@@ -326,25 +325,6 @@ struct scl_iris {
 
 namespace {
 
-#define IRIS_HIP(h_, call)                                                             \
-    do {                                                                               \
-        hipError_t err__ = (call);                                                     \
-        if (err__ != hipSuccess) {                                                     \
-            (h_)->last_error = std::string(#call) + ": " + hipGetErrorString(err__);   \
-            return err__ == hipErrorOutOfMemory ? SCL_ERR_NOMEM : SCL_ERR_HIP;         \
-        }                                                                              \
-    } while (0)
-
-int ifail(const scl_iris *h, int code, const char *msg) { if (h) h->last_error = msg; return code; }
-
-template <class T> int ialloc(scl_iris *h, T **p, size_t count)
-{
-    void *q = nullptr;
-    IRIS_HIP(h, hipMalloc(&q, sizeof(T) * (count ? count : 1)));
-    *p = static_cast<T *>(q);
-    return SCL_OK;
-}
-
 int grow(scl_iris *h, int need)
 {
     if (need <= h->cap) return SCL_OK;
@@ -353,14 +333,14 @@ int grow(scl_iris *h, int need)
     const size_t cells = (size_t)h->cfg.rows * h->cfg.cols, fw = (size_t)h->cfg.cols * h->words;
     unsigned char *ni = nullptr; float *nk = nullptr; unsigned int *nt = nullptr, *nm = nullptr;
     int rc;
-    if ((rc = ialloc(h, &ni, cells * ncap)) || (rc = ialloc(h, &nk, (size_t)h->cfg.rows * ncap)) || (rc = ialloc(h, &nt, fw * ncap)) || (rc = ialloc(h, &nm, fw * ncap))) return rc;
-    if (h->n > 0) {
-        IRIS_HIP(h, hipMemcpyAsync(ni, h->d_images, cells * h->n, hipMemcpyDeviceToDevice, h->stream));
-        IRIS_HIP(h, hipMemcpyAsync(nk, h->d_rowkeys, sizeof(float) * h->cfg.rows * h->n, hipMemcpyDeviceToDevice, h->stream));
-        IRIS_HIP(h, hipMemcpyAsync(nt, h->d_T, sizeof(unsigned int) * fw * h->n, hipMemcpyDeviceToDevice, h->stream));
-        IRIS_HIP(h, hipMemcpyAsync(nm, h->d_M, sizeof(unsigned int) * fw * h->n, hipMemcpyDeviceToDevice, h->stream));
+    if ((rc = dev_alloc(h, &ni, cells * ncap)) || (rc = dev_alloc(h, &nk, (size_t)h->cfg.rows * ncap)) || (rc = dev_alloc(h, &nt, fw * ncap)) || (rc = dev_alloc(h, &nm, fw * ncap))) return rc;
+    if (h->reg.n > 0) {
+        SCL_HIP(h, hipMemcpyAsync(ni, h->d_images, cells * h->reg.n, hipMemcpyDeviceToDevice, h->stream));
+        SCL_HIP(h, hipMemcpyAsync(nk, h->d_rowkeys, sizeof(float) * h->cfg.rows * h->reg.n, hipMemcpyDeviceToDevice, h->stream));
+        SCL_HIP(h, hipMemcpyAsync(nt, h->d_T, sizeof(unsigned int) * fw * h->reg.n, hipMemcpyDeviceToDevice, h->stream));
+        SCL_HIP(h, hipMemcpyAsync(nm, h->d_M, sizeof(unsigned int) * fw * h->reg.n, hipMemcpyDeviceToDevice, h->stream));
     }
-    IRIS_HIP(h, hipStreamSynchronize(h->stream));
+    SCL_HIP(h, hipStreamSynchronize(h->stream));
     if (h->d_images) (void)hipFree(h->d_images);
     if (h->d_rowkeys) (void)hipFree(h->d_rowkeys);
     if (h->d_T) (void)hipFree(h->d_T);
@@ -372,80 +352,76 @@ int grow(scl_iris *h, int need)
 // points (host) -> d_img1 / d_key1
 int make_image_locked(scl_iris *h, const void *points, int n_points, int stride)
 {
-    if (n_points < 0 || stride < 12 || (stride & 3) || (n_points > 0 && !points)) return ifail(h, SCL_ERR_INVALID_ARG, "bad point layout");
+    if (n_points < 0 || stride < 12 || (stride & 3) || (n_points > 0 && !points)) return fail(h, SCL_ERR_INVALID_ARG, "bad point layout");
     const int rows = h->cfg.rows, cols = h->cfg.cols;
     const size_t bytes = (size_t)n_points * stride;
     if (bytes > h->points_cap) {
-        if (h->d_points) (void)hipFree(h->d_points);
         h->points_cap = 0;
-        int rc = ialloc(h, &h->d_points, bytes + bytes / 4 + 4096);
+        int rc = dev_regrow(h, &h->d_points, bytes + bytes / 4 + 4096);
         if (rc) return rc;
         h->points_cap = bytes + bytes / 4 + 4096;
     }
-    if (bytes) IRIS_HIP(h, hipMemcpyAsync(h->d_points, points, bytes, hipMemcpyHostToDevice, h->stream));
-    IRIS_HIP(h, hipMemsetAsync(h->d_cells, 0, sizeof(unsigned int) * (size_t)rows * cols, h->stream));
-    IRIS_HIP(h, hipMemsetAsync(h->d_zmax, 0, sizeof(int) * (size_t)rows * cols, h->stream));
+    if (bytes) SCL_HIP(h, hipMemcpyAsync(h->d_points, points, bytes, hipMemcpyHostToDevice, h->stream));
+    SCL_HIP(h, hipMemsetAsync(h->d_cells, 0, sizeof(unsigned int) * (size_t)rows * cols, h->stream));
+    SCL_HIP(h, hipMemsetAsync(h->d_zmax, 0, sizeof(int) * (size_t)rows * cols, h->stream));
     if (n_points > 0 && (h->cfg.nscan == 16 || h->cfg.nscan == 64)) {             // D.h:538 / 560: other beam counts leave the image empty
         int blocks = (n_points + 255) / 256; blocks = blocks > 2048 ? 2048 : blocks;
         hipLaunchKernelGGL(iris_image_kernel, dim3(blocks), dim3(256), 0, h->stream, h->d_points, n_points, stride, rows, cols,
                            h->cfg.nscan == 16 ? 15.0 : 24.9, h->d_cells, h->d_zmax);
     }
     hipLaunchKernelGGL(iris_rowkey_kernel, dim3(rows), dim3(128), 0, h->stream, h->d_zmax, h->d_cells, rows, cols, h->d_key1, h->d_img1);
-    IRIS_HIP(h, hipGetLastError());
+    SCL_HIP(h, hipGetLastError());
     return SCL_OK;
 }
 
 // d_img1 / d_key1 -> database slot n (image, row key, templates)
 int append_locked(scl_iris *h, int8_t robot, int index)
 {
-    if (robot < 0 || robot >= h->cfg.robot_num) return ifail(h, SCL_ERR_INVALID_ARG, "robot id outside [0, robot_num)");
-    int rc = grow(h, h->n + 1);
-    if (rc) return rc;
+    int rc;
+    if ((rc = check_robot(h, robot, SCL_ERR_INVALID_ARG)) || (rc = grow(h, h->reg.n + 1))) return rc;
     const int rows = h->cfg.rows, cols = h->cfg.cols;
     const size_t cells = (size_t)rows * cols, fw = (size_t)cols * h->words;
-    IRIS_HIP(h, hipMemcpyAsync(h->d_images + cells * h->n, h->d_img1, cells, hipMemcpyDeviceToDevice, h->stream));
-    IRIS_HIP(h, hipMemcpyAsync(h->d_rowkeys + (size_t)rows * h->n, h->d_key1, sizeof(float) * rows, hipMemcpyDeviceToDevice, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(h->d_images + cells * h->reg.n, h->d_img1, cells, hipMemcpyDeviceToDevice, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(h->d_rowkeys + (size_t)rows * h->reg.n, h->d_key1, sizeof(float) * rows, hipMemcpyDeviceToDevice, h->stream));
     hipLaunchKernelGGL(iris_encode_kernel, dim3(cols), dim3(256), sizeof(unsigned int) * 2 * h->words, h->stream,
-                       h->d_img1, h->d_h, rows, cols, h->cfg.nscale, h->d_T + fw * h->n, h->d_M + fw * h->n, h->words);
-    IRIS_HIP(h, hipGetLastError());
-    IRIS_HIP(h, hipStreamSynchronize(h->stream));
-    h->local2global[(size_t)robot].push_back(h->n);                                // D.h:1055
-    h->robots.push_back(robot); h->indexs.push_back(index); h->n++;            // D.h:1057
+                       h->d_img1, h->d_h, rows, cols, h->cfg.nscale, h->d_T + fw * h->reg.n, h->d_M + fw * h->reg.n, h->words);
+    SCL_HIP(h, hipGetLastError());
+    SCL_HIP(h, hipStreamSynchronize(h->stream));
+    h->reg.commit(robot, index);                                                  // D.h:1055-1057
     return SCL_OK;
 }
 
 int hamming_jobs_locked(scl_iris *h, int key1, const int *cand, const int *shifts, int n, int per, float *dis, int *bias, bool window, const int *rolls2 = nullptr)
 {
-    if (key1 < 0 || key1 >= h->n) return ifail(h, SCL_ERR_OUT_OF_RANGE, "key1 out of range");
-    for (int i = 0; i < n; ++i) if (cand[i] < 0 || cand[i] >= h->n) return ifail(h, SCL_ERR_OUT_OF_RANGE, "candidate out of range");
+    if (key1 < 0 || key1 >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "key1 out of range");
+    for (int i = 0; i < n; ++i) if (cand[i] < 0 || cand[i] >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "candidate out of range");
     const size_t jobs = (size_t)n * per;
     if (jobs > h->job_cap) {
         for (int **p : {&h->d_cand, &h->d_shifts, &h->d_diff, &h->d_total}) { if (*p) (void)hipFree(*p); *p = nullptr; }
         h->job_cap = 0;
         int rc;
-        if ((rc = ialloc(h, &h->d_cand, jobs + 64)) || (rc = ialloc(h, &h->d_shifts, jobs + 64)) || (rc = ialloc(h, &h->d_diff, jobs + 64)) || (rc = ialloc(h, &h->d_total, jobs + 64))) return rc;
+        if ((rc = dev_alloc(h, &h->d_cand, jobs + 64)) || (rc = dev_alloc(h, &h->d_shifts, jobs + 64)) || (rc = dev_alloc(h, &h->d_diff, jobs + 64)) || (rc = dev_alloc(h, &h->d_total, jobs + 64))) return rc;
         h->job_cap = jobs + 64;
     }
-    IRIS_HIP(h, hipMemcpyAsync(h->d_cand, cand, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
-    IRIS_HIP(h, hipMemcpyAsync(h->d_shifts, shifts, sizeof(int) * jobs, hipMemcpyHostToDevice, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(h->d_cand, cand, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(h->d_shifts, shifts, sizeof(int) * jobs, hipMemcpyHostToDevice, h->stream));
     if (rolls2) {
         if ((size_t)n > h->rolls_cap) {
-            if (h->d_rolls) (void)hipFree(h->d_rolls);
-            h->d_rolls = nullptr; h->rolls_cap = 0;
-            int rc = ialloc(h, &h->d_rolls, (size_t)n + 64);
+            h->rolls_cap = 0;
+            int rc = dev_regrow(h, &h->d_rolls, (size_t)n + 64);
             if (rc) return rc;
             h->rolls_cap = (size_t)n + 64;
         }
-        IRIS_HIP(h, hipMemcpyAsync(h->d_rolls, rolls2, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
+        SCL_HIP(h, hipMemcpyAsync(h->d_rolls, rolls2, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
     }
     const size_t fw = (size_t)h->cfg.cols * h->words;
     hipLaunchKernelGGL(iris_hamming_kernel, dim3((unsigned)jobs), dim3(64), 0, h->stream, h->d_T, h->d_M, fw, key1, h->d_cand, h->d_shifts, per,
                        h->cfg.cols, h->words, h->trows, h->d_diff, h->d_total, rolls2 ? h->d_rolls : (const int *)nullptr);
-    IRIS_HIP(h, hipGetLastError());
+    SCL_HIP(h, hipGetLastError());
     std::vector<int> diff(jobs), total(jobs);
-    IRIS_HIP(h, hipMemcpyAsync(diff.data(), h->d_diff, sizeof(int) * jobs, hipMemcpyDeviceToHost, h->stream));
-    IRIS_HIP(h, hipMemcpyAsync(total.data(), h->d_total, sizeof(int) * jobs, hipMemcpyDeviceToHost, h->stream));
-    IRIS_HIP(h, hipStreamSynchronize(h->stream));
+    SCL_HIP(h, hipMemcpyAsync(diff.data(), h->d_diff, sizeof(int) * jobs, hipMemcpyDeviceToHost, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(total.data(), h->d_total, sizeof(int) * jobs, hipMemcpyDeviceToHost, h->stream));
+    SCL_HIP(h, hipStreamSynchronize(h->stream));
     for (int c = 0; c < n; ++c) {                                             // the O(shifts) selection of D.h:937-962, float like the reference
         float best = NAN; int b = -1;
         for (int j = 0; j < per; ++j) {
@@ -465,7 +441,7 @@ int hamming_jobs_locked(scl_iris *h, int key1, const int *cand, const int *shift
 int fft_match_jobs_locked(scl_iris *h, const FftJob *jobs, int J, float *center_x, int *ok_out)
 {
     if (J <= 0) return SCL_OK;
-    if (!h->fm_ok) return ifail(h, SCL_ERR_UNSUPPORTED, "the FFT shift estimate takes even rows and columns only");
+    if (!h->fm_ok) return fail(h, SCL_ERR_UNSUPPORTED, "the FFT shift estimate takes even rows and columns only");
     const int R = h->cfg.rows, C = h->cfg.cols;
     const size_t n = (size_t)R * C;
     if ((size_t)J > h->fm_cap) {
@@ -474,14 +450,14 @@ int fft_match_jobs_locked(scl_iris *h, const FftJob *jobs, int J, float *center_
         h->fm_cap = 0;
         const size_t cap = (size_t)J + 8;
         int rc;
-        if ((rc = ialloc(h, &h->d_fjobs, cap)) || (rc = ialloc(h, &h->d_fa0, cap * n)) || (rc = ialloc(h, &h->d_fa1, cap * n)) || (rc = ialloc(h, &h->d_ff, cap * n)) ||
-            (rc = ialloc(h, &h->d_flp0, cap * n)) || (rc = ialloc(h, &h->d_flp1, cap * n)) || (rc = ialloc(h, &h->d_frs, cap * n)) || (rc = ialloc(h, &h->d_fw0, cap * n)) ||
-            (rc = ialloc(h, &h->d_fw1, cap * n)) || (rc = ialloc(h, &h->d_fw2, cap * n)) || (rc = ialloc(h, &h->d_fres, cap)) || (rc = ialloc(h, &h->d_fmats, cap * 6))) return rc;
+        if ((rc = dev_alloc(h, &h->d_fjobs, cap)) || (rc = dev_alloc(h, &h->d_fa0, cap * n)) || (rc = dev_alloc(h, &h->d_fa1, cap * n)) || (rc = dev_alloc(h, &h->d_ff, cap * n)) ||
+            (rc = dev_alloc(h, &h->d_flp0, cap * n)) || (rc = dev_alloc(h, &h->d_flp1, cap * n)) || (rc = dev_alloc(h, &h->d_frs, cap * n)) || (rc = dev_alloc(h, &h->d_fw0, cap * n)) ||
+            (rc = dev_alloc(h, &h->d_fw1, cap * n)) || (rc = dev_alloc(h, &h->d_fw2, cap * n)) || (rc = dev_alloc(h, &h->d_fres, cap)) || (rc = dev_alloc(h, &h->d_fmats, cap * 6))) return rc;
         h->fm_cap = cap;
     }
     hipStream_t st = h->stream;
     const dim3 ge((unsigned)((n + 255) / 256), (unsigned)J), blk(256);
-    IRIS_HIP(h, hipMemcpyAsync(h->d_fjobs, jobs, sizeof(FftJob) * (size_t)J, hipMemcpyHostToDevice, st));
+    SCL_HIP(h, hipMemcpyAsync(h->d_fjobs, jobs, sizeof(FftJob) * (size_t)J, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(fm_stage_kernel, ge, blk, 0, st, h->d_images, h->d_fjobs, R, C, h->d_fa0, h->d_fa1);
     // 2-D DFT of a float image: rows, then columns; result in w_out, w_tmp as scratch
     auto dft2 = [&](const float *src, double2 *w_out, double2 *w_tmp) {
@@ -506,10 +482,10 @@ int fft_match_jobs_locked(scl_iris *h, const FftJob *jobs, int J, float *center_
     logpolar(h->d_fa0, h->d_flp0);
     logpolar(h->d_fa1, h->d_flp1);
     phase_correlate(h->d_flp1, h->d_flp0);
-    IRIS_HIP(h, hipGetLastError());
+    SCL_HIP(h, hipGetLastError());
     std::vector<double2> res((size_t)J);
-    IRIS_HIP(h, hipMemcpyAsync(res.data(), h->d_fres, sizeof(double2) * (size_t)J, hipMemcpyDeviceToHost, st));
-    IRIS_HIP(h, hipStreamSynchronize(st));
+    SCL_HIP(h, hipMemcpyAsync(res.data(), h->d_fres, sizeof(double2) * (size_t)J, hipMemcpyDeviceToHost, st));
+    SCL_HIP(h, hipStreamSynchronize(st));
     // rotation and scale -> the inverted affine map of warpAffine (D.h:884-912; the expressions of iriso_fft_match)
     std::vector<double> mats((size_t)J * 6);
     std::vector<int> ok((size_t)J, 1);
@@ -534,12 +510,12 @@ int fft_match_jobs_locked(scl_iris *h, const FftJob *jobs, int J, float *center_
         M[2] = b1; M[5] = b2;
         for (int k = 0; k < 6; ++k) mats[(size_t)j * 6 + k] = M[k];
     }
-    IRIS_HIP(h, hipMemcpyAsync(h->d_fmats, mats.data(), sizeof(double) * mats.size(), hipMemcpyHostToDevice, st));
+    SCL_HIP(h, hipMemcpyAsync(h->d_fmats, mats.data(), sizeof(double) * mats.size(), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(fm_warp_kernel, ge, blk, 0, st, h->d_fa1, h->d_fmats, R, C, h->d_frs);
     phase_correlate(h->d_frs, h->d_fa0);
-    IRIS_HIP(h, hipGetLastError());
-    IRIS_HIP(h, hipMemcpyAsync(res.data(), h->d_fres, sizeof(double2) * (size_t)J, hipMemcpyDeviceToHost, st));
-    IRIS_HIP(h, hipStreamSynchronize(st));
+    SCL_HIP(h, hipGetLastError());
+    SCL_HIP(h, hipMemcpyAsync(res.data(), h->d_fres, sizeof(double2) * (size_t)J, hipMemcpyDeviceToHost, st));
+    SCL_HIP(h, hipStreamSynchronize(st));
     for (int j = 0; j < J; ++j) {
         center_x[j] = ok[(size_t)j] ? (float)(res[(size_t)j].x + (double)(C / 2)) : 0.0f;
         if (ok_out) ok_out[j] = ok[(size_t)j];
@@ -592,20 +568,18 @@ int detect_core_locked(scl_iris *h, int cur, const std::vector<int> &list, int *
     const int n = (int)list.size(), k = h->cfg.num_candidates;
     if (n <= 0 || k <= 0) return SCL_OK;
     if ((size_t)n > h->list_cap) {
-        if (h->d_list) (void)hipFree(h->d_list);
-        if (h->d_d2) (void)hipFree(h->d_d2);
-        h->d_list = nullptr; h->d_d2 = nullptr; h->list_cap = 0;
+        h->list_cap = 0;
         const size_t cap = (size_t)n + (size_t)n / 2 + 256;
         int rc;
-        if ((rc = ialloc(h, &h->d_list, cap)) || (rc = ialloc(h, &h->d_d2, cap))) return rc;
+        if ((rc = dev_regrow(h, &h->d_list, cap)) || (rc = dev_regrow(h, &h->d_d2, cap))) return rc;
         h->list_cap = cap;
     }
-    IRIS_HIP(h, hipMemcpyAsync(h->d_list, list.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(h->d_list, list.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(iris_rowkey_d2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_rowkeys, h->cfg.rows, cur, h->d_list, n, h->d_d2);
-    IRIS_HIP(h, hipGetLastError());
+    SCL_HIP(h, hipGetLastError());
     std::vector<float> d2((size_t)n);
-    IRIS_HIP(h, hipMemcpyAsync(d2.data(), h->d_d2, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    IRIS_HIP(h, hipStreamSynchronize(h->stream));
+    SCL_HIP(h, hipMemcpyAsync(d2.data(), h->d_d2, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    SCL_HIP(h, hipStreamSynchronize(h->stream));
     // the k nearest: ascending distance, equal distances by ascending position; libnabo without ALLOW_SELF_MATCH skips
     // d2 <= eps; NaN / inf never enter (insertion like the engine's ring-key search)
     std::vector<int> pos; std::vector<float> pd;
@@ -671,16 +645,16 @@ int scl_iris_create(const scl_iris_config *cfg, scl_iris **out)
     scl_iris *h = new (std::nothrow) scl_iris();
     if (!h) return SCL_ERR_NOMEM;
     h->cfg = *cfg; h->device = cfg->device;
-    h->local2global.resize((size_t)cfg->robot_num);                             // D.h:501-509
+    h->reg.init(cfg->robot_num);                                                // D.h:501-509
     h->trows = 2 * cfg->nscale * cfg->rows; h->words = (h->trows + 31) / 32;
     auto bail = [&](int code) { scl_iris_destroy(h); return code; };
     if (hipSetDevice(h->device) != hipSuccess) return bail(SCL_ERR_HIP);
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(SCL_ERR_HIP);
     const size_t cells = (size_t)cfg->rows * cfg->cols;
     int rc;
-    if ((rc = ialloc(h, &h->d_cells, cells)) || (rc = ialloc(h, &h->d_zmax, cells)) || (rc = ialloc(h, &h->d_img1, cells)) ||
-        (rc = ialloc(h, &h->d_key1, (size_t)cfg->rows)) || (rc = ialloc(h, &h->d_h, (size_t)cfg->nscale * cfg->cols)) ||
-        (rc = ialloc(h, &h->d_unpack, (size_t)h->trows * cfg->cols))) return bail(rc);
+    if ((rc = dev_alloc(h, &h->d_cells, cells)) || (rc = dev_alloc(h, &h->d_zmax, cells)) || (rc = dev_alloc(h, &h->d_img1, cells)) ||
+        (rc = dev_alloc(h, &h->d_key1, (size_t)cfg->rows)) || (rc = dev_alloc(h, &h->d_h, (size_t)cfg->nscale * cfg->cols)) ||
+        (rc = dev_alloc(h, &h->d_unpack, (size_t)h->trows * cfg->cols))) return bail(rc);
     // the one-sided log-Gabor transfer functions, D.h:622-640 (float arithmetic like cv::log / pow / exp on Mat1f)
     const int N = cfg->cols, ndata = N - (N & 1);
     std::vector<float> g((size_t)cfg->nscale * N, 0.0f);
@@ -744,8 +718,8 @@ int scl_iris_create(const scl_iris_config *cfg, scl_iris **out)
             theta += d_theta;
         }
         h->log_base = log_base;
-        if ((rc = ialloc(h, &h->d_wcR, (size_t)R)) || (rc = ialloc(h, &h->d_wsR, (size_t)R)) || (rc = ialloc(h, &h->d_wcC, (size_t)C)) || (rc = ialloc(h, &h->d_wsC, (size_t)C)) ||
-            (rc = ialloc(h, &h->d_hp, cells)) || (rc = ialloc(h, &h->d_lpmap, cells))) return bail(rc);
+        if ((rc = dev_alloc(h, &h->d_wcR, (size_t)R)) || (rc = dev_alloc(h, &h->d_wsR, (size_t)R)) || (rc = dev_alloc(h, &h->d_wcC, (size_t)C)) || (rc = dev_alloc(h, &h->d_wsC, (size_t)C)) ||
+            (rc = dev_alloc(h, &h->d_hp, cells)) || (rc = dev_alloc(h, &h->d_lpmap, cells))) return bail(rc);
         if (hipMemcpy(h->d_wcR, wcR.data(), sizeof(double) * R, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(h->d_wsR, wsR.data(), sizeof(double) * R, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(h->d_wcC, wcC.data(), sizeof(double) * C, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(h->d_wsC, wsC.data(), sizeof(double) * C, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(h->d_hp, hp.data(), sizeof(float) * cells, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(h->d_lpmap, map.data(), sizeof(int2) * cells, hipMemcpyHostToDevice) != hipSuccess)
@@ -778,9 +752,9 @@ int scl_iris_make_image(scl_iris *h, const void *points, int n_points, int strid
     (void)hipSetDevice(h->device);
     int rc = make_image_locked(h, points, n_points, stride_bytes);
     if (rc) return rc;
-    IRIS_HIP(h, hipMemcpyAsync(image, h->d_img1, (size_t)h->cfg.rows * h->cfg.cols, hipMemcpyDeviceToHost, h->stream));
-    IRIS_HIP(h, hipMemcpyAsync(rowkey, h->d_key1, sizeof(float) * h->cfg.rows, hipMemcpyDeviceToHost, h->stream));
-    IRIS_HIP(h, hipStreamSynchronize(h->stream));
+    SCL_HIP(h, hipMemcpyAsync(image, h->d_img1, (size_t)h->cfg.rows * h->cfg.cols, hipMemcpyDeviceToHost, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(rowkey, h->d_key1, sizeof(float) * h->cfg.rows, hipMemcpyDeviceToHost, h->stream));
+    SCL_HIP(h, hipStreamSynchronize(h->stream));
     return SCL_OK;
 }
 
@@ -795,9 +769,9 @@ int scl_iris_make_and_save(scl_iris *h, const void *points, int n_points, int st
     if (out_values) {                                                         // D.h:1067-1081: image values row-major, then the row key
         const size_t cells = (size_t)h->cfg.rows * h->cfg.cols;
         std::vector<unsigned char> img(cells);
-        IRIS_HIP(h, hipMemcpyAsync(img.data(), h->d_img1, cells, hipMemcpyDeviceToHost, h->stream));
-        IRIS_HIP(h, hipMemcpyAsync(out_values + cells, h->d_key1, sizeof(float) * h->cfg.rows, hipMemcpyDeviceToHost, h->stream));
-        IRIS_HIP(h, hipStreamSynchronize(h->stream));
+        SCL_HIP(h, hipMemcpyAsync(img.data(), h->d_img1, cells, hipMemcpyDeviceToHost, h->stream));
+        SCL_HIP(h, hipMemcpyAsync(out_values + cells, h->d_key1, sizeof(float) * h->cfg.rows, hipMemcpyDeviceToHost, h->stream));
+        SCL_HIP(h, hipStreamSynchronize(h->stream));
         for (size_t i = 0; i < cells; ++i) out_values[i] = (float)img[i];
     }
     return SCL_OK;
@@ -808,8 +782,8 @@ int scl_iris_save_image(scl_iris *h, const uint8_t *image, const float *rowkey, 
     if (!h || !image || !rowkey) return SCL_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     (void)hipSetDevice(h->device);
-    IRIS_HIP(h, hipMemcpyAsync(h->d_img1, image, (size_t)h->cfg.rows * h->cfg.cols, hipMemcpyHostToDevice, h->stream));
-    IRIS_HIP(h, hipMemcpyAsync(h->d_key1, rowkey, sizeof(float) * h->cfg.rows, hipMemcpyHostToDevice, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(h->d_img1, image, (size_t)h->cfg.rows * h->cfg.cols, hipMemcpyHostToDevice, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(h->d_key1, rowkey, sizeof(float) * h->cfg.rows, hipMemcpyHostToDevice, h->stream));
     return append_locked(h, robot, index);
 }
 
@@ -828,30 +802,15 @@ int scl_iris_save_from_wire(scl_iris *h, const float *values, int8_t robot, int 
         for (int c = 0; c < cols; ++c)
             img[(size_t)r * cols + c] = to_u8(h->cfg.wire_decode ? values[(size_t)r * cols + c]             // D.h:1067-1074's layout
                                                                : values[(size_t)r * (cols + 1) + c + 1]);   // D.h:1035
-    IRIS_HIP(h, hipMemcpyAsync(h->d_img1, img.data(), img.size(), hipMemcpyHostToDevice, h->stream));
-    IRIS_HIP(h, hipMemcpyAsync(h->d_key1, values + (size_t)rows * cols, sizeof(float) * rows, hipMemcpyHostToDevice, h->stream));   // D.h:1039-1042
+    SCL_HIP(h, hipMemcpyAsync(h->d_img1, img.data(), img.size(), hipMemcpyHostToDevice, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(h->d_key1, values + (size_t)rows * cols, sizeof(float) * rows, hipMemcpyHostToDevice, h->stream));   // D.h:1039-1042
     return append_locked(h, robot, index);                                    // synchronises before `img` goes away
 }
 
-int scl_iris_get_size_of(const scl_iris *h, int id)
-{
-    if (!h) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (id == -1) return h->n;                                                // D.h:1262-1265
-    if (id < 0 || id >= h->cfg.robot_num) return ifail(h, SCL_ERR_OUT_OF_RANGE, "robot id outside [0, robot_num)");
-    return (int)h->local2global[(size_t)id].size();                           // D.h:1268
-}
-
-int scl_iris_local_to_global(const scl_iris *h, int robot, int local, int *key)
-{
-    if (!h || !key) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (robot < 0 || robot >= h->cfg.robot_num) return ifail(h, SCL_ERR_OUT_OF_RANGE, "robot id outside [0, robot_num)");
-    const std::vector<int> &l2g = h->local2global[(size_t)robot];
-    if (local < 0 || local >= (int)l2g.size()) return ifail(h, SCL_ERR_OUT_OF_RANGE, "local index out of range");
-    *key = l2g[(size_t)local];
-    return SCL_OK;
-}
+int scl_iris_get_size(const scl_iris *h) { return get_size(h); }
+int scl_iris_get_size_of(const scl_iris *h, int id) { return get_size_of(h, id); }
+int scl_iris_get_index(const scl_iris *h, int key, int8_t *robot, int *index) { return get_index(h, key, robot, index); }
+int scl_iris_local_to_global(const scl_iris *h, int robot, int local, int *key) { return local_to_global(h, robot, local, key); }
 
 int scl_iris_detect_intra(scl_iris *h, int cur, int *loop_id, float *bias, float *dist)
 {
@@ -860,8 +819,8 @@ int scl_iris_detect_intra(scl_iris *h, int cur, int *loop_id, float *bias, float
     (void)hipSetDevice(h->device);
     *loop_id = -1; *bias = 0.0f;
     if (dist) *dist = 10000000.0f;
-    const std::vector<int> &mine = h->local2global[(size_t)h->cfg.this_id];
-    if (cur < 0 || cur >= (int)mine.size()) return ifail(h, SCL_ERR_OUT_OF_RANGE, "detect_intra: no such keyframe of this robot");
+    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
+    if (cur < 0 || cur >= (int)mine.size()) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_intra: no such keyframe of this robot");
     if (cur < h->cfg.num_exclude_recent + h->cfg.num_candidates + 1) return SCL_OK;     // D.h:1092-1095
     const int history = cur - h->cfg.num_exclude_recent;                                 // D.h:1097-1101
     std::vector<int> list(mine.begin(), mine.begin() + history);
@@ -880,16 +839,8 @@ int scl_iris_detect_inter(scl_iris *h, int cur, int *loop_id, float *bias, float
     (void)hipSetDevice(h->device);
     *loop_id = -1; *bias = 0.0f;
     if (dist) *dist = 10000000.0f;
-    if (cur < 0 || cur >= h->n) return ifail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter: key out of range");
-    const int cur_robot = h->robots[(size_t)cur];                                        // D.h:1156
-    std::vector<int> list;                                                               // newLocal2Global, D.h:1167-1195
-    if (cur_robot == h->cfg.this_id) {
-        for (int i = 0; i < h->cfg.robot_num; ++i)
-            if (i != h->cfg.this_id) list.insert(list.end(), h->local2global[(size_t)i].begin(), h->local2global[(size_t)i].end());
-    } else {
-        const std::vector<int> &mine = h->local2global[(size_t)h->cfg.this_id];
-        list.assign(mine.begin(), mine.end());
-    }
+    if (cur < 0 || cur >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter: key out of range");
+    const std::vector<int> list = h->reg.inter_candidates(cur, h->cfg.this_id);        // newLocal2Global, D.h:1156-1195
     if ((int)list.size() < h->cfg.num_candidates + 1) return SCL_OK;                     // D.h:1198-1201
     int pos, b; float d;
     int rc = detect_core_locked(h, cur, list, &pos, &d, &b);
@@ -899,32 +850,16 @@ int scl_iris_detect_inter(scl_iris *h, int cur, int *loop_id, float *bias, float
     return SCL_OK;
 }
 
-int scl_iris_get_size(const scl_iris *h)
-{
-    if (!h) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    return h->n;
-}
-
-int scl_iris_get_index(const scl_iris *h, int key, int8_t *robot, int *index)
-{
-    if (!h || !robot || !index) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (key < 0 || key >= h->n) return ifail(h, SCL_ERR_OUT_OF_RANGE, "key out of range");
-    *robot = h->robots[(size_t)key]; *index = h->indexs[(size_t)key];
-    return SCL_OK;
-}
-
 int scl_iris_get_image(scl_iris *h, int key, uint8_t *image, float *rowkey)
 {
     if (!h || !image || !rowkey) return SCL_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     (void)hipSetDevice(h->device);
-    if (key < 0 || key >= h->n) return ifail(h, SCL_ERR_OUT_OF_RANGE, "key out of range");
+    if (key < 0 || key >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "key out of range");
     const size_t cells = (size_t)h->cfg.rows * h->cfg.cols;
-    IRIS_HIP(h, hipMemcpyAsync(image, h->d_images + cells * key, cells, hipMemcpyDeviceToHost, h->stream));
-    IRIS_HIP(h, hipMemcpyAsync(rowkey, h->d_rowkeys + (size_t)h->cfg.rows * key, sizeof(float) * h->cfg.rows, hipMemcpyDeviceToHost, h->stream));
-    IRIS_HIP(h, hipStreamSynchronize(h->stream));
+    SCL_HIP(h, hipMemcpyAsync(image, h->d_images + cells * key, cells, hipMemcpyDeviceToHost, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(rowkey, h->d_rowkeys + (size_t)h->cfg.rows * key, sizeof(float) * h->cfg.rows, hipMemcpyDeviceToHost, h->stream));
+    SCL_HIP(h, hipStreamSynchronize(h->stream));
     return SCL_OK;
 }
 
@@ -933,14 +868,14 @@ int scl_iris_get_feature(scl_iris *h, int key, uint8_t *T, uint8_t *M)
     if (!h || !T || !M) return SCL_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     (void)hipSetDevice(h->device);
-    if (key < 0 || key >= h->n) return ifail(h, SCL_ERR_OUT_OF_RANGE, "key out of range");
+    if (key < 0 || key >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "key out of range");
     const size_t fw = (size_t)h->cfg.cols * h->words, tot = (size_t)h->trows * h->cfg.cols;
     for (int which = 0; which < 2; ++which) {
         hipLaunchKernelGGL(iris_unpack_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream,
                            (which ? h->d_M : h->d_T) + fw * key, h->cfg.cols, h->words, h->trows, h->d_unpack);
-        IRIS_HIP(h, hipGetLastError());
-        IRIS_HIP(h, hipMemcpyAsync(which ? M : T, h->d_unpack, tot, hipMemcpyDeviceToHost, h->stream));
-        IRIS_HIP(h, hipStreamSynchronize(h->stream));
+        SCL_HIP(h, hipGetLastError());
+        SCL_HIP(h, hipMemcpyAsync(which ? M : T, h->d_unpack, tot, hipMemcpyDeviceToHost, h->stream));
+        SCL_HIP(h, hipStreamSynchronize(h->stream));
     }
     return SCL_OK;
 }
@@ -966,7 +901,7 @@ int scl_iris_fft_match(scl_iris *h, int key0, int roll0, int key1, float *center
     if (!h || !center_x) return SCL_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     (void)hipSetDevice(h->device);
-    if (key0 < 0 || key0 >= h->n || key1 < 0 || key1 >= h->n) return ifail(h, SCL_ERR_OUT_OF_RANGE, "fft_match: key out of range");
+    if (key0 < 0 || key0 >= h->reg.n || key1 < 0 || key1 >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "fft_match: key out of range");
     const FftJob jb{key0, roll0, key1};
     return fft_match_jobs_locked(h, &jb, 1, center_x, compatible);
 }
@@ -977,8 +912,8 @@ int scl_iris_compare(scl_iris *h, int key1, const int *cand, int n, float *dis, 
     if (n == 0) return SCL_OK;
     std::lock_guard<std::mutex> lk(h->mu);
     (void)hipSetDevice(h->device);
-    if (key1 < 0 || key1 >= h->n) return ifail(h, SCL_ERR_OUT_OF_RANGE, "compare: key1 out of range");
-    for (int i = 0; i < n; ++i) if (cand[i] < 0 || cand[i] >= h->n) return ifail(h, SCL_ERR_OUT_OF_RANGE, "compare: candidate out of range");
+    if (key1 < 0 || key1 >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "compare: key1 out of range");
+    for (int i = 0; i < n; ++i) if (cand[i] < 0 || cand[i] >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "compare: candidate out of range");
     return compare_jobs_locked(h, key1, cand, n, dis, bias);
 }
 

@@ -16,9 +16,8 @@
 //                          merged into the scan's global counts by integer atomics (order-free, exact);
 //   m2dp_signature_kernel  one workgroup per scan: G = C C^T of the counts (exact integers in fp64), G^(2^16) by repeated
 //                          squaring, four power steps through C, u and v = C^T u / |C^T u|, written as floats straight into
-//                          the database slot (A = C / n has the same singular vectors);
-//   m2dp_nn_kernel         detection: squared L2 in nanoflann's float order over the robot-filtered key list, the
-//                          (distance bits, position) keys reduced by a 64-bit atomic min (ties to the lowest position).
+//                          the database slot (A = C / n has the same singular vectors).
+// The database, the keyframe registry, make_and_save_many and the 1-NN detection (nn_l2_kernel<192>): plugin_host.hpp.
 #include "scl_m2dp.h"
 
 #include <hip/hip_runtime.h>
@@ -33,8 +32,9 @@
 #include <vector>
 
 #include "device_common.hpp"
+#include "plugin_host.hpp"
 
-using scl::jacobi3;
+using namespace scl;
 
 namespace {
 
@@ -367,31 +367,6 @@ __global__ __launch_bounds__(kThreads) void m2dp_signature_kernel(const M2Scan *
     if (t < SCL_M2DP_COLS) o[SCL_M2DP_ROWS + t] = (float)(nrm != 0.0 ? w[t] / nrm : 0.0);
 }
 
-__global__ __launch_bounds__(kThreads) void m2dp_nn_kernel(const float *db, const int *list, int n, int qkey, unsigned long long *best)
-{
-    __shared__ float q[SCL_M2DP_DIM];
-    for (int i = threadIdx.x; i < SCL_M2DP_DIM; i += kThreads) q[i] = db[(size_t)qkey * SCL_M2DP_DIM + i];
-    __syncthreads();
-    const int i = blockIdx.x * kThreads + threadIdx.x;
-    unsigned long long key = ~0ull;
-    if (i < n) {
-        const float4 *c = reinterpret_cast<const float4 *>(db + (size_t)list[i] * SCL_M2DP_DIM);
-        const float4 *a = reinterpret_cast<const float4 *>(q);
-        float s = 0.0f;
-        for (int k = 0; k < SCL_M2DP_DIM / 4; ++k) {                // nanoflann's L2_Adaptor: groups of four
-            const float4 x = a[k], y = c[k];
-            const float d0 = x.x - y.x, d1 = x.y - y.y, d2 = x.z - y.z, d3 = x.w - y.w;
-            s += ((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3;
-        }
-        key = ((unsigned long long)__float_as_uint(s) << 32) | (unsigned int)i;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(key, off);
-        key = o < key ? o : key;
-    }
-    if ((threadIdx.x & 63) == 0 && key != ~0ull) atomicMin(best, key);
-}
-
 }  // namespace
 
 struct scl_m2dp {
@@ -401,10 +376,8 @@ struct scl_m2dp {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     mutable std::mutex mu;
     mutable std::string last_error;
-    int n = 0, cap = 0;
-    float *d_db = nullptr;
-    std::vector<int8_t> robots; std::vector<int> indexs;
-    std::vector<std::vector<int>> local2global;
+    scl::KeyframeRegistry reg;
+    scl::FloatRows<SCL_M2DP_DIM> db;
     // the launch group's workspace
     unsigned char *d_pts = nullptr; size_t pts_cap = 0;
     M2Scan *d_scans = nullptr;
@@ -420,45 +393,11 @@ struct scl_m2dp {
 
 namespace {
 
-#define M2_HIP(h_, call)                                                               \
-    do {                                                                               \
-        hipError_t err__ = (call);                                                     \
-        if (err__ != hipSuccess) {                                                     \
-            (h_)->last_error = std::string(#call) + ": " + hipGetErrorString(err__);   \
-            return err__ == hipErrorOutOfMemory ? SCL_ERR_NOMEM : SCL_ERR_HIP;         \
-        }                                                                              \
-    } while (0)
-
-int mfail(const scl_m2dp *h, int code, const char *msg) { if (h) h->last_error = msg; return code; }
-
-template <class T> int malloc_dev(scl_m2dp *h, T **p, size_t count)
-{
-    void *q = nullptr;
-    M2_HIP(h, hipMalloc(&q, sizeof(T) * (count ? count : 1)));
-    *p = static_cast<T *>(q);
-    return SCL_OK;
-}
-
-int grow(scl_m2dp *h, int need)
-{
-    if (need <= h->cap) return SCL_OK;
-    int ncap = h->cap > 0 ? h->cap : 256;
-    while (ncap < need) ncap *= 2;
-    float *nd = nullptr;
-    int rc = malloc_dev(h, &nd, (size_t)ncap * SCL_M2DP_DIM);
-    if (rc) return rc;
-    if (h->n > 0) M2_HIP(h, hipMemcpyAsync(nd, h->d_db, sizeof(float) * SCL_M2DP_DIM * h->n, hipMemcpyDeviceToDevice, h->stream));
-    M2_HIP(h, hipStreamSynchronize(h->stream));
-    if (h->d_db) (void)hipFree(h->d_db);
-    h->d_db = nd; h->cap = ncap;
-    return SCL_OK;
-}
-
 int check_layout(scl_m2dp *h, const void *points, int n_points, int stride)
 {
-    if (stride < 12 || (stride & 3)) return mfail(h, SCL_ERR_INVALID_ARG, "bad point layout (stride_bytes >= 12, multiple of 4)");
-    if (n_points < 3) return mfail(h, SCL_ERR_INVALID_ARG, "M2DP needs at least 3 points (PCA)");
-    if (!points) return mfail(h, SCL_ERR_INVALID_ARG, "null point pointer");
+    if (stride < 12 || (stride & 3)) return fail(h, SCL_ERR_INVALID_ARG, "bad point layout (stride_bytes >= 12, multiple of 4)");
+    if (n_points < 3) return fail(h, SCL_ERR_INVALID_ARG, "M2DP needs at least 3 points (PCA)");
+    if (!points) return fail(h, SCL_ERR_INVALID_ARG, "null point pointer");
     return SCL_OK;
 }
 
@@ -474,36 +413,35 @@ int run_group_locked(scl_m2dp *h, const void *const *clouds, const int *n_points
         bytes += (unsigned long long)n_points[g] * (unsigned long long)stride;
     }
     if (bytes > h->pts_cap) {
-        if (h->d_pts) (void)hipFree(h->d_pts);
-        h->d_pts = nullptr; h->pts_cap = 0;
+        h->pts_cap = 0;
         const size_t c = bytes + bytes / 4 + 4096;
-        int rc = malloc_dev(h, &h->d_pts, c);
+        int rc = dev_regrow(h, &h->d_pts, c);
         if (rc) return rc;
         h->pts_cap = c;
     }
     for (int g = 0; g < G; ++g)
-        M2_HIP(h, hipMemcpyAsync(h->d_pts + scans[g].byte_off, clouds[g], (size_t)n_points[g] * stride, hipMemcpyHostToDevice, h->stream));
-    M2_HIP(h, hipMemcpyAsync(h->d_scans, scans, sizeof(M2Scan) * G, hipMemcpyHostToDevice, h->stream));
-    M2_HIP(h, hipMemsetAsync(h->d_bad, 0, sizeof(int) * G, h->stream));
-    M2_HIP(h, hipMemsetAsync(h->d_max_rho, 0, sizeof(unsigned int) * G, h->stream));
-    M2_HIP(h, hipMemsetAsync(h->d_counts, 0, sizeof(unsigned int) * kBins * G, h->stream));
-    M2_HIP(h, hipEventRecord(h->ev0, h->stream));
+        SCL_HIP(h, hipMemcpyAsync(h->d_pts + scans[g].byte_off, clouds[g], (size_t)n_points[g] * stride, hipMemcpyHostToDevice, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(h->d_scans, scans, sizeof(M2Scan) * G, hipMemcpyHostToDevice, h->stream));
+    SCL_HIP(h, hipMemsetAsync(h->d_bad, 0, sizeof(int) * G, h->stream));
+    SCL_HIP(h, hipMemsetAsync(h->d_max_rho, 0, sizeof(unsigned int) * G, h->stream));
+    SCL_HIP(h, hipMemsetAsync(h->d_counts, 0, sizeof(unsigned int) * kBins * G, h->stream));
+    SCL_HIP(h, hipEventRecord(h->ev0, h->stream));
     hipLaunchKernelGGL(m2dp_moments_kernel, dim3(kParts, G), dim3(kThreads), 0, h->stream, h->d_pts, h->d_scans, stride, h->d_part, h->d_bad);
     hipLaunchKernelGGL(m2dp_frame_kernel, dim3(G), dim3(64), 0, h->stream, h->d_scans, h->d_part, h->d_framef);
     hipLaunchKernelGGL(m2dp_project_kernel, dim3(kParts, G), dim3(kThreads), 0, h->stream, h->d_pts, h->d_scans, stride, h->d_framef,
                        h->d_cube, h->d_max_rho);
     hipLaunchKernelGGL(m2dp_hist_kernel, dim3(kParts, G), dim3(kThreads), 0, h->stream, h->d_pts, h->d_scans, stride, h->d_cube, h->d_max_rho,
                        h->d_planes, h->d_theta, h->d_framef, h->d_frame_out, h->d_counts, h->d_exact);
-    hipLaunchKernelGGL(m2dp_signature_kernel, dim3(G), dim3(kThreads), 0, h->stream, h->d_scans, h->d_counts, h->d_db);
-    M2_HIP(h, hipGetLastError());
-    M2_HIP(h, hipEventRecord(h->ev1, h->stream));
+    hipLaunchKernelGGL(m2dp_signature_kernel, dim3(G), dim3(kThreads), 0, h->stream, h->d_scans, h->d_counts, h->db.d_db);
+    SCL_HIP(h, hipGetLastError());
+    SCL_HIP(h, hipEventRecord(h->ev1, h->stream));
     int bad[kGroup];
-    M2_HIP(h, hipMemcpyAsync(bad, h->d_bad, sizeof(int) * G, hipMemcpyDeviceToHost, h->stream));
-    if (counts_out) M2_HIP(h, hipMemcpyAsync(counts_out, h->d_counts, sizeof(unsigned int) * kBins, hipMemcpyDeviceToHost, h->stream));
-    if (frame_out) M2_HIP(h, hipMemcpyAsync(frame_out, h->d_frame_out, sizeof(float) * kFrame, hipMemcpyDeviceToHost, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(bad, h->d_bad, sizeof(int) * G, hipMemcpyDeviceToHost, h->stream));
+    if (counts_out) SCL_HIP(h, hipMemcpyAsync(counts_out, h->d_counts, sizeof(unsigned int) * kBins, hipMemcpyDeviceToHost, h->stream));
+    if (frame_out) SCL_HIP(h, hipMemcpyAsync(frame_out, h->d_frame_out, sizeof(float) * kFrame, hipMemcpyDeviceToHost, h->stream));
     unsigned int mr = 0;
-    if (max_rho_out) M2_HIP(h, hipMemcpyAsync(&mr, h->d_max_rho, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
-    M2_HIP(h, hipStreamSynchronize(h->stream));
+    if (max_rho_out) SCL_HIP(h, hipMemcpyAsync(&mr, h->d_max_rho, sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+    SCL_HIP(h, hipStreamSynchronize(h->stream));
     if (max_rho_out) std::memcpy(max_rho_out, &mr, sizeof(float));
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) h->kernel_us += 1000.0 * (double)ms;
@@ -512,42 +450,6 @@ int run_group_locked(scl_m2dp *h, const void *const *clouds, const int *n_points
         if (bad[g]) *any_bad = 1;
         h->decisions += (unsigned long long)n_points[g] * SCL_M2DP_ROWS;
     }
-    return SCL_OK;
-}
-
-void commit_locked(scl_m2dp *h, int8_t robot, int index)
-{
-    h->local2global[(size_t)robot].push_back(h->n);
-    h->robots.push_back(robot); h->indexs.push_back(index); h->n++;
-}
-
-// the nearest of `list` (global keys, ascending) to key `q`: position in list (-1 if empty) and float distance
-int nearest_locked(scl_m2dp *h, int q, const std::vector<int> &list, int *pos, float *dist)
-{
-    *pos = -1; *dist = INFINITY;
-    const int n = (int)list.size();
-    if (n == 0) return SCL_OK;
-    if ((size_t)n > h->list_cap) {
-        if (h->d_list) (void)hipFree(h->d_list);
-        h->d_list = nullptr; h->list_cap = 0;
-        const size_t c = (size_t)n + (size_t)n / 2 + 256;
-        int rc = malloc_dev(h, &h->d_list, c);
-        if (rc) return rc;
-        h->list_cap = c;
-    }
-    M2_HIP(h, hipMemcpyAsync(h->d_list, list.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    M2_HIP(h, hipMemsetAsync(h->d_best, 0xff, sizeof(unsigned long long), h->stream));
-    hipLaunchKernelGGL(m2dp_nn_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, h->d_db, h->d_list, n, q, h->d_best);
-    M2_HIP(h, hipGetLastError());
-    unsigned long long best = ~0ull;
-    M2_HIP(h, hipMemcpyAsync(&best, h->d_best, sizeof(best), hipMemcpyDeviceToHost, h->stream));
-    M2_HIP(h, hipStreamSynchronize(h->stream));
-    if (best == ~0ull) return mfail(h, SCL_ERR_HIP, "nearest neighbour: no key reduced");
-    const unsigned int bits = (unsigned int)(best >> 32);
-    float d2;
-    std::memcpy(&d2, &bits, sizeof(d2));
-    *pos = (int)(best & 0xffffffffu);
-    *dist = sqrtf(d2);
     return SCL_OK;
 }
 
@@ -577,20 +479,20 @@ int scl_m2dp_create(const scl_m2dp_config *cfg, scl_m2dp **out)
     scl_m2dp *h = new (std::nothrow) scl_m2dp();
     if (!h) return SCL_ERR_NOMEM;
     h->cfg = *cfg; h->device = cfg->device;
-    h->local2global.resize((size_t)cfg->robot_num);
+    h->reg.init(cfg->robot_num);
     auto bail = [&](int code) { scl_m2dp_destroy(h); return code; };
     if (hipSetDevice(h->device) != hipSuccess) return bail(SCL_ERR_HIP);
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(SCL_ERR_HIP);
     if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return bail(SCL_ERR_HIP);
     int rc;
-    if ((rc = malloc_dev(h, &h->d_scans, kGroup)) || (rc = malloc_dev(h, &h->d_part, (size_t)kGroup * kParts * 9)) ||
-        (rc = malloc_dev(h, &h->d_cube, (size_t)kGroup * kParts * 2)) || (rc = malloc_dev(h, &h->d_planes, 6 * SCL_M2DP_ROWS)) ||
-        (rc = malloc_dev(h, &h->d_theta, 17)) || (rc = malloc_dev(h, &h->d_framef, (size_t)kGroup * kFrame)) ||
-        (rc = malloc_dev(h, &h->d_frame_out, (size_t)kGroup * kFrame)) || (rc = malloc_dev(h, &h->d_max_rho, kGroup)) ||
-        (rc = malloc_dev(h, &h->d_counts, (size_t)kGroup * kBins)) || (rc = malloc_dev(h, &h->d_bad, kGroup)) ||
-        (rc = malloc_dev(h, &h->d_exact, 1)) || (rc = malloc_dev(h, &h->d_best, 1)))
+    if ((rc = dev_alloc(h, &h->d_scans, kGroup)) || (rc = dev_alloc(h, &h->d_part, (size_t)kGroup * kParts * 9)) ||
+        (rc = dev_alloc(h, &h->d_cube, (size_t)kGroup * kParts * 2)) || (rc = dev_alloc(h, &h->d_planes, 6 * SCL_M2DP_ROWS)) ||
+        (rc = dev_alloc(h, &h->d_theta, 17)) || (rc = dev_alloc(h, &h->d_framef, (size_t)kGroup * kFrame)) ||
+        (rc = dev_alloc(h, &h->d_frame_out, (size_t)kGroup * kFrame)) || (rc = dev_alloc(h, &h->d_max_rho, kGroup)) ||
+        (rc = dev_alloc(h, &h->d_counts, (size_t)kGroup * kBins)) || (rc = dev_alloc(h, &h->d_bad, kGroup)) ||
+        (rc = dev_alloc(h, &h->d_exact, 1)) || (rc = dev_alloc(h, &h->d_best, 1)))
         return bail(rc);
-    if ((rc = grow(h, 1))) return bail(rc);
+    if ((rc = h->db.grow(h, 1))) return bail(rc);
     // the planes with the host's libm, as the reference computes them (D.h:1808-1818, 1885-1906; Eigen's cross product)
     std::vector<double> pl(6 * SCL_M2DP_ROWS);
     for (int i = 0; i < SCL_M2DP_NUM_P; ++i) {
@@ -620,7 +522,7 @@ int scl_m2dp_destroy(scl_m2dp *h)
     if (!h) return SCL_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void *p : {(void *)h->d_db, (void *)h->d_pts, (void *)h->d_scans, (void *)h->d_part, (void *)h->d_cube,
+    for (void *p : {(void *)h->db.d_db, (void *)h->d_pts, (void *)h->d_scans, (void *)h->d_part, (void *)h->d_cube,
                     (void *)h->d_planes, (void *)h->d_theta, (void *)h->d_framef, (void *)h->d_frame_out, (void *)h->d_max_rho,
                     (void *)h->d_counts, (void *)h->d_bad, (void *)h->d_exact, (void *)h->d_best, (void *)h->d_list})
         if (p) (void)hipFree(p);
@@ -638,12 +540,10 @@ int scl_m2dp_make(scl_m2dp *h, const void *points, int n_points, int stride_byte
     (void)hipSetDevice(h->device);
     int rc = check_layout(h, points, n_points, stride_bytes), bad = 0;
     if (rc) return rc;
-    if ((rc = grow(h, h->n + 1))) return rc;
-    if ((rc = run_group_locked(h, &points, &n_points, stride_bytes, 1, h->n, &bad))) return rc;     // row n: scratch, not committed
-    if (bad) return mfail(h, SCL_ERR_INVALID_ARG, "non-finite coordinate");
-    M2_HIP(h, hipMemcpyAsync(out_values, h->d_db + (size_t)h->n * SCL_M2DP_DIM, sizeof(float) * SCL_M2DP_DIM, hipMemcpyDeviceToHost, h->stream));
-    M2_HIP(h, hipStreamSynchronize(h->stream));
-    return SCL_OK;
+    if ((rc = h->db.grow(h, h->reg.n + 1))) return rc;
+    if ((rc = run_group_locked(h, &points, &n_points, stride_bytes, 1, h->reg.n, &bad))) return rc;     // row n: scratch, not committed
+    if (bad) return fail(h, SCL_ERR_INVALID_ARG, "non-finite coordinate");
+    return h->db.read(h, h->reg.n, 1, out_values);
 }
 
 int scl_m2dp_make_and_save_many(scl_m2dp *h, const void *const *clouds, const int *n_points, int stride_bytes,
@@ -652,30 +552,8 @@ int scl_m2dp_make_and_save_many(scl_m2dp *h, const void *const *clouds, const in
     if (!h || count < 0 || (count > 0 && (!clouds || !n_points || !robots || !indexs))) return SCL_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     (void)hipSetDevice(h->device);
-    for (int i = 0; i < count; ++i) {
-        int rc = check_layout(h, clouds[i], n_points[i], stride_bytes);
-        if (rc) return rc;
-        if (robots[i] < 0 || robots[i] >= h->cfg.robot_num) return mfail(h, SCL_ERR_INVALID_ARG, "robot id outside [0, robot_num)");
-    }
-    if (count == 0) return SCL_OK;
-    int rc = grow(h, h->n + count);
-    if (rc) return rc;
-    int any_bad = 0;
-    for (int s = 0; s < count; s += kGroup) {
-        const int G = std::min(kGroup, count - s);
-        int bad = 0;
-        if ((rc = run_group_locked(h, clouds + s, n_points + s, stride_bytes, G, h->n + s, &bad))) return rc;
-        any_bad |= bad;
-        if (any_bad) break;
-    }
-    if (any_bad) return mfail(h, SCL_ERR_INVALID_ARG, "non-finite coordinate: nothing of the call was stored");
-    if (out_values) {
-        M2_HIP(h, hipMemcpyAsync(out_values, h->d_db + (size_t)h->n * SCL_M2DP_DIM, sizeof(float) * SCL_M2DP_DIM * (size_t)count,
-                                 hipMemcpyDeviceToHost, h->stream));
-        M2_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    for (int i = 0; i < count; ++i) commit_locked(h, robots[i], indexs[i]);
-    return SCL_OK;
+    auto run = [&](const void *const *c, const int *np, int G, int slot0, int *bad) { return run_group_locked(h, c, np, stride_bytes, G, slot0, bad); };
+    return make_and_save_many_locked(h, clouds, n_points, stride_bytes, robots, indexs, count, out_values, kGroup, check_layout, run);
 }
 
 int scl_m2dp_make_and_save(scl_m2dp *h, const void *points, int n_points, int stride_bytes, int8_t robot, int index, float *out_values)
@@ -688,60 +566,24 @@ int scl_m2dp_save_from_wire(scl_m2dp *h, const float *values, int8_t robot, int 
     if (!h || !values) return SCL_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     (void)hipSetDevice(h->device);
-    if (robot < 0 || robot >= h->cfg.robot_num) return mfail(h, SCL_ERR_INVALID_ARG, "robot id outside [0, robot_num)");
-    int rc = grow(h, h->n + 1);
-    if (rc) return rc;
-    M2_HIP(h, hipMemcpyAsync(h->d_db + (size_t)h->n * SCL_M2DP_DIM, values, sizeof(float) * SCL_M2DP_DIM, hipMemcpyHostToDevice, h->stream));
-    M2_HIP(h, hipStreamSynchronize(h->stream));
-    commit_locked(h, robot, index);
+    int rc;
+    if ((rc = check_robot(h, robot, SCL_ERR_INVALID_ARG)) || (rc = h->db.grow(h, h->reg.n + 1)) || (rc = h->db.write(h, h->reg.n, values))) return rc;
+    h->reg.commit(robot, index);
     return SCL_OK;
 }
 
-int scl_m2dp_get_size(const scl_m2dp *h)
-{
-    if (!h) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    return h->n;
-}
-
-int scl_m2dp_get_size_of(const scl_m2dp *h, int id)
-{
-    if (!h) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (id == -1) return h->n;
-    if (id < 0 || id >= h->cfg.robot_num) return mfail(h, SCL_ERR_OUT_OF_RANGE, "robot id outside [0, robot_num)");
-    return (int)h->local2global[(size_t)id].size();
-}
-
-int scl_m2dp_get_index(const scl_m2dp *h, int key, int8_t *robot, int *index)
-{
-    if (!h || !robot || !index) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (key < 0 || key >= h->n) return mfail(h, SCL_ERR_OUT_OF_RANGE, "key out of range");
-    *robot = h->robots[(size_t)key]; *index = h->indexs[(size_t)key];
-    return SCL_OK;
-}
-
-int scl_m2dp_local_to_global(const scl_m2dp *h, int robot, int local, int *key)
-{
-    if (!h || !key) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (robot < 0 || robot >= h->cfg.robot_num) return mfail(h, SCL_ERR_OUT_OF_RANGE, "robot id outside [0, robot_num)");
-    const std::vector<int> &l2g = h->local2global[(size_t)robot];
-    if (local < 0 || local >= (int)l2g.size()) return mfail(h, SCL_ERR_OUT_OF_RANGE, "local index out of range");
-    *key = l2g[(size_t)local];
-    return SCL_OK;
-}
+int scl_m2dp_get_size(const scl_m2dp *h) { return get_size(h); }
+int scl_m2dp_get_size_of(const scl_m2dp *h, int id) { return get_size_of(h, id); }
+int scl_m2dp_get_index(const scl_m2dp *h, int key, int8_t *robot, int *index) { return get_index(h, key, robot, index); }
+int scl_m2dp_local_to_global(const scl_m2dp *h, int robot, int local, int *key) { return local_to_global(h, robot, local, key); }
 
 int scl_m2dp_get_signature(scl_m2dp *h, int key, float *values)
 {
     if (!h || !values) return SCL_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     (void)hipSetDevice(h->device);
-    if (key < 0 || key >= h->n) return mfail(h, SCL_ERR_OUT_OF_RANGE, "key out of range");
-    M2_HIP(h, hipMemcpyAsync(values, h->d_db + (size_t)key * SCL_M2DP_DIM, sizeof(float) * SCL_M2DP_DIM, hipMemcpyDeviceToHost, h->stream));
-    M2_HIP(h, hipStreamSynchronize(h->stream));
-    return SCL_OK;
+    if (key < 0 || key >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "key out of range");
+    return h->db.read(h, key, 1, values);
 }
 
 int scl_m2dp_detect_intra(scl_m2dp *h, int cur, int *loop_id, float *dist)
@@ -751,14 +593,14 @@ int scl_m2dp_detect_intra(scl_m2dp *h, int cur, int *loop_id, float *dist)
     (void)hipSetDevice(h->device);
     *loop_id = -1;
     if (dist) *dist = INFINITY;
-    const std::vector<int> &mine = h->local2global[(size_t)h->cfg.this_id];
-    if (cur < 0 || cur >= (int)mine.size()) return mfail(h, SCL_ERR_OUT_OF_RANGE, "detect_intra: no such keyframe of this robot");
+    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
+    if (cur < 0 || cur >= (int)mine.size()) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_intra: no such keyframe of this robot");
     const int history = cur - h->cfg.num_exclude_recent;
     if (history <= 0) return SCL_OK;
-    std::vector<int> list(mine.begin(), mine.begin() + history);          // ascending keys: position = local index
-    int pos; float d;
-    int rc = nearest_locked(h, mine[(size_t)cur], list, &pos, &d);
+    int pos; float d2;
+    int rc = nearest_locked(h, mine[(size_t)cur], mine.data(), history, &pos, &d2);     // ascending keys: position = local index
     if (rc) return rc;
+    const float d = sqrtf(d2);
     if (dist) *dist = d;
     if (pos >= 0 && (double)d < h->cfg.dist_thres) *loop_id = pos;
     return SCL_OK;
@@ -771,18 +613,13 @@ int scl_m2dp_detect_inter(scl_m2dp *h, int cur, int *loop_id, float *dist)
     (void)hipSetDevice(h->device);
     *loop_id = -1;
     if (dist) *dist = INFINITY;
-    if (cur < 0 || cur >= h->n) return mfail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter: key out of range");
-    std::vector<int> list;
-    if (h->robots[(size_t)cur] == h->cfg.this_id) {
-        for (int i = 0; i < h->cfg.robot_num; ++i)
-            if (i != h->cfg.this_id) list.insert(list.end(), h->local2global[(size_t)i].begin(), h->local2global[(size_t)i].end());
-    } else {
-        list = h->local2global[(size_t)h->cfg.this_id];
-    }
+    if (cur < 0 || cur >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter: key out of range");
+    std::vector<int> list = h->reg.inter_candidates(cur, h->cfg.this_id);
     std::sort(list.begin(), list.end());                                   // ties go to the lowest key
-    int pos; float d;
-    int rc = nearest_locked(h, cur, list, &pos, &d);
+    int pos; float d2;
+    int rc = nearest_locked(h, cur, list.data(), (int)list.size(), &pos, &d2);
     if (rc) return rc;
+    const float d = sqrtf(d2);
     if (dist) *dist = d;
     if (pos >= 0 && (double)d < h->cfg.dist_thres) *loop_id = list[(size_t)pos];
     return SCL_OK;
@@ -796,11 +633,11 @@ int scl_m2dp_signature_matrix(scl_m2dp *h, const void *points, int n_points, int
     (void)hipSetDevice(h->device);
     int rc = check_layout(h, points, n_points, stride_bytes), bad = 0;
     if (rc) return rc;
-    if ((rc = grow(h, h->n + 1))) return rc;
+    if ((rc = h->db.grow(h, h->reg.n + 1))) return rc;
     float fr[kFrame], mr = 0.0f;
     std::vector<uint32_t> c(kBins);
-    if ((rc = run_group_locked(h, &points, &n_points, stride_bytes, 1, h->n, &bad, c.data(), fr, &mr))) return rc;
-    if (bad) return mfail(h, SCL_ERR_INVALID_ARG, "non-finite coordinate");
+    if ((rc = run_group_locked(h, &points, &n_points, stride_bytes, 1, h->reg.n, &bad, c.data(), fr, &mr))) return rc;
+    if (bad) return fail(h, SCL_ERR_INVALID_ARG, "non-finite coordinate");
     if (counts) std::memcpy(counts, c.data(), sizeof(uint32_t) * kBins);
     if (mean) std::memcpy(mean, fr, sizeof(float) * 3);
     if (axes) std::memcpy(axes, fr + 3, sizeof(float) * 9);
@@ -814,7 +651,7 @@ int scl_m2dp_stats(const scl_m2dp *h, unsigned long long *decisions, unsigned lo
     std::lock_guard<std::mutex> lk(h->mu);
     (void)hipSetDevice(h->device);
     unsigned long long e = 0;
-    M2_HIP(h, hipMemcpy(&e, h->d_exact, sizeof(e), hipMemcpyDeviceToHost));
+    SCL_HIP(h, hipMemcpy(&e, h->d_exact, sizeof(e), hipMemcpyDeviceToHost));
     if (decisions) *decisions = h->decisions;
     if (exact) *exact = e;
     if (kernel_us) *kernel_us = h->kernel_us;

@@ -17,6 +17,7 @@
 // A query keyframe lives on one shard; the others get a device-to-device copy of its slot in one of their
 // staging slots (engine_internal.hpp), so the same kernels run everywhere.
 #include "engine_internal.hpp"
+#include "plugin_host.hpp"
 
 #include <dlfcn.h>
 
@@ -179,11 +180,7 @@ struct ShardedFront {
 
 namespace {
 
-int ffail(const scl_engine *e, int code, const std::string &msg)
-{
-    e->last_error = msg;
-    return code;
-}
+using scl::fail;
 
 int child_fail(const scl_engine *e, const scl_engine *child, int rc, const char *where)
 {
@@ -233,11 +230,11 @@ int place_query(scl_engine *e, int query, int stage_slot, int *qid)
 {
     ShardedFront *f = e->front;
     if (query < 0) {
-        if (query != SCL_QUERY_STAGED || !f->staged0) return ffail(e, SCL_ERR_INVALID_ARG, "no staged query (call scl_stage_query first)");
+        if (query != SCL_QUERY_STAGED || !f->staged0) return fail(e, SCL_ERR_INVALID_ARG, "no staged query (call scl_stage_query first)");
         for (int c = 0; c < f->G; ++c) qid[c] = SCL_QUERY_STAGED;
         return SCL_OK;
     }
-    if (query >= f->n) return ffail(e, SCL_ERR_OUT_OF_RANGE, "query keyframe out of range");
+    if (query >= f->n) return fail(e, SCL_ERR_OUT_OF_RANGE, "query keyframe out of range");
     const int owner = query % f->G, slot = query / f->G;
     const bool in_mirror = mirrored(f, query);
     for (int c = 0; c < f->G; ++c) {
@@ -256,7 +253,7 @@ struct TopRec { float d2; int g; double dist; int shift; };
 int sharded_topk(scl_engine *e, int query, int lo, int hi, int k, float eps, bool want_dist, std::vector<TopRec> *out)
 {
     ShardedFront *f = e->front;
-    if (k <= 0 || k > kTopkMaxK) return ffail(e, SCL_ERR_INVALID_ARG, "k out of range (1..64)");
+    if (k <= 0 || k > kTopkMaxK) return fail(e, SCL_ERR_INVALID_ARG, "k out of range (1..64)");
     if (lo < 0) lo = 0;
     if (hi > f->n) hi = f->n;
     int qid[kMaxShards];
@@ -475,7 +472,7 @@ int front_get_index(const scl_engine *e, int key, int8_t *robot, int *index)
 {
     std::lock_guard<std::mutex> lk(e->mu);
     const ShardedFront *f = e->front;
-    if (key < 0 || key >= f->n) return ffail(e, SCL_ERR_OUT_OF_RANGE, "key out of range");
+    if (key < 0 || key >= f->n) return fail(e, SCL_ERR_OUT_OF_RANGE, "key out of range");
     *robot = f->robots[(size_t)key]; *index = f->indexs[(size_t)key];
     return SCL_OK;
 }
@@ -490,7 +487,7 @@ int front_get_slot(const scl_engine *e, int key, scl_engine **child, int *slot)
 {
     std::lock_guard<std::mutex> lk(e->mu);
     const ShardedFront *f = e->front;
-    if (key < 0 || key >= f->n) return ffail(e, SCL_ERR_OUT_OF_RANGE, "key out of range");
+    if (key < 0 || key >= f->n) return fail(e, SCL_ERR_OUT_OF_RANGE, "key out of range");
     *child = f->sh[key % f->G]; *slot = key / f->G;
     return SCL_OK;
 }
@@ -503,7 +500,7 @@ int front_detect_intra(scl_engine *e, int cur, int *loop_id, float *shift, doubl
     ShardedFront *f = e->front;
     *loop_id = -1; *shift = 0.0f;                                         /* D.h:1615 */
     if (dist) *dist = kBigDist;
-    if (cur < 0 || cur >= f->n) return ffail(e, SCL_ERR_OUT_OF_RANGE, "cur out of range");
+    if (cur < 0 || cur >= f->n) return fail(e, SCL_ERR_OUT_OF_RANGE, "cur out of range");
     const int k = e->cfg.num_candidates;
     if (cur < e->cfg.num_exclude_recent + k + 1) return SCL_OK;           /* D.h:1620-1623 */
     const int history = cur - e->cfg.num_exclude_recent;                  /* D.h:1627, on global indices */
@@ -532,7 +529,7 @@ int front_detect_inter(scl_engine *e, int cur, int *loop_id, float *yaw_rad, dou
     ShardedFront *f = e->front;
     *loop_id = -1; *yaw_rad = 0.0f;                                       /* D.h:1678,1686 */
     if (dist) *dist = kBigDist;
-    if (cur < 0 || cur >= f->n) return ffail(e, SCL_ERR_OUT_OF_RANGE, "cur out of range");
+    if (cur < 0 || cur >= f->n) return fail(e, SCL_ERR_OUT_OF_RANGE, "cur out of range");
     if (f->n < e->cfg.num_exclude_recent + 1) return SCL_OK;              /* D.h:1684-1688 */
     if (f->tree_counter % e->cfg.tree_making_period == 0)                 /* D.h:1691-1702 */
         f->tree_n = f->n - e->cfg.num_exclude_recent;
@@ -591,7 +588,7 @@ int front_sc_distance_batch(scl_engine *e, int query, const int *cand, int n, do
 {
     std::lock_guard<std::mutex> lk(e->mu);
     ShardedFront *f = e->front;
-    if (!cand && n > f->n) return ffail(e, SCL_ERR_OUT_OF_RANGE, "n exceeds database size");
+    if (!cand && n > f->n) return fail(e, SCL_ERR_OUT_OF_RANGE, "n exceeds database size");
     int qid[kMaxShards];
     int rc = place_query(e, query, 1 + kFrontSlots, qid);
     if (rc) return rc;
@@ -601,7 +598,7 @@ int front_sc_distance_batch(scl_engine *e, int query, const int *cand, int n, do
         local.clear(); where.clear();
         for (int i = 0; i < n; ++i) {
             const int g = cand ? cand[i] : i;
-            if (g >= f->n) return ffail(e, SCL_ERR_OUT_OF_RANGE, "candidate keyframe out of range");
+            if (g >= f->n) return fail(e, SCL_ERR_OUT_OF_RANGE, "candidate keyframe out of range");
             if (g < 0) { if (c == 0) { dist[i] = kBigDist; shift[i] = 0; } continue; }
             if (g % f->G == c) { local.push_back(g / f->G); where.push_back(i); }
         }
@@ -618,7 +615,7 @@ int front_sc_distance_matrix(scl_engine *e, const int *queries, int nq, int lo, 
 {   // row by row through the per-shard candidate lists (a diagnostic / bulk-export call on a sharded database)
     int n_all;
     { std::lock_guard<std::mutex> lk(e->mu); n_all = e->front->n; }
-    if (lo < 0 || hi > n_all || hi < lo) return ffail(e, SCL_ERR_OUT_OF_RANGE, "keyframe range out of the database");
+    if (lo < 0 || hi > n_all || hi < lo) return fail(e, SCL_ERR_OUT_OF_RANGE, "keyframe range out of the database");
     const int n = hi - lo;
     if (n == 0) return SCL_OK;
     std::vector<int> cand((size_t)n);
@@ -641,7 +638,7 @@ int enqueue_group_exchange(scl_engine *e, const int *front_tickets, int m)
     ShardedFront *f = e->front;
     Rccl *r = f->coll;
     const int g = (int)(f->next_group % kFrontSlots);
-    if (f->group[g].active) return ffail(e, SCL_ERR_INVALID_ARG, "too many full-DB passes in flight: collect first");
+    if (f->group[g].active) return fail(e, SCL_ERR_INVALID_ARG, "too many full-DB passes in flight: collect first");
     const size_t goff = (size_t)g * 4 * kMaxQueryBatch;
     for (int c = 0; c < f->G; ++c) {
         PackArgs a{};
@@ -652,10 +649,10 @@ int enqueue_group_exchange(scl_engine *e, const int *front_tickets, int m)
             const double *rec = tk >= 0 ? eng_ticket_record(f->sh[c], tk, &lo, &empty) : nullptr;
             a.rec[i] = rec; a.slot_lo[i] = lo; a.empty[i] = (!rec || empty) ? 1 : 0;
         }
-        if (hipSetDevice(f->dev[c]) != hipSuccess) return ffail(e, SCL_ERR_HIP, "hipSetDevice");
+        if (hipSetDevice(f->dev[c]) != hipSuccess) return fail(e, SCL_ERR_HIP, "hipSetDevice");
         unsigned long long *k = f->d_key[c] + goff;
         hipLaunchKernelGGL(pack_winner_keys_kernel, dim3(1), dim3(64), 0, eng_stream(f->sh[c]), a, k, k + kMaxQueryBatch);
-        if (hipGetLastError() != hipSuccess) return ffail(e, SCL_ERR_HIP, "pack_winner_keys_kernel launch");
+        if (hipGetLastError() != hipSuccess) return fail(e, SCL_ERR_HIP, "pack_winner_keys_kernel launch");
     }
     auto all_reduce = [&](int in_word, int out_word) -> int {
         if (r->GroupStart() != ncclSuccess) return SCL_ERR_HIP;
@@ -667,20 +664,20 @@ int enqueue_group_exchange(scl_engine *e, const int *front_tickets, int m)
         }
         return r->GroupEnd() == ncclSuccess ? SCL_OK : SCL_ERR_HIP;
     };
-    if (all_reduce(0, 2)) return ffail(e, SCL_ERR_HIP, "ncclAllReduce(min) on the distance keys failed");
+    if (all_reduce(0, 2)) return fail(e, SCL_ERR_HIP, "ncclAllReduce(min) on the distance keys failed");
     for (int c = 0; c < f->G; ++c) {
         (void)hipSetDevice(f->dev[c]);
         unsigned long long *k = f->d_key[c] + goff;
         hipLaunchKernelGGL(select_winner_keys_kernel, dim3(1), dim3(64), 0, eng_stream(f->sh[c]), k, k + 2 * kMaxQueryBatch, k + kMaxQueryBatch, m);
-        if (hipGetLastError() != hipSuccess) return ffail(e, SCL_ERR_HIP, "select_winner_keys_kernel launch");
+        if (hipGetLastError() != hipSuccess) return fail(e, SCL_ERR_HIP, "select_winner_keys_kernel launch");
     }
-    if (all_reduce(1, 3)) return ffail(e, SCL_ERR_HIP, "ncclAllReduce(min) on the index keys failed");
+    if (all_reduce(1, 3)) return fail(e, SCL_ERR_HIP, "ncclAllReduce(min) on the index keys failed");
     (void)hipSetDevice(f->dev[0]);
     unsigned long long *k0 = f->d_key[0] + goff;
     unsigned long long *h = f->h_keys + (size_t)g * 2 * kMaxQueryBatch;
     if (hipMemcpyAsync(h, k0 + 2 * kMaxQueryBatch, sizeof(unsigned long long) * 2 * kMaxQueryBatch, hipMemcpyDeviceToHost, eng_stream(f->sh[0])) != hipSuccess ||
         hipEventRecord(f->ev_group[g], eng_stream(f->sh[0])) != hipSuccess)
-        return ffail(e, SCL_ERR_HIP, "result copy of the exchange");
+        return fail(e, SCL_ERR_HIP, "result copy of the exchange");
     ShardedFront::Group &gr = f->group[g];
     gr.active = true; gr.m = m; gr.delivered = false; gr.first_ticket = front_tickets[0];
     for (int i = 0; i < m; ++i) f->pass[front_tickets[i]].group = g * kMaxQueryBatch + i;
@@ -688,17 +685,17 @@ int enqueue_group_exchange(scl_engine *e, const int *front_tickets, int m)
     return SCL_OK;
 #else
     (void)front_tickets; (void)m;
-    return ffail(e, SCL_ERR_UNSUPPORTED, "built without the RCCL header");
+    return fail(e, SCL_ERR_UNSUPPORTED, "built without the RCCL header");
 #endif
 }
 
 int submit_many_locked(scl_engine *e, const int *queries, const int *lo, const int *hi, int nq, int *tickets)
 {
     ShardedFront *f = e->front;
-    if (nq < 1 || nq > kMaxQueryBatch) return ffail(e, SCL_ERR_INVALID_ARG, "1..4 queries per launch");
+    if (nq < 1 || nq > kMaxQueryBatch) return fail(e, SCL_ERR_INVALID_ARG, "1..4 queries per launch");
     for (int i = 0; i < nq; ++i)
         if (f->pass[(f->next_pass + (unsigned)i) % kFrontSlots].busy)
-            return ffail(e, SCL_ERR_INVALID_ARG, "too many full-DB passes in flight: collect first");
+            return fail(e, SCL_ERR_INVALID_ARG, "too many full-DB passes in flight: collect first");
     int qid[kMaxQueryBatch][kMaxShards];
     for (int i = 0; i < nq; ++i) {
         const int t = (int)((f->next_pass + (unsigned)i) % kFrontSlots);
@@ -749,7 +746,7 @@ int submit_many_locked(scl_engine *e, const int *queries, const int *lo, const i
 int collect_locked(scl_engine *e, int ticket, int *nn_idx, int *shift, double *dist)
 {
     ShardedFront *f = e->front;
-    if (ticket < 0 || ticket >= kFrontSlots || !f->pass[ticket].busy) return ffail(e, SCL_ERR_INVALID_ARG, "unknown ticket");
+    if (ticket < 0 || ticket >= kFrontSlots || !f->pass[ticket].busy) return fail(e, SCL_ERR_INVALID_ARG, "unknown ticket");
     ShardedFront::Pass &p = f->pass[ticket];
     *nn_idx = -1; *shift = 0; *dist = kBigDist;
     if (p.group >= 0) {
@@ -758,7 +755,7 @@ int collect_locked(scl_engine *e, int ticket, int *nn_idx, int *shift, double *d
         ShardedFront::Group &gr = f->group[g];
         if (!gr.delivered) {
             (void)hipSetDevice(f->dev[0]);
-            if (hipEventSynchronize(f->ev_group[g]) != hipSuccess) return ffail(e, SCL_ERR_HIP, "hipEventSynchronize(exchange)");
+            if (hipEventSynchronize(f->ev_group[g]) != hipSuccess) return fail(e, SCL_ERR_HIP, "hipEventSynchronize(exchange)");
             const unsigned long long *h = f->h_keys + (size_t)g * 2 * kMaxQueryBatch;
             for (int j = 0; j < gr.m; ++j) {
                 const unsigned long long m1 = h[j], m2 = h[kMaxQueryBatch + j];
@@ -809,7 +806,7 @@ int front_detect_full_stream(scl_engine *e, const int *queries, const int *lo, c
     std::lock_guard<std::mutex> lk(e->mu);
     ShardedFront *f = e->front;
     for (int t = 0; t < kFrontSlots; ++t)
-        if (f->pass[t].busy) return ffail(e, SCL_ERR_INVALID_ARG, "detect_full_stream: collect the passes in flight first");
+        if (f->pass[t].busy) return fail(e, SCL_ERR_INVALID_ARG, "detect_full_stream: collect the passes in flight first");
     // Block form (winners merged on the host whatever the exchange mode of the single passes: the results of a stream go to host arrays
     // anyway): the scans go to the shards in blocks of up to kStreamCall.  A scan whose keyframe the other shards hold in their mirror
     // rows (every recent keyframe: copied when it was appended) needs nothing; the others -- at most 64 per block -- are copied to the
@@ -848,7 +845,7 @@ int front_detect_full_stream(scl_engine *e, const int *queries, const int *lo, c
             for (int i = 0; i < m; ++i) {
                 const int g = queries[b0 + i];
                 if (g < 0 || g % G != o || mirrored(f, g)) continue;
-                if (g >= f->n) return ffail(e, SCL_ERR_OUT_OF_RANGE, "query keyframe out of range");
+                if (g >= f->n) return fail(e, SCL_ERR_OUT_OF_RANGE, "query keyframe out of range");
                 const int slot = g / G;
                 row_of[(size_t)i] = next_row++;
                 if (run_len > 0 && slot == run_slot + run_len) { ++run_len; continue; }
@@ -861,7 +858,7 @@ int front_detect_full_stream(scl_engine *e, const int *queries, const int *lo, c
         }
         for (int i = 0; i < m; ++i) {
             const int g = queries[b0 + i];
-            if (g < 0 && (g != SCL_QUERY_STAGED || !f->staged0)) return ffail(e, SCL_ERR_INVALID_ARG, "no staged query (call scl_stage_query first)");
+            if (g < 0 && (g != SCL_QUERY_STAGED || !f->staged0)) return fail(e, SCL_ERR_INVALID_ARG, "no staged query (call scl_stage_query first)");
             const int glo = lo[b0 + i] < 0 ? 0 : lo[b0 + i], ghi = hi[b0 + i] > f->n ? f->n : hi[b0 + i];
             for (int c = 0; c < G; ++c) {
                 const size_t k = (size_t)c * kStreamCall + (size_t)i;

@@ -1,10 +1,11 @@
 """ctypes binding of include/scl_iris.h: the LiDAR-Iris building blocks (image, templates, Hamming matching) on the GPU."""
 import ctypes
-from ctypes import POINTER, byref, c_char_p, c_double, c_float, c_int, c_int8, c_uint8, c_void_p
+from ctypes import POINTER, byref, c_double, c_float, c_int, c_int8, c_uint8, c_void_p
 
 import numpy as np
 
 from ._native import load_library
+from ._plugin import PluginEngine, PluginError, bind, plugin_signatures
 
 
 class IrisConfig(ctypes.Structure):
@@ -15,86 +16,45 @@ class IrisConfig(ctypes.Structure):
                 ("robot_num", c_int), ("this_id", c_int), ("knn_exclude_eps", c_float), ("wire_decode", c_int), ("shift_search", c_int)]
 
 
-_bound = None
+_P, _u8, _fp, _ip = c_void_p, POINTER(c_uint8), POINTER(c_float), POINTER(c_int)
+_SIG = plugin_signatures("scl_iris", IrisConfig)
+_SIG.update({
+    "scl_iris_make_image": (c_int, [_P, _P, c_int, c_int, _u8, _fp]),
+    "scl_iris_make_and_save": (c_int, [_P, _P, c_int, c_int, c_int8, c_int, _fp]),
+    "scl_iris_save_image": (c_int, [_P, _u8, _fp, c_int8, c_int]),
+    "scl_iris_detect_intra": (c_int, [_P, c_int, _ip, _fp, _fp]),
+    "scl_iris_detect_inter": (c_int, [_P, c_int, _ip, _fp, _fp]),
+    "scl_iris_get_image": (c_int, [_P, c_int, _u8, _fp]),
+    "scl_iris_get_feature": (c_int, [_P, c_int, _u8, _u8]),
+    "scl_iris_hamming": (c_int, [_P, c_int, c_int, c_int, _fp, _ip]),
+    "scl_iris_hamming_batch": (c_int, [_P, c_int, _ip, _ip, c_int, _fp, _ip]),
+    "scl_iris_hamming_all_shifts": (c_int, [_P, c_int, _ip, c_int, _fp, _ip]),
+    "scl_iris_fft_match": (c_int, [_P, c_int, c_int, c_int, _fp, _ip]),
+    "scl_iris_compare": (c_int, [_P, c_int, _ip, c_int, _fp, _ip]),
+})
 
 
 def _lib():
-    global _bound
-    if _bound is not None:
-        return _bound
-    L = load_library()
-    P, u8, fp, ip = c_void_p, POINTER(c_uint8), POINTER(c_float), POINTER(c_int)
-    sig = {
-        "scl_iris_default_config": (c_int, [POINTER(IrisConfig)]),
-        "scl_iris_create": (c_int, [POINTER(IrisConfig), POINTER(P)]),
-        "scl_iris_destroy": (c_int, [P]),
-        "scl_iris_last_error": (c_char_p, [P]),
-        "scl_iris_make_image": (c_int, [P, P, c_int, c_int, u8, fp]),
-        "scl_iris_make_and_save": (c_int, [P, P, c_int, c_int, c_int8, c_int, fp]),
-        "scl_iris_save_image": (c_int, [P, u8, fp, c_int8, c_int]),
-        "scl_iris_save_from_wire": (c_int, [P, fp, c_int8, c_int]),
-        "scl_iris_get_size": (c_int, [P]),
-        "scl_iris_get_size_of": (c_int, [P, c_int]),
-        "scl_iris_local_to_global": (c_int, [P, c_int, c_int, ip]),
-        "scl_iris_detect_intra": (c_int, [P, c_int, ip, fp, fp]),
-        "scl_iris_detect_inter": (c_int, [P, c_int, ip, fp, fp]),
-        "scl_iris_get_index": (c_int, [P, c_int, POINTER(c_int8), ip]),
-        "scl_iris_get_image": (c_int, [P, c_int, u8, fp]),
-        "scl_iris_get_feature": (c_int, [P, c_int, u8, u8]),
-        "scl_iris_hamming": (c_int, [P, c_int, c_int, c_int, fp, ip]),
-        "scl_iris_hamming_batch": (c_int, [P, c_int, ip, ip, c_int, fp, ip]),
-        "scl_iris_hamming_all_shifts": (c_int, [P, c_int, ip, c_int, fp, ip]),
-        "scl_iris_fft_match": (c_int, [P, c_int, c_int, c_int, fp, ip]),
-        "scl_iris_compare": (c_int, [P, c_int, ip, c_int, fp, ip]),
-    }
-    for name, (res, args) in sig.items():
-        fn = getattr(L, name); fn.restype = res; fn.argtypes = args
-    _bound = L
-    return L
+    return bind(load_library(), _SIG)
 
 
-class IrisEngine:
+class IrisError(PluginError):
+    pass
+
+
+class IrisEngine(PluginEngine):
     """Mirror of lidar_iris_descriptor (descriptor.h:462-1302): same constructor arguments and defaults, the six plugin
     calls (make_and_save, save_from_wire, detect_intra, detect_inter, get_index, get_size) and the building blocks."""
+    PREFIX, CONFIG, ERROR = "scl_iris", IrisConfig, IrisError
 
     def __init__(self, rows=80, cols=360, nscan=64, dist_thres=0.32, num_exclude_recent=30, match_num=2, num_candidates=10,
                  nscale=4, min_wavelength=18, mult=1.6, sigma_onf=0.75, robot_num=1, this_id=0, device=0,
                  knn_exclude_eps=None, wire_decode=0, shift_search=0):
-        self.L = _lib()
-        cfg = IrisConfig()
-        self._check_rc(self.L.scl_iris_default_config(byref(cfg)))
-        cfg.rows, cfg.cols, cfg.nscan, cfg.nscale, cfg.min_wavelength = rows, cols, nscan, nscale, min_wavelength
-        cfg.mult, cfg.sigma_onf, cfg.device = mult, sigma_onf, device
-        cfg.dist_thres, cfg.num_exclude_recent, cfg.match_num, cfg.num_candidates = dist_thres, num_exclude_recent, match_num, num_candidates
-        cfg.robot_num, cfg.this_id, cfg.wire_decode, cfg.shift_search = robot_num, this_id, wire_decode, shift_search
-        if knn_exclude_eps is not None:
-            cfg.knn_exclude_eps = knn_exclude_eps
-        self.cfg = cfg
-        self.h = c_void_p()
-        rc = self.L.scl_iris_create(byref(cfg), byref(self.h))
-        if rc != 0:
-            self.h = c_void_p()
-            raise RuntimeError(f"scl_iris_create: status {rc}")
+        super().__init__(_lib(), rows=rows, cols=cols, nscan=nscan, nscale=nscale, min_wavelength=min_wavelength, mult=mult,
+                         sigma_onf=sigma_onf, device=device, dist_thres=dist_thres, num_exclude_recent=num_exclude_recent,
+                         match_num=match_num, num_candidates=num_candidates, robot_num=robot_num, this_id=this_id,
+                         knn_exclude_eps=knn_exclude_eps, wire_decode=wire_decode, shift_search=shift_search)
         self.rows, self.cols, self.trows = rows, cols, 2 * nscale * rows
-
-    @staticmethod
-    def _check_rc(rc):
-        if rc != 0:
-            raise RuntimeError(f"scl_iris: status {rc}")
-
-    def _check(self, rc, where):
-        if rc != 0:
-            raise RuntimeError(f"{where}: status {rc} ({self.L.scl_iris_last_error(self.h).decode()})")
-
-    def close(self):
-        if self.h and self.h.value:
-            self.L.scl_iris_destroy(self.h); self.h = c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @staticmethod
     def _cloud(points):
@@ -125,17 +85,6 @@ class IrisEngine:
         assert v.size == self.rows * self.cols + self.rows
         self._check(self.L.scl_iris_save_from_wire(self.h, v.ctypes.data_as(POINTER(c_float)), robot, index), "scl_iris_save_from_wire")
 
-    def get_size(self, robot=-1):
-        n = self.L.scl_iris_get_size_of(self.h, robot)
-        if n < 0:
-            self._check(n, "scl_iris_get_size_of")
-        return n
-
-    def local_to_global(self, robot, local):
-        k = c_int()
-        self._check(self.L.scl_iris_local_to_global(self.h, robot, local, byref(k)), "scl_iris_local_to_global")
-        return k.value
-
     def _detect(self, fn, name, cur):
         loop, bias, dist = c_int(), c_float(), c_float()
         self._check(fn(self.h, cur, byref(loop), byref(bias), byref(dist)), name)
@@ -148,11 +97,6 @@ class IrisEngine:
     def detect_inter(self, cur):
         """(loop global key or -1, column shift, smallest distance seen) -- detectInterLoopClosureID, D.h:1153-1253"""
         return self._detect(self.L.scl_iris_detect_inter, "scl_iris_detect_inter", cur)
-
-    def get_index(self, key):
-        r, i = c_int8(), c_int()
-        self._check(self.L.scl_iris_get_index(self.h, key, byref(r), byref(i)), "scl_iris_get_index")
-        return r.value, i.value
 
     def get_image(self, key):
         img = np.empty((self.rows, self.cols), np.uint8); k = np.empty(self.rows, np.float32)
