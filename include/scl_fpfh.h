@@ -72,7 +72,10 @@ int  scl_fpfh_make_and_save(scl_fpfh *h, const void *points, int n_points, int s
  * SCL_ERR_INVALID_ARG and nothing of the call is stored. */
 int  scl_fpfh_make_and_save_many(scl_fpfh *h, const void *const *clouds, const int *n_points, int stride_bytes,
                                  const int8_t *robots, const int *indexs, int count, float *out_values);
-/* saveDescriptorAndKey(const float*), D.h:367-374: all 33 floats */
+/* saveDescriptorAndKey(const float*), D.h:367-374: all 33 floats.  The values are not checked.  In the detections a NaN 33-D
+ * squared distance (a row holding a NaN, or inf - inf) never beats another one, as in nanoflann's result set; when every
+ * candidate's is NaN (the query row itself holds a NaN, in any of the 33 floats) nothing is found: *loop_id = -1 and
+ * *dist = NaN, whatever report_dims is. */
 int  scl_fpfh_save_from_wire(scl_fpfh *h, const float *values, int8_t robot, int index);
 
 int  scl_fpfh_get_size(const scl_fpfh *h);

@@ -70,7 +70,10 @@ int  scl_m2dp_make_and_save(scl_m2dp *h, const void *points, int n_points, int s
  * floats) may be NULL.  If any cloud is invalid, SCL_ERR_INVALID_ARG and nothing of the call is stored. */
 int  scl_m2dp_make_and_save_many(scl_m2dp *h, const void *const *clouds, const int *n_points, int stride_bytes,
                                  const int8_t *robots, const int *indexs, int count, float *out_values);
-/* saveDescriptorAndKey(const float*), D.h:1989-1995, but all 192 floats as emitted above (the reference reads 128) */
+/* saveDescriptorAndKey(const float*), D.h:1989-1995, but all 192 floats as emitted above (the reference reads 128).  The
+ * values are not checked.  In the detections a NaN squared distance (a row holding a NaN, or inf - inf) never beats another
+ * one, as in nanoflann's result set; when every candidate's is NaN (the query row itself holds a NaN) nothing is found:
+ * *loop_id = -1 and *dist = NaN.  A row with an infinity is at distance +inf from every finite row. */
 int  scl_m2dp_save_from_wire(scl_m2dp *h, const float *values, int8_t robot, int index);
 
 /* getSize(idIn): id = -1 -> keyframes of all robots, else those of robot `id` */

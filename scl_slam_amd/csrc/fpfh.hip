@@ -710,6 +710,7 @@ int scl_fpfh_detect_intra(scl_fpfh *h, int cur, int *loop_id, float *dist)
     int pos; float d2, d;
     int rc = nearest_locked(h, mine[(size_t)cur], mine.data(), history, &pos, &d2);     // ascending keys: position = local index
     if (rc) return rc;
+    if (std::isnan(d2)) { if (dist) *dist = d2; return SCL_OK; }           // every 33-D distance NaN: nothing is nearest
     if ((rc = report_distance_locked(h, mine[(size_t)cur], mine[(size_t)pos], &d))) return rc;
     if (dist) *dist = d;
     if ((double)d < h->cfg.dist_thres) *loop_id = pos;
@@ -738,6 +739,7 @@ int scl_fpfh_detect_inter(scl_fpfh *h, int cur, int *loop_id, float *dist)
         if (pos < 0) return SCL_OK;
         pos = list[(size_t)pos];
     }
+    if (std::isnan(d2)) { if (dist) *dist = d2; return SCL_OK; }  // every 33-D distance NaN: nothing is nearest
     float d;
     if ((rc = report_distance_locked(h, cur, pos, &d))) return rc;
     if (dist) *dist = d;

@@ -199,13 +199,14 @@ int make_and_save_many_locked(H *h, const void *const *clouds, const int *n_poin
 
 // ---- 1-NN: squared L2 in nanoflann's float order (L2_Adaptor: groups of four, ((d0*d0 + d1*d1) + d2*d2) + d3*d3, then the
 // tail one element at a time) between row qkey and rows list[0 .. n) (list == nullptr: rows 0 .. n - 1); the (distance bits,
-// position) keys reduced by a 64-bit atomic min: ties go to the lowest position
+// position) keys reduced by a 64-bit atomic min: ties go to the lowest position.  A NaN sum (a non-finite row from the wire)
+// has a bit pattern above +inf's, so it loses to every other sum, as in nanoflann's result set (dist < worst)
 constexpr int kNnThreads = 256;
 
 template <int DIM>
 __global__ __launch_bounds__(kNnThreads) void nn_l2_kernel(const float *db, const int *list, int n, int qkey, unsigned long long *best)
 {
-    __shared__ float q[DIM];
+    __shared__ alignas(16) float q[DIM];                               // read through float4 * below when DIM % 4 == 0
     for (int i = threadIdx.x; i < DIM; i += kNnThreads) q[i] = db[(size_t)qkey * DIM + i];
     __syncthreads();
     const int i = blockIdx.x * kNnThreads + threadIdx.x;
