@@ -194,7 +194,7 @@ int ensure_capacity(scl_engine *e, int need)
     SCL_HIP(e, hipStreamSynchronize(e->stream));
     // passes still reading the old arrays: the exact pass of a stream's chunk on the side stream, the ring-key scan, the alternate lane
     // (an append may now run between the chunks of a stream call: stream_screened_locked)
-    for (hipStream_t s2 : {e->stream_alt, e->stream_surv, e->stream_align, e->stream2})
+    for (hipStream_t s2 : {e->stream_alt, e->stream_surv, e->stream2})
         if (s2) SCL_HIP(e, hipStreamSynchronize(s2));
     dev_free(e->d_desc); dev_free(e->d_vkey); dev_free(e->d_norm); dev_free(e->d_rkey); dev_free(e->d_rkey4);
     dev_free(e->d_hdesc); dev_free(e->d_kmask); dev_free(e->d_hkey); dev_free(e->d_halign);
@@ -283,7 +283,7 @@ int ingest_from_vals(scl_engine *e, int count, int first_slot)
     ProfScope ps(e, P_INGEST);
     SCL_HIP(e, launch_ingest(e->d_vals, count, first_slot, e->d_desc, e->d_vkey, e->d_norm, e->d_rkey,
                              e->d_rkey4, e->d_hdesc, e->d_kmask, e->d_hkey, e->hstride, e->cap, e->R, e->S, e->stream, e->d_halign));
-    e->db_version++;                                       // the alt lane orders itself behind this write
+    e->db_version++;                                       // the second lane (stream_alt) orders itself behind this write
     return SCL_OK;
 }
 
@@ -348,7 +348,7 @@ int group_ingest(scl_engine *e, int count, int first_slot, hipStream_t s)
     SCL_HIP(e, launch_ingest(nullptr, count, first_slot, e->d_desc, e->d_vkey, e->d_norm, e->d_rkey, e->d_rkey4, e->d_hdesc, e->d_kmask,
                              e->d_hkey, e->hstride, e->cap, e->R, e->S, s, e->d_halign, e->d_tiles, e->d_vals));
     e->tiles_clean = true;
-    e->db_version++;                                       // the alt lane orders itself behind this write
+    e->db_version++;                                       // the second lane (stream_alt) orders itself behind this write
     return SCL_OK;
 }
 
@@ -526,8 +526,8 @@ static void log_env_overrides_once()
     if (done.exchange(true)) return;
     static const char *const names[] = {"SCL_SCREEN", "SCL_SCREEN_FORM", "SCL_SCREEN_V2_MIN", "SCL_RCCL_LIB",
                                         // experiments: read by a diagnostics build only (kernels.hpp: scl_lab_int)
-                                        "SCL_SCREEN_VARIANT", "SCL_SCREEN_PROBE", "SCL_SCREEN_TAIL", "SCL_SCREEN_FUSE", "SCL_FUSE_PARTS", "SCL_ALIGN_FORM", "SCL_ALIGN_WGS",
-                                        "SCL_ALIGN2_WGS", "SCL_ALIGN_SIDE", "SCL_ALIGN_FILTER", "SCL_SC_KERNEL", "SCL_SC_WAVES", "SCL_STAMP", "SCL_ABLATE", "SCL_ALT_LANE",
+                                        "SCL_SCREEN_VARIANT", "SCL_SCREEN_PROBE", "SCL_SCREEN_TAIL", "SCL_ALIGN_WGS",
+                                        "SCL_ALIGN2_WGS", "SCL_ALIGN_FILTER", "SCL_SC_KERNEL", "SCL_SC_WAVES", "SCL_STAMP", "SCL_ABLATE",
                                         "SCL_ICP_REDUCE", "SCL_MATRIX_PLAIN", "SCL_MATRIX_KERNEL", "SCL_MATRIX_KR", "SCL_WIDE_EXACT", "SCL_STREAM_EXACT", "SCL_SMALL_EXACT_OFF",
                                         "SCL_SELF_ALIGN_OFF", "SCL_CAND_EXACT_OFF"};
     constexpr int kProduct = 4;
@@ -621,17 +621,12 @@ int scl_create(const scl_config *cfg, scl_engine **out)
             //  next chunk's screening did and the main stream ran dry for 60 us per chunk.  There it goes FIRST.)
             const bool wide_grid = e->S == 180 && e->RG == 20;
             if (hipStreamCreateWithPriority(&e->stream_surv, hipStreamNonBlocking, wide_grid ? hi_p : lo_p) != hipSuccess) return bail(SCL_ERR_HIP);
-            if (hipStreamCreateWithPriority(&e->stream_align, hipStreamNonBlocking, lo_p) != hipSuccess) return bail(SCL_ERR_HIP);
-            if (hipEventCreateWithFlags(&e->ev_afork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&e->ev_ajoin, hipEventDisableTiming) != hipSuccess) return bail(SCL_ERR_HIP);
+            // never used: HIP deals streams onto the hardware queues round robin in creation order, and this one keeps stream_alt and
+            // every stream created later on the queues they were measured on (engine_internal.hpp)
+            if (hipStreamCreateWithPriority(&e->stream_queue_place, hipStreamNonBlocking, lo_p) != hipSuccess) return bail(SCL_ERR_HIP);
         }
     }
-    if ((rc = dev_alloc(e, &e->a_blk_part, (size_t)1024 * kTailRec))) return bail(rc);
-    if ((rc = dev_alloc(e, &e->a_done_counter, (size_t)4))) return bail(rc);
-    if (hipMemset(e->a_done_counter, 0, 16) != hipSuccess) return bail(SCL_ERR_HIP);
-    if ((rc = dev_alloc(e, &e->a_topk_idx, (size_t)kTopkMaxK))) return bail(rc);
-    if ((rc = dev_alloc(e, &e->a_topk_d2, (size_t)kTopkMaxK))) return bail(rc);
     if (hipStreamCreateWithFlags(&e->stream_alt, hipStreamNonBlocking) != hipSuccess) return bail(SCL_ERR_HIP);
-    e->alt_lane = scl_lab_int("SCL_ALT_LANE", 0) == 1;
     if (hipEventCreateWithFlags(&e->ev_db, hipEventDisableTiming) != hipSuccess) return bail(SCL_ERR_HIP);
     if ((rc = dev_alloc(e, &e->d_align_fallbacks, (size_t)1))) return bail(rc);
     if (hipMemset(e->d_align_fallbacks, 0, sizeof(unsigned long long)) != hipSuccess) return bail(SCL_ERR_HIP);
@@ -694,16 +689,12 @@ int scl_destroy(scl_engine *e)
     if (e->h_stream_out) (void)hipHostFree(e->h_stream_out);
     for (auto ev : e->ev_chunk) if (ev) (void)hipEventDestroy(ev);
     if (e->stream_surv) { (void)hipStreamSynchronize(e->stream_surv); (void)hipStreamDestroy(e->stream_surv); }
-    if (e->stream_align) { (void)hipStreamSynchronize(e->stream_align); (void)hipStreamDestroy(e->stream_align); }
-    if (e->ev_afork) (void)hipEventDestroy(e->ev_afork);
-    if (e->ev_ajoin) (void)hipEventDestroy(e->ev_ajoin);
+    if (e->stream_queue_place) (void)hipStreamDestroy(e->stream_queue_place);
     for (auto ev : e->ev_k1) if (ev) (void)hipEventDestroy(ev);
     for (auto ev : e->ev_sub0) if (ev) (void)hipEventDestroy(ev);
     if (e->ev_align_gate) (void)hipEventDestroy(e->ev_align_gate);
     dev_free(e->d_topk_scratch); dev_free(e->d_topk_idx); dev_free(e->d_topk_d2); dev_free(e->d_out3);
     dev_free(e->d_blk_part); dev_free(e->d_done_counter);
-    dev_free(e->a_blk_part); dev_free(e->a_done_counter); dev_free(e->a_topk_idx); dev_free(e->a_topk_d2);
-    dev_free(e->a_dist); dev_free(e->a_shift); dev_free(e->a_ring_d2);
     if (e->ev_db) (void)hipEventDestroy(e->ev_db);
     if (e->stream_alt) { (void)hipStreamSynchronize(e->stream_alt); (void)hipStreamDestroy(e->stream_alt); }
     if (e->h_pinned) (void)hipHostFree(e->h_pinned);
@@ -1120,7 +1111,7 @@ struct ScreenGroup { const int *qslot, *lo, *n; int nq, set0; int part_half = 0;
 // next (optional, nq > 0): the launch that will follow; its alignment rides in this one (the next call then passes
 // kScreenProducts only).
 int launch_screen_group(scl_engine *e, const ScreenGroup &cur, int phases = kScreenAlign | kScreenProducts,
-                        const ScreenGroup *next = nullptr, hipStream_t stream = nullptr, const ScreenGroup *prev = nullptr)
+                        const ScreenGroup *next = nullptr, hipStream_t stream = nullptr)
 {
     if (!stream) stream = e->stream;
     auto fill = [&](ScreenBatch &sb, const ScreenGroup &g) {
@@ -1132,19 +1123,12 @@ int launch_screen_group(scl_engine *e, const ScreenGroup &cur, int phases = kScr
         sb.smask = (g.masks || sc_screen_is_wide(db_view(e), e->SR)) ? e->d_smask : nullptr;   // (the 64 x 120 stream's exact pass scores all 13 shifts of its few survivors: no masks)
         sb.part = e->d_part + (g.part_half ? e->part_cap / 2 : 0);
         sb.no_ring_metric = g.keys_later;
-        sb.side = stream == e->stream ? e->stream_align : nullptr; sb.ev_fork = e->ev_afork; sb.ev_join = e->ev_ajoin;
         sb.k = e->cfg.num_candidates; sb.exclude_eps = e->cfg.knn_exclude_eps; sb.topk_idx = e->d_topk_idx; sb.topk_d2 = e->d_topk_d2;
     };
-    ScreenBatch sb{}, nx{}, pv{};
+    ScreenBatch sb{}, nx{};
     fill(sb, cur);
     const bool has_next = next && next->nq > 0;
     if (has_next) fill(nx, *next);
-    const bool has_prev = prev && prev->nq > 0;
-    if (has_prev) fill(pv, *prev);
-    if (phases == kScreenFinish) {                          // a deferred finishing on its own (the end of a stream)
-        SCL_HIP(e, launch_sc_screen_batch(db_view(e), sb, e->SR, sc_align_filter_enabled(), e->num_cu, stream, kScreenFinish, nullptr, nullptr));
-        return SCL_OK;
-    }
     if (phases & kScreenAlign) for (int j = 0; j < cur.nq; ++j) e->align_pairs += (uint64_t)cur.n[j];
     if (has_next) for (int j = 0; j < next->nq; ++j) e->align_pairs += (uint64_t)next->n[j];
     if ((phases & kScreenAlign) && (phases & kScreenProducts) && has_next) {   // a sequence's first launch: its own alignment outside the
@@ -1152,7 +1136,7 @@ int launch_screen_group(scl_engine *e, const ScreenGroup &cur, int phases = kScr
         phases = kScreenProducts;
     }
     ProfScope ps(e, P_SC, stream);
-    SCL_HIP(e, launch_sc_screen_batch(db_view(e), sb, e->SR, sc_align_filter_enabled(), e->num_cu, stream, phases, has_next ? &nx : nullptr, has_prev ? &pv : nullptr));
+    SCL_HIP(e, launch_sc_screen_batch(db_view(e), sb, e->SR, sc_align_filter_enabled(), e->num_cu, stream, phases, has_next ? &nx : nullptr));
     if (ps.active()) { for (int j = 0; j < cur.nq; ++j) e->prof.sc_distance_pairs += (uint64_t)cur.n[j]; }
     return SCL_OK;
 }
@@ -1383,7 +1367,6 @@ int submit_full_locked(scl_engine *e, int query, int lo, int hi, int *ticket)
     e->slot_lo[sl] = lo;
     e->slot_empty[sl] = n <= 0;
     double *out3 = e->h_out3 + (size_t)sl * 8;
-    bool use_alt = false;
     if (n > 0) {
         if ((rc = ensure_pairs(e, (size_t)n))) return rc;
         // "full ring-key + shifted SC distance per incoming scan".  On the two-sectors-per-lane grids the
@@ -1394,35 +1377,13 @@ int submit_full_locked(scl_engine *e, int query, int lo, int hi, int *ticket)
         const bool fuse = k <= kTailTop && sc_distance_fuses_ring(db_view(e), e->SR);
         if (!fuse) SCL_HIP(e, hipEventRecord(e->ev_fork, e->stream));
         bool fused = false;
-        // every other fused pass on a database-resident query runs on the alt lane (see scl_engine::stream_alt)
-        use_alt = e->alt_lane && fuse && query >= 0 && (e->next_slot & 1u);
-        if (use_alt) {
-            if ((size_t)n > e->a_pair_cap) {
-                dev_free(e->a_dist); dev_free(e->a_shift); dev_free(e->a_ring_d2);
-                const size_t nn = (size_t)n + (size_t)n / 2 + 64;
-                e->a_pair_cap = 0;
-                if ((rc = dev_alloc(e, &e->a_ring_d2, nn))) return rc;
-                if ((rc = dev_alloc(e, &e->a_dist, nn))) return rc;
-                if ((rc = dev_alloc(e, &e->a_shift, nn))) return rc;
-                e->a_pair_cap = nn;
-            }
-            if (e->alt_seen_version != e->db_version) {               // descriptors written on `stream` since the last alt pass
-                SCL_HIP(e, hipEventRecord(e->ev_db, e->stream));
-                SCL_HIP(e, hipStreamWaitEvent(e->stream_alt, e->ev_db, 0));
-                e->alt_seen_version = e->db_version;
-            }
-        }
-        hipStream_t ks = use_alt ? e->stream_alt : e->stream;
-        FullTail tail{use_alt ? e->a_blk_part : e->d_blk_part, use_alt ? e->a_done_counter : e->d_done_counter, out3,
-                      use_alt ? e->a_topk_idx : e->d_topk_idx, use_alt ? e->a_topk_d2 : e->d_topk_d2, k, e->cfg.knn_exclude_eps};
+        FullTail tail{e->d_blk_part, e->d_done_counter, out3, e->d_topk_idx, e->d_topk_d2, k, e->cfg.knn_exclude_eps};
         {
-            ProfScope ps(e, P_SC, ks);
-            SCL_HIP(e, launch_sc_distance(db_view(e), q, nullptr, lo, n, e->SR, use_alt ? e->a_dist : e->d_dist,
-                                          use_alt ? e->a_shift : e->d_shift, e->num_cu, ks,
-                                          fuse ? (use_alt ? e->a_ring_d2 : e->d_ring_d2) : nullptr, &fused, fuse ? &tail : nullptr));
+            ProfScope ps(e, P_SC);
+            SCL_HIP(e, launch_sc_distance(db_view(e), q, nullptr, lo, n, e->SR, e->d_dist, e->d_shift, e->num_cu, e->stream,
+                                          fuse ? e->d_ring_d2 : nullptr, &fused, fuse ? &tail : nullptr));
             if (ps.active()) e->prof.sc_distance_pairs += (uint64_t)n;
         }
-        if (fuse && fused) e->last_pass_alt = use_alt;
         if (fuse && fused) {
             // arg-min and top-k were reduced inside the kernel (last workgroup)
         } else {
@@ -1438,7 +1399,7 @@ int submit_full_locked(scl_engine *e, int query, int lo, int hi, int *ticket)
         }
     }
     e->last_pass_empty = n <= 0;                            // nothing ran: the top-k buffers still hold an older pass
-    SCL_HIP(e, hipEventRecord(e->ev_done[sl], use_alt ? e->stream_alt : e->stream));
+    SCL_HIP(e, hipEventRecord(e->ev_done[sl], e->stream));
     e->slot_ev[sl] = sl; e->slot_seq[sl] = 0;
     e->slot_busy[sl] = true;
     e->next_slot++;
@@ -1523,7 +1484,6 @@ int submit_full_many_locked(scl_engine *e, const int *queries, const int *los, c
             SCL_HIP(e, launch_sc_distance_batch(db_view(e), qb, e->SR, e->d_dist, e->d_shift, e->d_ring_d2, tail, e->num_cu, e->stream));
             if (ps.active()) { for (int j = 0; j < qb.nq; ++j) e->prof.sc_distance_pairs += (uint64_t)qb.n[j]; }
         }
-        e->last_pass_alt = false;
     }
     e->last_pass_empty = qb.nq == 0 || empty_of[0];
     SCL_HIP(e, hipEventRecord(e->ev_done[first], e->stream));
@@ -1638,42 +1598,11 @@ int stream_screened_locked(scl_engine *e, std::unique_lock<std::mutex> &db, cons
     struct List { int qslot[CH], qlo[CH], qn[CH], pos[CH], m = 0; };     // the scans of a chunk that have something to score
     struct Chunk { int first = 0, count = 0; bool busy = false, aligned = false, small = false; std::vector<int> lo, empty; };
     Chunk ch[2];
-    // A launch's finishing (bound, flags, ring-key metric: what the exact pass reads) rides in the NEXT launch's extra waves
-    // (sc_screen.hip): `pend` is the launch whose finishing is still owed, `owed` the chunk whose exact pass waits for it.
-    struct Pending { int qslot[kMaxScreenBatch], lo[kMaxScreenBatch], n[kMaxScreenBatch], nq = 0, set0 = 0, half = 0; bool valid = false; } pend;
-    struct Owed { List L; int c = 0, region = 0; bool valid = false, small = false; } owed;
-    int part_half = 0;
     bool sub0_valid[2] = {false, false};                    // ev_sub0[c] was recorded by the exact pass that ev_chunk[c] ends
     // 64 x 120: the chunk's exact pass by one workgroup per scan (SCL_STREAM_EXACT=survivors keeps round 3's kernel, which also forms the
     // ring-key metric of its ranges -- keys_later)
     const bool small_exact = sc_small_exact_supported(db_view(e), e->SR) && (!wide || e->d_smask) && !scl_lab_is("SCL_STREAM_EXACT", "s");
     const bool keys_later = !wide && !small_exact;
-    auto pend_group = [&]() { ScreenGroup g{pend.qslot, pend.lo, pend.n, pend.nq, pend.set0}; g.part_half = pend.half; g.keys_later = keys_later; return g; };
-    // the exact pass of chunk `o.c` on the side stream, behind everything the main stream holds now
-    auto run_owed = [&]() -> int {
-        if (!owed.valid) return SCL_OK;
-        const int oc = owed.c;
-        double *out3[CH];
-        for (int j = 0; j < owed.L.m; ++j) out3[j] = e->h_stream_out + ((size_t)oc * NS + (size_t)owed.L.pos[j]) * 8;
-        SCL_HIP(e, hipEventRecord(e->ev_k1[oc], e->stream));
-        SCL_HIP(e, hipStreamWaitEvent(e->stream_surv, e->ev_k1[oc], 0));
-        int r2 = SCL_OK;
-        if (owed.L.m > 0) r2 = owed.small ? launch_small_exact_chunk(e, owed.L.qslot, owed.L.qlo, owed.L.qn, owed.L.m, oc * CH, out3, e->stream_surv, kSurvivorKernel, owed.region)
-                               : wide ? launch_survivor_pass_wide(e, owed.L.qslot, owed.L.qlo, owed.L.qn, owed.L.m, oc * CH, out3, e->stream_surv, e->ev_sub0[oc])
-                                    : launch_survivor_pass(e, owed.L.qslot, owed.L.qlo, owed.L.qn, owed.L.m, oc * CH, out3, e->stream_surv, kSurvivorKernel, owed.region, keys_later);
-        if (r2) return r2;
-        sub0_valid[oc] = wide && !owed.small && owed.L.m > 0;
-        SCL_HIP(e, hipEventRecord(e->ev_chunk[oc], e->stream_surv));
-        owed.valid = false;
-        return SCL_OK;
-    };
-    // the owed finishing as a launch of its own (nothing follows that could carry it)
-    auto flush_pending = [&]() -> int {
-        if (!pend.valid) return SCL_OK;
-        const ScreenGroup g = pend_group();
-        pend.valid = false;
-        return launch_screen_group(e, g, kScreenFinish);
-    };
     int nmax = 1;
     for (int i = 0; i < n_queries; ++i) {
         const int l = lo[i] < 0 ? 0 : lo[i], h = hi[i] > n0 ? n0 : hi[i];
@@ -1746,16 +1675,10 @@ int stream_screened_locked(scl_engine *e, std::unique_lock<std::mutex> &db, cons
             span_start = nullptr;
         };
         bool next_aligned = false;
-        if (cur.m == 0) {                                    // nothing to launch: what earlier chunks are owed cannot ride along
-            if ((rc = flush_pending())) return rc;
-            if ((rc = run_owed())) return rc;
-        }
         for (int g = 0; g < cur.m; g += spl) {
             const int w = cur.m - g < spl ? cur.m - g : spl;
             ScreenGroup grp{cur.qslot + g, cur.qlo + g, cur.qn + g, w, set0 + g};
-            grp.part_half = part_half; grp.keys_later = keys_later;
-            const bool defer = sc_screen_can_defer(db_view(e), e->SR, w);
-            if (!defer && (rc = flush_pending())) return rc;   // (a batch the first form scores has no extra waves to carry it)
+            grp.keys_later = keys_later;
             ScreenGroup nx{nullptr, nullptr, nullptr, 0, 0};
             if (g + w < cur.m) {
                 const int wn = cur.m - g - w < spl ? cur.m - g - w : spl;
@@ -1770,33 +1693,14 @@ int stream_screened_locked(scl_engine *e, std::unique_lock<std::mutex> &db, cons
                 if (ch[c ^ 1].busy) SCL_HIP(e, hipStreamWaitEvent(e->stream, (wide && sub0_valid[c ^ 1] && wn <= kWideExactBatch) ? e->ev_sub0[c ^ 1] : e->ev_chunk[c ^ 1], 0));
                 next_aligned = true;
             }
-            const int phases = ((g == 0 && !k.aligned) ? (kScreenAlign | kScreenProducts) : kScreenProducts) | (defer ? kScreenDeferFinish : 0);
-            const ScreenGroup pv = pend_group();
-            if ((rc = launch_screen_group(e, grp, phases, nx.nq > 0 ? &nx : nullptr, nullptr, pend.valid ? &pv : nullptr))) return rc;
+            const int phases = (g == 0 && !k.aligned) ? (kScreenAlign | kScreenProducts) : kScreenProducts;
+            if ((rc = launch_screen_group(e, grp, phases, nx.nq > 0 ? &nx : nullptr))) return rc;
             ++span_groups;
-            pend.valid = false;
-            if (defer) {
-                for (int j = 0; j < w; ++j) { pend.qslot[j] = grp.qslot[j]; pend.lo[j] = grp.lo[j]; pend.n[j] = grp.n[j]; }
-                pend.nq = w; pend.set0 = grp.set0; pend.half = part_half; pend.valid = true;
-                part_half ^= 1;
-            }
-            if (g == 0 && (rc = run_owed())) return rc;      // the chunk before this one is finished now: its exact pass may start
         }
         span_end();
         // The exact pass of a chunk runs beside the next chunk's products, on the side stream -- except the call's last one,
         // which nothing follows: it stays on the main stream (no hop between streams in front of it; its argument sets are
         // already on the device: wait for their copy only).
-        if (ncount > 0 && pend.valid) {
-            // this chunk's last finishing rides in the next chunk's first launch: the exact pass is owed until then
-            owed.L = cur; owed.c = c; owed.region = region; owed.valid = true; owed.small = k.small;
-            k.busy = true;
-            k.aligned = false;
-            ch[c ^ 1].aligned = next_aligned;
-            e->last_pass_empty = cur.m == 0;
-            e->last_pass_alt = false;
-            return SCL_OK;
-        }
-        if ((rc = flush_pending())) return rc;
         hipStream_t xs = ncount > 0 ? e->stream_surv : e->stream;
         if (ncount > 0) {
             SCL_HIP(e, hipEventRecord(e->ev_k1[c], e->stream));
@@ -1816,7 +1720,6 @@ int stream_screened_locked(scl_engine *e, std::unique_lock<std::mutex> &db, cons
         k.aligned = false;
         ch[c ^ 1].aligned = next_aligned;                    // the next chunk's first launch needs no alignment of its own
         e->last_pass_empty = cur.m == 0;
-        e->last_pass_alt = false;
         return SCL_OK;
     };
     auto collect = [&](int c, bool last) -> int {
@@ -1834,7 +1737,7 @@ int stream_screened_locked(scl_engine *e, std::unique_lock<std::mutex> &db, cons
             }
             return q;
         };
-        if (last || owed.valid || pend.valid) {
+        if (last) {
             SCL_HIP(e, wait_chunk());
         } else {
             // more to submit behind this wait: the database lock is free meanwhile (appends get in; nothing of this call's state
@@ -2552,12 +2455,6 @@ int scl_get_last_topk(scl_engine *e, int k, int *idx, float *d2)
     (void)hipSetDevice(e->device);
     if (e->last_pass_empty) {                              // the last pass had an empty range: no neighbours
         for (int i = 0; i < k; ++i) { idx[i] = -1; d2[i] = FLT_MAX; }
-        return SCL_OK;
-    }
-    if (e->last_pass_alt) {                                // the most recent pass ran on the alt lane
-        SCL_HIP(e, hipMemcpyAsync(idx, e->a_topk_idx, sizeof(int) * k, hipMemcpyDeviceToHost, e->stream_alt));
-        SCL_HIP(e, hipMemcpyAsync(d2, e->a_topk_d2, sizeof(float) * k, hipMemcpyDeviceToHost, e->stream_alt));
-        SCL_HIP(e, hipStreamSynchronize(e->stream_alt));
         return SCL_OK;
     }
     SCL_HIP(e, hipMemcpyAsync(idx, e->d_topk_idx, sizeof(int) * k, hipMemcpyDeviceToHost, e->stream));

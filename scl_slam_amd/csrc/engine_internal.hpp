@@ -116,27 +116,22 @@ struct scl_engine {
     hipStream_t stream_surv = nullptr;
     hipEvent_t ev_k1[2] = {nullptr, nullptr};
     hipEvent_t ev_align_gate = nullptr;
-    // second form of the screening products: the next batch's alignment runs as its own kernel on a low-priority stream beside them
-    hipStream_t stream_align = nullptr;
-    hipEvent_t ev_afork = nullptr, ev_ajoin = nullptr;
+    // Nothing is ever enqueued on this stream (it carried the side-stream alignment experiment).  It is still created,
+    // between stream_surv and stream_alt, because HIP maps streams onto the hardware queues round robin in creation order: without it
+    // stream_alt and every stream created later (copy streams, ICP lanes, a second engine's) move one queue on, and what that does to
+    // the rates that depend on queue sharing (standing notes: 340 against 460 M pairs/s on 80 x 180) has not been measured.
+    hipStream_t stream_queue_place = nullptr;
     bool screen = false;                                   // grid supported and not switched off (SCL_SCREEN=0)
     bool in_single_fallback = false;                       // submit_full_locked <-> submit_full_many_locked recursion guard
     unsigned long long *d_topk_scratch = nullptr; int *d_topk_idx = nullptr; float *d_topk_d2 = nullptr;
     double *d_out3 = nullptr;
     unsigned long long *d_blk_part = nullptr; unsigned int *d_done_counter = nullptr;   // fused full-DB epilogue
-    // Second lane for fused full-DB passes: consecutive passes alternate between `stream` and `stream_alt`
-    // (own epilogue scratch and per-pair outputs), so the next pass's workgroups move onto CUs as the previous
-    // pass's workgroups retire instead of waiting behind its completion packet.
+    // Second lane of the distance matrix on 80 x 180 (matrix_screened_locked): its launch groups alternate between `stream` and
+    // `stream_alt`, each lane with its own half of d_part, so that one group's screening runs beside the other's exact pass.
     hipStream_t stream_alt = nullptr;
-    hipEvent_t ev_db = nullptr;                            // database writes on `stream` the alt lane must see
+    hipEvent_t ev_db = nullptr;                            // database writes on `stream` the second lane must see
     uint64_t db_version = 0, alt_seen_version = 0;
-    unsigned long long *a_blk_part = nullptr; unsigned int *a_done_counter = nullptr;
-    int *a_topk_idx = nullptr; float *a_topk_d2 = nullptr;
-    double *a_dist = nullptr; int *a_shift = nullptr; float *a_ring_d2 = nullptr; size_t a_pair_cap = 0;
-    bool last_pass_alt = false;
     bool last_pass_empty = false;                          // the most recent full-DB pass had nothing to score
-    bool alt_lane = false;                                 // SCL_ALT_LANE=1: lowest latency per scan; kernels of the two lanes overlap,
-                                                           // so per-kernel durations no longer measure one pass (default off)
     void *h_pinned = nullptr; size_t pinned_cap = 0;       // small result read-back
     // scl_sc_distance_matrix: two halves of (rows of a launch) x (row length) device results and their pinned copies
     double *d_mat_dist = nullptr; int *d_mat_shift = nullptr; void *h_mat = nullptr; size_t mat_cap = 0;

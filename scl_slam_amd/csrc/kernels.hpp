@@ -203,7 +203,6 @@ struct ScreenBatch {
     unsigned int *smask;                        // optional, like approx: per pair the shifts whose screened distance is within 2 eps of the pair's smallest
                                                 // (bit t: shift (first + t) mod S; every shift for a pair the screening cannot bound): sc_masked.hip's input
     int k; float exclude_eps; int *topk_idx; float *topk_d2;
-    hipStream_t side; hipEvent_t ev_fork, ev_join;   // second form: stream and events for the next batch's alignment beside the products (nullptr: in line)
     float *part;                                // scratch of the second form of the 64 x 120 products: nq * pair_stride * 32 floats (nullptr: first form)
     bool no_ring_metric;                        // the caller's exact pass forms the ring-key metric itself (SurvivorPass::ring_from_keys) or has no use for
                                                 // it (the distance matrix): the second form's tail launch leaves ring_d2 alone (the first form and the
@@ -214,18 +213,13 @@ bool sc_screen_is_wide(const struct DbView &db, int SR);      // 80 x 180: scree
 float sc_screen_eps();
 int sc_screen_max_batch(const struct DbView &db, int SR);            // scans per screening launch on this grid (16; 12 on 80 x 180)
 size_t sc_screen_scratch_floats(const struct DbView &db, int SR);   // partial-sum scratch of the second form per keyframe of a buffer set
-// phases: 1 = the alignment kernel (first shifts + ring-key metric into sb.starts / sb.ring_d2), 2 = the screening products
-// (which read sb.starts), 3 = both, one after the other on `stream`.  next (optional): the batch that follows; its
-// alignment rides in the launch of this batch's products (further workgroups of the same grid: one is matrix-core bound,
-// the other HBM bound), so the next call needs phase 2 only.
-// kScreenDeferFinish (with kScreenProducts, second form only: sc_screen_can_defer): the batch's finishing -- bound d~, flags, ring-key
-// metric: what the exact pass reads -- is left to the extra waves of the NEXT launch, which gets this batch as `prev` (same buffer
-// sets, same sb.part, which therefore must not be the next launch's own), or to a last call with phases = kScreenFinish.
-// prev: the batch whose finishing rides in this launch.
-constexpr int kScreenAlign = 1, kScreenProducts = 2, kScreenDeferFinish = 4, kScreenFinish = 8;
+// phases: kScreenAlign = the alignment kernel (first shifts + ring-key metric into sb.starts / sb.ring_d2), kScreenProducts = the
+// screening products (which read sb.starts) and their finishing; both = one after the other on `stream`.  next (optional): the batch
+// that follows; its alignment rides in this batch's launches (first form: further workgroups of the products' grid; second form: the
+// tail launch beside the finishing), so the next call needs kScreenProducts only.
+constexpr int kScreenAlign = 1, kScreenProducts = 2;
 hipError_t launch_sc_screen_batch(const struct DbView &db, const ScreenBatch &sb, int SR, int align_filter, int num_cu, hipStream_t stream,
-                                  int phases = kScreenAlign | kScreenProducts, const ScreenBatch *next = nullptr, const ScreenBatch *prev = nullptr);
-bool sc_screen_can_defer(const struct DbView &db, int SR, int nq);
+                                  int phases = kScreenAlign | kScreenProducts, const ScreenBatch *next = nullptr);
 hipError_t launch_sc_select_batch(const ScreenBatch &sb, hipStream_t stream);
 // Exact pass over the survivors of nq screened queries (any number: the argument sets travel through device memory).
 // Query i: keyframe slot[i] against the range [base[i], base[i] + n[i]); its screening results live in buffer set

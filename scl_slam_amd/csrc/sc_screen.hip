@@ -1192,31 +1192,17 @@ hipError_t launch_sc_select_batch(const ScreenBatch &sb, hipStream_t stream)
 #ifndef S2WV_A
 #define S2WV_A 16
 #endif
-#ifndef S2WVF_A
-#define S2WVF_A 12
-#endif
-#ifndef S2XW_A
-#define S2XW_A 4
-#endif
-#ifndef S2XPRIO
-#define S2XPRIO 0
-#endif
-#ifndef S2XW_B
-#define S2XW_B 2
-#endif
 #ifdef S2_STAMP
 // experiments only (scripts/build_variant.sh): s_memtime of one wave of two workgroups at every iteration of its second keyframe
 __device__ unsigned long long g_s2_stamps[4 * 64];
 #endif
 template <int RG, int S, int W> struct S2Cfg;
-// WV: waves of the products per workgroup; XW: EXTRA waves of the same workgroup that align the NEXT batch and finish the PREVIOUS
-// one beside the products (sc_screen2_kernel): the products leave two thirds of the vector and matrix-core issue slots idle
-// NP ring parts, NPASS passes of 13 shift rows, STEPS k-steps per iteration (= per keyframe fragment), SPK sectors per k-step:
+// WV: waves per workgroup; NP ring parts, NPASS passes of 13 shift rows, STEPS k-steps per iteration (= per keyframe fragment), SPK sectors per k-step:
 // a k-step's 32 products are 32 rings of one sector (SPK = 1) or 16 rings of two consecutive sectors (SPK = 2)
-template <> struct S2Cfg<16, 120, 13> { static constexpr int NP = 2, NPASS = 1, STEPS = 4, SPK = 1, PS = 13, NQ = 16, RS = S2RS_A, WV = S2WV_A, WVF = S2WVF_A, XW = S2XW_A, NBUF = S2NBUF_A; };
+template <> struct S2Cfg<16, 120, 13> { static constexpr int NP = 2, NPASS = 1, STEPS = 4, SPK = 1, PS = 13, NQ = 16, RS = S2RS_A, WV = S2WV_A, NBUF = S2NBUF_A; };
 #ifdef S2_WIDE_THIRDS
 // (rounds 3-4: 96 padded rings as three thirds of 32, twelve scans per launch -- 141 KB of LDS; 37 % of the matrix-core work useful)
-template <> struct S2Cfg<20, 180, 19> { static constexpr int NP = 3, NPASS = 2, STEPS = 4, SPK = 1, PS = 13, NQ = 12, RS = 9, WV = S2WV_B, WVF = 8, XW = S2XW_B, NBUF = S2NBUF_B; };
+template <> struct S2Cfg<20, 180, 19> { static constexpr int NP = 3, NPASS = 2, STEPS = 4, SPK = 1, PS = 13, NQ = 12, RS = 9, WV = S2WV_B, NBUF = S2NBUF_B; };
 #else
 // 80 rings as five slices of 16, two sectors per k-step: no padded rings, sixteen scans per launch (16 x 183 sectors x 32 B = 94 KB)
 // PS = 12: the two passes share the scans' fragments -- pass 1 (shifts 5 .. 0 in rows 1 .. 6) multiplies the keyframe fragment of this
@@ -1225,7 +1211,7 @@ template <> struct S2Cfg<20, 180, 19> { static constexpr int NP = 3, NPASS = 2, 
 #ifndef S2_WIDE_PS
 #define S2_WIDE_PS 12
 #endif
-template <> struct S2Cfg<20, 180, 19> { static constexpr int NP = 5, NPASS = 2, STEPS = 2, SPK = 2, PS = S2_WIDE_PS, NQ = 16, RS = 9, WV = S2WV_B, WVF = 8, XW = S2XW_B, NBUF = S2NBUF_B; };
+template <> struct S2Cfg<20, 180, 19> { static constexpr int NP = 5, NPASS = 2, STEPS = 2, SPK = 2, PS = S2_WIDE_PS, NQ = 16, RS = 9, WV = S2WV_B, NBUF = S2NBUF_B; };
 #endif
 constexpr int kS2PassRows = 13;                    // shift rows per pass: row m of pass p = shift W - 1 - PS p - m (PS = 13; 12: row 0 of pass 1 repeats row 12 of pass 0)
 
@@ -1245,10 +1231,6 @@ template <int RG, int S, int W> constexpr int s2_pass_f4(int p) { int n = 0; for
 template <int RG, int S, int W> constexpr int s2_pass_off(int p) { int o = 0; for (int q = 0; q < p; ++q) o += s2_pass_f4<RG, S, W>(q); return o; }   // in float4
 template <int RG, int S, int W> constexpr int s2_part_f4() { return s2_pass_off<RG, S, W>(S2Cfg<RG, S, W>::NPASS); }
 template <int RG, int S, int W> constexpr int s2_part_floats() { return S2Cfg<RG, S, W>::NP * s2_part_f4<RG, S, W>() * 4; }   // partial sums per pair
-// LDS tile of one extra wave: the alignment image (both parts) / the exact evaluation's scratch, or the finishing's rotated masks
-template <int S> constexpr int s2_xlds() { return Align2Cfg<S>::LDS_WAVE > S * ((((S + 63) / 64) + 1) / 2) * 16 ? Align2Cfg<S>::LDS_WAVE : S * ((((S + 63) / 64) + 1) / 2) * 16; }
-template <int RG, int S, int W, bool FUSED> constexpr size_t s2_lds_total() { return s2_lds<RG, S, W>() + (FUSED ? (size_t)S2Cfg<RG, S, W>::XW * s2_xlds<S>() : 0); }
-template <int RG, int S, int W, bool FUSED> constexpr int s2_waves() { return FUSED ? S2Cfg<RG, S, W>::WVF + S2Cfg<RG, S, W>::XW : S2Cfg<RG, S, W>::WV; }
 
 struct Screen2Args {
     ScreenBatchArgs prod;
@@ -1258,21 +1240,10 @@ struct Screen2Args {
 };
 
 template <int RG, int S, int W>
-__device__ __forceinline__ void sc_screen2_finish_waves(const Screen2Args &fa, const int nb64, const int unit0, const int unit_stride, unsigned char *lds_wave);
-
-// What the extra waves of a launch do: the alignment of the batch BEHIND this one (a_n > 0) and the finishing of the batch in
-// FRONT of it (f_nb64 > 0), whose products the launch before wrote.
-struct Screen2Extra {
-    ScreenBatchArgs next; const unsigned char *halign; int a_lo, a_n;
-    Screen2Args prev; int f_nb64;
-};
-
-// FUSED: the workgroup has XW extra waves behind its WVF product waves; otherwise WV product waves and nothing else
-template <int RG, int S, int W, bool FUSED>
-__global__ __launch_bounds__((s2_waves<RG, S, W, FUSED>() * kWave), 1) void sc_screen2_kernel(Screen2Args fa, Screen2Extra xa)
+__global__ __launch_bounds__((S2Cfg<RG, S, W>::WV * kWave), 1) void sc_screen2_kernel(Screen2Args fa)
 {
-    constexpr int WVP = FUSED ? S2Cfg<RG, S, W>::WVF : S2Cfg<RG, S, W>::WV;
     using C = S2Cfg<RG, S, W>;
+    constexpr int WVP = C::WV;                         // waves of the workgroup: each takes every (workgroups x WVP)-th keyframe of its ring part
     constexpr int NP = C::NP, NPASS = C::NPASS, STEPS = C::STEPS, NQ = C::NQ, SPK = C::SPK, PS = C::PS;
     constexpr bool AOFF = PS != kS2PassRows;           // the passes share the scans' fragments (see S2Cfg)
     constexpr int NB = AOFF ? 1 : NPASS;               // fragment sets of the scans per iteration
@@ -1305,7 +1276,6 @@ __global__ __launch_bounds__((s2_waves<RG, S, W, FUSED>() * kWave), 1) void sc_s
 #define S2_STAMP_AT(slot) do { } while (0)
 #endif
     S2_STAMP_AT(32);
-    const bool xwave = FUSED && wave >= WVP;           // an extra wave (alignment / finishing): no part in the products
     const int c16 = lane & 15, j4 = lane >> 4;         // A: row m = c16; B / output: scan q = c16
     // columns past the launch's scans shadow the column 12 below: the SAME address as a lane of the same ds_read_b128 group
     // (lanes 12-15 beside 0-3, 28-31 beside 16-19, ...): a broadcast.  (Shadowing column c - 4 put them on the slots of
@@ -1366,7 +1336,7 @@ __global__ __launch_bounds__((s2_waves<RG, S, W, FUSED>() * kWave), 1) void sc_s
         // cost a division and a per-lane read of the launch's argument block for its scan's slot: the waves took 5-10 k cycles to ISSUE
         // their requests, and the workgroup met at the barrier 15 k cycles into the kernel -- a quarter of it.)
         constexpr int PPS = 4 / SPK;                           // 16-byte pieces of a scan per sector
-        constexpr int NWV = s2_waves<RG, S, W, FUSED>(), NPIECE = ROWS * PPS, BATCH = 8;
+        constexpr int NWV = WVP, NPIECE = ROWS * PPS, BATCH = 8;
         constexpr int NBATCH = (NPIECE + BATCH * kWave - 1) / (BATCH * kWave);
         static_assert(NBATCH <= 2 && NQ <= 2 * NWV, "staging turns");
         // (named variables, straight-line code: as arrays -- behind lambdas or inside macros' loops -- the pieces were placed in scratch)
@@ -1386,7 +1356,7 @@ __global__ __launch_bounds__((s2_waves<RG, S, W, FUSED>() * kWave), 1) void sc_s
                                S2_STAGE_RQ(BASE, 4, pc4, ds4) S2_STAGE_RQ(BASE, 5, pc5, ds5) S2_STAGE_RQ(BASE, 6, pc6, ds6) S2_STAGE_RQ(BASE, 7, pc7, ds7)
 #define S2_STAGE_STORE(BASE) S2_STAGE_ST(BASE, 0, pc0, ds0) S2_STAGE_ST(BASE, 1, pc1, ds1) S2_STAGE_ST(BASE, 2, pc2, ds2) S2_STAGE_ST(BASE, 3, pc3, ds3) \
                              S2_STAGE_ST(BASE, 4, pc4, ds4) S2_STAGE_ST(BASE, 5, pc5, ds5) S2_STAGE_ST(BASE, 6, pc6, ds6) S2_STAGE_ST(BASE, 7, pc7, ds7)
-        // (a second turn only where the workgroup has fewer waves than the launch has scans: the fused experiment's 12 + 4)
+        // (a second turn only where the workgroup has fewer waves than the launch has scans: an S2WV_* override)
         if (wave + NWV < NQ) {
             const int q2 = wave + NWV;
             const unsigned char *sbase = reinterpret_cast<const unsigned char *>(ab.hdesc + (size_t)ab.q[q2].slot * HS) + part * SCB;
@@ -1403,38 +1373,20 @@ __global__ __launch_bounds__((s2_waves<RG, S, W, FUSED>() * kWave), 1) void sc_s
         S2_STAMP_AT(61);
         __builtin_amdgcn_sched_barrier(0);
         constexpr int NPRE = NBUF - 1 < 4 ? NBUF - 1 : 4;     // (the pieces in flight + every fragment buffer would not fit the registers)
-        if (!xwave) {
 #pragma unroll
-            for (int j = 0; j < NPRE; ++j) F[j] = *reinterpret_cast<const u32x4 *>(base_cur + load_off(j));
-            b_cur = first_shift(0); b_nxt = first_shift(1);
-        }
+        for (int j = 0; j < NPRE; ++j) F[j] = *reinterpret_cast<const u32x4 *>(base_cur + load_off(j));
+        b_cur = first_shift(0); b_nxt = first_shift(1);
         __builtin_amdgcn_sched_barrier(0);
         S2_STAMP_AT(62);
         if (wave < NQ) { S2_STAGE_STORE((NBATCH - 1) * BATCH * kWave) }
         S2_STAMP_AT(63);
         __builtin_amdgcn_sched_barrier(0);
-        if (!xwave) {
 #pragma unroll
-            for (int j = NPRE; j < NBUF - 1; ++j) F[j] = *reinterpret_cast<const u32x4 *>(base_cur + load_off(j));
-        }
+        for (int j = NPRE; j < NBUF - 1; ++j) F[j] = *reinterpret_cast<const u32x4 *>(base_cur + load_off(j));
     }
     __syncthreads();
     S2_STAMP_AT(33);
-    if (xwave) {                                       // ---- the extra waves: next batch's alignment, previous batch's finishing ----
-        const int xw = wave - WVP;
-        const int xg = b * C::XW + xw, xtotal = (int)gridDim.x * C::XW;
-#if S2XPRIO > 0
-        __builtin_amdgcn_s_setprio(S2XPRIO);           // few instructions, long dependent chains: issue them ahead of the products' waves
-#endif
-        unsigned char *xs = smem2 + s2_lds<RG, S, W>() + (size_t)xw * s2_xlds<S>();
-        if (xa.a_n > 0) sc_align2_role<S, W>(xa.next, xa.halign, xa.a_lo, xa.a_n, xg, xtotal, xs);
-        if (xa.f_nb64 > 0) sc_screen2_finish_waves<RG, S, W>(xa.prev, xa.f_nb64, xg, xtotal, xs);
-        return;
-    }
     if (gw >= fa.u_n) return;
-#ifdef S2_NO_PRODUCTS
-    return;                                            // experiment: what the extra waves take on their own
-#endif
     // Scan sector that meets keyframe sector 0 in pass p: c0 = first shift + W - 1 - 13 p; iteration `it` reads sectors c0 + 4 it .. + 3
     // (mod S; the image repeats STEPS - 1 sectors so that the reads of an iteration never wrap).  The lane's address is ONE of two
     // fixed bases -- before and after its wrap -- plus a compile-time offset of 1 KB per iteration: a compare and a select per
@@ -1652,7 +1604,6 @@ template <int RG, int S, int W, bool D2 = true>
 __device__ __forceinline__ FinishLoads<RG, S, W, D2> sc_screen2_finish_request(const Screen2Args &fa, const ScreenArgs &a, const int qi, const int ci)
 {
     using L = FinishLoads<RG, S, W, D2>;
-    using C = S2Cfg<RG, S, W>;
     const ScreenBatchArgs &ab = fa.prod;
     L l;
     const unsigned int *kp = a.kmask + (size_t)(a.slot_base + ci) * 8;
@@ -1792,13 +1743,6 @@ __device__ __forceinline__ float sc_screen2_finish_compute(const ScreenArgs &a, 
     }
     return exact_only ? kInf : dmin;
 }
-template <int RG, int S, int W>
-__device__ __forceinline__ float sc_screen2_finish_pair(const Screen2Args &fa, const ScreenArgs &a, const int qi, const int ci, const uint4 *rotq, const bool q_bad, float &pair_eps)
-{
-    FinishLoads<RG, S, W> l = sc_screen2_finish_request<RG, S, W>(fa, a, qi, ci);
-    return sc_screen2_finish_compute<RG, S, W>(a, ci, rotq, q_bad, __uint_as_float(a.q_kmask[6]), l, pair_eps);
-}
-
 template <int RG, int S, int W, bool MASKS = true, bool D2 = true>
 __device__ __forceinline__ void sc_screen2_finish_body(const Screen2Args &fa, const int qi, const int chunk)
 {
@@ -1826,33 +1770,6 @@ __device__ __forceinline__ void sc_screen2_finish_body(const Screen2Args &fa, co
         if (m < kInf) atomicMin(a.t_min, float_to_ordered_u(m));
         const float pe = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
         if (pe > 0.0f) atomicMax(a.t_min + kTminEpsOffset, __float_as_uint(pe));      // (positive floats order like their bits)
-    }
-}
-
-// ... by single waves (the extra waves of the products' launch): wave unit0, unit0 + stride, ... of the (scan, block of 64 pairs)
-// units of the batch; rotq in the wave's own LDS tile
-template <int RG, int S, int W>
-__device__ __forceinline__ void sc_screen2_finish_waves(const Screen2Args &fa, const int nb64, const int unit0, const int unit_stride, unsigned char *lds_wave)
-{
-    const ScreenBatchArgs &ab = fa.prod;
-    const int lane = threadIdx.x & (kWave - 1);
-    uint4 *rotq = reinterpret_cast<uint4 *>(lds_wave);
-    const float kInf = __int_as_float(0x7f800000);
-    for (int u = unit0; u < ab.nq * nb64; u += unit_stride) {
-        const int qi = u / nb64, blk = u - qi * nb64;
-        const ScreenArgs a = screen_args_of(ab, qi);
-        if (blk * kWave >= a.n) continue;                                        // (wave uniform)
-        wave_fence();
-        build_rotq<S>(a.q_kmask, rotq, lane, kWave);
-        const bool q_bad = a.q_kmask[7] != 0;
-        wave_fence();
-        const int ci = blk * kWave + lane;
-        float contrib = kInf, peps = 0.0f;
-        if (ci < a.n) contrib = sc_screen2_finish_pair<RG, S, W>(fa, a, qi, ci, rotq, q_bad, peps);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) { contrib = fminf(contrib, __shfl_xor(contrib, off, kWave)); peps = fmaxf(peps, __shfl_xor(peps, off, kWave)); }
-        if (lane == 0 && contrib < kInf) atomicMin(a.t_min, float_to_ordered_u(contrib));
-        if (lane == 0 && peps > 0.0f) atomicMax(a.t_min + kTminEpsOffset, __float_as_uint(peps));
     }
 }
 
@@ -1936,14 +1853,16 @@ static int fill_screen_args(const DbView &db, const ScreenBatch &sb, int align_f
 // one grid: RG ring groups, S sectors, W shifts; OCC0 / OCC1 = waves per SIMD of the default kernel / of variant 1
 template <int RG, int S, int W, int OCC0, int OCC1>
 static hipError_t launch_screen_grid(const DbView &db, const ScreenBatch &sb, int align_filter, int num_cu, hipStream_t stream, int phases,
-                                     const ScreenBatch *next, const ScreenBatch *prev)
+                                     const ScreenBatch *next)
 {
     constexpr int RGH = hdesc_rgh(RG);
     ScreenBatchArgs ab{};
     const int nmax = fill_screen_args(db, sb, align_filter, &ab);
     if (nmax < 0) return hipErrorInvalidValue;
     const int ngroups = (nmax + kGroup - 1) / kGroup;
-    if (db.hstride != hdesc_stride(RG, S) || !sb.starts) return hipErrorInvalidValue;
+    // (the alignment's second form reads the keyframes' alignment images: both screened grids have them, allocated with the database)
+    static_assert(halign_bytes(S) > 0, "alignment image");
+    if (db.hstride != hdesc_stride(RG, S) || !sb.starts || !db.halign) return hipErrorInvalidValue;
     static std::atomic<bool> attr_set_dev[64];                 // per grid (template instance) and device
     int dev_ = 0; (void)hipGetDevice(&dev_);
     std::atomic<bool> &attr_set = attr_set_dev[dev_ & 63];
@@ -1997,9 +1916,6 @@ static hipError_t launch_screen_grid(const DbView &db, const ScreenBatch &sb, in
     const bool use_v2 = second_form_for(sb);
     const bool next_v2 = next && second_form_for(*next);
     ab.skip_d2 = use_v2 ? 1 : 0;
-    // SCL_ALIGN_FORM=1 keeps the alignment's first form (one scan against 16 keyframes per tile, inline fp32 / fp64 fallbacks)
-    static const int align_form_env = scl_lab_int("SCL_ALIGN_FORM", 2);
-    const bool align2 = align_form_env != 1 && db.halign != nullptr && halign_bytes(S) > 0;
     constexpr size_t lds_a2 = (size_t)kScreenWaves * Align2Cfg<S>::LDS_WAVE;
     auto union_of = [](const ScreenBatch &b, int *lo_out, int *n_out) {
         int lo = b.base[0], hi = b.base[0] + b.n[0];
@@ -2014,23 +1930,12 @@ static hipError_t launch_screen_grid(const DbView &db, const ScreenBatch &sb, in
         b = b > cap ? cap : b;
         return b < 1 ? 1 : b;
     };
-    // SCL_SCREEN_FUSE=1 (experiment; measured slower): the next batch's alignment and the previous batch's
-    // finishing in extra waves inside the products' launch instead of a launch of their own behind it (sc_screen2_tail2_kernel)
-    static const int fuse_env = scl_lab_int("SCL_SCREEN_FUSE", 0);
-    const bool fuse = fuse_env != 0 && align2;
-    if (phases & kScreenFinish) {                                // this batch's finishing alone (the end of a sequence of deferred ones)
-        if (!use_v2) return hipErrorInvalidValue;
-        Screen2Args f2{};
-        f2.prod = ab; f2.part = sb.part;
-        hipLaunchKernelGGL((sc_screen2_finish_kernel<RG, S, W>), dim3((nmax + 255) / 256, sb.nq), dim3(256), 0, stream, f2);
-        return hipGetLastError();
-    }
     // a batch of the first form that has to align for itself and has a products launch coming (a blocking call of one to three
     // scans): the products' workgroups align their own groups (sc_screen_kernel), no launch in front of them
     const bool self_align = (phases & kScreenAlign) && (phases & kScreenProducts) && !use_v2 && probe == 0 && !scl_lab_int("SCL_SELF_ALIGN_OFF", 0);
     // the alignment of this batch, on its own (the first launch of a sequence, or a caller that has only one)
     if ((phases & kScreenAlign) && probe != 3 && !self_align) {
-        if (align2 && use_v2) {                                  // (the products' first form takes the ring-key metric from the alignment's first form)
+        if (use_v2) {                                            // (the products' first form takes the ring-key metric from the alignment's first form)
             int ulo, un;
             union_of(sb, &ulo, &un);
             hipLaunchKernelGGL((sc_align2_kernel<RG, S, W>), dim3(align2_blocks(un)), dim3(kScreenWaves * kWave), lds_a2, stream, ab, db.halign, ulo, un);
@@ -2042,141 +1947,74 @@ static hipError_t launch_screen_grid(const DbView &db, const ScreenBatch &sb, in
         if (e != hipSuccess) return e;
     }
     if (probe == 4 || !(phases & kScreenProducts)) return hipSuccess;
-    {
-        if (use_v2) {
-            static std::atomic<bool> attr2_dev[64];
-            std::atomic<bool> &attr2 = attr2_dev[dev_ & 63];
-            if (!attr2.load(std::memory_order_acquire)) {
-                hipError_t e = hipFuncSetAttribute((const void *)sc_screen2_kernel<RG, S, W, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(s2_lds_total<RG, S, W, false>()));
-#ifdef SCL_DIAGNOSTICS
-                if (e == hipSuccess) e = hipFuncSetAttribute((const void *)sc_screen2_kernel<RG, S, W, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(s2_lds_total<RG, S, W, true>()));
-#endif
-                if (e != hipSuccess) return e;
-                attr2.store(true, std::memory_order_release);
-            }
-            Screen2Args f2{};
-            f2.prod = ab; f2.part = sb.part;
-            int lo = sb.base[0], hi = sb.base[0] + sb.n[0];
-            for (int i = 1; i < sb.nq; ++i) { lo = sb.base[i] < lo ? sb.base[i] : lo; hi = sb.base[i] + sb.n[i] > hi ? sb.base[i] + sb.n[i] : hi; }
-            f2.u_lo = lo; f2.u_n = hi - lo;
-            constexpr int WGU = 8 * S2Cfg<RG, S, W>::NP;                           // the ring parts of an index on one XCD
-            int nwg = (num_cu / WGU) * WGU;
-            if (nwg < WGU) nwg = WGU;
-            f2.nwg = nwg;
-            // SCL_ALIGN_SIDE: where the next batch's alignment runs -- 0 (default): in line on the main stream, behind the finishing
-            // kernel; 1: on the low-priority side stream from the end of this batch's products, beside the finishing kernel; 2: from
-            // the start of the products.  Measured: 1.45 G pairs/s in line, 0.51 G (1) and 0.67 G (2) -- the two event hops between
-            // the queues per launch cost more than the alignment itself.
-            static const int side_env = scl_lab_int("SCL_ALIGN_SIDE", 0);
-            const int side = (next && sb.side) ? side_env : 0;
-            hipError_t e = hipSuccess;
-            auto launch_align = [&](hipStream_t as) -> hipError_t {
-                if (next->nq < 1 || next->nq > kMaxScreenBatch) return hipErrorInvalidValue;
-                ScreenBatchArgs nb{};
-                const int nmax2 = fill_screen_args(db, *next, align_filter, &nb);
-                if (nmax2 < 0) return hipErrorInvalidValue;
-                nb.skip_d2 = next_v2 ? 1 : 0;
-                if (align2 && next_v2) {
-                    int ulo, un;
-                    union_of(*next, &ulo, &un);
-                    hipLaunchKernelGGL((sc_align2_kernel<RG, S, W>), dim3(align2_blocks(un)), dim3(kScreenWaves * kWave), lds_a2, as, nb, db.halign, ulo, un);
-                    return hipGetLastError();
-                }
-                const int ng2 = (nmax2 + kGroup - 1) / kGroup;
-                // persistent workgroups: three per CU (167 registers: three waves per SIMD; 128 spill and double the time) over the
-                // whole batch, every wave walks several groups with the next group's keys in flight
-                int per_q = 3 * num_cu / next->nq;                                   // (two to nine per CU measure the same 29 us)
-                per_q = per_q < 1 ? 1 : per_q;
-                nb.nb = (ng2 + kScreenWaves - 1) / kScreenWaves;
-                nb.nb = nb.nb > per_q ? per_q : nb.nb;
-                hipLaunchKernelGGL((sc_align_kernel<RG, S, W>), dim3(nb.nb * next->nq), dim3(kScreenWaves * kWave), lds0, as, nb);
-                return hipGetLastError();
-            };
-            auto fork = [&]() -> hipError_t {
-                hipError_t r = hipEventRecord(sb.ev_fork, stream);
-                if (r == hipSuccess) r = hipStreamWaitEvent(sb.side, sb.ev_fork, 0);
-                if (r == hipSuccess) r = launch_align(sb.side);
-                if (r == hipSuccess) r = hipEventRecord(sb.ev_join, sb.side);
-                return r;
-            };
-            if (side == 2 && (e = fork()) != hipSuccess) return e;
-
-            // what the extra waves of this launch carry: the next batch's alignment, the previous batch's finishing
-            Screen2Extra xa{};
-            static const int parts_env = scl_lab_int("SCL_FUSE_PARTS", 3);   // experiments: 1 = only the alignment rides, 2 = only the finishing
-            const bool ride_align = fuse && side == 0 && next && next_v2 && (parts_env & 1);
-            if (ride_align) {
-                if (next->nq < 1 || next->nq > kMaxScreenBatch) return hipErrorInvalidValue;
-                if (fill_screen_args(db, *next, align_filter, &xa.next) < 0) return hipErrorInvalidValue;
-                xa.next.skip_d2 = 1;
-                xa.halign = db.halign;
-                union_of(*next, &xa.a_lo, &xa.a_n);
-            }
-            if (prev) {
-                if (!fuse || prev->nq < 1 || prev->nq > kMaxScreenBatch || !prev->part) return hipErrorInvalidValue;
-                const int pmax = fill_screen_args(db, *prev, align_filter, &xa.prev.prod);
-                if (pmax < 0) return hipErrorInvalidValue;
-                xa.prev.prod.skip_d2 = 1;
-                xa.prev.part = prev->part;
-                xa.f_nb64 = (pmax + kWave - 1) / kWave;
-            }
-#ifdef SCL_DIAGNOSTICS
-            if (fuse) hipLaunchKernelGGL((sc_screen2_kernel<RG, S, W, true>), dim3(nwg), dim3(s2_waves<RG, S, W, true>() * kWave), (s2_lds_total<RG, S, W, true>()), stream, f2, xa);
-            else
-#endif
-            hipLaunchKernelGGL((sc_screen2_kernel<RG, S, W, false>), dim3(nwg), dim3(s2_waves<RG, S, W, false>() * kWave), (s2_lds_total<RG, S, W, false>()), stream, f2, xa);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-            if (fuse && side == 0) {
-                // this batch's finishing: deferred to the next launch's extra waves (the caller passes this batch as its `prev`, or
-                // ends the sequence with phases = kScreenFinish), or now
-                if (!(phases & kScreenDeferFinish)) {
-                    hipLaunchKernelGGL((sc_screen2_finish_kernel<RG, S, W>), dim3((nmax + 255) / 256, sb.nq), dim3(256), 0, stream, f2);
-                    if ((e = hipGetLastError()) != hipSuccess) return e;
-                }
-                if (next && !ride_align && (e = launch_align(stream)) != hipSuccess) return e;   // (a batch the first form will score)
-                return hipSuccess;
-            }
-            if (prev || (phases & kScreenDeferFinish)) return hipErrorInvalidValue;
-            if (side == 1 && (e = fork()) != hipSuccess) return e;
-            static const int tail_env = scl_lab_int("SCL_SCREEN_TAIL", 1);   // 0: finish and alignment as two launches
-            if (next && side == 0 && tail_env) {
-                if (next->nq < 1 || next->nq > kMaxScreenBatch) return hipErrorInvalidValue;
-                ScreenBatchArgs nb{};
-                const int nmax2 = fill_screen_args(db, *next, align_filter, &nb);
-                if (nmax2 < 0) return hipErrorInvalidValue;
-                nb.skip_d2 = next_v2 ? 1 : 0;
-                const int chunks = (nmax + 255) / 256;
-                if (align2 && next_v2) {
-                    // (the first form of the products forms the ring-key metric in its own alignment role: only batches that the
-                    //  second form will score take the alignment's second form here)
-                    int ulo, un;
-                    union_of(*next, &ulo, &un);
-                    const int ablocks = align2_blocks(un);
-                    const dim3 tgrid(ablocks + chunks * sb.nq), tblock(kScreenWaves * kWave);
-                    const bool d2 = !sb.no_ring_metric;                       // (left to the exact pass of the range: kernels.hpp)
-                    if (sb.smask && d2) hipLaunchKernelGGL((sc_screen2_tail2_kernel<RG, S, W, true, true>), tgrid, tblock, lds_a2, stream, f2, nb, db.halign, ulo, un, ablocks, chunks);
-                    else if (sb.smask) hipLaunchKernelGGL((sc_screen2_tail2_kernel<RG, S, W, true, false>), tgrid, tblock, lds_a2, stream, f2, nb, db.halign, ulo, un, ablocks, chunks);
-                    else if (d2) hipLaunchKernelGGL((sc_screen2_tail2_kernel<RG, S, W, false, true>), tgrid, tblock, lds_a2, stream, f2, nb, db.halign, ulo, un, ablocks, chunks);
-                    else hipLaunchKernelGGL((sc_screen2_tail2_kernel<RG, S, W, false, false>), tgrid, tblock, lds_a2, stream, f2, nb, db.halign, ulo, un, ablocks, chunks);
-                } else {
-                    const int ng2 = (nmax2 + kGroup - 1) / kGroup;
-                    int per_q = 3 * num_cu / next->nq;
-                    per_q = per_q < 1 ? 1 : per_q;
-                    nb.nb = (ng2 + kScreenWaves - 1) / kScreenWaves;
-                    nb.nb = nb.nb > per_q ? per_q : nb.nb;
-                    const int ablocks = nb.nb * next->nq;
-                    hipLaunchKernelGGL((sc_screen2_tail_kernel<RG, S, W>), dim3(ablocks + chunks * sb.nq), dim3(kScreenWaves * kWave), lds0, stream, f2, nb, ablocks, chunks);
-                }
-                if ((e = hipGetLastError()) != hipSuccess) return e;
-            } else {
-                hipLaunchKernelGGL((sc_screen2_finish_kernel<RG, S, W>), dim3((nmax + 255) / 256, sb.nq), dim3(256), 0, stream, f2);
-                if ((e = hipGetLastError()) != hipSuccess) return e;
-                if (next && side == 0 && (e = launch_align(stream)) != hipSuccess) return e;
-            }
-            if (side != 0 && (e = hipStreamWaitEvent(stream, sb.ev_join, 0)) != hipSuccess) return e;
-            return hipSuccess;
+    if (use_v2) {
+        // ---- second form: attributes -> products -> (tail launch | finish [+ in-line alignment]) ----
+        static std::atomic<bool> attr2_dev[64];
+        std::atomic<bool> &attr2 = attr2_dev[dev_ & 63];
+        if (!attr2.load(std::memory_order_acquire)) {
+            hipError_t e = hipFuncSetAttribute((const void *)sc_screen2_kernel<RG, S, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(s2_lds<RG, S, W>()));
+            if (e != hipSuccess) return e;
+            attr2.store(true, std::memory_order_release);
         }
+        Screen2Args f2{};
+        f2.prod = ab; f2.part = sb.part;
+        union_of(sb, &f2.u_lo, &f2.u_n);
+        constexpr int WGU = 8 * S2Cfg<RG, S, W>::NP;                           // the ring parts of an index on one XCD
+        int nwg = (num_cu / WGU) * WGU;
+        if (nwg < WGU) nwg = WGU;
+        f2.nwg = nwg;
+        hipError_t e = hipSuccess;
+        hipLaunchKernelGGL((sc_screen2_kernel<RG, S, W>), dim3(nwg), dim3(S2Cfg<RG, S, W>::WV * kWave), (s2_lds<RG, S, W>()), stream, f2);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        // The next batch's alignment runs in line on this stream.  (On a low-priority side stream, forked at the start or at the end of
+        // the products, it measured 0.67 / 0.51 G pairs/s against 1.45 G in line: the two event hops between the queues per launch cost
+        // more than the alignment itself.  As extra waves of the products' workgroups: one launch of 81-87 us against 47.8 + 26.9.
+        // Both removed)
+        const dim3 fgrid((nmax + 255) / 256, sb.nq), ablock(kScreenWaves * kWave);
+        if (!next) {
+            hipLaunchKernelGGL((sc_screen2_finish_kernel<RG, S, W>), fgrid, dim3(256), 0, stream, f2);
+            return hipGetLastError();
+        }
+        // the next batch's argument block and the grid of its alignment
+        if (next->nq < 1 || next->nq > kMaxScreenBatch) return hipErrorInvalidValue;
+        ScreenBatchArgs nb{};
+        const int nmax2 = fill_screen_args(db, *next, align_filter, &nb);
+        if (nmax2 < 0) return hipErrorInvalidValue;
+        nb.skip_d2 = next_v2 ? 1 : 0;
+        int ulo = 0, un = 0, ablocks;
+        if (next_v2) {
+            union_of(*next, &ulo, &un);
+            ablocks = align2_blocks(un);
+        } else {
+            // first form: persistent workgroups, three per CU (167 registers: three waves per SIMD; 128 spill and double the time) over the
+            // whole batch, every wave walks several groups with the next group's keys in flight
+            const int ng2 = (nmax2 + kGroup - 1) / kGroup;
+            int per_q = 3 * num_cu / next->nq;                                   // (two to nine per CU measure the same 29 us)
+            per_q = per_q < 1 ? 1 : per_q;
+            nb.nb = (ng2 + kScreenWaves - 1) / kScreenWaves;
+            nb.nb = nb.nb > per_q ? per_q : nb.nb;
+            ablocks = nb.nb * next->nq;
+        }
+        static const int tail_env = scl_lab_int("SCL_SCREEN_TAIL", 1);   // 0: finish and alignment as two launches
+        if (tail_env) {
+            // one launch: the alignment's workgroups in front, this batch's finishing behind them
+            const int chunks = (nmax + 255) / 256;
+            const dim3 tgrid(ablocks + chunks * sb.nq);
+            const bool d2 = !sb.no_ring_metric;                       // (left to the exact pass of the range: kernels.hpp)
+            if (!next_v2) hipLaunchKernelGGL((sc_screen2_tail_kernel<RG, S, W>), tgrid, ablock, lds0, stream, f2, nb, ablocks, chunks);
+            else if (sb.smask && d2) hipLaunchKernelGGL((sc_screen2_tail2_kernel<RG, S, W, true, true>), tgrid, ablock, lds_a2, stream, f2, nb, db.halign, ulo, un, ablocks, chunks);
+            else if (sb.smask) hipLaunchKernelGGL((sc_screen2_tail2_kernel<RG, S, W, true, false>), tgrid, ablock, lds_a2, stream, f2, nb, db.halign, ulo, un, ablocks, chunks);
+            else if (d2) hipLaunchKernelGGL((sc_screen2_tail2_kernel<RG, S, W, false, true>), tgrid, ablock, lds_a2, stream, f2, nb, db.halign, ulo, un, ablocks, chunks);
+            else hipLaunchKernelGGL((sc_screen2_tail2_kernel<RG, S, W, false, false>), tgrid, ablock, lds_a2, stream, f2, nb, db.halign, ulo, un, ablocks, chunks);
+            return hipGetLastError();
+        }
+        hipLaunchKernelGGL((sc_screen2_finish_kernel<RG, S, W>), fgrid, dim3(256), 0, stream, f2);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (next_v2) hipLaunchKernelGGL((sc_align2_kernel<RG, S, W>), dim3(ablocks), ablock, lds_a2, stream, nb, db.halign, ulo, un);
+        else hipLaunchKernelGGL((sc_align_kernel<RG, S, W>), dim3(ablocks), ablock, lds0, stream, nb);
+        return hipGetLastError();
     }
+    // ---- first form ----
     // the products of this batch + the alignment of the next one
     ScreenFusedArgs fa{};
     fa.prod = ab;
@@ -2207,29 +2045,13 @@ static hipError_t launch_screen_grid(const DbView &db, const ScreenBatch &sb, in
 }
 
 hipError_t launch_sc_screen_batch(const DbView &db, const ScreenBatch &sb, int SR, int align_filter, int num_cu, hipStream_t stream, int phases,
-                                  const ScreenBatch *next, const ScreenBatch *prev)
+                                  const ScreenBatch *next)
 {
     if (sb.nq < 1 || sb.nq > kMaxScreenBatch || !sc_screen_supported(db, SR)) return hipErrorInvalidValue;
-    if (sc_screen_is_wide(db, SR)) return launch_screen_grid<20, 180, 19, 2, 2>(db, sb, align_filter, num_cu, stream, phases, next, prev);   // 80 x 180
+    if (sc_screen_is_wide(db, SR)) return launch_screen_grid<20, 180, 19, 2, 2>(db, sb, align_filter, num_cu, stream, phases, next);   // 80 x 180
     // (64 x 120: the first form scores batches of one to three scans -- blocking calls -- and the kernel built for two waves per SIMD takes
     //  4 us less of a one-scan call than the one for three, which was the better one when the first form still scored batches of four)
-    return launch_screen_grid<16, 120, 13, 2, 3>(db, sb, align_filter, num_cu, stream, phases, next, prev);                                   // 64 x 120
-}
-
-// Can a batch of nq scans have its finishing deferred (second form of the products, extra waves available)?
-bool sc_screen_can_defer(const DbView &db, int SR, int nq)
-{
-    static const int fuse_env = scl_lab_int("SCL_SCREEN_FUSE", 0);
-    static const int align_form_env = scl_lab_int("SCL_ALIGN_FORM", 2);
-    static const int side_env = scl_lab_int("SCL_ALIGN_SIDE", 0);
-    static const int variant = scl_lab_int("SCL_SCREEN_VARIANT", 0);
-    static const int probe = scl_lab_int("SCL_SCREEN_PROBE", 0);
-    static const int parts_env = scl_lab_int("SCL_FUSE_PARTS", 3);
-    if (!(parts_env & 2)) return false;
-    if (!fuse_env || align_form_env == 1 || side_env != 0 || variant != 0 || probe != 0 || !screen_second_form() || !db.halign || !sc_screen_supported(db, SR)) return false;
-    const bool wide = sc_screen_is_wide(db, SR);
-    const int v2_min = screen_v2_min_env() > 0 ? screen_v2_min_env() : (wide ? 2 : 4);
-    return nq >= v2_min && nq <= sc_screen_max_batch(db, SR);
+    return launch_screen_grid<16, 120, 13, 2, 3>(db, sb, align_filter, num_cu, stream, phases, next);                                   // 64 x 120
 }
 
 }  // namespace scl
