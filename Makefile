@@ -10,12 +10,12 @@ CSRC    := scl_slam_amd/csrc
 LIBDIR  := scl_slam_amd/lib
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math \
             -fhip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-result -Iinclude -I$(CSRC) $(EXTRA)
-SRCS    := $(CSRC)/engine.hip $(CSRC)/sc_distance.hip $(CSRC)/ringkey_topk.hip $(CSRC)/make_sc.hip $(CSRC)/icp.hip $(CSRC)/voxel.hip $(CSRC)/sharded_front.hip $(CSRC)/sc_screen.hip $(CSRC)/sc_masked.hip $(CSRC)/sc_matrix.hip $(CSRC)/messages.hip $(CSRC)/iris.hip $(CSRC)/device_sort.hip $(CSRC)/m2dp.hip $(CSRC)/fpfh.hip
+SRCS    := $(CSRC)/engine.hip $(CSRC)/sc_distance.hip $(CSRC)/ringkey_topk.hip $(CSRC)/make_sc.hip $(CSRC)/icp.hip $(CSRC)/voxel.hip $(CSRC)/sharded_front.hip $(CSRC)/sc_screen.hip $(CSRC)/sc_masked.hip $(CSRC)/sc_matrix.hip $(CSRC)/messages.hip $(CSRC)/iris.hip $(CSRC)/device_sort.hip $(CSRC)/m2dp.hip $(CSRC)/fpfh.hip $(CSRC)/grsd.hip
 OBJS    := $(SRCS:.hip=.o)
 
-all: $(LIBDIR)/libscl_engine.so oracle tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/libfpfh_checker.so tests/cpp/libmock_rccl.so
+all: $(LIBDIR)/libscl_engine.so oracle tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/grsd_adapter_check tests/cpp/libfpfh_checker.so tests/cpp/libgrsd_checker.so tests/cpp/libmock_rccl.so
 
-$(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.hpp) include/scl_engine.h include/scl_m2dp.h include/scl_fpfh.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.hpp) include/scl_engine.h include/scl_m2dp.h include/scl_fpfh.h include/scl_grsd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(LIBDIR)/libscl_engine.so: $(OBJS)
@@ -38,10 +38,18 @@ tests/cpp/m2dp_adapter_check: tests/cpp/m2dp_adapter_check.cpp tests/cpp/pcl_typ
 tests/cpp/fpfh_adapter_check: tests/cpp/fpfh_adapter_check.cpp tests/cpp/pcl_types_for_adapter_check.h include/scl/fpfh_hip_descriptor.hpp include/scl_fpfh.h $(LIBDIR)/libscl_engine.so
 	g++ -std=c++14 -O2 -Wall -Iinclude -Itests/cpp -o $@ tests/cpp/fpfh_adapter_check.cpp -L$(LIBDIR) -lscl_engine -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
+# the GRSD adapter (include/scl/grsd_hip_descriptor.hpp) against the C ABI; runs on the GPU box (tests/test_gpu_grsd.py)
+tests/cpp/grsd_adapter_check: tests/cpp/grsd_adapter_check.cpp tests/cpp/pcl_types_for_adapter_check.h include/scl/grsd_hip_descriptor.hpp include/scl_grsd.h $(LIBDIR)/libscl_engine.so
+	g++ -std=c++14 -O2 -Wall -Iinclude -Itests/cpp -o $@ tests/cpp/grsd_adapter_check.cpp -L$(LIBDIR) -lscl_engine -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
+
 # TEST INFRASTRUCTURE: the FPFH CPU checker (tests/fpfh_checker.py loads it); atan2f from oracle/liboracle.so.  No -march, no
 # contraction: every float operation is the one written
 tests/cpp/libfpfh_checker.so: tests/cpp/fpfh_checker.c | oracle
 	gcc -O2 -ffp-contract=off -fno-fast-math -fPIC -shared -Wall -std=gnu11 -o $@ tests/cpp/fpfh_checker.c -Loracle -loracle -Wl,-rpath,'$$ORIGIN/../../oracle' -lm -lpthread
+
+# TEST INFRASTRUCTURE: the GRSD CPU checker (tests/grsd_checker.py loads it); acosf from tests/cpp/libfpfh_checker.so.  Same flags
+tests/cpp/libgrsd_checker.so: tests/cpp/grsd_checker.c tests/cpp/libfpfh_checker.so
+	gcc -O2 -ffp-contract=off -fno-fast-math -fPIC -shared -Wall -std=gnu11 -o $@ tests/cpp/grsd_checker.c -Ltests/cpp -lfpfh_checker -Wl,-rpath,'$$ORIGIN' -lm -lpthread
 
 # TEST INFRASTRUCTURE: the stand-in collective the sharded front's G > 1 test loads through SCL_RCCL_LIB (never linked into the product)
 tests/cpp/libmock_rccl.so: tests/cpp/mock_rccl.cpp
@@ -79,7 +87,7 @@ sanitize: tests/cpp/fuzz_host
 	@cat $(SAN_LOG)
 
 clean:
-	rm -f $(OBJS) $(LIBDIR)/libscl_engine.so tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/libfpfh_checker.so tests/cpp/libmock_rccl.so
+	rm -f $(OBJS) $(LIBDIR)/libscl_engine.so tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/grsd_adapter_check tests/cpp/libfpfh_checker.so tests/cpp/libgrsd_checker.so tests/cpp/libmock_rccl.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean sanitize

@@ -1,0 +1,146 @@
+// grsd_hip_descriptor.hpp -- header-only adapter that plugs the MI355X GRSD engine (scl_grsd.h) into the reference's descriptor
+// plugin interface, beside scan_context_hip_descriptor.hpp, lidar_iris_hip_descriptor.hpp, m2dp_hip_descriptor.hpp and
+// fpfh_hip_descriptor.hpp.
+//
+// Include it AFTER the reference's descriptor.h (it needs `class scan_descriptor`, descriptor.h:21-36, and
+// pcl::PointCloud<pcl::PointXYZI>).  The DescriptorType switch changes by one line:
+//
+//   distributedMapping.h:416   scanDescriptor = std::unique_ptr<scan_descriptor>(new grsd_descriptor());
+//   becomes                    scanDescriptor = std::unique_ptr<scan_descriptor>(new grsd_hip_descriptor(numberOfRobots, id));
+//
+// What differs from the reference's class, on purpose (scl_grsd.h has the details):
+//   * normals come from an exact integer scatter in fp64 and a Jacobi eigensolver (PCL: float covariance, eigen33), the RSD angles
+//     from the float acosf (PCL: double acos): descriptors agree with PCL's up to voxels that sit on a class threshold, not bit for bit;
+//   * detectIntraLoopClosureID works (empty in the reference, descriptor.h:111-114): this robot's keyframes [0, cur - 30);
+//   * the inter detection is the reference's by default (all robots, a snapshot rebuilt every 10th call, loop below 160); the 1-NN
+//     is exact with ties to the lowest key.
+// Errors are written to stderr and mapped to "no loop" / empty results, as the reference only logs.
+// Lifetime: as for scan_context_hip_descriptor -- scan_descriptor has no virtual destructor, call close() before
+// dropping the object if the host re-creates descriptors.
+#pragma once
+
+#include <cstdint>
+#include <cstdio>
+#include <utility>
+#include <vector>
+
+#include "scl_grsd.h"
+
+class grsd_hip_descriptor : public scan_descriptor
+{
+public:
+    grsd_hip_descriptor(int robotNum = 1, int thisID = 0, int device = 0)
+    {
+        scl_grsd_config cfg;
+        scl_grsd_default_config(&cfg);
+        cfg.robot_num = robotNum; cfg.this_id = thisID; cfg.device = device;
+        init(cfg);
+    }
+
+    // every field of scl_grsd_config (ne_radius, grsd_radius, dist_thres, num_exclude_recent, tree_making_period, inter_mode, ...)
+    explicit grsd_hip_descriptor(const scl_grsd_config &cfg) { init(cfg); }
+
+    void init(const scl_grsd_config &cfg)
+    {
+        const int rc = scl_grsd_create(&cfg, &grsd_);
+        if (rc != SCL_OK) {
+            std::fprintf(stderr, "[grsd_hip_descriptor] engine creation failed: %s\n", scl_status_string(rc));
+            grsd_ = nullptr;
+        }
+    }
+
+    ~grsd_hip_descriptor() { close(); }
+    void close()
+    {
+        if (grsd_) scl_grsd_destroy(grsd_);
+        grsd_ = nullptr;
+    }
+    grsd_hip_descriptor(const grsd_hip_descriptor &) = delete;
+    grsd_hip_descriptor &operator=(const grsd_hip_descriptor &) = delete;
+
+    // descriptor.h:25 / 57-100: the 21 floats of the symmetrised class-transition matrix
+    std::vector<float> makeAndSaveDescriptorAndKey(const pcl::PointCloud<pcl::PointXYZI> &scan,
+                                                   const int8_t robot, const int index) override
+    {
+        std::vector<float> v(SCL_GRSD_DIM, 0.0f);
+        report(scl_grsd_make_and_save(grsd_, scan.points.data(), static_cast<int>(scan.points.size()),
+                                      static_cast<int>(sizeof(pcl::PointXYZI)), robot, index, v.data()),
+               "makeAndSaveDescriptorAndKey");
+        return v;
+    }
+
+    // the batch form: scans[i] appended as (robots[i], indexs[i]); returns scans.size() * 21 floats
+    std::vector<float> makeAndSaveDescriptorsAndKeys(const std::vector<const pcl::PointCloud<pcl::PointXYZI> *> &scans,
+                                                     const std::vector<int8_t> &robots, const std::vector<int> &indexs)
+    {
+        std::vector<float> v(scans.size() * SCL_GRSD_DIM, 0.0f);
+        if (robots.size() != scans.size() || indexs.size() != scans.size()) {
+            std::fprintf(stderr, "[grsd_hip_descriptor] makeAndSaveDescriptorsAndKeys: %zu scans, %zu robots, %zu indexs\n",
+                         scans.size(), robots.size(), indexs.size());
+            return v;
+        }
+        std::vector<const void *> ptrs(scans.size());
+        std::vector<int> counts(scans.size());
+        for (size_t i = 0; i < scans.size(); ++i) { ptrs[i] = scans[i]->points.data(); counts[i] = static_cast<int>(scans[i]->points.size()); }
+        report(scl_grsd_make_and_save_many(grsd_, ptrs.data(), counts.data(), static_cast<int>(sizeof(pcl::PointXYZI)), robots.data(),
+                                           indexs.data(), static_cast<int>(scans.size()), v.data()),
+               "makeAndSaveDescriptorsAndKeys");
+        return v;
+    }
+
+    // descriptor.h:27 / 102-109, 21 floats
+    void saveDescriptorAndKey(const float *descriptorMat, const int8_t robot, const int index) override
+    {
+        report(scl_grsd_save_from_wire(grsd_, descriptorMat, robot, index), "saveDescriptorAndKey");
+    }
+
+    // descriptor.h:29 / 111-114 (empty there): {local index of the loop keyframe or -1, distance}
+    std::pair<int, float> detectIntraLoopClosureID(const int curPtr) override
+    {
+        int loop_id = -1; float dist = 0.0f;
+        if (!report(scl_grsd_detect_intra(grsd_, curPtr, &loop_id, &dist), "detectIntraLoopClosureID"))
+            return std::pair<int, float>(-1, 0.0f);
+        return std::pair<int, float>(loop_id, dist);
+    }
+
+    // descriptor.h:31 / 116-167: {global key of the loop keyframe or -1, distance}
+    std::pair<int, float> detectInterLoopClosureID(const int curPtr) override
+    {
+        int loop_id = -1; float dist = 0.0f;
+        if (!report(scl_grsd_detect_inter(grsd_, curPtr, &loop_id, &dist), "detectInterLoopClosureID"))
+            return std::pair<int, float>(-1, 0.0f);
+        return std::pair<int, float>(loop_id, dist);
+    }
+
+    // descriptor.h:33 / 169-172
+    std::pair<int8_t, int> getIndex(const int key) override
+    {
+        int8_t robot = 0; int index = -1;
+        report(scl_grsd_get_index(grsd_, key, &robot, &index), "getIndex");
+        return std::pair<int8_t, int>(robot, index);
+    }
+
+    // descriptor.h:35 / 174-177
+    int getSize(const int idIn = -1) override
+    {
+        if (!grsd_) return 0;
+        const int n = scl_grsd_get_size_of(grsd_, idIn);
+        return n < 0 ? 0 : n;
+    }
+
+    scl_grsd *engine() { return grsd_; }
+
+private:
+    bool report(int rc, const char *where) const
+    {
+        if (!grsd_) {
+            std::fprintf(stderr, "[grsd_hip_descriptor] %s: no engine (creation failed or close() was called)\n", where);
+            return false;
+        }
+        if (rc == SCL_OK) return true;
+        std::fprintf(stderr, "[grsd_hip_descriptor] %s: %s (%s)\n", where, scl_status_string(rc), scl_grsd_last_error(grsd_));
+        return false;
+    }
+
+    scl_grsd *grsd_ = nullptr;
+};

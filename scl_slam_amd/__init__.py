@@ -12,9 +12,11 @@ from .engine import (  # noqa: F401
 )
 from .m2dp import M2dpConfig, M2dpEngine, M2dpError  # noqa: F401
 from .fpfh import FpfhConfig, FpfhEngine, FpfhError  # noqa: F401
+from .grsd import GrsdConfig, GrsdEngine, GrsdError  # noqa: F401
 
 __all__ = [
     "load_library", "LIB_PATH", "NativeLibraryError", "SclConfig", "SclError",
     "ScanContextEngine", "ScanContextDescriptor", "IcpParams", "QUERY_STAGED",
     "M2dpConfig", "M2dpEngine", "M2dpError", "FpfhConfig", "FpfhEngine", "FpfhError",
+    "GrsdConfig", "GrsdEngine", "GrsdError",
 ]

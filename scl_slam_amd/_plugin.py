@@ -1,5 +1,5 @@
-"""The ctypes layer the descriptor plugin mirrors share (iris.py, m2dp.py, fpfh.py): signature binding, the error class, the
-handle life-cycle and the keyframe-registry calls; for the vector plugins (M2DP, FPFH) also the database, build and 1-NN calls."""
+"""The ctypes layer the descriptor plugin mirrors share (iris.py, m2dp.py, fpfh.py, grsd.py): signature binding, the error class, the
+handle life-cycle and the keyframe-registry calls; for the vector plugins (M2DP, FPFH, GRSD) also the database, build and 1-NN calls."""
 from ctypes import POINTER, byref, c_char_p, c_float, c_int, c_int8, c_void_p
 
 import numpy as np
@@ -33,7 +33,7 @@ def plugin_signatures(prefix, config):
 
 
 def vector_signatures(prefix, config):
-    """plugin_signatures plus the float-descriptor calls of M2DP and FPFH."""
+    """plugin_signatures plus the float-descriptor calls of M2DP, FPFH and GRSD."""
     P, fp, ip = c_void_p, POINTER(c_float), POINTER(c_int)
     sig = plugin_signatures(prefix, config)
     sig.update({
@@ -111,7 +111,7 @@ class PluginEngine:
 
 
 class VectorPluginEngine(PluginEngine):
-    """A plugin whose descriptor is DIM floats (M2DP, FPFH): make, make_and_save(_many), save_from_wire, get_signature and the
+    """A plugin whose descriptor is DIM floats (M2DP, FPFH, GRSD): make, make_and_save(_many), save_from_wire, get_signature and the
     1-NN detections."""
     DIM = None
 

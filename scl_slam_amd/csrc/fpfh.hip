@@ -60,47 +60,6 @@ struct FpGrid {
     int dx, dy, dz, cells;
 };
 
-// glibc 2.35's float acosf (sysdeps/ieee754/flt-32/e_acosf.c, fdlibm's algorithm) restated operation by operation, constants by bit
-// pattern; tests/cpp/fpfh_checker.c has the same restatement, equal to libm on all 2^32 inputs; this copy is checked against the
-// block checksums of tests/golden/acosf_blocks.json (tests/test_gpu_fpfh.py)
-__device__ __forceinline__ float acosf_glibc(float x)
-{
-    const float one = 1.0f, pi = __int_as_float(0x40490fda), pio2_hi = __int_as_float(0x3fc90fda), pio2_lo = __int_as_float(0x33a22168);
-    const float pS0 = __int_as_float(0x3e2aaaab), pS1 = __int_as_float(0xbea6b090), pS2 = __int_as_float(0x3e4e0aa8);
-    const float pS3 = __int_as_float(0xbd241146), pS4 = __int_as_float(0x3a4f7f04), pS5 = __int_as_float(0x3811ef08);
-    const float qS1 = __int_as_float(0xc019d139), qS2 = __int_as_float(0x4001572d), qS3 = __int_as_float(0xbf303361);
-    const float qS4 = __int_as_float(0x3d9dc62e);
-    const int hx = __float_as_int(x), ix = hx & 0x7fffffff;
-    if (ix == 0x3f800000) return hx > 0 ? 0.0f : pi + 2.0f * pio2_lo;
-    if (ix > 0x3f800000) return (x - x) / (x - x);
-    if (ix < 0x3f000000) {
-        if (ix <= 0x32800000) return pio2_hi + pio2_lo;
-        const float z = x * x;
-        const float p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
-        const float q = one + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
-        const float r = p / q;
-        return pio2_hi - (x - (pio2_lo - x * r));
-    }
-    if (hx < 0) {
-        const float z = (one + x) * 0.5f;
-        const float p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
-        const float q = one + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
-        const float s = sqrtf(z);
-        const float r = p / q;
-        const float w = r * s - pio2_lo;
-        return pi - 2.0f * (s + w);
-    }
-    const float z = (one - x) * 0.5f;
-    const float s = sqrtf(z);
-    const float df = __int_as_float(__float_as_int(s) & (int)0xfffff000u);
-    const float c = (z - df * df) / (s + df);
-    const float p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
-    const float q = one + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
-    const float r = p / q;
-    const float w = r * s + c;
-    return 2.0f * (df + w);
-}
-
 __device__ __forceinline__ const float *point_at(const unsigned char *pts, const FpScan &sc, int stride, int i)
 {
     return reinterpret_cast<const float *>(pts + sc.byte_off + (unsigned long long)i * (unsigned long long)stride);

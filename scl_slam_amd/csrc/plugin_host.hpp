@@ -1,6 +1,6 @@
-// plugin_host.hpp -- the host layer the descriptor plugins share (iris.hip, m2dp.hip, fpfh.hip; engine.hip and sharded_front.hip
+// plugin_host.hpp -- the host layer the descriptor plugins share (iris.hip, m2dp.hip, fpfh.hip, grsd.hip; engine.hip and sharded_front.hip
 // take the error helpers): the HIP-check macro and error helpers, the keyframe registry behind the get_size / get_index / local_to_global
-// entry points and the inter-detection candidate rule, and for the vector plugins (M2DP, FPFH) the float-row database, the
+// entry points and the inter-detection candidate rule, and for the vector plugins (M2DP, FPFH, GRSD) the float-row database, the
 // make_and_save_many driver and the 1-NN search.  No descriptor logic lives here.
 //
 // Every helper that touches a handle assumes its lock is held (the `_locked` convention; std::mutex is not recursive), except
