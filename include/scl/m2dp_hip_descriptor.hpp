@@ -80,6 +80,53 @@ public:
         return v;
     }
 
+    // the batch forms (scl_m2dp.h "THE BATCH FORMS"): what the single calls in the same order return, one device wait per call.
+    // {local index of the loop keyframe or -1, distance} per entry of curPtrs; on an error every entry is {-1, 0}
+    std::vector<std::pair<int, float>> detectIntraLoopClosureIDs(const std::vector<int> &curPtrs)
+    {
+        std::vector<int> loops(curPtrs.size(), -1);
+        std::vector<float> dists(curPtrs.size(), 0.0f);
+        const bool ok = report(scl_m2dp_detect_intra_many(m2dp_, curPtrs.data(), static_cast<int>(curPtrs.size()), loops.data(), dists.data()),
+                               "detectIntraLoopClosureIDs");
+        return pairs(loops, dists, ok);
+    }
+
+    // {global key of the loop keyframe or -1, distance} per entry of curPtrs
+    std::vector<std::pair<int, float>> detectInterLoopClosureIDs(const std::vector<int> &curPtrs)
+    {
+        std::vector<int> loops(curPtrs.size(), -1);
+        std::vector<float> dists(curPtrs.size(), 0.0f);
+        const bool ok = report(scl_m2dp_detect_inter_many(m2dp_, curPtrs.data(), static_cast<int>(curPtrs.size()), loops.data(), dists.data()),
+                               "detectInterLoopClosureIDs");
+        return pairs(loops, dists, ok);
+    }
+
+    // scans[i] appended as (robots[i], indexs[i]), then the intra detection of every new keyframe of this robot in the same call:
+    // {local index of the loop keyframe or -1, distance} per scan ({-1, +inf} for another robot's); descriptors: lastDescriptors()
+    std::vector<std::pair<int, float>> makeSaveAndDetect(const std::vector<const pcl::PointCloud<pcl::PointXYZI> *> &scans,
+                                                         const std::vector<int8_t> &robots, const std::vector<int> &indexs)
+    {
+        std::vector<int> loops(scans.size(), -1);
+        std::vector<float> dists(scans.size(), 0.0f);
+        last_.assign(scans.size() * SCL_M2DP_DIM, 0.0f);
+        if (robots.size() != scans.size() || indexs.size() != scans.size()) {
+            std::fprintf(stderr, "[m2dp_hip_descriptor] makeSaveAndDetect: %zu scans, %zu robots, %zu indexs\n", scans.size(), robots.size(),
+                         indexs.size());
+            return pairs(loops, dists, false);
+        }
+        std::vector<const void *> ptrs(scans.size());
+        std::vector<int> counts(scans.size());
+        for (size_t i = 0; i < scans.size(); ++i) { ptrs[i] = scans[i]->points.data(); counts[i] = static_cast<int>(scans[i]->points.size()); }
+        const bool ok = report(scl_m2dp_make_save_and_detect(m2dp_, ptrs.data(), counts.data(), static_cast<int>(sizeof(pcl::PointXYZI)),
+                                                          robots.data(), indexs.data(), static_cast<int>(scans.size()), loops.data(),
+                                                          dists.data(), last_.data()),
+                               "makeSaveAndDetect");
+        return pairs(loops, dists, ok);
+    }
+
+    // the descriptors of the last makeSaveAndDetect: scans.size() * 192 floats
+    const std::vector<float> &lastDescriptors() const { return last_; }
+
     // descriptor.h:27 / 1989-1995, all 192 floats
     void saveDescriptorAndKey(const float *m2dpVec, const int8_t robot, const int index) override
     {
@@ -135,4 +182,13 @@ private:
     }
 
     scl_m2dp *m2dp_ = nullptr;
+
+    static std::vector<std::pair<int, float>> pairs(const std::vector<int> &loops, const std::vector<float> &dists, bool ok)
+    {
+        std::vector<std::pair<int, float>> out(loops.size(), std::pair<int, float>(-1, 0.0f));
+        for (size_t i = 0; ok && i < loops.size(); ++i) out[i] = std::pair<int, float>(loops[i], dists[i]);
+        return out;
+    }
+
+    std::vector<float> last_;
 };

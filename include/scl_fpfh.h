@@ -34,6 +34,7 @@
 #include <stdint.h>
 
 #include "scl_engine.h"
+#include "scl_plugin_batch.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -94,6 +95,11 @@ int  scl_fpfh_detect_intra(scl_fpfh *h, int cur, int *loop_id, float *dist);
 /* cur = GLOBAL key; inter_mode 0: the reference's semantics above (*dist = 0 before num_exclude_recent + 1 keyframes);
  * inter_mode 1: as scl_m2dp_detect_inter.  *loop_id = GLOBAL key or -1. */
 int  scl_fpfh_detect_inter(scl_fpfh *h, int cur, int *loop_id, float *dist);
+
+/* THE BATCH FORMS (scl_plugin_batch.h has the rules): scl_fpfh_detect_intra_many, scl_fpfh_detect_inter_many,
+ * scl_fpfh_save_from_wire_many and scl_fpfh_make_save_and_detect -- what the single calls in array order answer, bit for bit,
+ * 16 queries per launch and one wait for the device per call */
+SCL_PLUGIN_BATCH_API(scl_fpfh);
 
 /* TEST HOOKS (one cloud each; any output may be NULL):
  * neighbours: n_points x min(10, n_points) int32 indices and float d2, in (d2, index) order, rows in input order */

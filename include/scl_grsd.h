@@ -39,6 +39,7 @@
 #include <stdint.h>
 
 #include "scl_engine.h"
+#include "scl_plugin_batch.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -100,6 +101,11 @@ int  scl_grsd_detect_intra(scl_grsd *h, int cur, int *loop_id, float *dist);
 /* cur = GLOBAL key; inter_mode 0: the reference's semantics above (*dist = 0 before num_exclude_recent + 1 keyframes);
  * inter_mode 1: as scl_m2dp_detect_inter.  *loop_id = GLOBAL key or -1. */
 int  scl_grsd_detect_inter(scl_grsd *h, int cur, int *loop_id, float *dist);
+
+/* THE BATCH FORMS (scl_plugin_batch.h has the rules): scl_grsd_detect_intra_many, scl_grsd_detect_inter_many,
+ * scl_grsd_save_from_wire_many and scl_grsd_make_save_and_detect -- what the single calls in array order answer, bit for bit,
+ * 16 queries per launch and one wait for the device per call */
+SCL_PLUGIN_BATCH_API(scl_grsd);
 
 /* TEST HOOKS (one cloud each; any output may be NULL):
  * normals: n_points x 3 floats in input order (NaN triples where invalid) and n_points validity flags (1 / 0) */

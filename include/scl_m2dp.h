@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "scl_engine.h"
+#include "scl_plugin_batch.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -94,6 +95,11 @@ int  scl_m2dp_detect_intra(scl_m2dp *h, int cur, int *loop_id, float *dist);
 /* detectInterLoopClosureID(cur): cur = GLOBAL key; a keyframe of this robot is searched among all other robots' keyframes,
  * a received one among this robot's (as scl_iris_detect_inter); *loop_id = GLOBAL key or -1. */
 int  scl_m2dp_detect_inter(scl_m2dp *h, int cur, int *loop_id, float *dist);
+
+/* THE BATCH FORMS (scl_plugin_batch.h has the rules): scl_m2dp_detect_intra_many, scl_m2dp_detect_inter_many,
+ * scl_m2dp_save_from_wire_many and scl_m2dp_make_save_and_detect -- what the single calls in array order answer, bit for bit,
+ * 16 queries per launch and one wait for the device per call */
+SCL_PLUGIN_BATCH_API(scl_m2dp);
 
 /* TEST HOOK: for one cloud, the 64 x 128 integer counts of A (row-major: plane row, bin column; A = counts / n_points), the
  * float frame (mean[3], axes[9]: axis k = axes[3k .. 3k+2], signs applied) and maxRho.  Any output may be NULL. */

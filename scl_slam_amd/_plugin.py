@@ -43,6 +43,10 @@ def vector_signatures(prefix, config):
         f"{prefix}_get_signature": (c_int, [P, c_int, fp]),
         f"{prefix}_detect_intra": (c_int, [P, c_int, ip, fp]),
         f"{prefix}_detect_inter": (c_int, [P, c_int, ip, fp]),
+        f"{prefix}_detect_intra_many": (c_int, [P, ip, c_int, ip, fp]),
+        f"{prefix}_detect_inter_many": (c_int, [P, ip, c_int, ip, fp]),
+        f"{prefix}_save_from_wire_many": (c_int, [P, fp, POINTER(c_int8), ip, c_int]),
+        f"{prefix}_make_save_and_detect": (c_int, [P, POINTER(c_void_p), ip, c_int, POINTER(c_int8), ip, c_int, ip, fp, fp]),
     })
     return sig
 
@@ -112,7 +116,7 @@ class PluginEngine:
 
 class VectorPluginEngine(PluginEngine):
     """A plugin whose descriptor is DIM floats (M2DP, FPFH, GRSD): make, make_and_save(_many), save_from_wire, get_signature and the
-    1-NN detections."""
+    1-NN detections, each with its batch form (numpy arrays in and out)."""
     DIM = None
 
     @staticmethod
@@ -134,21 +138,52 @@ class VectorPluginEngine(PluginEngine):
         self._call("make_and_save", a.ctypes.data_as(c_void_p), n, st, robot, index, out.ctypes.data_as(POINTER(c_float)))
         return out
 
-    def make_and_save_many(self, clouds, robots=None, indexs=None, want_values=True):
-        """clouds: list of (n_i, k) float32 arrays with one record width k; returns (count, DIM) float32 (None if not wanted)"""
+    def _clouds(self, clouds, robots, indexs, where):
+        """the arguments of a batched build: (arrays kept alive, pointers, counts, stride, robots, indexs, count)"""
         arrs = [self._cloud(c) for c in clouds]
         count = len(arrs)
         if count and len({st for _, _, st in arrs}) != 1:
-            raise ValueError("make_and_save_many: one stride for all clouds")
+            raise ValueError(f"{where}: one stride for all clouds")
         st = arrs[0][2] if count else 12
         ptrs = (c_void_p * max(count, 1))(*[a.ctypes.data for a, _, _ in arrs])
         ns = np.ascontiguousarray([n for _, n, _ in arrs], np.int32)
         rb = np.ascontiguousarray(robots if robots is not None else np.zeros(count), np.int8)
         ix = np.ascontiguousarray(indexs if indexs is not None else np.arange(count), np.int32)
+        if rb.size != count or ix.size != count:
+            raise ValueError(f"{where}: one robot id and one index per cloud")
+        return arrs, ptrs, ns, st, rb, ix, count
+
+    def make_and_save_many(self, clouds, robots=None, indexs=None, want_values=True):
+        """clouds: list of (n_i, k) float32 arrays with one record width k; returns (count, DIM) float32 (None if not wanted)"""
+        _keep, ptrs, ns, st, rb, ix, count = self._clouds(clouds, robots, indexs, "make_and_save_many")
         out = np.empty((count, self.DIM), np.float32) if want_values else None
         self._call("make_and_save_many", ptrs, ns.ctypes.data_as(POINTER(c_int)), st, rb.ctypes.data_as(POINTER(c_int8)),
                    ix.ctypes.data_as(POINTER(c_int)), count, out.ctypes.data_as(POINTER(c_float)) if out is not None else None)
         return out
+
+    def make_save_and_detect(self, clouds, robots=None, indexs=None, want_values=True, loops=None, dists=None):
+        """make_and_save_many, then detect_intra of every new keyframe of this robot in the same call: (loops int32, dists float32,
+        values (count, DIM) float32 or None).  loops / dists: arrays to fill (left untouched when the call fails)"""
+        _keep, ptrs, ns, st, rb, ix, count = self._clouds(clouds, robots, indexs, "make_save_and_detect")
+        loops = np.empty(count, np.int32) if loops is None else loops
+        dists = np.empty(count, np.float32) if dists is None else dists
+        self._batch_out(loops, dists, count)
+        out = np.empty((count, self.DIM), np.float32) if want_values else None
+        self._call("make_save_and_detect", ptrs, ns.ctypes.data_as(POINTER(c_int)), st, rb.ctypes.data_as(POINTER(c_int8)),
+                   ix.ctypes.data_as(POINTER(c_int)), count, loops.ctypes.data_as(POINTER(c_int)), dists.ctypes.data_as(POINTER(c_float)),
+                   out.ctypes.data_as(POINTER(c_float)) if out is not None else None)
+        return loops, dists, out
+
+    def save_from_wire_many(self, values, robots=None, indexs=None):
+        """values: (count, DIM) float32 rows appended in order as robots[i] / indexs[i]"""
+        v = np.ascontiguousarray(values, np.float32).reshape(-1, self.DIM)
+        count = v.shape[0]
+        rb = np.ascontiguousarray(robots if robots is not None else np.zeros(count), np.int8)
+        ix = np.ascontiguousarray(indexs if indexs is not None else np.arange(count), np.int32)
+        if rb.size != count or ix.size != count:
+            raise ValueError("save_from_wire_many: one robot id and one index per row")
+        self._call("save_from_wire_many", v.ctypes.data_as(POINTER(c_float)), rb.ctypes.data_as(POINTER(c_int8)),
+                   ix.ctypes.data_as(POINTER(c_int)), count)
 
     def save_from_wire(self, values, robot=0, index=0):
         v = np.ascontiguousarray(values, np.float32)
@@ -171,3 +206,28 @@ class VectorPluginEngine(PluginEngine):
         loop, d = c_int(), c_float()
         self._call("detect_inter", cur, byref(loop), byref(d))
         return loop.value, np.float32(d.value)
+
+    @staticmethod
+    def _batch_out(loops, dists, count):
+        for a, t in ((loops, np.int32), (dists, np.float32)):
+            if a is not None and (a.dtype != t or a.size != count or not a.flags.c_contiguous):
+                raise ValueError(f"a contiguous {np.dtype(t).name} array of {count} elements")
+
+    def _detect_many(self, name, curs, loops, dists, want_dists):
+        c = np.ascontiguousarray(curs, np.int32).ravel()
+        loops = np.empty(c.size, np.int32) if loops is None else loops
+        if dists is None and want_dists:
+            dists = np.empty(c.size, np.float32)
+        self._batch_out(loops, dists, c.size)
+        self._call(name, c.ctypes.data_as(POINTER(c_int)), c.size, loops.ctypes.data_as(POINTER(c_int)),
+                   dists.ctypes.data_as(POINTER(c_float)) if dists is not None else None)
+        return loops, dists
+
+    def detect_intra_many(self, curs, loops=None, dists=None, want_dists=True):
+        """detect_intra for every local index of curs, as the single calls in that order answer: (loops int32, dists float32; dists
+        None with want_dists=False).  loops / dists: arrays to fill (left untouched when the call fails)"""
+        return self._detect_many("detect_intra_many", curs, loops, dists, want_dists)
+
+    def detect_inter_many(self, curs, loops=None, dists=None, want_dists=True):
+        """detect_inter for every global key of curs, as the single calls in that order answer: (loops int32, dists float32)"""
+        return self._detect_many("detect_inter_many", curs, loops, dists, want_dists)

@@ -402,6 +402,7 @@ struct scl_fpfh {
     unsigned int *d_counts = nullptr;
     unsigned long long *d_cand = nullptr, *d_best = nullptr;
     int *d_list = nullptr; size_t list_cap = 0;
+    scl::NnManyWork many;                    // the batched detections' work buffers
     int *d_nbr = nullptr; float *d_nbr_d2 = nullptr; size_t nbr_cap = 0;
     unsigned long long points = 0;
     double kernel_us = 0.0;
@@ -598,6 +599,7 @@ int scl_fpfh_destroy(scl_fpfh *h)
                     (void *)h->d_grids, (void *)h->d_bad, (void *)h->d_counts, (void *)h->d_cand, (void *)h->d_best, (void *)h->d_list,
                     (void *)h->d_nbr, (void *)h->d_nbr_d2})
         if (p) (void)hipFree(p);
+    h->many.release();
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -704,6 +706,42 @@ int scl_fpfh_detect_inter(scl_fpfh *h, int cur, int *loop_id, float *dist)
     if (dist) *dist = d;
     if ((double)d < h->cfg.dist_thres) *loop_id = pos;
     return SCL_OK;
+}
+
+int scl_fpfh_detect_intra_many(scl_fpfh *h, const int *curs, int count, int *loop_ids, float *dists)
+{
+    if (!h || count < 0 || (count > 0 && (!curs || !loop_ids))) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    return detect_intra_many_locked(h, curs, count, h->cfg.report_dims, loop_ids, dists);
+}
+
+int scl_fpfh_detect_inter_many(scl_fpfh *h, const int *curs, int count, int *loop_ids, float *dists)
+{
+    if (!h || count < 0 || (count > 0 && (!curs || !loop_ids))) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    if (h->cfg.inter_mode == 0) return detect_inter_snapshot_many_locked(h, curs, count, h->cfg.report_dims, loop_ids, dists);
+    return detect_inter_lists_many_locked(h, curs, count, h->cfg.report_dims, loop_ids, dists);
+}
+
+int scl_fpfh_save_from_wire_many(scl_fpfh *h, const float *values, const int8_t *robots, const int *indexs, int count)
+{
+    if (!h || count < 0 || (count > 0 && (!values || !robots || !indexs))) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    return save_from_wire_many_locked(h, values, robots, indexs, count);
+}
+
+int scl_fpfh_make_save_and_detect(scl_fpfh *h, const void *const *clouds, const int *n_points, int stride_bytes, const int8_t *robots,
+                               const int *indexs, int count, int *loop_ids, float *dists, float *out_values)
+{
+    if (!h || count < 0 || (count > 0 && (!clouds || !n_points || !robots || !indexs || !loop_ids))) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    auto run = [&](const void *const *c, const int *np, int G, int slot0, int *bad) { return run_group_locked(h, c, np, stride_bytes, G, slot0, bad); };
+    return make_save_and_detect_locked(h, clouds, n_points, stride_bytes, robots, indexs, count, h->cfg.report_dims, loop_ids, dists, out_values, kGroup,
+                                       check_layout, run);
 }
 
 int scl_fpfh_neighbors(scl_fpfh *h, const void *points, int n_points, int stride_bytes, int32_t *idx, float *d2)

@@ -459,6 +459,7 @@ struct scl_grsd {
     unsigned int *d_T = nullptr;
     unsigned long long *d_best = nullptr;
     int *d_list = nullptr; size_t list_cap = 0;
+    scl::NnManyWork many;                    // the batched detections' work buffers
     int last_voxels = 0;                     // voxels of the last launch group (the hooks read one cloud's)
     unsigned long long points = 0, voxels = 0;
     double kernel_us = 0.0;
@@ -657,6 +658,7 @@ int scl_grsd_destroy(scl_grsd *h)
                     (void *)h->d_rmin, (void *)h->d_rmax, h->d_sort, (void *)h->d_scans, (void *)h->d_grids, (void *)h->d_bad,
                     (void *)h->d_nvox, (void *)h->d_T, (void *)h->d_best, (void *)h->d_list})
         if (p) (void)hipFree(p);
+    h->many.release();
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -757,6 +759,42 @@ int scl_grsd_detect_inter(scl_grsd *h, int cur, int *loop_id, float *dist)
     }
     report_locked(h, pos, d2, loop_id, dist);
     return SCL_OK;
+}
+
+int scl_grsd_detect_intra_many(scl_grsd *h, const int *curs, int count, int *loop_ids, float *dists)
+{
+    if (!h || count < 0 || (count > 0 && (!curs || !loop_ids))) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    return detect_intra_many_locked(h, curs, count, kDim, loop_ids, dists);
+}
+
+int scl_grsd_detect_inter_many(scl_grsd *h, const int *curs, int count, int *loop_ids, float *dists)
+{
+    if (!h || count < 0 || (count > 0 && (!curs || !loop_ids))) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    if (h->cfg.inter_mode == 0) return detect_inter_snapshot_many_locked(h, curs, count, kDim, loop_ids, dists);
+    return detect_inter_lists_many_locked(h, curs, count, kDim, loop_ids, dists);
+}
+
+int scl_grsd_save_from_wire_many(scl_grsd *h, const float *values, const int8_t *robots, const int *indexs, int count)
+{
+    if (!h || count < 0 || (count > 0 && (!values || !robots || !indexs))) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    return save_from_wire_many_locked(h, values, robots, indexs, count);
+}
+
+int scl_grsd_make_save_and_detect(scl_grsd *h, const void *const *clouds, const int *n_points, int stride_bytes, const int8_t *robots,
+                               const int *indexs, int count, int *loop_ids, float *dists, float *out_values)
+{
+    if (!h || count < 0 || (count > 0 && (!clouds || !n_points || !robots || !indexs || !loop_ids))) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    auto run = [&](const void *const *c, const int *np, int G, int slot0, int *bad) { return run_group_locked(h, c, np, stride_bytes, G, slot0, bad); };
+    return make_save_and_detect_locked(h, clouds, n_points, stride_bytes, robots, indexs, count, kDim, loop_ids, dists, out_values, kGroup,
+                                       check_layout, run);
 }
 
 int scl_grsd_normals(scl_grsd *h, const void *points, int n_points, int stride_bytes, float *normals, uint8_t *valid)

@@ -387,6 +387,7 @@ struct scl_m2dp {
     int *d_bad = nullptr;
     unsigned long long *d_exact = nullptr, *d_best = nullptr;
     int *d_list = nullptr; size_t list_cap = 0;
+    scl::NnManyWork many;                    // the batched detections' work buffers
     unsigned long long decisions = 0;
     double kernel_us = 0.0;
 };
@@ -526,6 +527,7 @@ int scl_m2dp_destroy(scl_m2dp *h)
                     (void *)h->d_planes, (void *)h->d_theta, (void *)h->d_framef, (void *)h->d_frame_out, (void *)h->d_max_rho,
                     (void *)h->d_counts, (void *)h->d_bad, (void *)h->d_exact, (void *)h->d_best, (void *)h->d_list})
         if (p) (void)hipFree(p);
+    h->many.release();
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -623,6 +625,41 @@ int scl_m2dp_detect_inter(scl_m2dp *h, int cur, int *loop_id, float *dist)
     if (dist) *dist = d;
     if (pos >= 0 && (double)d < h->cfg.dist_thres) *loop_id = list[(size_t)pos];
     return SCL_OK;
+}
+
+int scl_m2dp_detect_intra_many(scl_m2dp *h, const int *curs, int count, int *loop_ids, float *dists)
+{
+    if (!h || count < 0 || (count > 0 && (!curs || !loop_ids))) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    return detect_intra_many_locked(h, curs, count, SCL_M2DP_DIM, loop_ids, dists);
+}
+
+int scl_m2dp_detect_inter_many(scl_m2dp *h, const int *curs, int count, int *loop_ids, float *dists)
+{
+    if (!h || count < 0 || (count > 0 && (!curs || !loop_ids))) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    return detect_inter_lists_many_locked(h, curs, count, SCL_M2DP_DIM, loop_ids, dists);
+}
+
+int scl_m2dp_save_from_wire_many(scl_m2dp *h, const float *values, const int8_t *robots, const int *indexs, int count)
+{
+    if (!h || count < 0 || (count > 0 && (!values || !robots || !indexs))) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    return save_from_wire_many_locked(h, values, robots, indexs, count);
+}
+
+int scl_m2dp_make_save_and_detect(scl_m2dp *h, const void *const *clouds, const int *n_points, int stride_bytes, const int8_t *robots,
+                               const int *indexs, int count, int *loop_ids, float *dists, float *out_values)
+{
+    if (!h || count < 0 || (count > 0 && (!clouds || !n_points || !robots || !indexs || !loop_ids))) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    auto run = [&](const void *const *c, const int *np, int G, int slot0, int *bad) { return run_group_locked(h, c, np, stride_bytes, G, slot0, bad); };
+    return make_save_and_detect_locked(h, clouds, n_points, stride_bytes, robots, indexs, count, SCL_M2DP_DIM, loop_ids, dists, out_values, kGroup,
+                                       check_layout, run);
 }
 
 int scl_m2dp_signature_matrix(scl_m2dp *h, const void *points, int n_points, int stride_bytes, uint32_t *counts,

@@ -1,13 +1,15 @@
 // plugin_host.hpp -- the host layer the descriptor plugins share (iris.hip, m2dp.hip, fpfh.hip, grsd.hip; engine.hip and sharded_front.hip
 // take the error helpers): the HIP-check macro and error helpers, the keyframe registry behind the get_size / get_index / local_to_global
 // entry points and the inter-detection candidate rule, and for the vector plugins (M2DP, FPFH, GRSD) the float-row database, the
-// make_and_save_many driver and the 1-NN search.  No descriptor logic lives here.
+// make_and_save_many driver, the 1-NN search and its batched form with the *_many detections built on it.  No descriptor logic
+// lives here.
 //
 // Every helper that touches a handle assumes its lock is held (the `_locked` convention; std::mutex is not recursive), except
 // the registry's C entry points below, which take it once.  A handle provides `mutable std::mutex mu`, `mutable std::string
 // last_error`, `hipStream_t stream` and `scl::KeyframeRegistry reg`; a vector plugin's also `scl::FloatRows<DIM> db`,
-// `int *d_list`, `size_t list_cap` and `unsigned long long *d_best` (one element).
-// Included from .hip files only (nn_l2_kernel is device code).  Everything here has internal linkage (the unnamed namespace): the
+// `int *d_list`, `size_t list_cap`, `unsigned long long *d_best` (one element) and `scl::NnManyWork many` (the batched search).
+// Included from .hip files only (nn_l2_kernel and nn_l2_many_kernel are device code).  Everything here has internal linkage (the
+// unnamed namespace): the
 // library exports its C ABI and nothing of this layer.
 #pragma once
 
@@ -22,6 +24,7 @@
 #include <vector>
 
 #include "scl_engine.h"
+#include "scl_plugin_batch.h"
 
 // a failed HIP call: its text and the runtime's message into h->last_error, SCL_ERR_NOMEM / SCL_ERR_HIP returned
 #define SCL_HIP(h_, call)                                                              \
@@ -266,6 +269,336 @@ template <class H> int nearest_locked(H *h, int q, const int *list, int n, int *
     const unsigned int bits = (unsigned int)(best >> 32);
     std::memcpy(d2, &bits, sizeof(float));
     *pos = (int)(best & 0xffffffffu);
+    return SCL_OK;
+}
+
+// ---- batched 1-NN: one launch scores up to SCL_PLUGIN_DETECT_GROUP queries against one shared candidate list, the database rows
+// read once per launch.  Query q (row qkey[q]) searches the prefix list[0 .. limit[q]) -- every search set the plugins use is a
+// prefix of one list: intra = this robot's keys [0, cur - num_exclude_recent), the reference's inter mode = keys [0, snap_n), M2DP's
+// inter rule = a whole sorted list -- and best[q] receives the same (distance bits, position) key as nn_l2_kernel's.
+//
+// A workgroup is one wave and owns a tile of 64 candidates, one per lane.  Their rows go through LDS in chunks of kChunk floats
+// (coalesced loads: consecutive lanes read consecutive floats of a row), the group's query rows are staged once.  A lane then reads
+// its candidate's values once per chunk and every query value as a broadcast, and keeps the 16 running sums in registers: per
+// (candidate, query) pair the sum over k stays in one lane, in nn_l2_kernel's order (the chunks are whole groups of four; the
+// tail exists only where a row is one chunk).  The row pitch in LDS is odd: lane l reads dword l * pitch + k, bank (l * pitch + k)
+// % 32 for ds_read_b32, distinct over a 32-lane half (a pitch of 192 would put every lane on one bank).
+constexpr int kDetectGroup = SCL_PLUGIN_DETECT_GROUP;
+constexpr int kManyTile = 64;
+
+template <int DIM> struct NnManyShape {
+    static constexpr int kChunk = DIM <= 64 ? DIM : 32;
+    static constexpr int kPitch = kChunk | 1;
+    static_assert(DIM % kChunk == 0 && (kChunk % 4 == 0 || kChunk == DIM), "a chunk is whole groups of four, or the whole row");
+};
+
+template <int DIM>
+__global__ __launch_bounds__(kManyTile) void nn_l2_many_kernel(const float *db, const int *list, int n, const int *qkey, const int *limit,
+                                                               int nq, unsigned long long *best)
+{
+    constexpr int KC = NnManyShape<DIM>::kChunk, P = NnManyShape<DIM>::kPitch;
+    __shared__ alignas(16) float qs[kDetectGroup * DIM];               // rows of absent queries (q >= nq): zeros, their sums unused
+    __shared__ float cs[kManyTile * P];
+    __shared__ int ks[kManyTile], lim[kDetectGroup];
+    const int t = threadIdx.x, base = blockIdx.x * kManyTile, i = base + t;
+    const int rows = min(kManyTile, n - base);
+    for (int e = t; e < kDetectGroup * DIM; e += kManyTile) {
+        const int q = e / DIM;
+        qs[e] = q < nq ? db[(size_t)qkey[q] * DIM + (e - q * DIM)] : 0.0f;
+    }
+    if (t < kDetectGroup) lim[t] = t < nq ? limit[t] : 0;
+    if (t < rows) ks[t] = list ? list[i] : i;
+    float s[kDetectGroup];
+#pragma unroll
+    for (int q = 0; q < kDetectGroup; ++q) s[q] = 0.0f;
+    for (int k0 = 0; k0 < DIM; k0 += KC) {
+        __syncthreads();                                               // ks / qs written; the previous chunk read
+        for (int e = t; e < rows * KC; e += kManyTile) {
+            const int c = e / KC, k = e - c * KC;
+            cs[c * P + k] = db[(size_t)ks[c] * DIM + k0 + k];
+        }
+        __syncthreads();
+        if (t < rows) {
+            const float *c = cs + t * P;
+#pragma unroll
+            for (int k = 0; k + 4 <= KC; k += 4) {
+                const float c0 = c[k], c1 = c[k + 1], c2 = c[k + 2], c3 = c[k + 3];
+#pragma unroll
+                for (int q = 0; q < kDetectGroup; ++q) {
+                    const float *a = qs + q * DIM + k0 + k;
+                    const float d0 = a[0] - c0, d1 = a[1] - c1, d2 = a[2] - c2, d3 = a[3] - c3;
+                    s[q] += ((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3;
+                }
+            }
+#pragma unroll
+            for (int k = KC / 4 * 4; k < KC; ++k) {
+                const float ck = c[k];
+#pragma unroll
+                for (int q = 0; q < kDetectGroup; ++q) {
+                    const float d = qs[q * DIM + k0 + k] - ck;
+                    s[q] += d * d;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < kDetectGroup; ++q) {
+        unsigned long long key = i < lim[q] ? ((unsigned long long)__float_as_uint(s[q]) << 32) | (unsigned int)i : ~0ull;   // lim[q] <= n
+        for (int off = 32; off > 0; off >>= 1) {
+            const unsigned long long o = __shfl_xor(key, off);
+            key = o < key ? o : key;
+        }
+        if (t == 0 && key != ~0ull) atomicMin(best + q, key);
+    }
+}
+
+// what a batched search answers per query: the winner's position in its list and its global key (-1, -1: nothing reduced, an empty
+// prefix), the 1-NN's squared distance (+inf then) and sqrtf of the squared distance over the first report_dims floats (+inf then)
+struct NnManyResult {
+    int pos, key;
+    float d2, dist;
+};
+
+// the finishing step, one thread per query of the whole call: best[q] -> NnManyResult without the host in between.  list_off[q]:
+// where the query's list starts in `list`, -1 for keys 0 .. n - 1.  The distance over report_dims floats in nanoflann's order
+template <int DIM>
+__global__ __launch_bounds__(kNnThreads) void nn_finish_many_kernel(const float *db, const int *list, const int *qkey, const int *list_off,
+                                                                    const unsigned long long *best, int count,
+                                                                    int report_dims, NnManyResult *res)
+{
+    const int q = blockIdx.x * kNnThreads + threadIdx.x;
+    if (q >= count) return;
+    NnManyResult r = {-1, -1, INFINITY, INFINITY};
+    const unsigned long long b = best[q];
+    if (b != ~0ull) {
+        r.pos = (int)(b & 0xffffffffu);
+        r.key = list_off[q] < 0 ? r.pos : list[list_off[q] + r.pos];
+        r.d2 = __uint_as_float((unsigned int)(b >> 32));
+        const float *a = db + (size_t)qkey[q] * DIM, *c = db + (size_t)r.key * DIM;
+        float s = 0.0f;
+        int k = 0;
+        for (; k + 4 <= report_dims; k += 4) {
+            const float d0 = a[k] - c[k], d1 = a[k + 1] - c[k + 1], d2 = a[k + 2] - c[k + 2], d3 = a[k + 3] - c[k + 3];
+            s += ((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3;
+        }
+        for (; k < report_dims; ++k) {
+            const float d = a[k] - c[k];
+            s += d * d;
+        }
+        r.dist = sqrtf(s);
+    }
+    res[q] = r;
+}
+
+// the batched search's work buffers of a handle (`scl::NnManyWork many`; the lists share d_list): they grow like d_list
+struct NnManyWork {
+    int *d_q = nullptr;                          // qkey | limit | list_off, `count` elements each
+    unsigned long long *d_best = nullptr;
+    NnManyResult *d_res = nullptr;
+    size_t cap = 0;
+    void release()
+    {
+        for (void *p : {(void *)d_q, (void *)d_best, (void *)d_res})
+            if (p) (void)hipFree(p);
+        d_q = nullptr; d_best = nullptr; d_res = nullptr; cap = 0;
+    }
+};
+
+// a candidate list of a batched search: n global keys, keys == nullptr for keys 0 .. n - 1
+struct NnList {
+    const int *keys;
+    int n;
+};
+
+// `count` queries in one call: query i is row qkey[i] against the prefix [0, limit[i]) of lists[which[i]] (limit[i] <= its n).
+// The queries are grouped by list and run in groups of 16 back to back on the stream, then the finishing kernel; ONE device-to-host
+// copy and ONE synchronisation for the whole call.  out[i]: as NnManyResult says, in the caller's order.
+template <class H>
+int nearest_many_locked(H *h, const int *qkey, const int *limit, const int *which, const NnList lists[2], int count, int report_dims,
+                        NnManyResult *out)
+{
+    constexpr int DIM = decltype(h->db)::kDim;
+    if (count <= 0) return SCL_OK;
+    std::vector<int> order((size_t)count);
+    int seg[3] = {0, 0, count}, used[2] = {0, 0};
+    for (int i = 0; i < count; ++i) {
+        seg[1] += which[i] == 0;
+        used[which[i]] = std::max(used[which[i]], limit[i]);
+    }
+    for (int i = 0, a = 0, b = seg[1]; i < count; ++i) order[(size_t)(which[i] == 0 ? a++ : b++)] = i;
+    // the prefixes of the lists the queries reach, one after the other in d_list
+    int off[2] = {-1, -1};
+    size_t keys = 0;
+    for (int l = 0; l < 2; ++l)
+        if (lists[l].keys && used[l] > 0) { off[l] = (int)keys; keys += (size_t)used[l]; }
+    if (keys > h->list_cap) {
+        h->list_cap = 0;
+        const size_t c = keys + keys / 2 + 256;
+        int rc = dev_regrow(h, &h->d_list, c);
+        if (rc) return rc;
+        h->list_cap = c;
+    }
+    NnManyWork &w = h->many;
+    if ((size_t)count > w.cap) {
+        w.cap = 0;
+        const size_t c = (size_t)count + (size_t)count / 2 + 256;
+        int rc;
+        if ((rc = dev_regrow(h, &w.d_q, 3 * c)) || (rc = dev_regrow(h, &w.d_best, c)) || (rc = dev_regrow(h, &w.d_res, c))) return rc;
+        w.cap = c;
+    }
+    std::vector<int> hq(3 * (size_t)count);
+    for (int j = 0; j < count; ++j) {
+        const int i = order[(size_t)j];
+        hq[(size_t)j] = qkey[i]; hq[(size_t)count + j] = limit[i]; hq[2 * (size_t)count + j] = off[which[i]];
+    }
+    for (int l = 0; l < 2; ++l)
+        if (off[l] >= 0)
+            SCL_HIP(h, hipMemcpyAsync(h->d_list + off[l], lists[l].keys, sizeof(int) * (size_t)used[l], hipMemcpyHostToDevice, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(w.d_q, hq.data(), sizeof(int) * hq.size(), hipMemcpyHostToDevice, h->stream));
+    SCL_HIP(h, hipMemsetAsync(w.d_best, 0xff, sizeof(unsigned long long) * (size_t)count, h->stream));
+    const int *d_qkey = w.d_q, *d_limit = w.d_q + count, *d_off = w.d_q + 2 * (size_t)count;
+    for (int l = 0; l < 2; ++l)
+        for (int s = seg[l]; s < seg[l + 1]; s += kDetectGroup) {
+            const int G = std::min(kDetectGroup, seg[l + 1] - s);
+            int n = 0;
+            for (int j = s; j < s + G; ++j) n = std::max(n, hq[(size_t)count + j]);
+            if (n <= 0) continue;                                      // every prefix of the group empty: best stays unset
+            hipLaunchKernelGGL(nn_l2_many_kernel<DIM>, dim3((unsigned)((n + kManyTile - 1) / kManyTile)), dim3(kManyTile), 0, h->stream,
+                               h->db.d_db, off[l] >= 0 ? h->d_list + off[l] : nullptr, n, d_qkey + s, d_limit + s, G, w.d_best + s);
+        }
+    hipLaunchKernelGGL(nn_finish_many_kernel<DIM>, dim3((unsigned)((count + kNnThreads - 1) / kNnThreads)), dim3(kNnThreads), 0, h->stream,
+                       h->db.d_db, h->d_list, d_qkey, d_off, w.d_best, count, report_dims, w.d_res);
+    SCL_HIP(h, hipGetLastError());
+    std::vector<NnManyResult> res((size_t)count);
+    SCL_HIP(h, hipMemcpyAsync(res.data(), w.d_res, sizeof(NnManyResult) * (size_t)count, hipMemcpyDeviceToHost, h->stream));
+    SCL_HIP(h, hipStreamSynchronize(h->stream));
+    for (int j = 0; j < count; ++j) out[order[(size_t)j]] = res[(size_t)j];
+    return SCL_OK;
+}
+
+// the detections' answers from the search results, as the single calls give them: nothing searched -> (-1, +inf); every distance
+// NaN -> (-1, that NaN); else the reported distance, and the loop (the position for intra, the key for inter) when it is below
+// dist_thres, compared in double.  dists may be null
+template <class H> void report_many(const H *h, const NnManyResult *res, int count, bool local_ids, int *loop_ids, float *dists)
+{
+    for (int i = 0; i < count; ++i) {
+        const NnManyResult &r = res[i];
+        int loop = -1;
+        float d = INFINITY;
+        if (r.pos >= 0) {
+            if (std::isnan(r.d2)) d = r.d2;
+            else {
+                d = r.dist;
+                if ((double)d < h->cfg.dist_thres) loop = local_ids ? r.pos : r.key;
+            }
+        }
+        loop_ids[i] = loop;
+        if (dists) dists[i] = d;
+    }
+}
+
+// detect_intra for curs[0 .. count): every cur validated first, then one batched search over this robot's keys
+template <class H> int detect_intra_many_locked(H *h, const int *curs, int count, int report_dims, int *loop_ids, float *dists)
+{
+    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
+    for (int i = 0; i < count; ++i)
+        if (curs[i] < 0 || curs[i] >= (int)mine.size()) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_intra: no such keyframe of this robot");
+    std::vector<int> qkey((size_t)count), limit((size_t)count), which((size_t)count, 0);
+    for (int i = 0; i < count; ++i) {
+        qkey[(size_t)i] = mine[(size_t)curs[i]];
+        limit[(size_t)i] = std::max(0, curs[i] - h->cfg.num_exclude_recent);
+    }
+    const NnList lists[2] = {{mine.data(), (int)mine.size()}, {nullptr, 0}};       // ascending keys: position = local index
+    std::vector<NnManyResult> res((size_t)count);
+    int rc = nearest_many_locked(h, qkey.data(), limit.data(), which.data(), lists, count, report_dims, res.data());
+    if (rc) return rc;
+    report_many(h, res.data(), count, true, loop_ids, dists);
+    return SCL_OK;
+}
+
+// detect_inter by M2DP's rule (inter_mode 1 of FPFH and GRSD) for curs[0 .. count): a keyframe of this robot searches the sorted
+// keys of every other robot, a received keyframe searches this robot's
+template <class H> int detect_inter_lists_many_locked(H *h, const int *curs, int count, int report_dims, int *loop_ids, float *dists)
+{
+    for (int i = 0; i < count; ++i)
+        if (curs[i] < 0 || curs[i] >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter: key out of range");
+    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
+    std::vector<int> others;
+    for (int r = 0; r < h->reg.robot_num; ++r)
+        if (r != h->cfg.this_id) others.insert(others.end(), h->reg.keys_of(r).begin(), h->reg.keys_of(r).end());
+    std::sort(others.begin(), others.end());                                      // ties go to the lowest key
+    const NnList lists[2] = {{others.data(), (int)others.size()}, {mine.data(), (int)mine.size()}};
+    std::vector<int> limit((size_t)count), which((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        which[(size_t)i] = h->reg.robots[(size_t)curs[i]] == h->cfg.this_id ? 0 : 1;
+        limit[(size_t)i] = lists[which[(size_t)i]].n;
+    }
+    std::vector<NnManyResult> res((size_t)count);
+    int rc = nearest_many_locked(h, curs, limit.data(), which.data(), lists, count, report_dims, res.data());
+    if (rc) return rc;
+    report_many(h, res.data(), count, false, loop_ids, dists);
+    return SCL_OK;
+}
+
+// detect_inter of the reference (inter_mode 0 of FPFH and GRSD) for curs[0 .. count), the handle's tree_counter and snap_n walked
+// as `count` single calls in order would: before num_exclude_recent + 1 keyframes (-1, 0) and the counter stays; else the snapshot
+// [0, snap_n) is retaken when tree_counter % tree_making_period == 0 and the counter advances.  Both are committed on success only
+template <class H> int detect_inter_snapshot_many_locked(H *h, const int *curs, int count, int report_dims, int *loop_ids, float *dists)
+{
+    for (int i = 0; i < count; ++i)
+        if (curs[i] < 0 || curs[i] >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter: key out of range");
+    if (h->reg.n < h->cfg.num_exclude_recent + 1) {
+        for (int i = 0; i < count; ++i) { loop_ids[i] = -1; if (dists) dists[i] = 0.0f; }
+        return SCL_OK;
+    }
+    int counter = h->tree_counter, snap_n = h->snap_n;
+    std::vector<int> limit((size_t)count), which((size_t)count, 0);
+    for (int i = 0; i < count; ++i) {
+        if (counter % h->cfg.tree_making_period == 0) snap_n = h->reg.n - h->cfg.num_exclude_recent;
+        counter += 1;
+        limit[(size_t)i] = snap_n;
+    }
+    const NnList lists[2] = {{nullptr, h->reg.n}, {nullptr, 0}};
+    std::vector<NnManyResult> res((size_t)count);
+    int rc = nearest_many_locked(h, curs, limit.data(), which.data(), lists, count, report_dims, res.data());
+    if (rc) return rc;
+    h->tree_counter = counter; h->snap_n = snap_n;
+    report_many(h, res.data(), count, false, loop_ids, dists);
+    return SCL_OK;
+}
+
+// save_from_wire for `count` rows: every robot id validated, the database grown once, the rows copied in one transfer, then committed
+template <class H> int save_from_wire_many_locked(H *h, const float *values, const int8_t *robots, const int *indexs, int count)
+{
+    constexpr int DIM = decltype(h->db)::kDim;
+    for (int i = 0; i < count; ++i)
+        if (int rc = check_robot(h, robots[i], SCL_ERR_INVALID_ARG)) return rc;
+    if (count == 0) return SCL_OK;
+    int rc = h->db.grow(h, h->reg.n + count);
+    if (rc) return rc;
+    SCL_HIP(h, hipMemcpyAsync(h->db.row(h->reg.n), values, sizeof(float) * DIM * (size_t)count, hipMemcpyHostToDevice, h->stream));
+    SCL_HIP(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < count; ++i) h->reg.commit(robots[i], indexs[i]);
+    return SCL_OK;
+}
+
+// make_and_save_many, then on the same stream the intra detection of every new keyframe of this robot; entries of other robots
+// answer (-1, +inf).  An invalid cloud: nothing stored, nothing detected, the outputs untouched
+template <class H, class Check, class Run>
+int make_save_and_detect_locked(H *h, const void *const *clouds, const int *n_points, int stride, const int8_t *robots, const int *indexs,
+                                int count, int report_dims, int *loop_ids, float *dists, float *out_values, int max_group, Check check, Run run)
+{
+    const int first = (int)h->reg.keys_of(h->cfg.this_id).size();
+    int rc = make_and_save_many_locked(h, clouds, n_points, stride, robots, indexs, count, out_values, max_group, check, run);
+    if (rc) return rc;
+    std::vector<int> curs, at;
+    for (int i = 0; i < count; ++i)
+        if (robots[i] == h->cfg.this_id) { curs.push_back(first + (int)curs.size()); at.push_back(i); }
+    std::vector<int> loops(curs.size());
+    std::vector<float> ds(curs.size());
+    if ((rc = detect_intra_many_locked(h, curs.data(), (int)curs.size(), report_dims, loops.data(), ds.data()))) return rc;
+    for (int i = 0; i < count; ++i) { loop_ids[i] = -1; if (dists) dists[i] = INFINITY; }
+    for (size_t j = 0; j < at.size(); ++j) { loop_ids[at[j]] = loops[j]; if (dists) dists[at[j]] = ds[j]; }
     return SCL_OK;
 }
 

@@ -57,6 +57,8 @@ def main():
     for q in range(a.queries):
         det.detect_inter(a.keyframes - 1 - (q % 100))
     det_us = (time.perf_counter() - t0) / a.queries * 1e6
+    from bench_plugin_detect import time_detect
+    many = time_detect(det, "inter", a.keyframes, a.queries)             # the batch form at 16 and 256 queries, [min, median, max]
     chk_ms = None
     if a.checker_scans > 0:
         import fpfh_checker as fc
@@ -70,6 +72,7 @@ def main():
         "device_us_per_scan": round(dev_us, 2), "wall_us_per_scan": round(wall / scans * 1e6, 2),
         "candidates_per_point": round((c1 - c0) / max(1, p1 - p0), 1),
         "detect_inter_us_at_keyframes": round(det_us, 2), "keyframes": a.keyframes,
+        "detect_inter_many_us_per_query": {"16": many["detect_inter_many_us_per_query_at_16"], "256": many["detect_inter_many_us_per_query_at_256"]},
         "checker_ms_per_scan": chk_ms,
     }))
     eng.close(); det.close()

@@ -50,6 +50,7 @@ def main():
     ap.add_argument("--leaf", type=float, default=0.4)
     ap.add_argument("--groups", type=int, default=4, help="timed launch groups of 16 scans per repetition")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--keyframes", type=int, default=10000, help="stored keyframes of the detection timing")
     ap.add_argument("--checker", type=int, default=1, help="0: skip the CPU checker's one-core time")
     a = ap.parse_args()
     from scl_slam_amd import GrsdEngine, ScanContextEngine
@@ -71,6 +72,18 @@ def main():
             t0 = time.perf_counter()
             gc.describe(clouds[0], threads=1)
             out[name]["checker_one_core_ms_per_scan"] = round((time.perf_counter() - t0) * 1e3, 1)
+    # detect_inter over --keyframes stored keyframes (from the wire: 21 floats each), the reference's mode: the single call and the
+    # batch form at 16 and 256 queries, [min, median, max]
+    from bench_plugin_detect import time_detect, wire_rows
+    det = GrsdEngine()
+    rows = wire_rows("grsd", a.keyframes)
+    for k in range(a.keyframes):
+        det.save_from_wire(rows[k], 0, k)
+    many = time_detect(det, "inter", a.keyframes, 200, max(5, a.reps))
+    det.close()
+    out["keyframes"] = a.keyframes
+    out["detect_inter_us_at_keyframes"] = many["detect_inter_us_per_query"]
+    out["detect_inter_many_us_per_query"] = {"16": many["detect_inter_many_us_per_query_at_16"], "256": many["detect_inter_many_us_per_query_at_256"]}
     print(json.dumps(out))
 
 

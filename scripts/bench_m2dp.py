@@ -53,6 +53,8 @@ def main():
     for q in range(a.queries):
         det.detect_intra(a.keyframes - 1 - (q % 100))
     det_us = (time.perf_counter() - t0) / a.queries * 1e6
+    from bench_plugin_detect import time_detect
+    many = time_detect(det, "intra", a.keyframes, a.queries)             # the batch form at 16 and 256 queries, [min, median, max]
     t0 = time.perf_counter()
     for i in range(a.checker_scans):
         mc.signature(clouds[i])
@@ -63,6 +65,7 @@ def main():
         "decisions_per_s": round((d1 - d0) / ((us1 - us0) * 1e-6), 1) if us1 > us0 else None,
         "exact_path_share": (e1 - e0) / max(1, d1 - d0),
         "detect_intra_us_at_keyframes": round(det_us, 2), "keyframes": a.keyframes,
+        "detect_intra_many_us_per_query": {"16": many["detect_intra_many_us_per_query_at_16"], "256": many["detect_intra_many_us_per_query_at_256"]},
         "checker_ms_per_scan": round(chk_ms, 1),
     }))
     eng.close(); det.close()
