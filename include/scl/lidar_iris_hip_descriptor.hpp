@@ -86,6 +86,82 @@ public:
         return vT;
     }
 
+    // the batch form: scans[i] appended as (robots[i], indexs[i]); returns scans.size() * (rows * cols + rows) floats
+    std::vector<float> makeAndSaveDescriptorsAndKeys(const std::vector<const pcl::PointCloud<pcl::PointXYZI> *> &scans,
+                                                     const std::vector<int8_t> &robots, const std::vector<int> &indexs)
+    {
+        std::vector<float> v(scans.size() * static_cast<size_t>(values_), 0.0f);
+        if (robots.size() != scans.size() || indexs.size() != scans.size()) {
+            std::fprintf(stderr, "[lidar_iris_hip_descriptor] makeAndSaveDescriptorsAndKeys: %zu scans, %zu robots, %zu indexs\n",
+                         scans.size(), robots.size(), indexs.size());
+            return v;
+        }
+        std::vector<const void *> ptrs(scans.size());
+        std::vector<int> counts(scans.size());
+        for (size_t i = 0; i < scans.size(); ++i) { ptrs[i] = scans[i]->points.data(); counts[i] = static_cast<int>(scans[i]->points.size()); }
+        report(scl_iris_make_and_save_many(iris_, ptrs.data(), counts.data(), static_cast<int>(sizeof(pcl::PointXYZI)), robots.data(),
+                                           indexs.data(), static_cast<int>(scans.size()), v.data()),
+               "makeAndSaveDescriptorsAndKeys");
+        return v;
+    }
+
+    // the batch form of saveDescriptorAndKey: robots.size() vectors of rows * cols + rows floats, one after the other in `iris`
+    void saveDescriptorsAndKeys(const float *iris, const std::vector<int8_t> &robots, const std::vector<int> &indexs)
+    {
+        if (robots.size() != indexs.size()) {
+            std::fprintf(stderr, "[lidar_iris_hip_descriptor] saveDescriptorsAndKeys: %zu robots, %zu indexs\n", robots.size(), indexs.size());
+            return;
+        }
+        report(scl_iris_save_from_wire_many(iris_, iris, robots.data(), indexs.data(), static_cast<int>(robots.size())), "saveDescriptorsAndKeys");
+    }
+
+    // the batch forms (scl_iris.h "THE BATCH FORMS"): what the single calls in the same order return.
+    // {local index of the loop keyframe or -1, column shift} per entry of curPtrs; on an error every entry is {-1, 0}
+    std::vector<std::pair<int, float>> detectIntraLoopClosureIDs(const std::vector<int> &curPtrs)
+    {
+        std::vector<int> loops(curPtrs.size(), -1);
+        std::vector<float> biases(curPtrs.size(), 0.0f);
+        const bool ok = report(scl_iris_detect_intra_many(iris_, curPtrs.data(), static_cast<int>(curPtrs.size()), loops.data(), biases.data(), nullptr),
+                               "detectIntraLoopClosureIDs");
+        return pairs(loops, biases, ok);
+    }
+
+    // {global key of the loop keyframe or -1, column shift} per entry of curPtrs
+    std::vector<std::pair<int, float>> detectInterLoopClosureIDs(const std::vector<int> &curPtrs)
+    {
+        std::vector<int> loops(curPtrs.size(), -1);
+        std::vector<float> biases(curPtrs.size(), 0.0f);
+        const bool ok = report(scl_iris_detect_inter_many(iris_, curPtrs.data(), static_cast<int>(curPtrs.size()), loops.data(), biases.data(), nullptr),
+                               "detectInterLoopClosureIDs");
+        return pairs(loops, biases, ok);
+    }
+
+    // scans[i] appended as (robots[i], indexs[i]), then the intra detection of every new keyframe of this robot in the same call:
+    // {local index of the loop keyframe or -1, column shift} per scan ({-1, 0} for another robot's); descriptors: lastDescriptors()
+    std::vector<std::pair<int, float>> makeSaveAndDetect(const std::vector<const pcl::PointCloud<pcl::PointXYZI> *> &scans,
+                                                         const std::vector<int8_t> &robots, const std::vector<int> &indexs)
+    {
+        std::vector<int> loops(scans.size(), -1);
+        std::vector<float> biases(scans.size(), 0.0f);
+        last_.assign(scans.size() * static_cast<size_t>(values_), 0.0f);
+        if (robots.size() != scans.size() || indexs.size() != scans.size()) {
+            std::fprintf(stderr, "[lidar_iris_hip_descriptor] makeSaveAndDetect: %zu scans, %zu robots, %zu indexs\n", scans.size(), robots.size(),
+                         indexs.size());
+            return pairs(loops, biases, false);
+        }
+        std::vector<const void *> ptrs(scans.size());
+        std::vector<int> counts(scans.size());
+        for (size_t i = 0; i < scans.size(); ++i) { ptrs[i] = scans[i]->points.data(); counts[i] = static_cast<int>(scans[i]->points.size()); }
+        const bool ok = report(scl_iris_make_save_and_detect(iris_, ptrs.data(), counts.data(), static_cast<int>(sizeof(pcl::PointXYZI)),
+                                                          robots.data(), indexs.data(), static_cast<int>(scans.size()), loops.data(),
+                                                          biases.data(), nullptr, last_.data()),
+                               "makeSaveAndDetect");
+        return pairs(loops, biases, ok);
+    }
+
+    // the descriptors of the last makeSaveAndDetect: scans.size() * (rows * cols + rows) floats
+    const std::vector<float> &lastDescriptors() const { return last_; }
+
     // descriptor.h:27 / 1026-1044 (iris = global_descriptor.values.data(), DM.h:627)
     void saveDescriptorAndKey(const float *iris, const int8_t robot, const int index) override
     {
@@ -140,6 +216,14 @@ private:
         return false;
     }
 
+    static std::vector<std::pair<int, float>> pairs(const std::vector<int> &loops, const std::vector<float> &biases, bool ok)
+    {
+        std::vector<std::pair<int, float>> out(loops.size(), std::pair<int, float>(-1, 0.0f));
+        for (size_t i = 0; ok && i < loops.size(); ++i) out[i] = std::pair<int, float>(loops[i], biases[i]);
+        return out;
+    }
+
     scl_iris *iris_ = nullptr;
     int values_ = 0;
+    std::vector<float> last_;
 };

@@ -116,6 +116,38 @@ int  scl_iris_compare(scl_iris *h, int key1, const int *cand, int n, float *dis,
 /* every column shift 0 .. cols-1 (first minimum): what cfg.shift_search = 1 uses */
 int  scl_iris_hamming_all_shifts(scl_iris *h, int key1, const int *cand, int n, float *dis, int *bias);
 
+/*
+ * THE BATCH FORMS.  The contract is the one include/scl_plugin_batch.h states for the float-row plugins, with a shift beside
+ * every loop: each call answers, element by element and bit for bit, what the same single calls made in array order answer,
+ * and leaves the handle in the same state (images, row keys, templates, registry).  count == 0 is SCL_OK; dists and out_values
+ * may be NULL.  Everything is validated before anything runs: a bad point layout or robot id in the builders returns
+ * SCL_ERR_INVALID_ARG, one cur out of range in the detections SCL_ERR_OUT_OF_RANGE -- nothing stored, nothing detected, no
+ * output written, no state changed.  With odd rows or cols and shift_search = 0 a detection batch returns SCL_ERR_UNSUPPORTED
+ * whenever one of the single calls in order would (a query with at least one row-key candidate), outputs untouched.
+ *   * make_and_save_many: `count` make_and_save calls; out_values = count * (rows*cols + rows) floats.  The scans run in launch
+ *     groups of SCL_IRIS_MAX_GROUP; the host waits for the device once per call (once more when the database has to grow).
+ *   * save_from_wire_many: `count` save_from_wire calls; values = count * (rows*cols + rows) floats, one transfer, decoded on the
+ *     device as cfg.wire_decode says.
+ *   * detect_*_many: launch groups of SCL_IRIS_DETECT_GROUP queries; candidate search, selection, Hamming matching and the choice
+ *     of the best candidate run on the device.  The host waits once per launch group with shift_search = 1; with shift_search = 0
+ *     twice more per pass of the FFT shift estimate (its rotation / scale and its translation pass through the host's C library, as
+ *     in the single call; one pass per group unless the work memory bound of iris.hip splits it).
+ *   * make_save_and_detect: make_and_save_many followed, in the same call and on the same stream, by detect_intra of every new
+ *     keyframe whose robots[i] is this_id (loop_ids LOCAL); entries of other robots answer loop -1, bias 0, distance 10000000.
+ *     A later query of the call sees the keyframes the call stored before it.  An invalid cloud: nothing stored, outputs untouched.
+ */
+#define SCL_IRIS_MAX_GROUP     16   /* scans per launch group of the builders      */
+#define SCL_IRIS_DETECT_GROUP  16   /* queries per launch group of the detections  */
+
+int scl_iris_make_and_save_many(scl_iris *h, const void *const *clouds, const int *n_points, int stride_bytes,
+                                const int8_t *robots, const int *indexs, int count, float *out_values);
+int scl_iris_save_from_wire_many(scl_iris *h, const float *values, const int8_t *robots, const int *indexs, int count);
+int scl_iris_detect_intra_many(scl_iris *h, const int *curs, int count, int *loop_ids, float *biases, float *dists);
+int scl_iris_detect_inter_many(scl_iris *h, const int *curs, int count, int *loop_ids, float *biases, float *dists);
+int scl_iris_make_save_and_detect(scl_iris *h, const void *const *clouds, const int *n_points, int stride_bytes,
+                                  const int8_t *robots, const int *indexs, int count,
+                                  int *loop_ids, float *biases, float *dists, float *out_values);
+
 #ifdef __cplusplus
 }
 #endif

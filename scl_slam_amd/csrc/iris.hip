@@ -297,9 +297,375 @@ __global__ void fm_warp_kernel(const float *src, const double *mats, int R, int 
     dst[(size_t)blockIdx.y * n + i] = fm_bilinear32(src + (size_t)blockIdx.y * n, R, C, X, Y);
 }
 
+
+// ---- the batch forms (scl_iris.h "THE BATCH FORMS") ------------------------------------------------------------------------------
+// The kernels below restate the single kernels over a launch group: integer results (cells, popcounts, bit words) are exact
+// however they are partitioned, and every floating-point sum keeps the single kernel's order, so a batch call stores and answers
+// the single calls' bits.  The single kernels above stay as they are: the tests hold these to them.
+constexpr int kIrisMaxGroup = SCL_IRIS_MAX_GROUP, kIrisDetectGroup = SCL_IRIS_DETECT_GROUP;
+constexpr int kEncodeStageBytes = 32 * 1024;               // image rows a workgroup of iris_encode_many_kernel holds in LDS at a time
+
+// iris_image_kernel over a launch group: blockIdx.y = scan, its points at pts + offs[scan], its planes at scan * rows * cols
+__global__ void iris_image_many_kernel(const unsigned char *pts, const unsigned long long *offs, const int *counts, int stride, int rows,
+                                       int cols, double add, unsigned int *cells, int *zmax)
+{
+    const int g = blockIdx.y, n = counts[g];
+    const unsigned char *p = pts + offs[g];
+    unsigned int *cg = cells + (size_t)g * rows * cols;
+    int *zg = zmax + (size_t)g * rows * cols;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const float *f = reinterpret_cast<const float *>(p + (size_t)i * (size_t)stride);
+        const float x = f[0], y = f[1], z = f[2];
+        const float dis = sqrtf(x * x + y * y);
+        const float arc = (float)((double)(iris_atan2f(z, dis) * 180.0f) / 3.14159265358979323846 + add);
+        const float yaw = (float)((double)(iris_atan2f(y, x) * 180.0f) / 3.14159265358979323846 + 180);
+        const int q_dis = clampi(floor_to_int_x86((double)dis), 0, rows - 1);
+        const int q_arc = clampi(floor_to_int_x86((double)(arc / 4.0f)), 0, 7);
+        const int q_yaw = clampi(floor_to_int_x86((double)yaw + 0.5), 0, cols - 1);
+        const int cell = q_dis * cols + q_yaw;
+        atomicOr(&cg[cell], 1u << q_arc);
+        if (z > 0.0f) atomicMax(&zg[cell], __float_as_int(z));
+    }
+}
+
+// grid (rows, scans): the byte image and the row key of scan g straight into database slot slot0 + g.  The heights of a row go
+// through LDS so that the one thread that adds them, left to right as iris_rowkey_kernel does, reads them at LDS latency
+__global__ __launch_bounds__(128) void iris_finish_many_kernel(const int *zmax, const unsigned int *cells, int rows, int cols, int slot0,
+                                                               float *rowkeys, unsigned char *images)
+{
+    extern __shared__ float zrow[];                        // [cols]
+    const int r = blockIdx.x, g = blockIdx.y;
+    const size_t src = ((size_t)g * rows + r) * cols, slot = (size_t)slot0 + g;
+    for (int c = threadIdx.x; c < cols; c += blockDim.x) {
+        images[(slot * rows + r) * cols + c] = (unsigned char)cells[src + c];
+        zrow[c] = __int_as_float(zmax[src + c]);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.0f;
+        for (int c = 0; c < cols; ++c) s += zrow[c];
+        rowkeys[slot * rows + r] = s / (float)cols;
+    }
+}
+
+// iris_encode_kernel over a launch group: grid (cols, keyframes), the image of slot0 + blockIdx.y read from the database.  The image
+// rows go through LDS, chunk_rows at a time (all of them where rows * cols fits kEncodeStageBytes: 28.8 KB at 80 x 360), as words of
+// four pixels at a row pitch of whole words: a thread walks its row a word at a time and skips a zero word at once -- the pixels it
+// does add come in ascending m with zeros skipped, iris_encode_kernel's sum.  LDS: [2 * words] bit words, then the rows
+__global__ __launch_bounds__(256) void iris_encode_many_kernel(const unsigned char *images, const double2 *h, int rows, int N, int nscale,
+                                                               unsigned int *T, unsigned int *M, int words, int slot0, int chunk_rows)
+{
+    extern __shared__ unsigned int lds_words[];
+    const int n = blockIdx.x, pw = (N + 3) >> 2;
+    const size_t slot = (size_t)slot0 + blockIdx.y;
+    const unsigned char *image = images + slot * rows * N;
+    unsigned int *img = lds_words + 2 * words;
+    for (int i = threadIdx.x; i < 2 * words; i += blockDim.x) lds_words[i] = 0u;
+    for (int r0 = 0; r0 < rows; r0 += chunk_rows) {
+        const int rc = min(chunk_rows, rows - r0);
+        __syncthreads();                                    // the bit words zeroed; the previous chunk read
+        if ((N & 3) == 0) {                                 // rows start on words (slots and hipMalloc are aligned)
+            const unsigned int *src = reinterpret_cast<const unsigned int *>(image + (size_t)r0 * N);
+            for (int i = threadIdx.x; i < rc * pw; i += blockDim.x) img[i] = src[i];
+        } else {
+            unsigned char *ib = reinterpret_cast<unsigned char *>(img);
+            for (int i = threadIdx.x; i < rc * pw * 4; i += blockDim.x) {
+                const int rr = i / (pw * 4), c = i - rr * (pw * 4);
+                ib[i] = c < N ? image[(size_t)(r0 + rr) * N + c] : (unsigned char)0;
+            }
+        }
+        __syncthreads();
+        for (int job = threadIdx.x; job < nscale * rc; job += blockDim.x) {
+            const int s = job / rc, rr = job - s * rc, r = r0 + rr;
+            const unsigned int *xw = img + rr * pw;
+            const double2 *hs = h + (size_t)s * N;
+            double re = 0.0, im = 0.0;
+            for (int w = 0; w < pw; ++w) {
+                const unsigned int v = xw[w];
+                if (v == 0u) continue;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const unsigned int xv = (v >> (8 * b)) & 255u;
+                    if (xv == 0u) continue;
+                    int d = n - (4 * w + b); d = d < 0 ? d + N : d;
+                    const double2 hv = hs[d];
+                    re += (double)xv * hv.x; im += (double)xv * hv.y;
+                }
+            }
+            const float fre = (float)re, fim = (float)im;
+            const float mag = sqrtf(fre * fre + fim * fim);
+            const int ta = s * rows + r, tb = (s + nscale) * rows + r;
+            if (fre > 0.0f) atomicOr(&lds_words[ta >> 5], 1u << (ta & 31));
+            if (fim > 0.0f) atomicOr(&lds_words[tb >> 5], 1u << (tb & 31));
+            if (mag < 0.0001f) { atomicOr(&lds_words[words + (ta >> 5)], 1u << (ta & 31)); atomicOr(&lds_words[words + (tb >> 5)], 1u << (tb & 31)); }
+        }
+    }
+    __syncthreads();
+    const size_t out = (slot * N + n) * words;
+    for (int i = threadIdx.x; i < words; i += blockDim.x) { T[out + i] = lds_words[i]; M[out + i] = lds_words[words + i]; }
+}
+
+// save_from_wire's decoder: grid (ceil((rows * cols + rows) / 256), vectors).  Pixel (r, c) from r * (cols + 1) + c + 1 (wire_decode 0,
+// D.h:1035; the largest index read is rows * cols + rows - 1) or r * cols + c (1); float -> byte as x86 converts: out of int range
+// or NaN -> 0, else truncation and the low byte.  The tests are explicit: the device's own conversion saturates.  The row key is copied
+__global__ void iris_wire_decode_kernel(const float *values, int rows, int cols, int wire_decode, int slot0, unsigned char *images, float *rowkeys)
+{
+    const int cells = rows * cols, per = cells + rows;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= per) return;
+    const float *v = values + (size_t)blockIdx.y * per;
+    const size_t slot = (size_t)slot0 + blockIdx.y;
+    if (i < cells) {
+        const int r = i / cols, c = i - r * cols;
+        const float f = wire_decode ? v[(size_t)r * cols + c] : v[(size_t)r * (cols + 1) + c + 1];
+        unsigned char b = 0;
+        if (f > -2147483904.0f && f < 2147483648.0f) b = (unsigned char)((unsigned int)(int)f & 255u);
+        images[slot * cells + i] = b;
+    } else {
+        rowkeys[slot * rows + (i - cells)] = v[i];
+    }
+}
+
+// iris_rowkey_d2_kernel for up to kIrisDetectGroup queries that share one candidate list (nn_l2_many_kernel's scheme): query q is
+// keyframe qkey[q] against the prefix list[0 .. limit[q]); a thread owns one candidate, reads its row key once and keeps the
+// queries' running sums in registers, each in iris_rowkey_d2_kernel's order.  LDS: the queries' row keys, [kIrisDetectGroup][rows]
+__global__ __launch_bounds__(256) void iris_rowkey_d2_many_kernel(const float *rowkeys, int rows, const int *qkey, const int *limit, int nq,
+                                                                  const int *list, int n, float *d2 /* [nq][d2_stride] */, int d2_stride)
+{
+    extern __shared__ float qs[];
+    for (int e = threadIdx.x; e < kIrisDetectGroup * rows; e += blockDim.x) {
+        const int q = e / rows;
+        qs[e] = q < nq ? rowkeys[(size_t)qkey[q] * rows + (e - q * rows)] : 0.0f;
+    }
+    __syncthreads();
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *b = rowkeys + (size_t)list[i] * rows;
+    float result[kIrisDetectGroup];
+#pragma unroll
+    for (int q = 0; q < kIrisDetectGroup; ++q) result[q] = 0.0f;
+    int r = 0;
+    for (; r + 3 < rows; r += 4) {
+        const float b0 = b[r], b1 = b[r + 1], b2 = b[r + 2], b3 = b[r + 3];
+#pragma unroll
+        for (int q = 0; q < kIrisDetectGroup; ++q) {
+            const float *a = qs + q * rows + r;
+            const float d0 = __fsub_rn(a[0], b0), d1 = __fsub_rn(a[1], b1), d2v = __fsub_rn(a[2], b2), d3 = __fsub_rn(a[3], b3);
+            const float t = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2v, d2v)), __fmul_rn(d3, d3));
+            result[q] = __fadd_rn(result[q], t);
+        }
+    }
+    for (; r < rows; ++r) {
+        const float b0 = b[r];
+#pragma unroll
+        for (int q = 0; q < kIrisDetectGroup; ++q) {
+            const float d0 = __fsub_rn(qs[q * rows + r], b0);
+            result[q] = __fadd_rn(result[q], __fmul_rn(d0, d0));
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < kIrisDetectGroup; ++q)
+        if (q < nq && i < limit[q]) d2[(size_t)q * d2_stride + i] = result[q];
+}
+
+// The candidate selection of detect_core_locked, one workgroup per query: the m smallest squared distances of d2[q][0 .. limit[q])
+// in ascending order, equal ones by ascending position; d <= eps is skipped when eps > 0 and !(d < FLT_MAX) never enters.  What
+// enters is a non-negative finite float, whose bits order as integers: round c takes the smallest 64-bit (distance bits, position)
+// key above round c - 1's.  cand_pos[q][c] = the position, -1 from the first round that finds nothing
+__global__ __launch_bounds__(256) void iris_select_kernel(const float *d2, int d2_stride, const int *limit, int m, float eps, int *cand_pos)
+{
+    __shared__ unsigned long long part[4];
+    const int q = blockIdx.x, n = limit[q];
+    const float *d = d2 + (size_t)q * d2_stride;
+    unsigned long long prev = 0ull;
+    for (int c = 0; c < m; ++c) {
+        unsigned long long best = ~0ull;
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const float v = d[i];
+            if (eps > 0.0f && v <= eps) continue;
+            if (!(v < FLT_MAX)) continue;
+            const unsigned long long key = ((unsigned long long)__float_as_uint(v) << 32) | (unsigned int)i;
+            if ((c == 0 || key > prev) && key < best) best = key;
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            const unsigned long long o = __shfl_xor(best, off, 64);
+            best = o < best ? o : best;
+        }
+        __syncthreads();                                    // the previous round's partials read
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = best;
+        __syncthreads();
+        best = part[0];
+        for (int w = 1; w < 4; ++w) best = part[w] < best ? part[w] : best;
+        if (best == ~0ull) {                                // uniform over the workgroup
+            for (int j = c + threadIdx.x; j < m; j += 256) cand_pos[(size_t)q * m + j] = -1;
+            return;
+        }
+        if (threadIdx.x == 0) cand_pos[(size_t)q * m + c] = (int)(best & 0xffffffffu);
+        prev = best;
+    }
+}
+
+// cand_pos -> the candidates' global keys and, with passes > 0, compare()'s FftJob list on the device: per (query, candidate) the
+// pass against the candidate as it is and / or turned by 180 columns (roll_first: the roll of the first pass run).  An empty
+// candidate slot gives key -1 and jobs with key0 = -1, which every later kernel skips.  One thread per (query, candidate)
+__global__ void iris_jobs_kernel(const int *cand_pos, const int *qkey, const int *list_off, const int *list, int nq, int m, int passes,
+                                 int roll_first, int *cand_key, FftJob *jobs)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nq * m) return;
+    const int q = i / m, pos = cand_pos[i];
+    const int key = pos < 0 ? -1 : list[list_off[q] + pos];
+    cand_key[i] = key;
+    for (int p = 0; p < passes; ++p) jobs[(size_t)i * passes + p] = FftJob{key, p == 0 ? roll_first : 180, qkey[q]};
+}
+
+// fm_stage_kernel with the job list made on the device: an empty job (key0 < 0) stages zeros, so that the transforms behind it read
+// nothing undefined; its estimate is never used
+__global__ void fm_stage_many_kernel(const unsigned char *images, const FftJob *jobs, int R, int C, float *a0, float *a1)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+    if (i >= R * C) return;
+    const FftJob jb = jobs[j];
+    const size_t n = (size_t)R * C;
+    if (jb.key0 < 0) { a0[(size_t)j * n + i] = 0.0f; a1[(size_t)j * n + i] = 0.0f; return; }
+    const int r = i / C, c = i - r * C;
+    int s0 = (c - jb.roll0) % C; s0 = s0 < 0 ? s0 + C : s0;
+    a0[(size_t)j * n + i] = (float)images[(size_t)jb.key0 * n + (size_t)r * C + s0] * (float)(1.0 / 255.0);
+    a1[(size_t)j * n + i] = (float)images[(size_t)jb.key1 * n + i] * (float)(1.0 / 255.0);
+}
+
+// compare()'s Hamming window of one job per workgroup: the query jobs[j].key1 shifted by est[j] - 2 .. est[j] + 2 against the
+// candidate jobs[j].key0 turned by roll0 columns, as iris_hamming_kernel takes them.  The candidate's T / M words are read once, the
+// query's once per shift (five neighbouring columns); (diff, total) per shift to [j][5]
+__global__ __launch_bounds__(256) void iris_hamming_window_kernel(const unsigned int *T, const unsigned int *M, size_t feat_words, const FftJob *jobs,
+                                                                  const int *est, int N, int words, int trows, int *bits_diff, int *total_bits)
+{
+    __shared__ int part[4][10];
+    const int j = blockIdx.x;
+    const FftJob jb = jobs[j];
+    if (jb.key0 < 0) return;
+    int sh[5];
+#pragma unroll
+    for (int t = 0; t < 5; ++t) { int s = (int)((unsigned int)est[j] - 2u + (unsigned int)t) % N; sh[t] = s < 0 ? s + N : s; }
+    int r2 = jb.roll0 % N; r2 = r2 < 0 ? r2 + N : r2;
+    const unsigned int *T1 = T + (size_t)jb.key1 * feat_words, *M1 = M + (size_t)jb.key1 * feat_words;
+    const unsigned int *T2 = T + (size_t)jb.key0 * feat_words, *M2 = M + (size_t)jb.key0 * feat_words;
+    int acc[10];
+#pragma unroll
+    for (int t = 0; t < 10; ++t) acc[t] = 0;
+    for (int i = threadIdx.x; i < N * words; i += 256) {
+        const int k = i / words, w = i - k * words;
+        int k2 = k - r2; k2 = k2 < 0 ? k2 + N : k2;
+        const unsigned int t2 = T2[(size_t)k2 * words + w], m2 = M2[(size_t)k2 * words + w];
+#pragma unroll
+        for (int t = 0; t < 5; ++t) {
+            int src = k - sh[t]; src = src < 0 ? src + N : src;
+            const unsigned int mask = M1[(size_t)src * words + w] | m2;
+            acc[t] += __popc((T1[(size_t)src * words + w] ^ t2) & ~mask); acc[5 + t] += __popc(mask);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 10; ++t) {
+        for (int off = 32; off > 0; off >>= 1) acc[t] += __shfl_xor(acc[t], off, 64);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][t] = acc[t];
+    }
+    __syncthreads();
+    if (threadIdx.x < 5) {
+        const int t = threadIdx.x;
+        bits_diff[(size_t)j * 5 + t] = part[0][t] + part[1][t] + part[2][t] + part[3][t];
+        total_bits[(size_t)j * 5 + t] = trows * N - (part[0][5 + t] + part[1][5 + t] + part[2][5 + t] + part[3][5 + t]);
+    }
+}
+
+// shift_search = 1: iris_hamming_kernel with the query per candidate slot -- one wave per (slot, column shift), slot = query * m + c
+__global__ __launch_bounds__(64) void iris_hamming_all_many_kernel(const unsigned int *T, const unsigned int *M, size_t feat_words, const int *qkey,
+                                                                   const int *cand_key, int m, int N, int words, int trows, int *bits_diff, int *total_bits)
+{
+    const int job = blockIdx.x, slot = job / N, sh = job - slot * N;
+    const int key2 = cand_key[slot];
+    if (key2 < 0) return;
+    const int key1 = qkey[slot / m];
+    const unsigned int *T1 = T + (size_t)key1 * feat_words, *M1 = M + (size_t)key1 * feat_words;
+    const unsigned int *T2 = T + (size_t)key2 * feat_words, *M2 = M + (size_t)key2 * feat_words;
+    int diff = 0, masked = 0;
+    for (int i = threadIdx.x; i < N * words; i += 64) {
+        const int k = i / words, w = i - k * words;
+        int src = k - sh; src = src < 0 ? src + N : src;
+        const unsigned int mask = M1[(size_t)src * words + w] | M2[i];
+        diff += __popc((T1[(size_t)src * words + w] ^ T2[i]) & ~mask); masked += __popc(mask);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { diff += __shfl_xor(diff, off, 64); masked += __shfl_xor(masked, off, 64); }
+    if (threadIdx.x == 0) { bits_diff[job] = diff; total_bits[job] = trows * N - masked; }
+}
+
+// what a batched detection answers per query: the best candidate's position in the query's list (-1: none), its shift and distance
+struct IrisAnswer { int pos, bias; float dis; };
+
+// One thread per query of the launch group, the host's steps behind the Hamming counts: per job the selection over its shifts
+// (hamming_jobs_locked: cur = diff / total correctly rounded; total == 0 resets the running best to NaN in window mode and is
+// skipped in the exhaustive mode; else cur < best || isnan(best)), compare()'s merge by match_num in C's integer arithmetic, and
+// the best candidate in candidate order with strict < from 10000000 (a NaN never wins).  window: per = 5 shifts est - 2 + t and
+// `passes` jobs per candidate; else per = N shifts t and one job per candidate
+__global__ void iris_finish_detect_kernel(const int *cand_pos, const int *est, const int *bits_diff, const int *total_bits, int nq, int m, int per,
+                                          int window, int passes, int match_num, IrisAnswer *out)
+{
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    IrisAnswer a = {-1, 0, 10000000.0f};
+    for (int c = 0; c < m; ++c) {
+        const size_t slot = (size_t)q * m + c;
+        if (cand_pos[slot] < 0) break;                      // the empty slots trail
+        float ds[2] = {0.0f, 0.0f}; int bs[2] = {0, 0};
+        for (int p = 0; p < passes; ++p) {
+            const size_t j = slot * passes + p;
+            float best = NAN; int b = -1;
+            for (int t = 0; t < per; ++t) {
+                const int total = total_bits[j * per + t];
+                if (total == 0) { if (window) best = NAN; continue; }
+                const float cur = __fdiv_rn((float)bits_diff[j * per + t], (float)total);
+                if (cur < best || isnan(best)) { best = cur; b = window ? (int)((unsigned int)est[j] - 2u + (unsigned int)t) : t; }
+            }
+            ds[p] = best; bs[p] = b;
+        }
+        float dis = ds[0]; int bias = bs[0];
+        if (window && match_num == 2) { if (!(ds[0] < ds[1])) { dis = ds[1]; bias = (bs[1] + 180) % 360; } }     // D.h:986-997
+        else if (window && match_num == 1) bias = (bs[0] + 180) % 360;                                            // the one pass run is the second
+        if (dis < a.dis) { a.dis = dis; a.pos = cand_pos[slot]; a.bias = bias; }
+    }
+    out[q] = a;
+}
+
+}  // namespace
+
+namespace {
+
+// a device work buffer of the batch forms: regrown on demand (nothing is kept), never shrunk
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;                                            // bytes
+    template <class T> T *as() const { return static_cast<T *>(p); }
+};
+
+// The batch forms' own work buffers: the single calls never see them, and a later single call finds its buffers as it left them
+struct IrisBatchWork {
+    DevBuf points, planes, table;                              // builders: a group's clouds, its cell | zmax planes, the offset | count tables
+    DevBuf wire;                                               // save_from_wire_many: the vectors as received
+    DevBuf list, query, d2, cand, jobs, est, counts, answers;  // detections
+    DevBuf fm, fres, fmats;                                    // FFT shift estimate: the work planes of one pass, its results and matrices
+    void release()
+    {
+        for (DevBuf *b : {&points, &planes, &table, &wire, &list, &query, &d2, &cand, &jobs, &est, &counts, &answers, &fm, &fres, &fmats}) {
+            if (b->p) (void)hipFree(b->p);
+            b->p = nullptr; b->cap = 0;
+        }
+    }
+};
+
 }  // namespace
 
 struct scl_iris {
+    IrisBatchWork bw;
     scl_iris_config cfg;
     int device = 0;
     hipStream_t stream = nullptr;
@@ -614,6 +980,370 @@ int detect_core_locked(scl_iris *h, int cur, const std::vector<int> &list, int *
     return SCL_OK;
 }
 
+
+// ---- the batch forms: host side ------------------------------------------------------------------------------------------------
+int reserve(scl_iris *h, DevBuf &b, size_t bytes)
+{
+    if (bytes <= b.cap) return SCL_OK;
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr; b.cap = 0;
+    const size_t cap = bytes + bytes / 4 + 256;
+    SCL_HIP(h, hipMalloc(&b.p, cap));
+    b.cap = cap;
+    return SCL_OK;
+}
+
+// templates of the keyframes in slots slot0 .. slot0 + count - 1 from their stored images
+int encode_slots_locked(scl_iris *h, int slot0, int count)
+{
+    const int rows = h->cfg.rows, cols = h->cfg.cols, pitch = (cols + 3) & ~3;
+    int chunk_rows = kEncodeStageBytes / pitch;
+    chunk_rows = chunk_rows < 1 ? 1 : (chunk_rows > rows ? rows : chunk_rows);
+    const size_t lds = sizeof(unsigned int) * (2 * (size_t)h->words + (size_t)chunk_rows * (pitch / 4));
+    for (int s = 0; s < count; s += 16384) {
+        const int G = std::min(16384, count - s);
+        hipLaunchKernelGGL(iris_encode_many_kernel, dim3((unsigned)cols, (unsigned)G), dim3(256), lds, h->stream, h->d_images, h->d_h, rows, cols,
+                           h->cfg.nscale, h->d_T, h->d_M, h->words, slot0 + s, chunk_rows);
+    }
+    SCL_HIP(h, hipGetLastError());
+    return SCL_OK;
+}
+
+// make_and_save for `count` scans: everything validated first, the database grown once, then launch groups of kIrisMaxGroup scans
+// -- clouds to the device (neighbours in host memory in one transfer), one image launch over the group's points, one finishing
+// launch into the slots, one encode launch -- and ONE wait for the device at the end, behind the copies for out_values
+int make_and_save_many_locked(scl_iris *h, const void *const *clouds, const int *n_points, int stride, const int8_t *robots, const int *indexs,
+                              int count, float *out_values)
+{
+    if (count < 0 || (count > 0 && (!clouds || !n_points || !robots || !indexs))) return fail(h, SCL_ERR_INVALID_ARG, "make_and_save_many: null array");
+    for (int i = 0; i < count; ++i) {
+        if (n_points[i] < 0 || stride < 12 || (stride & 3) || (n_points[i] > 0 && !clouds[i])) return fail(h, SCL_ERR_INVALID_ARG, "bad point layout");
+        if (int rc = check_robot(h, robots[i], SCL_ERR_INVALID_ARG)) return rc;
+    }
+    if (count == 0) return SCL_OK;
+    int rc = grow(h, h->reg.n + count);
+    if (rc) return rc;
+    const int rows = h->cfg.rows, cols = h->cfg.cols, slot0 = h->reg.n;
+    const size_t cells = (size_t)rows * cols;
+    // where every scan's points start in its group's buffer, and how many there are: one table for the call
+    std::vector<unsigned long long> offs((size_t)count);
+    size_t group_bytes = 0;
+    for (int s = 0; s < count; s += kIrisMaxGroup) {
+        size_t at = 0;
+        for (int i = s; i < std::min(count, s + kIrisMaxGroup); ++i) { offs[(size_t)i] = at; at += (size_t)n_points[i] * stride; }
+        group_bytes = std::max(group_bytes, at);
+    }
+    const int gmax = std::min(count, kIrisMaxGroup);
+    if ((rc = reserve(h, h->bw.points, group_bytes)) || (rc = reserve(h, h->bw.planes, 2 * sizeof(int) * cells * gmax)) ||
+        (rc = reserve(h, h->bw.table, (sizeof(unsigned long long) + sizeof(int)) * (size_t)count))) return rc;
+    unsigned long long *d_offs = h->bw.table.as<unsigned long long>();
+    int *d_counts = reinterpret_cast<int *>(d_offs + count);
+    SCL_HIP(h, hipMemcpyAsync(d_offs, offs.data(), sizeof(unsigned long long) * (size_t)count, hipMemcpyHostToDevice, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(d_counts, n_points, sizeof(int) * (size_t)count, hipMemcpyHostToDevice, h->stream));
+    unsigned char *d_pts = h->bw.points.as<unsigned char>();
+    const bool beams_ok = h->cfg.nscan == 16 || h->cfg.nscan == 64;            // D.h:538 / 560: other beam counts leave the image empty
+    for (int s = 0; s < count; s += kIrisMaxGroup) {
+        const int G = std::min(kIrisMaxGroup, count - s);
+        unsigned int *d_cells = h->bw.planes.as<unsigned int>();
+        int *d_zmax = reinterpret_cast<int *>(d_cells + cells * G);
+        int nmax = 0;
+        for (int i = s; i < s + G;) {                                          // a run of clouds that lie back to back: one transfer
+            const unsigned char *p0 = static_cast<const unsigned char *>(clouds[i]);
+            size_t bytes = (size_t)n_points[i] * stride;
+            int e = i + 1;
+            while (e < s + G && (n_points[e] == 0 || (bytes > 0 && static_cast<const unsigned char *>(clouds[e]) == p0 + bytes))) { bytes += (size_t)n_points[e] * stride; ++e; }
+            if (bytes) SCL_HIP(h, hipMemcpyAsync(d_pts + offs[(size_t)i], p0, bytes, hipMemcpyHostToDevice, h->stream));
+            for (; i < e; ++i) nmax = std::max(nmax, n_points[i]);
+        }
+        SCL_HIP(h, hipMemsetAsync(d_cells, 0, 2 * sizeof(int) * cells * G, h->stream));
+        if (nmax > 0 && beams_ok) {
+            int blocks = (nmax + 255) / 256; blocks = blocks > 2048 ? 2048 : blocks;
+            hipLaunchKernelGGL(iris_image_many_kernel, dim3((unsigned)blocks, (unsigned)G), dim3(256), 0, h->stream, d_pts, d_offs + s, d_counts + s, stride,
+                               rows, cols, h->cfg.nscan == 16 ? 15.0 : 24.9, d_cells, d_zmax);
+        }
+        hipLaunchKernelGGL(iris_finish_many_kernel, dim3((unsigned)rows, (unsigned)G), dim3(128), sizeof(float) * cols, h->stream, d_zmax, d_cells, rows, cols,
+                           slot0 + s, h->d_rowkeys, h->d_images);
+        SCL_HIP(h, hipGetLastError());
+        if ((rc = encode_slots_locked(h, slot0 + s, G))) return rc;
+    }
+    std::vector<unsigned char> img;
+    std::vector<float> keys;
+    if (out_values) {                                                          // D.h:1067-1081: image values row-major, then the row key
+        img.resize(cells * count); keys.resize((size_t)rows * count);
+        SCL_HIP(h, hipMemcpyAsync(img.data(), h->d_images + cells * slot0, cells * count, hipMemcpyDeviceToHost, h->stream));
+        SCL_HIP(h, hipMemcpyAsync(keys.data(), h->d_rowkeys + (size_t)rows * slot0, sizeof(float) * rows * count, hipMemcpyDeviceToHost, h->stream));
+    }
+    SCL_HIP(h, hipStreamSynchronize(h->stream));
+    if (out_values)
+        for (int i = 0; i < count; ++i) {
+            float *o = out_values + (size_t)i * (cells + rows);
+            for (size_t c = 0; c < cells; ++c) o[c] = (float)img[(size_t)i * cells + c];
+            std::memcpy(o + cells, keys.data() + (size_t)i * rows, sizeof(float) * rows);
+        }
+    for (int i = 0; i < count; ++i) h->reg.commit(robots[i], indexs[i]);
+    return SCL_OK;
+}
+
+// save_from_wire for `count` vectors: robot ids validated, the database grown once, one transfer, decode and encode on the device
+int save_from_wire_many_locked(scl_iris *h, const float *values, const int8_t *robots, const int *indexs, int count)
+{
+    if (count < 0 || (count > 0 && (!values || !robots || !indexs))) return fail(h, SCL_ERR_INVALID_ARG, "save_from_wire_many: null array");
+    for (int i = 0; i < count; ++i)
+        if (int rc = check_robot(h, robots[i], SCL_ERR_INVALID_ARG)) return rc;
+    if (count == 0) return SCL_OK;
+    int rc = grow(h, h->reg.n + count);
+    if (rc) return rc;
+    const int rows = h->cfg.rows, cols = h->cfg.cols, slot0 = h->reg.n;
+    const size_t per = (size_t)rows * cols + rows;
+    if ((rc = reserve(h, h->bw.wire, sizeof(float) * per * count))) return rc;
+    SCL_HIP(h, hipMemcpyAsync(h->bw.wire.p, values, sizeof(float) * per * count, hipMemcpyHostToDevice, h->stream));
+    for (int s = 0; s < count; s += 16384) {
+        const int G = std::min(16384, count - s);
+        hipLaunchKernelGGL(iris_wire_decode_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)G), dim3(256), 0, h->stream,
+                           h->bw.wire.as<float>() + per * s, rows, cols, h->cfg.wire_decode, slot0 + s, h->d_images, h->d_rowkeys);
+    }
+    SCL_HIP(h, hipGetLastError());
+    if ((rc = encode_slots_locked(h, slot0, count))) return rc;
+    SCL_HIP(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < count; ++i) h->reg.commit(robots[i], indexs[i]);
+    return SCL_OK;
+}
+
+// Work memory of the batched FFT shift estimate.  A job takes 72 bytes per pixel -- six float planes (both staged images, the
+// highpassed magnitude, both log-polar images, the warped image) and three double2 planes -- 2.07 MB at 80 x 360, and a launch
+// group of 16 queries x 10 candidates x 2 passes of compare() has 320 jobs: 664 MB.  One GiB holds that group in one pass (517 jobs
+// at 80 x 360); a larger group, or a larger image, runs in ceil(jobs / (kIrisFftWorkBytes / (72 rows cols))) passes of two host
+// visits each
+constexpr size_t kIrisFftWorkBytes = (size_t)1 << 30;
+
+// fft_match_jobs_locked for J jobs listed on the device (d_jobs; key0 < 0: an empty job): est[j] = (int)(center_x - (float)(cols / 2)),
+// compare()'s shift estimate (D.h:969 / 980), to `est` on the host and, with the copy queued on the stream, to d_est.  The caller
+// keeps `est` alive until it has synchronised.  Per pass the two host visits of the single call, for the same reason: the rotation
+// and scale go through the C library's pow / cos / sin
+int fft_estimate_many_locked(scl_iris *h, const FftJob *d_jobs, int J, std::vector<int> &est, int *d_est)
+{
+    est.assign((size_t)J, 0);
+    if (J <= 0) return SCL_OK;
+    const int R = h->cfg.rows, C = h->cfg.cols;
+    const size_t n = (size_t)R * C;
+    size_t pass = kIrisFftWorkBytes / (72 * n);
+    pass = pass < 1 ? 1 : (pass > (size_t)J ? (size_t)J : pass);
+    int rc;
+    if ((rc = reserve(h, h->bw.fm, 72 * n * pass)) || (rc = reserve(h, h->bw.fres, sizeof(double2) * pass)) || (rc = reserve(h, h->bw.fmats, sizeof(double) * 6 * pass))) return rc;
+    double2 *w0 = h->bw.fm.as<double2>(), *w1 = w0 + n * pass, *w2 = w1 + n * pass, *d_res = h->bw.fres.as<double2>();
+    float *a0 = reinterpret_cast<float *>(w2 + n * pass), *a1 = a0 + n * pass, *ff = a1 + n * pass, *lp0 = ff + n * pass, *lp1 = lp0 + n * pass, *rs = lp1 + n * pass;
+    double *d_mats = h->bw.fmats.as<double>();
+    hipStream_t st = h->stream;
+    std::vector<double2> res(pass);
+    std::vector<double> mats(pass * 6);
+    std::vector<int> ok(pass);
+    for (size_t j0 = 0; j0 < (size_t)J; j0 += pass) {
+        const size_t Jp = std::min(pass, (size_t)J - j0);
+        const dim3 ge((unsigned)((n + 255) / 256), (unsigned)Jp), blk(256);
+        hipLaunchKernelGGL(fm_stage_many_kernel, ge, blk, 0, st, h->d_images, d_jobs + j0, R, C, a0, a1);
+        auto dft2 = [&](const float *src, double2 *w_out, double2 *w_tmp) {
+            hipLaunchKernelGGL(fm_to_complex_kernel, ge, blk, 0, st, src, w_tmp, (int)n);
+            hipLaunchKernelGGL(fm_dft_lines_kernel, ge, blk, 0, st, w_tmp, w_out, C, 1, R, C, -1, h->d_wcC, h->d_wsC, n);
+            hipLaunchKernelGGL(fm_dft_lines_kernel, ge, blk, 0, st, w_out, w_tmp, R, C, C, 1, -1, h->d_wcR, h->d_wsR, n);
+            (void)hipMemcpyAsync(w_out, w_tmp, sizeof(double2) * n * Jp, hipMemcpyDeviceToDevice, st);
+        };
+        auto phase_correlate = [&](const float *s1, const float *s2) {
+            dft2(s1, w0, w2);
+            dft2(s2, w1, w2);
+            hipLaunchKernelGGL(fm_crosspower_kernel, ge, blk, 0, st, w0, w1, w2, (int)n);
+            hipLaunchKernelGGL(fm_dft_lines_kernel, ge, blk, 0, st, w2, w0, R, C, C, 1, +1, h->d_wcR, h->d_wsR, n);
+            hipLaunchKernelGGL(fm_dft_lines_kernel, ge, blk, 0, st, w0, w1, C, 1, R, C, +1, h->d_wcC, h->d_wsC, n);
+            hipLaunchKernelGGL(fm_peak_kernel, dim3((unsigned)Jp), blk, 0, st, w1, R, C, d_res);
+        };
+        auto logpolar = [&](const float *img, float *lp) {
+            dft2(img, w0, w1);
+            hipLaunchKernelGGL(fm_mag_highpass_kernel, ge, blk, 0, st, w0, h->d_hp, R, C, ff);
+            hipLaunchKernelGGL(fm_remap_kernel, ge, blk, 0, st, ff, h->d_lpmap, R, C, lp);
+        };
+        logpolar(a0, lp0);
+        logpolar(a1, lp1);
+        phase_correlate(lp1, lp0);
+        SCL_HIP(h, hipGetLastError());
+        SCL_HIP(h, hipMemcpyAsync(res.data(), d_res, sizeof(double2) * Jp, hipMemcpyDeviceToHost, st));
+        SCL_HIP(h, hipStreamSynchronize(st));
+        for (size_t j = 0; j < Jp; ++j) {                                      // the expressions of fft_match_jobs_locked (D.h:884-912)
+            const double rx = res[j].x, ry = res[j].y;
+            float angle = (float)(180.0 * ry / (double)R);
+            float scale = (float)std::pow((double)h->log_base, rx);
+            ok[j] = 1;
+            if (scale > 1.8f) {
+                angle = (float)(-180.0 * ry / (double)R);
+                scale = (float)(1.0 / std::pow((double)h->log_base, rx));
+                if (scale > 1.8f) ok[j] = 0;
+            }
+            if (angle < -90.0f) angle += 180.0f; else if (angle > 90.0f) angle -= 180.0f;
+            const double ang = (double)angle * M_PI / 180.0, sc = 1.0 / (double)scale;
+            const double alpha = std::cos(ang) * sc, beta = std::sin(ang) * sc, pcx = (double)(float)(C / 2), pcy = (double)(float)(R / 2);
+            double M[6] = {alpha, beta, (1.0 - alpha) * pcx - beta * pcy, -beta, alpha, beta * pcx + (1.0 - alpha) * pcy};
+            double D = M[0] * M[4] - M[1] * M[3];
+            D = D != 0.0 ? 1.0 / D : 0.0;
+            const double A11 = M[4] * D, A22 = M[0] * D;
+            M[0] = A11; M[1] *= -D; M[3] *= -D; M[4] = A22;
+            const double b1 = -M[0] * M[2] - M[1] * M[5], b2 = -M[3] * M[2] - M[4] * M[5];
+            M[2] = b1; M[5] = b2;
+            for (int k = 0; k < 6; ++k) mats[j * 6 + k] = M[k];
+        }
+        SCL_HIP(h, hipMemcpyAsync(d_mats, mats.data(), sizeof(double) * 6 * Jp, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(fm_warp_kernel, ge, blk, 0, st, a1, d_mats, R, C, rs);
+        phase_correlate(rs, a0);
+        SCL_HIP(h, hipGetLastError());
+        SCL_HIP(h, hipMemcpyAsync(res.data(), d_res, sizeof(double2) * Jp, hipMemcpyDeviceToHost, st));
+        SCL_HIP(h, hipStreamSynchronize(st));
+        for (size_t j = 0; j < Jp; ++j) {
+            const float center_x = ok[j] ? (float)(res[j].x + (double)(C / 2)) : 0.0f;
+            est[j0 + j] = (int)(center_x - (float)(C / 2));                    // int = float - int, D.h:969 / 980
+        }
+    }
+    SCL_HIP(h, hipMemcpyAsync(d_est, est.data(), sizeof(int) * (size_t)J, hipMemcpyHostToDevice, st));
+    return SCL_OK;
+}
+
+// a query of a batched detection: keyframe `key` against the prefix [0, limit) of lists[which]; limit < 0: no search (the early-outs
+// of the single calls, D.h:1092-1095 / 1198-1201), the query takes part in no launch
+struct ManyQuery { int key, which, limit; };
+
+// detect_core_locked for `count` queries.  The searching queries are ordered by list and cut into launch groups of kIrisDetectGroup;
+// per group: row-key distances (one launch per list the group reaches), the selection, the job list, the Hamming matching -- every
+// column shift, or the FFT estimate and the windows -- and the finishing kernel, all on the device; then one copy back and one wait
+// (plus fft_estimate_many_locked's visits).  out[i] = (position in the list, shift, distance), (-1, 0, 10000000) where nothing was
+// searched or found
+int detect_many_locked(scl_iris *h, const std::vector<ManyQuery> &qs, const std::vector<int> lists[2], std::vector<IrisAnswer> &out)
+{
+    const int count = (int)qs.size(), k = h->cfg.num_candidates, N = h->cfg.cols, rows = h->cfg.rows;
+    out.assign((size_t)count, IrisAnswer{-1, 0, 10000000.0f});
+    std::vector<int> order;
+    int used[2] = {0, 0};
+    for (int l = 0; l < 2; ++l)
+        for (int i = 0; i < count; ++i)
+            if (qs[(size_t)i].limit > 0 && qs[(size_t)i].which == l) { order.push_back(i); used[l] = std::max(used[l], qs[(size_t)i].limit); }
+    const int nact = (int)order.size();
+    if (nact == 0) return SCL_OK;
+    const bool window = h->cfg.shift_search != 1;
+    const int mn = h->cfg.match_num, passes = window ? (mn == 2 ? 2 : 1) : 0, per = window ? 5 : N;
+    const int off[2] = {0, used[0]};
+    int rc;
+    if ((rc = reserve(h, h->bw.list, sizeof(int) * ((size_t)used[0] + used[1]))) || (rc = reserve(h, h->bw.query, sizeof(int) * 3 * (size_t)nact)) ||
+        (rc = reserve(h, h->bw.answers, sizeof(IrisAnswer) * (size_t)nact))) return rc;
+    std::vector<int> hq(3 * (size_t)nact);                                     // key | limit | list offset
+    for (int j = 0; j < nact; ++j) {
+        const ManyQuery &q = qs[(size_t)order[(size_t)j]];
+        hq[(size_t)j] = q.key; hq[(size_t)nact + j] = q.limit; hq[2 * (size_t)nact + j] = off[q.which];
+    }
+    int *d_list = h->bw.list.as<int>(), *d_qkey = h->bw.query.as<int>(), *d_limit = d_qkey + nact, *d_off = d_limit + nact;
+    IrisAnswer *d_ans = h->bw.answers.as<IrisAnswer>();
+    for (int l = 0; l < 2; ++l)
+        if (used[l] > 0) SCL_HIP(h, hipMemcpyAsync(d_list + off[l], lists[l].data(), sizeof(int) * (size_t)used[l], hipMemcpyHostToDevice, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(d_qkey, hq.data(), sizeof(int) * hq.size(), hipMemcpyHostToDevice, h->stream));
+    const size_t fw = (size_t)N * h->words;
+    std::vector<IrisAnswer> ans((size_t)nact);
+    std::vector<int> est, cpos;
+    for (int s = 0; s < nact; s += kIrisDetectGroup) {
+        const int G = std::min(kIrisDetectGroup, nact - s);
+        int nmax = 0;
+        for (int j = s; j < s + G; ++j) nmax = std::max(nmax, hq[(size_t)nact + j]);
+        const int m = std::min(k, nmax);                                       // candidate slots per query: no more can qualify
+        const size_t slots = (size_t)G * m, J = slots * (window ? passes : 1);
+        if ((rc = reserve(h, h->bw.d2, sizeof(float) * (size_t)G * nmax)) || (rc = reserve(h, h->bw.cand, sizeof(int) * 2 * slots)) ||
+            (rc = reserve(h, h->bw.jobs, sizeof(FftJob) * J)) || (rc = reserve(h, h->bw.est, sizeof(int) * J)) ||
+            (rc = reserve(h, h->bw.counts, sizeof(int) * 2 * J * per))) return rc;
+        float *d_d2 = h->bw.d2.as<float>();
+        int *d_cpos = h->bw.cand.as<int>(), *d_ckey = d_cpos + slots, *d_est = h->bw.est.as<int>();
+        int *d_diff = h->bw.counts.as<int>(), *d_total = d_diff + J * per;
+        FftJob *d_jobs = h->bw.jobs.as<FftJob>();
+        for (int a = s; a < s + G;) {                                          // the group's queries of one list: one launch
+            int b = a, n = 0;
+            while (b < s + G && hq[2 * (size_t)nact + b] == hq[2 * (size_t)nact + a]) { n = std::max(n, hq[(size_t)nact + b]); ++b; }
+            hipLaunchKernelGGL(iris_rowkey_d2_many_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), sizeof(float) * kIrisDetectGroup * rows, h->stream,
+                               h->d_rowkeys, rows, d_qkey + a, d_limit + a, b - a, d_list + hq[2 * (size_t)nact + a], n, d_d2 + (size_t)(a - s) * nmax, nmax);
+            a = b;
+        }
+        hipLaunchKernelGGL(iris_select_kernel, dim3((unsigned)G), dim3(256), 0, h->stream, d_d2, nmax, d_limit + s, m, h->cfg.knn_exclude_eps, d_cpos);
+        hipLaunchKernelGGL(iris_jobs_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, d_cpos, d_qkey + s, d_off + s, d_list, G, m,
+                           passes, mn == 1 ? 180 : 0, d_ckey, d_jobs);
+        SCL_HIP(h, hipGetLastError());
+        if (window && !h->fm_ok) {
+            // the single call fails where a query has a candidate to compare (fft_match_jobs_locked with J > 0): so does the batch
+            cpos.resize(slots);
+            SCL_HIP(h, hipMemcpyAsync(cpos.data(), d_cpos, sizeof(int) * slots, hipMemcpyDeviceToHost, h->stream));
+            SCL_HIP(h, hipStreamSynchronize(h->stream));
+            for (int q = 0; q < G; ++q)
+                if (cpos[(size_t)q * m] >= 0) return fail(h, SCL_ERR_UNSUPPORTED, "the FFT shift estimate takes even rows and columns only");
+            for (int q = 0; q < G; ++q) ans[(size_t)s + q] = IrisAnswer{-1, 0, 10000000.0f};
+            continue;
+        }
+        if (window) {
+            if ((rc = fft_estimate_many_locked(h, d_jobs, (int)J, est, d_est))) return rc;
+            hipLaunchKernelGGL(iris_hamming_window_kernel, dim3((unsigned)J), dim3(256), 0, h->stream, h->d_T, h->d_M, fw, d_jobs, d_est, N, h->words, h->trows,
+                               d_diff, d_total);
+        } else {
+            hipLaunchKernelGGL(iris_hamming_all_many_kernel, dim3((unsigned)(slots * N)), dim3(64), 0, h->stream, h->d_T, h->d_M, fw, d_qkey + s, d_ckey, m, N,
+                               h->words, h->trows, d_diff, d_total);
+        }
+        hipLaunchKernelGGL(iris_finish_detect_kernel, dim3(1), dim3(kIrisDetectGroup), 0, h->stream, d_cpos, d_est, d_diff, d_total, G, m, per, window ? 1 : 0,
+                           window ? passes : 1, mn, d_ans + s);
+        SCL_HIP(h, hipGetLastError());
+        SCL_HIP(h, hipMemcpyAsync(ans.data() + s, d_ans + s, sizeof(IrisAnswer) * (size_t)G, hipMemcpyDeviceToHost, h->stream));
+        SCL_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    for (int j = 0; j < nact; ++j) out[(size_t)order[(size_t)j]] = ans[(size_t)j];
+    return SCL_OK;
+}
+
+int detect_intra_many_locked(scl_iris *h, const int *curs, int count, int *loop_ids, float *biases, float *dists)
+{
+    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
+    for (int i = 0; i < count; ++i)
+        if (curs[i] < 0 || curs[i] >= (int)mine.size()) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_intra: no such keyframe of this robot");
+    std::vector<ManyQuery> qs((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        const bool search = curs[i] >= h->cfg.num_exclude_recent + h->cfg.num_candidates + 1;      // D.h:1092-1095
+        qs[(size_t)i] = ManyQuery{mine[(size_t)curs[i]], 0, search ? curs[i] - h->cfg.num_exclude_recent : -1};
+    }
+    const std::vector<int> lists[2] = {mine, std::vector<int>()};
+    std::vector<IrisAnswer> ans;
+    int rc = detect_many_locked(h, qs, lists, ans);
+    if (rc) return rc;
+    for (int i = 0; i < count; ++i) {
+        const IrisAnswer &a = ans[(size_t)i];
+        const bool loop = (double)a.dis < h->cfg.dist_thres;                   // D.h:1140-1144: the LOCAL index
+        loop_ids[i] = loop ? a.pos : -1; biases[i] = loop ? (float)a.bias : 0.0f;
+        if (dists) dists[i] = a.dis;
+    }
+    return SCL_OK;
+}
+
+int detect_inter_many_locked(scl_iris *h, const int *curs, int count, int *loop_ids, float *biases, float *dists)
+{
+    for (int i = 0; i < count; ++i)
+        if (curs[i] < 0 || curs[i] >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter: key out of range");
+    // a received keyframe searches this robot's keys (list 0), one of this robot every other robot's in the registry's
+    // concatenation order, unsorted (list 1): KeyframeRegistry::inter_candidates
+    std::vector<int> lists[2];
+    lists[0] = h->reg.keys_of(h->cfg.this_id);
+    for (int r = 0; r < h->reg.robot_num; ++r)
+        if (r != h->cfg.this_id) lists[1].insert(lists[1].end(), h->reg.keys_of(r).begin(), h->reg.keys_of(r).end());
+    std::vector<ManyQuery> qs((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        const int which = h->reg.robots[(size_t)curs[i]] == h->cfg.this_id ? 1 : 0, n = (int)lists[which].size();
+        qs[(size_t)i] = ManyQuery{curs[i], which, n >= h->cfg.num_candidates + 1 ? n : -1};          // D.h:1198-1201
+    }
+    std::vector<IrisAnswer> ans;
+    int rc = detect_many_locked(h, qs, lists, ans);
+    if (rc) return rc;
+    for (int i = 0; i < count; ++i) {
+        const IrisAnswer &a = ans[(size_t)i];
+        const bool loop = (double)a.dis < h->cfg.dist_thres && a.pos >= 0;     // D.h:1236, 1245-1248: the GLOBAL key
+        loop_ids[i] = loop ? lists[qs[(size_t)i].which][(size_t)a.pos] : -1; biases[i] = loop ? (float)a.bias : 0.0f;
+        if (dists) dists[i] = a.dis;
+    }
+    return SCL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -740,6 +1470,7 @@ int scl_iris_destroy(scl_iris *h)
                     (void *)h->d_hp, (void *)h->d_lpmap, (void *)h->d_fjobs, (void *)h->d_fa0, (void *)h->d_fa1, (void *)h->d_ff, (void *)h->d_flp0, (void *)h->d_flp1,
                     (void *)h->d_frs, (void *)h->d_fw0, (void *)h->d_fw1, (void *)h->d_fw2, (void *)h->d_fres, (void *)h->d_fmats, (void *)h->d_rolls})
         if (p) (void)hipFree(p);
+    h->bw.release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return SCL_OK;
@@ -847,6 +1578,62 @@ int scl_iris_detect_inter(scl_iris *h, int cur, int *loop_id, float *bias, float
     if (rc) return rc;
     if (dist) *dist = d;
     if ((double)d < h->cfg.dist_thres && pos >= 0) { *loop_id = list[(size_t)pos]; *bias = (float)b; }   // D.h:1236, 1245-1248: the GLOBAL key
+    return SCL_OK;
+}
+
+// ---- the batch forms (scl_iris.h): the handle's mutex for the whole call, everything on its stream
+int scl_iris_make_and_save_many(scl_iris *h, const void *const *clouds, const int *n_points, int stride_bytes, const int8_t *robots, const int *indexs,
+                                int count, float *out_values)
+{
+    if (!h) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    return make_and_save_many_locked(h, clouds, n_points, stride_bytes, robots, indexs, count, out_values);
+}
+
+int scl_iris_save_from_wire_many(scl_iris *h, const float *values, const int8_t *robots, const int *indexs, int count)
+{
+    if (!h) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    return save_from_wire_many_locked(h, values, robots, indexs, count);
+}
+
+int scl_iris_detect_intra_many(scl_iris *h, const int *curs, int count, int *loop_ids, float *biases, float *dists)
+{
+    if (!h || count < 0 || (count > 0 && (!curs || !loop_ids || !biases))) return SCL_ERR_INVALID_ARG;
+    if (count == 0) return SCL_OK;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    return detect_intra_many_locked(h, curs, count, loop_ids, biases, dists);
+}
+
+int scl_iris_detect_inter_many(scl_iris *h, const int *curs, int count, int *loop_ids, float *biases, float *dists)
+{
+    if (!h || count < 0 || (count > 0 && (!curs || !loop_ids || !biases))) return SCL_ERR_INVALID_ARG;
+    if (count == 0) return SCL_OK;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    return detect_inter_many_locked(h, curs, count, loop_ids, biases, dists);
+}
+
+int scl_iris_make_save_and_detect(scl_iris *h, const void *const *clouds, const int *n_points, int stride_bytes, const int8_t *robots, const int *indexs,
+                                  int count, int *loop_ids, float *biases, float *dists, float *out_values)
+{
+    if (!h || count < 0 || (count > 0 && (!loop_ids || !biases))) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    const int first = (int)h->reg.keys_of(h->cfg.this_id).size();
+    int rc = make_and_save_many_locked(h, clouds, n_points, stride_bytes, robots, indexs, count, out_values);
+    if (rc) return rc;
+    std::vector<int> curs, at;                                                // the new keyframes of this robot: LOCAL index, entry of the call
+    for (int i = 0; i < count; ++i)
+        if (robots[i] == h->cfg.this_id) { curs.push_back(first + (int)curs.size()); at.push_back(i); }
+    std::vector<int> loops(curs.size());
+    std::vector<float> bs(curs.size()), ds(curs.size());
+    if (!curs.empty() && (rc = detect_intra_many_locked(h, curs.data(), (int)curs.size(), loops.data(), bs.data(), ds.data()))) return rc;
+    for (int i = 0; i < count; ++i) { loop_ids[i] = -1; biases[i] = 0.0f; if (dists) dists[i] = 10000000.0f; }
+    for (size_t j = 0; j < at.size(); ++j) { loop_ids[at[j]] = loops[j]; biases[at[j]] = bs[j]; if (dists) dists[at[j]] = ds[j]; }
     return SCL_OK;
 }
 

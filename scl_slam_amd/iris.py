@@ -31,7 +31,15 @@ _SIG.update({
     "scl_iris_hamming_all_shifts": (c_int, [_P, c_int, _ip, c_int, _fp, _ip]),
     "scl_iris_fft_match": (c_int, [_P, c_int, c_int, c_int, _fp, _ip]),
     "scl_iris_compare": (c_int, [_P, c_int, _ip, c_int, _fp, _ip]),
+    # the batch forms
+    "scl_iris_make_and_save_many": (c_int, [_P, POINTER(c_void_p), _ip, c_int, POINTER(c_int8), _ip, c_int, _fp]),
+    "scl_iris_save_from_wire_many": (c_int, [_P, _fp, POINTER(c_int8), _ip, c_int]),
+    "scl_iris_detect_intra_many": (c_int, [_P, _ip, c_int, _ip, _fp, _fp]),
+    "scl_iris_detect_inter_many": (c_int, [_P, _ip, c_int, _ip, _fp, _fp]),
+    "scl_iris_make_save_and_detect": (c_int, [_P, POINTER(c_void_p), _ip, c_int, POINTER(c_int8), _ip, c_int, _ip, _fp, _fp, _fp]),
 })
+
+MAX_GROUP, DETECT_GROUP = 16, 16      # SCL_IRIS_MAX_GROUP, SCL_IRIS_DETECT_GROUP
 
 
 def _lib():
@@ -97,6 +105,80 @@ class IrisEngine(PluginEngine):
     def detect_inter(self, cur):
         """(loop global key or -1, column shift, smallest distance seen) -- detectInterLoopClosureID, D.h:1153-1253"""
         return self._detect(self.L.scl_iris_detect_inter, "scl_iris_detect_inter", cur)
+
+    # ---- the batch forms (scl_iris.h "THE BATCH FORMS"): the argument conventions of _plugin.VectorPluginEngine
+    def _clouds(self, clouds, robots, indexs, where):
+        """the arguments of a batched build: (arrays kept alive, pointers, counts, stride, robots, indexs, count)"""
+        arrs = [self._cloud(c) for c in clouds]
+        count = len(arrs)
+        if count and len({st for _, _, st in arrs}) != 1:
+            raise ValueError(f"{where}: one stride for all clouds")
+        st = arrs[0][2] if count else 12
+        ptrs = (c_void_p * max(count, 1))(*[a.ctypes.data for a, _, _ in arrs])
+        ns = np.ascontiguousarray([n for _, n, _ in arrs], np.int32)
+        rb = np.ascontiguousarray(robots if robots is not None else np.zeros(count), np.int8)
+        ix = np.ascontiguousarray(indexs if indexs is not None else np.arange(count), np.int32)
+        if rb.size != count or ix.size != count:
+            raise ValueError(f"{where}: one robot id and one index per cloud")
+        return arrs, ptrs, ns, st, rb, ix, count
+
+    @staticmethod
+    def _batch_out(count, **arrays):
+        for name, (a, t) in arrays.items():
+            if a is not None and (a.dtype != t or a.size != count or not a.flags.c_contiguous):
+                raise ValueError(f"{name}: a contiguous {np.dtype(t).name} array of {count} elements")
+
+    def make_and_save_many(self, clouds, robots=None, indexs=None, want_values=True):
+        """clouds: list of (n_i, k) float32 arrays with one record width k; returns (count, rows * cols + rows) float32, the
+        vectors make_and_save returns (None if not wanted)"""
+        _keep, ptrs, ns, st, rb, ix, count = self._clouds(clouds, robots, indexs, "make_and_save_many")
+        out = np.empty((count, self.rows * self.cols + self.rows), np.float32) if want_values else None
+        self._call("make_and_save_many", ptrs, ns.ctypes.data_as(_ip), st, rb.ctypes.data_as(POINTER(c_int8)), ix.ctypes.data_as(_ip), count,
+                   out.ctypes.data_as(_fp) if out is not None else None)
+        return out
+
+    def save_from_wire_many(self, values, robots=None, indexs=None):
+        """values: (count, rows * cols + rows) float32 vectors appended in order as robots[i] / indexs[i]"""
+        v = np.ascontiguousarray(values, np.float32).reshape(-1, self.rows * self.cols + self.rows)
+        count = v.shape[0]
+        rb = np.ascontiguousarray(robots if robots is not None else np.zeros(count), np.int8)
+        ix = np.ascontiguousarray(indexs if indexs is not None else np.arange(count), np.int32)
+        if rb.size != count or ix.size != count:
+            raise ValueError("save_from_wire_many: one robot id and one index per vector")
+        self._call("save_from_wire_many", v.ctypes.data_as(_fp), rb.ctypes.data_as(POINTER(c_int8)), ix.ctypes.data_as(_ip), count)
+
+    def _detect_many(self, name, curs, loops, biases, dists, want_dists):
+        c = np.ascontiguousarray(curs, np.int32).ravel()
+        loops = np.empty(c.size, np.int32) if loops is None else loops
+        biases = np.empty(c.size, np.float32) if biases is None else biases
+        if dists is None and want_dists:
+            dists = np.empty(c.size, np.float32)
+        self._batch_out(c.size, loops=(loops, np.int32), biases=(biases, np.float32), dists=(dists, np.float32))
+        self._call(name, c.ctypes.data_as(_ip), c.size, loops.ctypes.data_as(_ip), biases.ctypes.data_as(_fp),
+                   dists.ctypes.data_as(_fp) if dists is not None else None)
+        return loops, biases, dists
+
+    def detect_intra_many(self, curs, loops=None, biases=None, dists=None, want_dists=True):
+        """detect_intra for every local index of curs, as the single calls in that order answer: (loops int32, biases float32,
+        dists float32; dists None with want_dists=False).  loops / biases / dists: arrays to fill (untouched when the call fails)"""
+        return self._detect_many("detect_intra_many", curs, loops, biases, dists, want_dists)
+
+    def detect_inter_many(self, curs, loops=None, biases=None, dists=None, want_dists=True):
+        """detect_inter for every global key of curs, as the single calls in that order answer: (loops, biases, dists)"""
+        return self._detect_many("detect_inter_many", curs, loops, biases, dists, want_dists)
+
+    def make_save_and_detect(self, clouds, robots=None, indexs=None, want_values=True, loops=None, biases=None, dists=None):
+        """make_and_save_many, then detect_intra of every new keyframe of this robot in the same call: (loops int32, biases float32,
+        dists float32, values (count, rows * cols + rows) float32 or None); entries of other robots answer (-1, 0, 10000000)"""
+        _keep, ptrs, ns, st, rb, ix, count = self._clouds(clouds, robots, indexs, "make_save_and_detect")
+        loops = np.empty(count, np.int32) if loops is None else loops
+        biases = np.empty(count, np.float32) if biases is None else biases
+        dists = np.empty(count, np.float32) if dists is None else dists
+        self._batch_out(count, loops=(loops, np.int32), biases=(biases, np.float32), dists=(dists, np.float32))
+        out = np.empty((count, self.rows * self.cols + self.rows), np.float32) if want_values else None
+        self._call("make_save_and_detect", ptrs, ns.ctypes.data_as(_ip), st, rb.ctypes.data_as(POINTER(c_int8)), ix.ctypes.data_as(_ip), count,
+                   loops.ctypes.data_as(_ip), biases.ctypes.data_as(_fp), dists.ctypes.data_as(_fp), out.ctypes.data_as(_fp) if out is not None else None)
+        return loops, biases, dists, out
 
     def get_image(self, key):
         img = np.empty((self.rows, self.cols), np.uint8); k = np.empty(self.rows, np.float32)
