@@ -101,6 +101,20 @@ public:
         return pairs(loops, dists, ok);
     }
 
+    // the candidate lists (scl_plugin_batch.h "THE CANDIDATE LISTS"): per entry of curPtrs the up to k nearest of the set the
+    // detection searches, nearest first, as {local index, distance}, without the threshold -- for a verifier (ICP, RANSAC) to judge.
+    // The inner vectors hold n_found pairs (fewer than k when the set is smaller); on an error every one is empty
+    std::vector<std::vector<std::pair<int, float>>> detectIntraLoopCandidates(const std::vector<int> &curPtrs, int k)
+    {
+        return candidates(curPtrs, k, scl_m2dp_detect_intra_topk, "detectIntraLoopCandidates");
+    }
+
+    // the same for the inter detection: {global key, distance}
+    std::vector<std::vector<std::pair<int, float>>> detectInterLoopCandidates(const std::vector<int> &curPtrs, int k)
+    {
+        return candidates(curPtrs, k, scl_m2dp_detect_inter_topk, "detectInterLoopCandidates");
+    }
+
     // scans[i] appended as (robots[i], indexs[i]), then the intra detection of every new keyframe of this robot in the same call:
     // {local index of the loop keyframe or -1, distance} per scan ({-1, +inf} for another robot's); descriptors: lastDescriptors()
     std::vector<std::pair<int, float>> makeSaveAndDetect(const std::vector<const pcl::PointCloud<pcl::PointXYZI> *> &scans,
@@ -182,6 +196,23 @@ private:
     }
 
     scl_m2dp *m2dp_ = nullptr;
+
+    std::vector<std::vector<std::pair<int, float>>> candidates(const std::vector<int> &curPtrs, int k,
+                                                               int (*call)(scl_m2dp *, const int *, int, int, int *, float *, int *),
+                                                               const char *where)
+    {
+        std::vector<std::vector<std::pair<int, float>>> out(curPtrs.size());
+        if (k < 1 || k > SCL_PLUGIN_TOPK_MAX) {
+            std::fprintf(stderr, "[m2dp_hip_descriptor] %s: k = %d outside [1, %d]\n", where, k, SCL_PLUGIN_TOPK_MAX);
+            return out;
+        }
+        std::vector<int> ids(curPtrs.size() * static_cast<size_t>(k), -1), found(curPtrs.size(), 0);
+        std::vector<float> dists(ids.size(), 0.0f);
+        if (!report(call(m2dp_, curPtrs.data(), static_cast<int>(curPtrs.size()), k, ids.data(), dists.data(), found.data()), where)) return out;
+        for (size_t i = 0; i < curPtrs.size(); ++i)
+            for (int j = 0; j < found[i]; ++j) out[i].push_back(std::pair<int, float>(ids[i * k + j], dists[i * k + j]));
+        return out;
+    }
 
     static std::vector<std::pair<int, float>> pairs(const std::vector<int> &loops, const std::vector<float> &dists, bool ok)
     {

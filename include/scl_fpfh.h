@@ -101,6 +101,11 @@ int  scl_fpfh_detect_inter(scl_fpfh *h, int cur, int *loop_id, float *dist);
  * 16 queries per launch and one wait for the device per call */
 SCL_PLUGIN_BATCH_API(scl_fpfh);
 
+/* THE CANDIDATE LISTS (scl_plugin_batch.h has the rules): scl_fpfh_detect_intra_topk and scl_fpfh_detect_inter_topk -- the k <=
+ * SCL_PLUGIN_TOPK_MAX nearest of the set the _many form searches, without dist_thres; the ranking is over all 33 floats but the reported
+ * distance over report_dims (21) of them, so cand_dists need NOT be monotone in the rank */
+SCL_PLUGIN_TOPK_API(scl_fpfh);
+
 /* TEST HOOKS (one cloud each; any output may be NULL):
  * neighbours: n_points x min(10, n_points) int32 indices and float d2, in (d2, index) order, rows in input order */
 int  scl_fpfh_neighbors(scl_fpfh *h, const void *points, int n_points, int stride_bytes, int32_t *idx, float *d2);

@@ -107,6 +107,10 @@ int  scl_grsd_detect_inter(scl_grsd *h, int cur, int *loop_id, float *dist);
  * 16 queries per launch and one wait for the device per call */
 SCL_PLUGIN_BATCH_API(scl_grsd);
 
+/* THE CANDIDATE LISTS (scl_plugin_batch.h has the rules): scl_grsd_detect_intra_topk and scl_grsd_detect_inter_topk -- the k <=
+ * SCL_PLUGIN_TOPK_MAX nearest of the set the _many form searches, without dist_thres; the reported distance is over all 21 floats, so it rises with the rank */
+SCL_PLUGIN_TOPK_API(scl_grsd);
+
 /* TEST HOOKS (one cloud each; any output may be NULL):
  * normals: n_points x 3 floats in input order (NaN triples where invalid) and n_points validity flags (1 / 0) */
 int  scl_grsd_normals(scl_grsd *h, const void *points, int n_points, int stride_bytes, float *normals, uint8_t *valid);

@@ -101,6 +101,10 @@ int  scl_m2dp_detect_inter(scl_m2dp *h, int cur, int *loop_id, float *dist);
  * 16 queries per launch and one wait for the device per call */
 SCL_PLUGIN_BATCH_API(scl_m2dp);
 
+/* THE CANDIDATE LISTS (scl_plugin_batch.h has the rules): scl_m2dp_detect_intra_topk and scl_m2dp_detect_inter_topk -- the k <=
+ * SCL_PLUGIN_TOPK_MAX nearest of the set the _many form searches, without dist_thres; the reported distance is over all 192 floats, so it rises with the rank */
+SCL_PLUGIN_TOPK_API(scl_m2dp);
+
 /* TEST HOOK: for one cloud, the 64 x 128 integer counts of A (row-major: plane row, bin column; A = counts / n_points), the
  * float frame (mean[3], axes[9]: axis k = axes[3k .. 3k+2], signs applied) and maxRho.  Any output may be NULL. */
 int  scl_m2dp_signature_matrix(scl_m2dp *h, const void *points, int n_points, int stride_bytes, uint32_t *counts,

@@ -47,6 +47,8 @@ def vector_signatures(prefix, config):
         f"{prefix}_detect_inter_many": (c_int, [P, ip, c_int, ip, fp]),
         f"{prefix}_save_from_wire_many": (c_int, [P, fp, POINTER(c_int8), ip, c_int]),
         f"{prefix}_make_save_and_detect": (c_int, [P, POINTER(c_void_p), ip, c_int, POINTER(c_int8), ip, c_int, ip, fp, fp]),
+        f"{prefix}_detect_intra_topk": (c_int, [P, ip, c_int, c_int, ip, fp, ip]),
+        f"{prefix}_detect_inter_topk": (c_int, [P, ip, c_int, c_int, ip, fp, ip]),
     })
     return sig
 
@@ -116,7 +118,7 @@ class PluginEngine:
 
 class VectorPluginEngine(PluginEngine):
     """A plugin whose descriptor is DIM floats (M2DP, FPFH, GRSD): make, make_and_save(_many), save_from_wire, get_signature and the
-    1-NN detections, each with its batch form (numpy arrays in and out)."""
+    1-NN detections, each with its batch form (numpy arrays in and out), and the candidate lists (detect_*_topk)."""
     DIM = None
 
     @staticmethod
@@ -231,3 +233,27 @@ class VectorPluginEngine(PluginEngine):
     def detect_inter_many(self, curs, loops=None, dists=None, want_dists=True):
         """detect_inter for every global key of curs, as the single calls in that order answer: (loops int32, dists float32)"""
         return self._detect_many("detect_inter_many", curs, loops, dists, want_dists)
+
+    def _detect_topk(self, name, curs, k, ids, dists, n_found):
+        c = np.ascontiguousarray(curs, np.int32).ravel()
+        k = int(k)
+        rows = max(k, 0)
+        ids = np.empty((c.size, rows), np.int32) if ids is None else ids
+        dists = np.empty((c.size, rows), np.float32) if dists is None else dists
+        n_found = np.empty(c.size, np.int32) if n_found is None else n_found
+        for a, t, size in ((ids, np.int32, c.size * rows), (dists, np.float32, c.size * rows), (n_found, np.int32, c.size)):
+            if a.dtype != t or a.size != size or not a.flags.c_contiguous:
+                raise ValueError(f"a contiguous {np.dtype(t).name} array of {size} elements")
+        self._call(name, c.ctypes.data_as(POINTER(c_int)), c.size, k, ids.ctypes.data_as(POINTER(c_int)),
+                   dists.ctypes.data_as(POINTER(c_float)), n_found.ctypes.data_as(POINTER(c_int)))
+        return ids, dists, n_found
+
+    def detect_intra_topk(self, curs, k, ids=None, dists=None, n_found=None):
+        """the k nearest of the set detect_intra searches, for every local index of curs, without dist_thres: (ids (count, k) int32
+        LOCAL, dists (count, k) float32, n_found int32); entries past n_found[i] are (-1, +inf).  ids / dists / n_found: arrays to
+        fill (left untouched when the call fails)"""
+        return self._detect_topk("detect_intra_topk", curs, k, ids, dists, n_found)
+
+    def detect_inter_topk(self, curs, k, ids=None, dists=None, n_found=None):
+        """the k nearest of the set detect_inter searches, for every global key of curs: (ids (count, k) int32 GLOBAL, dists, n_found)"""
+        return self._detect_topk("detect_inter_topk", curs, k, ids, dists, n_found)

@@ -403,6 +403,7 @@ struct scl_fpfh {
     unsigned long long *d_cand = nullptr, *d_best = nullptr;
     int *d_list = nullptr; size_t list_cap = 0;
     scl::NnManyWork many;                    // the batched detections' work buffers
+    scl::NnTopkWork topk;                    // the candidate lists' work buffers
     int *d_nbr = nullptr; float *d_nbr_d2 = nullptr; size_t nbr_cap = 0;
     unsigned long long points = 0;
     double kernel_us = 0.0;
@@ -600,6 +601,7 @@ int scl_fpfh_destroy(scl_fpfh *h)
                     (void *)h->d_nbr, (void *)h->d_nbr_d2})
         if (p) (void)hipFree(p);
     h->many.release();
+    h->topk.release();
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -723,6 +725,23 @@ int scl_fpfh_detect_inter_many(scl_fpfh *h, const int *curs, int count, int *loo
     (void)hipSetDevice(h->device);
     if (h->cfg.inter_mode == 0) return detect_inter_snapshot_many_locked(h, curs, count, h->cfg.report_dims, loop_ids, dists);
     return detect_inter_lists_many_locked(h, curs, count, h->cfg.report_dims, loop_ids, dists);
+}
+
+int scl_fpfh_detect_intra_topk(scl_fpfh *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
+{
+    if (!h || count < 0 || (count > 0 && (!curs || !cand_ids))) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    return detect_intra_topk_locked(h, curs, count, k, h->cfg.report_dims, cand_ids, cand_dists, n_found);
+}
+
+int scl_fpfh_detect_inter_topk(scl_fpfh *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
+{
+    if (!h || count < 0 || (count > 0 && (!curs || !cand_ids))) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    if (h->cfg.inter_mode == 0) return detect_inter_snapshot_topk_locked(h, curs, count, k, h->cfg.report_dims, cand_ids, cand_dists, n_found);
+    return detect_inter_lists_topk_locked(h, curs, count, k, h->cfg.report_dims, cand_ids, cand_dists, n_found);
 }
 
 int scl_fpfh_save_from_wire_many(scl_fpfh *h, const float *values, const int8_t *robots, const int *indexs, int count)

@@ -388,6 +388,7 @@ struct scl_m2dp {
     unsigned long long *d_exact = nullptr, *d_best = nullptr;
     int *d_list = nullptr; size_t list_cap = 0;
     scl::NnManyWork many;                    // the batched detections' work buffers
+    scl::NnTopkWork topk;                    // the candidate lists' work buffers
     unsigned long long decisions = 0;
     double kernel_us = 0.0;
 };
@@ -528,6 +529,7 @@ int scl_m2dp_destroy(scl_m2dp *h)
                     (void *)h->d_counts, (void *)h->d_bad, (void *)h->d_exact, (void *)h->d_best, (void *)h->d_list})
         if (p) (void)hipFree(p);
     h->many.release();
+    h->topk.release();
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -641,6 +643,22 @@ int scl_m2dp_detect_inter_many(scl_m2dp *h, const int *curs, int count, int *loo
     std::lock_guard<std::mutex> lk(h->mu);
     (void)hipSetDevice(h->device);
     return detect_inter_lists_many_locked(h, curs, count, SCL_M2DP_DIM, loop_ids, dists);
+}
+
+int scl_m2dp_detect_intra_topk(scl_m2dp *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
+{
+    if (!h || count < 0 || (count > 0 && (!curs || !cand_ids))) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    return detect_intra_topk_locked(h, curs, count, k, SCL_M2DP_DIM, cand_ids, cand_dists, n_found);
+}
+
+int scl_m2dp_detect_inter_topk(scl_m2dp *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
+{
+    if (!h || count < 0 || (count > 0 && (!curs || !cand_ids))) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    return detect_inter_lists_topk_locked(h, curs, count, k, SCL_M2DP_DIM, cand_ids, cand_dists, n_found);
 }
 
 int scl_m2dp_save_from_wire_many(scl_m2dp *h, const float *values, const int8_t *robots, const int *indexs, int count)

@@ -7,7 +7,8 @@
 // Every helper that touches a handle assumes its lock is held (the `_locked` convention; std::mutex is not recursive), except
 // the registry's C entry points below, which take it once.  A handle provides `mutable std::mutex mu`, `mutable std::string
 // last_error`, `hipStream_t stream` and `scl::KeyframeRegistry reg`; a vector plugin's also `scl::FloatRows<DIM> db`,
-// `int *d_list`, `size_t list_cap`, `unsigned long long *d_best` (one element) and `scl::NnManyWork many` (the batched search).
+// `int *d_list`, `size_t list_cap`, `unsigned long long *d_best` (one element), `scl::NnManyWork many` (the batched search) and
+// `scl::NnTopkWork topk` (the candidate lists: nn_l2_topk_kernel, nn_topk_merge_kernel and the *_topk detections).
 // Included from .hip files only (nn_l2_kernel and nn_l2_many_kernel are device code).  Everything here has internal linkage (the
 // unnamed namespace): the
 // library exports its C ABI and nothing of this layer.
@@ -404,6 +405,170 @@ struct NnManyWork {
     }
 };
 
+// ---- batched k-NN (the candidate lists, SCL_PLUGIN_TOPK_API): the sums of nn_l2_many_kernel -- same launch geometry, same staging,
+// same operation order, so bit for bit the same floats -- but instead of the atomic min every wave emits, per query, the
+// min(k, valid) smallest (sum bits << 32 | position) keys of its tile in ascending order into part[(q * tiles + tile) * k + j];
+// unused slots are ~0ull.  Valid: position < limit[q] and the sum not NaN (nanoflann's KNNResultSet admits dist < worst only; +inf
+// is a distance like any other).  A tile at or past limit[q] writes nothing for q: the merge reads the tiles below the limit only.
+//
+// The selection is a bitonic sorting network over the wave's 64 keys, one per lane, through __shfl_xor: 21 compare-exchange stages
+// whatever k is, against 6 shuffle steps per listed entry for k rounds of wave-min with knock-out (192 at k = 32), and the sorted
+// order falls out of it.  The keys of a tile are distinct (the position is part of them) apart from the ~0ull fillers, which are
+// interchangeable, so the network's result does not depend on anything but the keys: no atomics, no workgroup order.
+constexpr int kTopkMax = SCL_PLUGIN_TOPK_MAX;
+static_assert(kTopkMax <= kManyTile, "a wave lists at most one key per lane");
+
+__device__ __forceinline__ unsigned long long wave_sort_ascending(unsigned long long key, int lane)
+{
+#pragma unroll
+    for (int k2 = 2; k2 <= kManyTile; k2 <<= 1)
+#pragma unroll
+        for (int j = k2 >> 1; j > 0; j >>= 1) {
+            const unsigned long long o = __shfl_xor(key, j);
+            const bool keep_min = ((lane & j) == 0) == ((lane & k2) == 0);        // k2 == 64: every pair ascending
+            key = (o < key) == keep_min ? o : key;
+        }
+    return key;
+}
+
+template <int DIM>
+__global__ __launch_bounds__(kManyTile) void nn_l2_topk_kernel(const float *db, const int *list, int n, const int *qkey, const int *limit,
+                                                               int nq, int k, unsigned long long *part)
+{
+    constexpr int KC = NnManyShape<DIM>::kChunk, P = NnManyShape<DIM>::kPitch;
+    __shared__ alignas(16) float qs[kDetectGroup * DIM];               // rows of absent queries (q >= nq): zeros, their sums unused
+    __shared__ float cs[kManyTile * P];
+    __shared__ int ks[kManyTile], lim[kDetectGroup];
+    const int t = threadIdx.x, base = blockIdx.x * kManyTile, i = base + t;
+    const int rows = min(kManyTile, n - base);
+    for (int e = t; e < kDetectGroup * DIM; e += kManyTile) {
+        const int q = e / DIM;
+        qs[e] = q < nq ? db[(size_t)qkey[q] * DIM + (e - q * DIM)] : 0.0f;
+    }
+    if (t < kDetectGroup) lim[t] = t < nq ? limit[t] : 0;
+    if (t < rows) ks[t] = list ? list[i] : i;
+    float s[kDetectGroup];
+#pragma unroll
+    for (int q = 0; q < kDetectGroup; ++q) s[q] = 0.0f;
+    for (int k0 = 0; k0 < DIM; k0 += KC) {
+        __syncthreads();                                               // ks / qs written; the previous chunk read
+        for (int e = t; e < rows * KC; e += kManyTile) {
+            const int c = e / KC, kk = e - c * KC;
+            cs[c * P + kk] = db[(size_t)ks[c] * DIM + k0 + kk];
+        }
+        __syncthreads();
+        if (t < rows) {
+            const float *c = cs + t * P;
+#pragma unroll
+            for (int kk = 0; kk + 4 <= KC; kk += 4) {
+                const float c0 = c[kk], c1 = c[kk + 1], c2 = c[kk + 2], c3 = c[kk + 3];
+#pragma unroll
+                for (int q = 0; q < kDetectGroup; ++q) {
+                    const float *a = qs + q * DIM + k0 + kk;
+                    const float d0 = a[0] - c0, d1 = a[1] - c1, d2 = a[2] - c2, d3 = a[3] - c3;
+                    s[q] += ((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3;
+                }
+            }
+#pragma unroll
+            for (int kk = KC / 4 * 4; kk < KC; ++kk) {
+                const float ck = c[kk];
+#pragma unroll
+                for (int q = 0; q < kDetectGroup; ++q) {
+                    const float d = qs[q * DIM + k0 + kk] - ck;
+                    s[q] += d * d;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < kDetectGroup; ++q) {
+        if (base >= lim[q]) continue;                                  // the same for every lane (lim[q] <= n; absent queries: 0)
+        const bool valid = i < lim[q] && s[q] == s[q];
+        unsigned long long key = valid ? ((unsigned long long)__float_as_uint(s[q]) << 32) | (unsigned int)i : ~0ull;
+        key = wave_sort_ascending(key, t);
+        if (t < k) part[((size_t)q * gridDim.x + blockIdx.x) * (size_t)k + t] = key;
+    }
+}
+
+// one listed candidate of a query: its position in the query's list and its global key (-1, -1: the slot is unused) and sqrtf of
+// the squared distance over the first report_dims floats (+inf for an unused slot)
+struct NnTopkEntry {
+    int pos, key;
+    float dist;
+};
+
+// the merge and the finishing step, one workgroup per query of the whole call: the query's (tiles below its limit) * k partial keys,
+// which start at part[part_row[q] * k], go through LDS in rounds of up to kTopkMergeCap - k keys beside the k best so far, each
+// round one bitonic sort of the next power of two; then one thread per listed entry does what nn_finish_many_kernel does for the
+// winner (list_off[q]: where the query's list starts in `list`, -1 for keys 0 .. n - 1) and writes res[q * k + j]
+constexpr int kTopkMergeCap = 2048;
+
+template <int DIM>
+__global__ __launch_bounds__(kNnThreads) void nn_topk_merge_kernel(const float *db, const int *list, const int *qkey, const int *list_off,
+                                                                   const int *limit, const int *part_row, const unsigned long long *part,
+                                                                   int k, int report_dims, NnTopkEntry *res)
+{
+    __shared__ unsigned long long buf[kTopkMergeCap];
+    __shared__ float a[DIM];
+    const int q = blockIdx.x, t = threadIdx.x;
+    for (int e = t; e < DIM; e += kNnThreads) a[e] = db[(size_t)qkey[q] * DIM + e];
+    if (t < k) buf[t] = ~0ull;
+    const size_t total = (size_t)((limit[q] + kManyTile - 1) / kManyTile) * (size_t)k;
+    const unsigned long long *src = part + (size_t)part_row[q] * (size_t)k;
+    for (size_t done = 0; done < total;) {
+        const int chunk = total - done < (size_t)(kTopkMergeCap - k) ? (int)(total - done) : kTopkMergeCap - k;
+        int m = 2;
+        while (m < k + chunk) m <<= 1;                                 // <= kTopkMergeCap
+        for (int e = t; e < m - k; e += kNnThreads) buf[k + e] = e < chunk ? src[done + e] : ~0ull;
+        __syncthreads();
+        for (int k2 = 2; k2 <= m; k2 <<= 1)
+            for (int j = k2 >> 1; j > 0; j >>= 1) {
+                for (int e = t; e < m / 2; e += kNnThreads) {
+                    const int lo = ((e & ~(j - 1)) << 1) | (e & (j - 1)), hi = lo | j;
+                    const unsigned long long x = buf[lo], y = buf[hi];
+                    if ((x > y) == ((lo & k2) == 0)) { buf[lo] = y; buf[hi] = x; }
+                }
+                __syncthreads();
+            }
+        done += (size_t)chunk;
+    }
+    __syncthreads();                                                   // total == 0: buf[0 .. k) and a[] written
+    if (t >= k) return;
+    NnTopkEntry r = {-1, -1, INFINITY};
+    const unsigned long long b = buf[t];
+    if (b != ~0ull) {
+        r.pos = (int)(b & 0xffffffffu);
+        r.key = list_off[q] < 0 ? r.pos : list[list_off[q] + r.pos];
+        const float *c = db + (size_t)r.key * DIM;
+        float s = 0.0f;
+        int d = 0;
+        for (; d + 4 <= report_dims; d += 4) {
+            const float d0 = a[d] - c[d], d1 = a[d + 1] - c[d + 1], d2 = a[d + 2] - c[d + 2], d3 = a[d + 3] - c[d + 3];
+            s += ((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3;
+        }
+        for (; d < report_dims; ++d) {
+            const float dd = a[d] - c[d];
+            s += dd * dd;
+        }
+        r.dist = sqrtf(s);
+    }
+    res[(size_t)q * (size_t)k + t] = r;
+}
+
+// the candidate lists' work buffers of a handle (`scl::NnTopkWork topk`; the lists share d_list): they grow like d_list
+struct NnTopkWork {
+    int *d_q = nullptr;                          // qkey | limit | list_off | part_row, `count` elements each
+    unsigned long long *d_part = nullptr;        // [query][tile][k], group after group
+    NnTopkEntry *d_res = nullptr;                // [query][k]
+    size_t q_cap = 0, part_cap = 0, res_cap = 0;
+    void release()
+    {
+        for (void *p : {(void *)d_q, (void *)d_part, (void *)d_res})
+            if (p) (void)hipFree(p);
+        d_q = nullptr; d_part = nullptr; d_res = nullptr; q_cap = part_cap = res_cap = 0;
+    }
+};
+
 // a candidate list of a batched search: n global keys, keys == nullptr for keys 0 .. n - 1
 struct NnList {
     const int *keys;
@@ -564,6 +729,191 @@ template <class H> int detect_inter_snapshot_many_locked(H *h, const int *curs, 
     if (rc) return rc;
     h->tree_counter = counter; h->snap_n = snap_n;
     report_many(h, res.data(), count, false, loop_ids, dists);
+    return SCL_OK;
+}
+
+// ---- the candidate lists: the k nearest instead of the nearest.  `count` queries as nearest_many_locked takes them; out[i * k + j]
+// is the j-th nearest of query i by (squared distance bits, position), an unused slot (fewer than k candidates with a non-NaN
+// distance) as NnTopkEntry says.  Grouped by list, groups of 16 back to back on the stream (nn_l2_topk_kernel into the partials),
+// then the merge over all queries; ONE device-to-host copy and ONE synchronisation for the whole call
+template <class H>
+int nearest_topk_many_locked(H *h, const int *qkey, const int *limit, const int *which, const NnList lists[2], int count, int k,
+                             int report_dims, NnTopkEntry *out)
+{
+    constexpr int DIM = decltype(h->db)::kDim;
+    if (count <= 0) return SCL_OK;
+    std::vector<int> order((size_t)count);
+    int seg[3] = {0, 0, count}, used[2] = {0, 0};
+    for (int i = 0; i < count; ++i) {
+        seg[1] += which[i] == 0;
+        used[which[i]] = std::max(used[which[i]], limit[i]);
+    }
+    for (int i = 0, a = 0, b = seg[1]; i < count; ++i) order[(size_t)(which[i] == 0 ? a++ : b++)] = i;
+    int off[2] = {-1, -1};
+    size_t keys = 0;
+    for (int l = 0; l < 2; ++l)
+        if (lists[l].keys && used[l] > 0) { off[l] = (int)keys; keys += (size_t)used[l]; }
+    // qkey | limit | list_off | part_row in the grouped order; a group's partials: [query][tile][k] over the tiles of its longest prefix
+    std::vector<int> hq(4 * (size_t)count);
+    for (int j = 0; j < count; ++j) {
+        const int i = order[(size_t)j];
+        hq[(size_t)j] = qkey[i]; hq[(size_t)count + j] = limit[i]; hq[2 * (size_t)count + j] = off[which[i]];
+    }
+    size_t rows = 0;
+    for (int l = 0; l < 2; ++l)
+        for (int s = seg[l]; s < seg[l + 1]; s += kDetectGroup) {
+            const int G = std::min(kDetectGroup, seg[l + 1] - s);
+            int n = 0;
+            for (int j = s; j < s + G; ++j) n = std::max(n, hq[(size_t)count + j]);
+            const size_t tiles = ((size_t)n + kManyTile - 1) / kManyTile;
+            if (rows + (size_t)G * tiles > (size_t)INT32_MAX) return fail(h, SCL_ERR_NOMEM, "candidate lists: the partial lists pass 2^31 rows");
+            for (int j = s; j < s + G; ++j) hq[3 * (size_t)count + j] = (int)(rows + (size_t)(j - s) * tiles);
+            rows += (size_t)G * tiles;
+        }
+    if (keys > h->list_cap) {
+        h->list_cap = 0;
+        const size_t c = keys + keys / 2 + 256;
+        int rc = dev_regrow(h, &h->d_list, c);
+        if (rc) return rc;
+        h->list_cap = c;
+    }
+    NnTopkWork &w = h->topk;
+    const size_t n_part = rows * (size_t)k, n_res = (size_t)count * (size_t)k;
+    int rc;
+    if ((size_t)count > w.q_cap) {
+        w.q_cap = 0;
+        const size_t c = (size_t)count + (size_t)count / 2 + 256;
+        if ((rc = dev_regrow(h, &w.d_q, 4 * c))) return rc;
+        w.q_cap = c;
+    }
+    if (n_part > w.part_cap) {
+        w.part_cap = 0;
+        const size_t c = n_part + n_part / 2 + 256;
+        if ((rc = dev_regrow(h, &w.d_part, c))) return rc;
+        w.part_cap = c;
+    }
+    if (n_res > w.res_cap) {
+        w.res_cap = 0;
+        const size_t c = n_res + n_res / 2 + 256;
+        if ((rc = dev_regrow(h, &w.d_res, c))) return rc;
+        w.res_cap = c;
+    }
+    for (int l = 0; l < 2; ++l)
+        if (off[l] >= 0)
+            SCL_HIP(h, hipMemcpyAsync(h->d_list + off[l], lists[l].keys, sizeof(int) * (size_t)used[l], hipMemcpyHostToDevice, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(w.d_q, hq.data(), sizeof(int) * hq.size(), hipMemcpyHostToDevice, h->stream));
+    const int *d_qkey = w.d_q, *d_limit = w.d_q + count, *d_off = w.d_q + 2 * (size_t)count, *d_row = w.d_q + 3 * (size_t)count;
+    for (int l = 0; l < 2; ++l)
+        for (int s = seg[l]; s < seg[l + 1]; s += kDetectGroup) {
+            const int G = std::min(kDetectGroup, seg[l + 1] - s);
+            int n = 0;
+            for (int j = s; j < s + G; ++j) n = std::max(n, hq[(size_t)count + j]);
+            if (n <= 0) continue;                                      // every prefix of the group empty: the merge reads no tile
+            hipLaunchKernelGGL(nn_l2_topk_kernel<DIM>, dim3((unsigned)((n + kManyTile - 1) / kManyTile)), dim3(kManyTile), 0, h->stream,
+                               h->db.d_db, off[l] >= 0 ? h->d_list + off[l] : nullptr, n, d_qkey + s, d_limit + s, G, k,
+                               w.d_part + (size_t)hq[3 * (size_t)count + s] * (size_t)k);
+        }
+    hipLaunchKernelGGL(nn_topk_merge_kernel<DIM>, dim3((unsigned)count), dim3(kNnThreads), 0, h->stream, h->db.d_db, h->d_list, d_qkey, d_off,
+                       d_limit, d_row, w.d_part, k, report_dims, w.d_res);
+    SCL_HIP(h, hipGetLastError());
+    std::vector<NnTopkEntry> res(n_res);
+    SCL_HIP(h, hipMemcpyAsync(res.data(), w.d_res, sizeof(NnTopkEntry) * n_res, hipMemcpyDeviceToHost, h->stream));
+    SCL_HIP(h, hipStreamSynchronize(h->stream));
+    for (int j = 0; j < count; ++j) std::copy_n(res.begin() + (size_t)j * k, k, out + (size_t)order[(size_t)j] * k);
+    return SCL_OK;
+}
+
+// the lists from the search results: the listed candidates first (the position for intra, the key for inter; the reported distance),
+// then (-1, +inf) up to k; dist_thres is not applied.  cand_dists and n_found may be null
+inline void report_topk(const NnTopkEntry *res, int count, int k, bool local_ids, int *cand_ids, float *cand_dists, int *n_found)
+{
+    for (int i = 0; i < count; ++i) {
+        int found = 0;
+        for (int j = 0; j < k; ++j) {
+            const NnTopkEntry &r = res[(size_t)i * k + j];
+            found += r.pos >= 0;
+            cand_ids[(size_t)i * k + j] = local_ids ? r.pos : r.key;
+            if (cand_dists) cand_dists[(size_t)i * k + j] = r.pos >= 0 ? r.dist : INFINITY;
+        }
+        if (n_found) n_found[i] = found;
+    }
+}
+
+inline bool topk_ok(int k) { return k >= 1 && k <= kTopkMax; }
+
+// the candidate list of detect_intra for curs[0 .. count): the search sets of detect_intra_many_locked
+template <class H>
+int detect_intra_topk_locked(H *h, const int *curs, int count, int k, int report_dims, int *cand_ids, float *cand_dists, int *n_found)
+{
+    if (!topk_ok(k)) return fail(h, SCL_ERR_INVALID_ARG, "detect_intra_topk: k outside [1, SCL_PLUGIN_TOPK_MAX]");
+    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
+    for (int i = 0; i < count; ++i)
+        if (curs[i] < 0 || curs[i] >= (int)mine.size()) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_intra_topk: no such keyframe of this robot");
+    std::vector<int> qkey((size_t)count), limit((size_t)count), which((size_t)count, 0);
+    for (int i = 0; i < count; ++i) {
+        qkey[(size_t)i] = mine[(size_t)curs[i]];
+        limit[(size_t)i] = std::max(0, curs[i] - h->cfg.num_exclude_recent);
+    }
+    const NnList lists[2] = {{mine.data(), (int)mine.size()}, {nullptr, 0}};       // ascending keys: position = local index
+    std::vector<NnTopkEntry> res((size_t)count * k);
+    int rc = nearest_topk_many_locked(h, qkey.data(), limit.data(), which.data(), lists, count, k, report_dims, res.data());
+    if (rc) return rc;
+    report_topk(res.data(), count, k, true, cand_ids, cand_dists, n_found);
+    return SCL_OK;
+}
+
+// the candidate list of detect_inter by M2DP's rule (inter_mode 1 of FPFH and GRSD): the search sets of detect_inter_lists_many_locked
+template <class H>
+int detect_inter_lists_topk_locked(H *h, const int *curs, int count, int k, int report_dims, int *cand_ids, float *cand_dists, int *n_found)
+{
+    if (!topk_ok(k)) return fail(h, SCL_ERR_INVALID_ARG, "detect_inter_topk: k outside [1, SCL_PLUGIN_TOPK_MAX]");
+    for (int i = 0; i < count; ++i)
+        if (curs[i] < 0 || curs[i] >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter_topk: key out of range");
+    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
+    std::vector<int> others;
+    for (int r = 0; r < h->reg.robot_num; ++r)
+        if (r != h->cfg.this_id) others.insert(others.end(), h->reg.keys_of(r).begin(), h->reg.keys_of(r).end());
+    std::sort(others.begin(), others.end());                                      // ties go to the lowest key
+    const NnList lists[2] = {{others.data(), (int)others.size()}, {mine.data(), (int)mine.size()}};
+    std::vector<int> limit((size_t)count), which((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        which[(size_t)i] = h->reg.robots[(size_t)curs[i]] == h->cfg.this_id ? 0 : 1;
+        limit[(size_t)i] = lists[which[(size_t)i]].n;
+    }
+    std::vector<NnTopkEntry> res((size_t)count * k);
+    int rc = nearest_topk_many_locked(h, curs, limit.data(), which.data(), lists, count, k, report_dims, res.data());
+    if (rc) return rc;
+    report_topk(res.data(), count, k, false, cand_ids, cand_dists, n_found);
+    return SCL_OK;
+}
+
+// the candidate list of detect_inter of the reference (inter_mode 0 of FPFH and GRSD): tree_counter and snap_n walk as in
+// detect_inter_snapshot_many_locked and are committed on success only; before num_exclude_recent + 1 keyframes every list is empty
+// and the counter stays
+template <class H>
+int detect_inter_snapshot_topk_locked(H *h, const int *curs, int count, int k, int report_dims, int *cand_ids, float *cand_dists, int *n_found)
+{
+    if (!topk_ok(k)) return fail(h, SCL_ERR_INVALID_ARG, "detect_inter_topk: k outside [1, SCL_PLUGIN_TOPK_MAX]");
+    for (int i = 0; i < count; ++i)
+        if (curs[i] < 0 || curs[i] >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter_topk: key out of range");
+    if (h->reg.n < h->cfg.num_exclude_recent + 1) {
+        for (size_t e = 0; e < (size_t)count * k; ++e) { cand_ids[e] = -1; if (cand_dists) cand_dists[e] = INFINITY; }
+        for (int i = 0; n_found && i < count; ++i) n_found[i] = 0;
+        return SCL_OK;
+    }
+    int counter = h->tree_counter, snap_n = h->snap_n;
+    std::vector<int> limit((size_t)count), which((size_t)count, 0);
+    for (int i = 0; i < count; ++i) {
+        if (counter % h->cfg.tree_making_period == 0) snap_n = h->reg.n - h->cfg.num_exclude_recent;
+        counter += 1;
+        limit[(size_t)i] = snap_n;
+    }
+    const NnList lists[2] = {{nullptr, h->reg.n}, {nullptr, 0}};
+    std::vector<NnTopkEntry> res((size_t)count * k);
+    int rc = nearest_topk_many_locked(h, curs, limit.data(), which.data(), lists, count, k, report_dims, res.data());
+    if (rc) return rc;
+    h->tree_counter = counter; h->snap_n = snap_n;
+    report_topk(res.data(), count, k, false, cand_ids, cand_dists, n_found);
     return SCL_OK;
 }
 

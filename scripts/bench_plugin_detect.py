@@ -1,7 +1,9 @@
 """Detection timing of the vector plugins (M2DP, FPFH, GRSD) over a database filled from the wire: the single call and the batch
-form (detect_*_many) at batch sizes 16 and 256, wall microseconds per query as [min, median, max] over --reps repetitions.
+form (detect_*_many) at batch sizes 16 and 256, and the candidate lists (detect_*_topk) at k = 10 and 32 over the same batches, wall
+microseconds per query as [min, median, max] over --reps repetitions.
 scripts/bench_m2dp.py, bench_fpfh.py and bench_grsd.py take time_detect() from here; run alone it prints one JSON line per plugin
-(--plugins).  --single-only: a library without the batch calls (an A/B against an older build).  The device time of
+(--plugins).  --single-only: a library without the batch calls (an A/B against an older build); a library without the candidate lists is timed
+without them.  The device time of
 nn_l2_many_kernel comes from a separate `rocprofv3 --kernel-trace --stats` run of this script."""
 import argparse
 import json
@@ -15,6 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 BATCHES = (16, 256)
+TOPK = (10, 32)
 
 
 def _range(xs):
@@ -58,6 +61,21 @@ def time_detect(det, form, keyframes, queries=200, reps=5, many=True):
                 batched(curs[size])
             us.append((time.perf_counter() - t0) / (calls * size) * 1e6)
         out[f"detect_{form}_many_us_per_query_at_{size}"] = _range(us)
+    topk = getattr(det, f"detect_{form}_topk", None)
+    if topk is None:
+        return out
+    for k in TOPK:
+        for size in BATCHES:
+            calls = max(1, queries // size)
+            for _ in range(3):
+                topk(curs[size], k)
+            us = []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                for _ in range(calls):
+                    topk(curs[size], k)
+                us.append((time.perf_counter() - t0) / (calls * size) * 1e6)
+            out[f"detect_{form}_topk{k}_us_per_query_at_{size}"] = _range(us)
     return out
 
 
