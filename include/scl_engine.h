@@ -423,6 +423,13 @@ int  scl_selftest_sort_pairs(scl_engine *e, int key_bytes, const void *keys, con
                              int n_segments, void *keys_out, uint32_t *values_out);
 /* ... and of its prefix sums (cell counts -> cell starts): out[i] = in[0] + ... + in[i - 1], + in[i] when inclusive != 0 */
 int  scl_selftest_prefix_sum(scl_engine *e, const int32_t *in, int n, int inclusive, int32_t *out);
+/* Self test of the batched voxel filter (csrc/voxel.hip, assemble_submaps_batch: the path of scl_loop_icp_batch_from_store, which
+ * shows only the submaps' sizes): the submaps of n_jobs windows of `robot`'s stored keyframes -- job j = keyframes keys[j] -
+ * search_nums[j] .. keys[j] + search_nums[j], each moved by its pose -- assembled and filtered in ONE batched call, copied back to
+ * back into `out` (records of the store's stride), n_out[j] points of job j.  More than 64 jobs: SCL_ERR_INVALID_ARG. */
+int  scl_selftest_submaps_batch(scl_engine *e, int robot, int n_jobs, const int *keys, const int *search_nums,
+                                const float *poses /* the jobs' windows behind each other: sum(2*sn_j+1) matrices */,
+                                float leaf, void *out, int out_capacity /* points, all jobs */, int *n_out /* n_jobs */);
 
 #ifdef __cplusplus
 }

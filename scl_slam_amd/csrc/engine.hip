@@ -3090,6 +3090,45 @@ int scl_loop_icp_batch_from_store(scl_engine *e, int robot, int key_cur, const f
     return SCL_OK;
 }
 
+/* test hook: the submaps of voxel.hip's batched filter themselves -- scl_loop_icp_batch_from_store shows only their sizes and the ICP
+ * result behind them.  Job j = the window of keys[j] with search_nums[j] (the production call: 0 for job 0), all jobs in ONE
+ * assemble_submaps_batch call on the engine's own workspace and stream, the results copied back to back into `out` */
+int scl_selftest_submaps_batch(scl_engine *e, int robot, int n_jobs, const int *keys, const int *search_nums, const float *poses,
+                               float leaf, void *out, int out_capacity, int *n_out)
+{
+    if (!e || n_jobs < 0 || out_capacity < 0 || (out_capacity > 0 && !out) || (n_jobs > 0 && (!keys || !search_nums || !poses || !n_out))) return SCL_ERR_INVALID_ARG;
+    if (e->front) e = front_primary(e);
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    const int stride = e->kf_stride ? e->kf_stride : 16;
+    std::vector<const void *> clouds, cl_all; std::vector<int> counts, cn_all, first_of; std::vector<float> Tw, tw_all;
+    std::string err;
+    int rc = SCL_OK;
+    size_t pose_off = 0;
+    first_of.push_back(0);
+    for (int j = 0; j < n_jobs; ++j) {
+        if ((rc = kf_window(e, robot, keys[j], search_nums[j], poses + 16 * pose_off, &clouds, &counts, &Tw))) return rc;
+        pose_off += 2 * (size_t)search_nums[j] + 1;
+        cl_all.insert(cl_all.end(), clouds.begin(), clouds.end()); cn_all.insert(cn_all.end(), counts.begin(), counts.end()); tw_all.insert(tw_all.end(), Tw.begin(), Tw.end());
+        first_of.push_back((int)cl_all.size());
+    }
+    std::vector<const void *> d_sub((size_t)n_jobs + 1); std::vector<int> n_sub((size_t)n_jobs + 1);
+    rc = assemble_submaps_batch(&e->vox_ws, e->stream, cl_all.data(), cn_all.data(), tw_all.data(), first_of.data(), n_jobs, stride, leaf,
+                                d_sub.data(), n_sub.data(), &err);
+    if (rc) { e->last_error = err; return rc; }
+    size_t total = 0;
+    for (int j = 0; j < n_jobs; ++j) total += (size_t)n_sub[(size_t)j];
+    if (total > (size_t)out_capacity) return fail(e, SCL_ERR_INVALID_ARG, "selftest_submaps_batch: output capacity too small");
+    size_t off = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        n_out[j] = n_sub[(size_t)j];
+        if (n_sub[(size_t)j]) SCL_HIP(e, hipMemcpyAsync(static_cast<unsigned char *>(out) + off * stride, d_sub[(size_t)j], (size_t)n_sub[(size_t)j] * stride, hipMemcpyDeviceToHost, e->stream));
+        off += (size_t)n_sub[(size_t)j];
+    }
+    SCL_HIP(e, hipStreamSynchronize(e->stream));
+    return SCL_OK;
+}
+
 int scl_geometric_verification_from_store(scl_engine *e, const void *src, int n_src, int stride_bytes, float src_leaf,
                                           int robot, int key_pre, int search_num, const float *poses_pre, float leaf,
                                           int min_src_points, int min_tgt_points,

@@ -144,6 +144,7 @@ def _bind(lib):
         "scl_selftest_bin_paths": (c_int, [P, c_int, c_uint64, c_uint64, POINTER(ctypes.c_uint64), POINTER(ctypes.c_uint64)]),
         "scl_selftest_sort_pairs": (c_int, [P, c_int, c_void_p, POINTER(ctypes.c_uint32), c_int, c_int, POINTER(c_int), c_int, c_void_p, POINTER(ctypes.c_uint32)]),
         "scl_selftest_prefix_sum": (c_int, [P, POINTER(ctypes.c_int32), c_int, c_int, POINTER(ctypes.c_int32)]),
+        "scl_selftest_submaps_batch": (c_int, [P, c_int, c_int, ip, ip, fp, c_float, P, c_int, ip]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -329,6 +330,26 @@ class ScanContextEngine:
         v = np.ascontiguousarray(values, dtype=np.int32); out = np.empty_like(v)
         self._check(self._lib.scl_selftest_prefix_sum(self._h, _ptr(v, ctypes.c_int32), v.size, 1 if inclusive else 0, _ptr(out, ctypes.c_int32)), "scl_selftest_prefix_sum")
         return out
+
+    def selftest_submaps_batch(self, robot, keys, search_nums, poses, leaf, floats_per_point=8):
+        """the submaps of voxel.hip's batched filter, one array per job: job j = the window of keys[j] with search_nums[j] of the
+        keyframe store, poses[j] its 2 * search_nums[j] + 1 matrices (as submap_from_store takes them)"""
+        keys = np.ascontiguousarray(keys, dtype=np.int32); sns = np.ascontiguousarray(search_nums, dtype=np.int32)
+        m = keys.size
+        assert sns.size == m and len(poses) == m
+        Ts = [_f32(np.asarray(p)).reshape(-1, 16) for p in poses]
+        assert all(T.shape[0] == 2 * int(sn) + 1 for T, sn in zip(Ts, sns))
+        Tp = np.concatenate(Ts) if m else np.zeros((1, 16), np.float32)
+        stored, cap, n = self.keyframe_count(robot), 0, c_int()
+        for k, sn in zip(keys, sns):                                   # room for every window unfiltered
+            for i in range(max(0, int(k) - int(sn)), min(stored, int(k) + int(sn) + 1)):
+                self._check(self._lib.scl_keyframe_get(self._h, robot, i, None, 0, byref(n)), "scl_keyframe_get")
+                cap += n.value
+        out = np.empty((max(cap, 1), floats_per_point), dtype=np.float32); n_out = np.zeros(max(m, 1), dtype=np.int32)
+        self._check(self._lib.scl_selftest_submaps_batch(self._h, robot, m, _ptr(keys, c_int), _ptr(sns, c_int), _ptr(Tp, c_float), leaf,
+                                                         out.ctypes.data_as(c_void_p), cap, _ptr(n_out, c_int)), "scl_selftest_submaps_batch")
+        ends = np.cumsum(n_out[:m])
+        return [out[e - c:e].copy() for e, c in zip(ends, n_out[:m])]
 
     def selftest_atanf_blocks(self, first_block, n_blocks):
         out = np.zeros(n_blocks, dtype=np.uint64)
