@@ -159,6 +159,23 @@ public:
         return pairs(loops, biases, ok);
     }
 
+    // one ranked candidate of the exhaustive search: the keyframe, the column shift and the distance over every shift
+    struct LoopCandidate { int id; float bias; float dist; };
+
+    // the exhaustive ranked search (scl_iris.h "THE EXHAUSTIVE SEARCH"): per entry of curPtrs the up to k best keyframes of the whole
+    // set detectIntraLoopClosureID searches, ascending by distance, distThres not applied -- for a verifier that takes several
+    // candidates; ids are local indices.  On an error (k outside [1, SCL_IRIS_SEARCH_MAX], an entry out of range) every list is empty
+    std::vector<std::vector<LoopCandidate>> searchIntraLoopClosureIDs(const std::vector<int> &curPtrs, int k)
+    {
+        return search(curPtrs, k, scl_iris_search_intra, "searchIntraLoopClosureIDs");
+    }
+
+    // the same over the set detectInterLoopClosureID searches: ids are global keys
+    std::vector<std::vector<LoopCandidate>> searchInterLoopClosureIDs(const std::vector<int> &curPtrs, int k)
+    {
+        return search(curPtrs, k, scl_iris_search_inter, "searchInterLoopClosureIDs");
+    }
+
     // the descriptors of the last makeSaveAndDetect: scans.size() * (rows * cols + rows) floats
     const std::vector<float> &lastDescriptors() const { return last_; }
 
@@ -214,6 +231,22 @@ private:
         if (rc == SCL_OK) return true;
         std::fprintf(stderr, "[lidar_iris_hip_descriptor] %s: %s (%s)\n", where, scl_status_string(rc), scl_iris_last_error(iris_));
         return false;
+    }
+
+    std::vector<std::vector<LoopCandidate>> search(const std::vector<int> &curPtrs, int k,
+                                                   int (*call)(scl_iris *, const int *, int, int, int *, float *, float *, int *), const char *where)
+    {
+        std::vector<std::vector<LoopCandidate>> out(curPtrs.size());
+        if (k < 1 || k > SCL_IRIS_SEARCH_MAX) {
+            std::fprintf(stderr, "[lidar_iris_hip_descriptor] %s: k = %d outside [1, %d]\n", where, k, SCL_IRIS_SEARCH_MAX);
+            return out;
+        }
+        std::vector<int> ids(curPtrs.size() * static_cast<size_t>(k), -1), found(curPtrs.size(), 0);
+        std::vector<float> biases(ids.size(), 0.0f), dists(ids.size(), 0.0f);
+        if (!report(call(iris_, curPtrs.data(), static_cast<int>(curPtrs.size()), k, ids.data(), biases.data(), dists.data(), found.data()), where)) return out;
+        for (size_t i = 0; i < curPtrs.size(); ++i)
+            for (int j = 0; j < found[i]; ++j) out[i].push_back(LoopCandidate{ids[i * k + j], biases[i * k + j], dists[i * k + j]});
+        return out;
     }
 
     static std::vector<std::pair<int, float>> pairs(const std::vector<int> &loops, const std::vector<float> &biases, bool ok)

@@ -148,6 +148,37 @@ int scl_iris_make_save_and_detect(scl_iris *h, const void *const *clouds, const 
                                   const int8_t *robots, const int *indexs, int count,
                                   int *loop_ids, float *biases, float *dists, float *out_values);
 
+/*
+ * THE EXHAUSTIVE SEARCH.  The detections compare only the num_candidates keyframes the row key pre-selects and report one winner;
+ * these two calls score a query against its WHOLE search set on the device and return the k best, ranked, for a verifier that
+ * takes several candidates (scl_loop_icp_batch_from_store) or for rank statistics.  Shape and conventions are those of
+ * SCL_PLUGIN_TOPK_API (scl_plugin_batch.h): cand_ids, cand_biases and cand_dists hold count * k elements, row i for curs[i];
+ * n_found holds count elements; cand_biases, cand_dists and n_found may be NULL; count == 0 is SCL_OK.
+ *   * Search set of query i.  intra: curs[i] is a LOCAL index of this_id, the set is this robot's keyframes
+ *     [0, curs[i] - num_exclude_recent) (empty when that is <= 0), ids are LOCAL.  inter: curs[i] is a GLOBAL key, the set is the one
+ *     detect_inter searches -- a received keyframe searches this robot's keys, one of this robot every other robot's in the
+ *     registry's concatenation order -- and ids are GLOBAL keys.  The minimum sizes of the detections (D.h:1092-1095, 1198-1201)
+ *     do NOT apply: they exist for the row-key kNN, and there is none here.
+ *   * Score of a pair: scl_iris_hamming_all_shifts(query, candidate), bit for bit -- every column shift 0 .. cols-1 of the query, a
+ *     shift without an unmasked bit skipped, diff / total correctly rounded, the first minimum; NaN (bias -1) when every shift is
+ *     fully masked.
+ *   * The list: the k smallest scores in ascending (float bits of the score, position in the search set) order -- equal scores go
+ *     to the lower position; a NaN pair is never listed.  n_found[i] = min(k, pairs with a score); entries j >= n_found[i] are id
+ *     -1, bias 0, distance +inf.  cand_biases is the shift as a float, as the detections return it.
+ *   * No threshold, no loop decision: the caller applies dist_thres.  The result does not depend on shift_search, match_num,
+ *     num_candidates, knn_exclude_eps, dist_thres, or on the parity of rows / cols (the FFT estimate is not involved).
+ *   * k < 1 or k > SCL_IRIS_SEARCH_MAX: SCL_ERR_INVALID_ARG.  A cur out of range anywhere: SCL_ERR_OUT_OF_RANGE.  Both before
+ *     anything runs: no output written, no state changed.  The calls change nothing a later single or batch call can see.
+ * Launch groups of SCL_IRIS_DETECT_GROUP queries; a group reads every candidate's templates from memory once, whatever cols and
+ * the number of its queries; the host waits for the device once per call.
+ */
+#define SCL_IRIS_SEARCH_MAX 32   /* the longest list; = SCL_PLUGIN_TOPK_MAX */
+
+int scl_iris_search_intra(scl_iris *h, const int *curs, int count, int k,
+                          int *cand_ids, float *cand_biases, float *cand_dists, int *n_found);
+int scl_iris_search_inter(scl_iris *h, const int *curs, int count, int k,
+                          int *cand_ids, float *cand_biases, float *cand_dists, int *n_found);
+
 #ifdef __cplusplus
 }
 #endif

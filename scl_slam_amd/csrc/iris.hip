@@ -636,6 +636,122 @@ __global__ void iris_finish_detect_kernel(const int *cand_pos, const int *est, c
     out[q] = a;
 }
 
+// ---- the exhaustive ranked search (scl_iris.h "THE EXHAUSTIVE SEARCH") ----------------------------------------------------------
+// iris_search_score_kernel: one workgroup per candidate of the search set, one LANE per column shift.  iris_hamming_kernel pairs
+// the query's column k - s with the candidate's column k; over k' = k - s that is the query's column k' with the candidate's column
+// (k' + s) mod N.  So at every step all lanes need the SAME query word -- a uniform address, which the compiler serves with scalar
+// loads from L2: the queries of a launch group are 16 x 57.6 KB at the defaults -- and lane s needs the candidate word s columns
+// further on, which comes from LDS, where the workgroup stages its candidate once: {T, M} pairs as [column][pitch], pitch = words | 1
+// pairs, so that the 32 lanes of a ds_read_b64 group, one column apart, fall on 32 different bank pairs.  Every pair a lane reads from
+// LDS serves kSearchQuad queries; a candidate crosses HBM once per launch group whatever the number of shifts and queries.  A lane
+// keeps its shift's two integer counts per query in registers over all N * words words, so nothing is reduced per shift; per pair
+// the (score bits << 32 | shift) keys of the shifts with total != 0 are reduced to their minimum -- the first minimum, scores being
+// non-negative floats -- and only (score, shift) leaves the kernel: NaN and -1 where every shift is fully masked.
+// kLds = false: a template that does not fit kSearchLdsBytes is read from global memory instead, column by column per lane.
+constexpr int kSearchQuad = 4;                             // queries a lane scores per candidate word it reads
+constexpr int kSearchMaxThreads = 512;                     // lanes = shifts rounded up to whole waves, at most this (more shifts: passes)
+constexpr size_t kSearchLdsBytes = 64 * 1024 - 256;        // the staged candidate (60 480 B at 80 x 360: two workgroups per CU); 256 B: `part`
+
+template <bool kLds>
+__global__ __launch_bounds__(kSearchMaxThreads) void iris_search_score_kernel(const unsigned int *__restrict__ T, const unsigned int *__restrict__ M,
+                                                                               size_t feat_words, const int *__restrict__ qkey,
+                                                                               const int *__restrict__ limit, int nq, const int *__restrict__ list,
+                                                                               int N, int words, int trows, float *__restrict__ score,
+                                                                               int *__restrict__ bias, int stride)
+{
+    extern __shared__ uint2 cand_lds[];                    // [N][pitch] {T, M} (kLds)
+    __shared__ unsigned long long part[kSearchQuad][kSearchMaxThreads / 64];
+    const int pos = blockIdx.x, tid = threadIdx.x, pitch = words | 1;
+    const size_t c_off = (size_t)list[pos] * feat_words;
+    const unsigned int *T2 = T + c_off, *M2 = M + c_off;
+    if (kLds) {
+        for (int i = tid; i < N * words; i += blockDim.x) {
+            const int k = i / words, w = i - k * words;
+            cand_lds[k * pitch + w] = make_uint2(T2[i], M2[i]);
+        }
+        __syncthreads();
+    }
+    for (int q0 = 0; q0 < nq; q0 += kSearchQuad) {
+        bool act[kSearchQuad], any = false;
+        const unsigned int *Tq[kSearchQuad], *Mq[kSearchQuad];
+#pragma unroll
+        for (int j = 0; j < kSearchQuad; ++j) {
+            act[j] = q0 + j < nq && pos < limit[q0 + j];
+            any = any || act[j];
+            const size_t q_off = act[j] ? (size_t)qkey[q0 + j] * feat_words : c_off;       // an idle slot scores the candidate itself, unused
+            Tq[j] = T + q_off; Mq[j] = M + q_off;
+        }
+        if (!any) continue;                                 // the same for every lane
+        unsigned long long best[kSearchQuad];
+#pragma unroll
+        for (int j = 0; j < kSearchQuad; ++j) best[j] = ~0ull;
+        for (int s0 = 0; s0 < N; s0 += blockDim.x) {
+            const bool live = s0 + tid < N;
+            const int s = live ? s0 + tid : 0;
+            int diff[kSearchQuad], masked[kSearchQuad];
+#pragma unroll
+            for (int j = 0; j < kSearchQuad; ++j) { diff[j] = 0; masked[j] = 0; }
+            int col = s;                                    // the candidate's column under the query's column k
+            for (int k = 0; k < N; ++k) {
+                const size_t qo = (size_t)k * words;
+                const uint2 *cl = cand_lds + col * pitch;
+                const unsigned int *ct = T2 + (size_t)col * words, *cm = M2 + (size_t)col * words;
+#pragma unroll 4
+                for (int w = 0; w < words; ++w) {
+                    const uint2 c = kLds ? cl[w] : make_uint2(ct[w], cm[w]);
+#pragma unroll
+                    for (int j = 0; j < kSearchQuad; ++j) {
+                        const unsigned int mask = Mq[j][qo + w] | c.y;
+                        diff[j] += __popc((Tq[j][qo + w] ^ c.x) & ~mask); masked[j] += __popc(mask);
+                    }
+                }
+                col = col + 1 == N ? 0 : col + 1;
+            }
+#pragma unroll
+            for (int j = 0; j < kSearchQuad; ++j) {
+                const int total = trows * N - masked[j];
+                if (live && total != 0) {
+                    const unsigned long long key = ((unsigned long long)__float_as_uint(__fdiv_rn((float)diff[j], (float)total)) << 32) | (unsigned int)s;
+                    best[j] = key < best[j] ? key : best[j];
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kSearchQuad; ++j) {
+            for (int off = 32; off > 0; off >>= 1) {
+                const unsigned long long o = __shfl_xor(best[j], off, 64);
+                best[j] = o < best[j] ? o : best[j];
+            }
+            if ((tid & 63) == 0) part[j][tid >> 6] = best[j];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < kSearchQuad; ++j) {
+            if (tid != j || !act[j]) continue;
+            unsigned long long b = part[j][0];
+            for (int w = 1; w < (int)(blockDim.x >> 6); ++w) b = part[j][w] < b ? part[j][w] : b;
+            const size_t o = (size_t)(q0 + j) * stride + pos;
+            score[o] = b == ~0ull ? NAN : __uint_as_float((unsigned int)(b >> 32));
+            bias[o] = b == ~0ull ? -1 : (int)(b & 0xffffffffu);
+        }
+        __syncthreads();                                    // part read before the next quad writes it
+    }
+}
+
+// one ranked entry of a query: its position in the query's search set (-1: the slot is unused), the shift and the score
+struct IrisSearchEntry { int pos, bias; float dis; };
+
+// cand_pos (iris_select_kernel over the scores) -> the entries of a launch group: one thread per (query, rank)
+__global__ void iris_search_finish_kernel(const int *cand_pos, const float *score, const int *bias, int stride, int nq, int k, IrisSearchEntry *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nq * k) return;
+    const int q = i / k, pos = cand_pos[i];
+    IrisSearchEntry e = {-1, 0, INFINITY};
+    if (pos >= 0) { e.pos = pos; e.bias = bias[(size_t)q * stride + pos]; e.dis = score[(size_t)q * stride + pos]; }
+    out[i] = e;
+}
+
 }  // namespace
 
 namespace {
@@ -653,9 +769,11 @@ struct IrisBatchWork {
     DevBuf wire;                                               // save_from_wire_many: the vectors as received
     DevBuf list, query, d2, cand, jobs, est, counts, answers;  // detections
     DevBuf fm, fres, fmats;                                    // FFT shift estimate: the work planes of one pass, its results and matrices
+    DevBuf sscore, sbias, spos, sres;                          // exhaustive search: a group's scores and shifts, the ranked positions, the entries
     void release()
     {
-        for (DevBuf *b : {&points, &planes, &table, &wire, &list, &query, &d2, &cand, &jobs, &est, &counts, &answers, &fm, &fres, &fmats}) {
+        for (DevBuf *b : {&points, &planes, &table, &wire, &list, &query, &d2, &cand, &jobs, &est, &counts, &answers, &fm, &fres, &fmats, &sscore, &sbias,
+                          &spos, &sres}) {
             if (b->p) (void)hipFree(b->p);
             b->p = nullptr; b->cap = 0;
         }
@@ -1344,6 +1462,128 @@ int detect_inter_many_locked(scl_iris *h, const int *curs, int count, int *loop_
     return SCL_OK;
 }
 
+// The exhaustive ranked search for `count` queries (ManyQuery as in detect_many_locked; limit <= 0: an empty search set).  The
+// searching queries are ordered by list and cut into launch groups of kIrisDetectGroup; per group the scoring launch (one per list
+// the group reaches: every candidate below the group's longest prefix against every query of the group), iris_select_kernel over the
+// scores -- k rounds over n floats per query, next to nothing beside n * cols * cols * words word steps of scoring, and the order
+// (score bits, position) with NaN left out is the one it already implements -- and the finishing kernel; everything on the stream,
+// ONE copy back and ONE wait for the whole call.  out[i * k + j]: rank j of query i, (-1, 0, +inf) from the first unused slot on
+int search_many_locked(scl_iris *h, const std::vector<ManyQuery> &qs, const std::vector<int> lists[2], int k, std::vector<IrisSearchEntry> &out)
+{
+    const int count = (int)qs.size(), N = h->cfg.cols;
+    out.assign((size_t)count * k, IrisSearchEntry{-1, 0, INFINITY});
+    std::vector<int> order;
+    int used[2] = {0, 0};
+    for (int l = 0; l < 2; ++l)
+        for (int i = 0; i < count; ++i)
+            if (qs[(size_t)i].limit > 0 && qs[(size_t)i].which == l) { order.push_back(i); used[l] = std::max(used[l], qs[(size_t)i].limit); }
+    const int nact = (int)order.size();
+    if (nact == 0) return SCL_OK;
+    const int off[2] = {0, used[0]}, nmax = std::max(used[0], used[1]);
+    const size_t n_res = (size_t)nact * k;
+    int rc;
+    if ((rc = reserve(h, h->bw.list, sizeof(int) * ((size_t)used[0] + used[1]))) || (rc = reserve(h, h->bw.query, sizeof(int) * 3 * (size_t)nact)) ||
+        (rc = reserve(h, h->bw.sscore, sizeof(float) * (size_t)kIrisDetectGroup * nmax)) || (rc = reserve(h, h->bw.sbias, sizeof(int) * (size_t)kIrisDetectGroup * nmax)) ||
+        (rc = reserve(h, h->bw.spos, sizeof(int) * n_res)) || (rc = reserve(h, h->bw.sres, sizeof(IrisSearchEntry) * n_res))) return rc;
+    std::vector<int> hq(3 * (size_t)nact);                                     // key | limit | list offset
+    for (int j = 0; j < nact; ++j) {
+        const ManyQuery &q = qs[(size_t)order[(size_t)j]];
+        hq[(size_t)j] = q.key; hq[(size_t)nact + j] = q.limit; hq[2 * (size_t)nact + j] = off[q.which];
+    }
+    int *d_list = h->bw.list.as<int>(), *d_qkey = h->bw.query.as<int>(), *d_limit = d_qkey + nact;
+    float *d_score = h->bw.sscore.as<float>();
+    int *d_bias = h->bw.sbias.as<int>(), *d_pos = h->bw.spos.as<int>();
+    IrisSearchEntry *d_res = h->bw.sres.as<IrisSearchEntry>();
+    for (int l = 0; l < 2; ++l)
+        if (used[l] > 0) SCL_HIP(h, hipMemcpyAsync(d_list + off[l], lists[l].data(), sizeof(int) * (size_t)used[l], hipMemcpyHostToDevice, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(d_qkey, hq.data(), sizeof(int) * hq.size(), hipMemcpyHostToDevice, h->stream));
+    const size_t fw = (size_t)N * h->words, lds = sizeof(uint2) * (size_t)N * (size_t)(h->words | 1);
+    const int threads = std::min(kSearchMaxThreads, (N + 63) / 64 * 64);
+    for (int s = 0; s < nact; s += kIrisDetectGroup) {
+        const int G = std::min(kIrisDetectGroup, nact - s);
+        for (int a = s; a < s + G;) {                                          // the group's queries of one list: one launch
+            int b = a, n = 0;
+            while (b < s + G && hq[2 * (size_t)nact + b] == hq[2 * (size_t)nact + a]) { n = std::max(n, hq[(size_t)nact + b]); ++b; }
+            float *sc = d_score + (size_t)(a - s) * nmax;
+            int *bi = d_bias + (size_t)(a - s) * nmax;
+            if (lds <= kSearchLdsBytes)
+                hipLaunchKernelGGL(iris_search_score_kernel<true>, dim3((unsigned)n), dim3((unsigned)threads), lds, h->stream, h->d_T, h->d_M, fw, d_qkey + a,
+                                   d_limit + a, b - a, d_list + hq[2 * (size_t)nact + a], N, h->words, h->trows, sc, bi, nmax);
+            else
+                hipLaunchKernelGGL(iris_search_score_kernel<false>, dim3((unsigned)n), dim3((unsigned)threads), 0, h->stream, h->d_T, h->d_M, fw, d_qkey + a,
+                                   d_limit + a, b - a, d_list + hq[2 * (size_t)nact + a], N, h->words, h->trows, sc, bi, nmax);
+            a = b;
+        }
+        hipLaunchKernelGGL(iris_select_kernel, dim3((unsigned)G), dim3(256), 0, h->stream, d_score, nmax, d_limit + s, k, 0.0f, d_pos + (size_t)s * k);
+        hipLaunchKernelGGL(iris_search_finish_kernel, dim3((unsigned)((G * k + 255) / 256)), dim3(256), 0, h->stream, d_pos + (size_t)s * k, d_score, d_bias, nmax, G, k,
+                           d_res + (size_t)s * k);
+        SCL_HIP(h, hipGetLastError());
+    }
+    std::vector<IrisSearchEntry> res(n_res);
+    SCL_HIP(h, hipMemcpyAsync(res.data(), d_res, sizeof(IrisSearchEntry) * n_res, hipMemcpyDeviceToHost, h->stream));
+    SCL_HIP(h, hipStreamSynchronize(h->stream));
+    for (int j = 0; j < nact; ++j) std::copy_n(res.begin() + (size_t)j * k, k, out.begin() + (size_t)order[(size_t)j] * k);
+    return SCL_OK;
+}
+
+// the lists from the entries: the listed candidates first, then (-1, 0, +inf) up to k; to_id: position in the query's list -> id
+template <class ToId>
+void report_search(const std::vector<IrisSearchEntry> &res, int count, int k, ToId to_id, int *cand_ids, float *cand_biases, float *cand_dists, int *n_found)
+{
+    for (int i = 0; i < count; ++i) {
+        int found = 0;
+        for (int j = 0; j < k; ++j) {
+            const IrisSearchEntry &e = res[(size_t)i * k + j];
+            found += e.pos >= 0;
+            cand_ids[(size_t)i * k + j] = e.pos >= 0 ? to_id(i, e.pos) : -1;
+            if (cand_biases) cand_biases[(size_t)i * k + j] = (float)e.bias;
+            if (cand_dists) cand_dists[(size_t)i * k + j] = e.dis;
+        }
+        if (n_found) n_found[i] = found;
+    }
+}
+
+inline bool search_k_ok(int k) { return k >= 1 && k <= SCL_IRIS_SEARCH_MAX; }
+
+int search_intra_locked(scl_iris *h, const int *curs, int count, int k, int *cand_ids, float *cand_biases, float *cand_dists, int *n_found)
+{
+    if (!search_k_ok(k)) return fail(h, SCL_ERR_INVALID_ARG, "search_intra: k outside [1, SCL_IRIS_SEARCH_MAX]");
+    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
+    for (int i = 0; i < count; ++i)
+        if (curs[i] < 0 || curs[i] >= (int)mine.size()) return fail(h, SCL_ERR_OUT_OF_RANGE, "search_intra: no such keyframe of this robot");
+    if (count == 0) return SCL_OK;
+    std::vector<ManyQuery> qs((size_t)count);
+    for (int i = 0; i < count; ++i) qs[(size_t)i] = ManyQuery{mine[(size_t)curs[i]], 0, curs[i] - h->cfg.num_exclude_recent};
+    const std::vector<int> lists[2] = {mine, std::vector<int>()};
+    std::vector<IrisSearchEntry> res;
+    int rc = search_many_locked(h, qs, lists, k, res);
+    if (rc) return rc;
+    report_search(res, count, k, [](int, int pos) { return pos; }, cand_ids, cand_biases, cand_dists, n_found);     // the LOCAL index
+    return SCL_OK;
+}
+
+int search_inter_locked(scl_iris *h, const int *curs, int count, int k, int *cand_ids, float *cand_biases, float *cand_dists, int *n_found)
+{
+    if (!search_k_ok(k)) return fail(h, SCL_ERR_INVALID_ARG, "search_inter: k outside [1, SCL_IRIS_SEARCH_MAX]");
+    for (int i = 0; i < count; ++i)
+        if (curs[i] < 0 || curs[i] >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "search_inter: key out of range");
+    if (count == 0) return SCL_OK;
+    std::vector<int> lists[2];                                                 // the lists of detect_inter_many_locked
+    lists[0] = h->reg.keys_of(h->cfg.this_id);
+    for (int r = 0; r < h->reg.robot_num; ++r)
+        if (r != h->cfg.this_id) lists[1].insert(lists[1].end(), h->reg.keys_of(r).begin(), h->reg.keys_of(r).end());
+    std::vector<ManyQuery> qs((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        const int which = h->reg.robots[(size_t)curs[i]] == h->cfg.this_id ? 1 : 0;
+        qs[(size_t)i] = ManyQuery{curs[i], which, (int)lists[which].size()};
+    }
+    std::vector<IrisSearchEntry> res;
+    int rc = search_many_locked(h, qs, lists, k, res);
+    if (rc) return rc;
+    report_search(res, count, k, [&](int i, int pos) { return lists[qs[(size_t)i].which][(size_t)pos]; }, cand_ids, cand_biases, cand_dists, n_found);   // the GLOBAL key
+    return SCL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1363,7 +1603,7 @@ int scl_iris_create(const scl_iris_config *cfg, scl_iris **out)
 {
     if (!cfg || !out) return SCL_ERR_INVALID_ARG;
     *out = nullptr;
-    if (cfg->rows < 1 || cfg->rows > 512 || cfg->cols < 2 || cfg->cols > 2048 || cfg->nscale < 1 || cfg->nscale > 8 ||
+    if (cfg->rows < 1 || cfg->rows > 512 || cfg->cols < 1 || cfg->cols > 2048 || cfg->nscale < 1 || cfg->nscale > 8 ||
         cfg->min_wavelength < 1 || !(cfg->mult > 0.f) || !(cfg->sigma_onf > 0.f) || cfg->sigma_onf == 1.0f ||
         cfg->robot_num < 1 || cfg->robot_num > 127 || cfg->this_id < 0 || cfg->this_id >= cfg->robot_num || cfg->num_candidates < 1 ||
         cfg->num_candidates > 4096 || cfg->num_exclude_recent < 0 || cfg->match_num < 0 || cfg->match_num > 2 || !(cfg->knn_exclude_eps >= 0.0f) ||
@@ -1635,6 +1875,23 @@ int scl_iris_make_save_and_detect(scl_iris *h, const void *const *clouds, const 
     for (int i = 0; i < count; ++i) { loop_ids[i] = -1; biases[i] = 0.0f; if (dists) dists[i] = 10000000.0f; }
     for (size_t j = 0; j < at.size(); ++j) { loop_ids[at[j]] = loops[j]; biases[at[j]] = bs[j]; if (dists) dists[at[j]] = ds[j]; }
     return SCL_OK;
+}
+
+// ---- the exhaustive ranked search (scl_iris.h "THE EXHAUSTIVE SEARCH")
+int scl_iris_search_intra(scl_iris *h, const int *curs, int count, int k, int *cand_ids, float *cand_biases, float *cand_dists, int *n_found)
+{
+    if (!h || count < 0 || (count > 0 && (!curs || !cand_ids))) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    return search_intra_locked(h, curs, count, k, cand_ids, cand_biases, cand_dists, n_found);
+}
+
+int scl_iris_search_inter(scl_iris *h, const int *curs, int count, int k, int *cand_ids, float *cand_biases, float *cand_dists, int *n_found)
+{
+    if (!h || count < 0 || (count > 0 && (!curs || !cand_ids))) return SCL_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    return search_inter_locked(h, curs, count, k, cand_ids, cand_biases, cand_dists, n_found);
 }
 
 int scl_iris_get_image(scl_iris *h, int key, uint8_t *image, float *rowkey)

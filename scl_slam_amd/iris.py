@@ -37,9 +37,13 @@ _SIG.update({
     "scl_iris_detect_intra_many": (c_int, [_P, _ip, c_int, _ip, _fp, _fp]),
     "scl_iris_detect_inter_many": (c_int, [_P, _ip, c_int, _ip, _fp, _fp]),
     "scl_iris_make_save_and_detect": (c_int, [_P, POINTER(c_void_p), _ip, c_int, POINTER(c_int8), _ip, c_int, _ip, _fp, _fp, _fp]),
+    # the exhaustive ranked search
+    "scl_iris_search_intra": (c_int, [_P, _ip, c_int, c_int, _ip, _fp, _fp, _ip]),
+    "scl_iris_search_inter": (c_int, [_P, _ip, c_int, c_int, _ip, _fp, _fp, _ip]),
 })
 
 MAX_GROUP, DETECT_GROUP = 16, 16      # SCL_IRIS_MAX_GROUP, SCL_IRIS_DETECT_GROUP
+SEARCH_MAX = 32                       # SCL_IRIS_SEARCH_MAX
 
 
 def _lib():
@@ -179,6 +183,34 @@ class IrisEngine(PluginEngine):
         self._call("make_save_and_detect", ptrs, ns.ctypes.data_as(_ip), st, rb.ctypes.data_as(POINTER(c_int8)), ix.ctypes.data_as(_ip), count,
                    loops.ctypes.data_as(_ip), biases.ctypes.data_as(_fp), dists.ctypes.data_as(_fp), out.ctypes.data_as(_fp) if out is not None else None)
         return loops, biases, dists, out
+
+    # ---- the exhaustive ranked search (scl_iris.h "THE EXHAUSTIVE SEARCH")
+    def _search(self, name, curs, k, ids, biases, dists, n_found):
+        c = np.ascontiguousarray(curs, np.int32).ravel()
+        k = int(k)
+        rows = max(k, 0)
+        ids = np.empty((c.size, rows), np.int32) if ids is None else ids
+        biases = np.empty((c.size, rows), np.float32) if biases is None else biases
+        dists = np.empty((c.size, rows), np.float32) if dists is None else dists
+        n_found = np.empty(c.size, np.int32) if n_found is None else n_found
+        for a, t, size in ((ids, np.int32, c.size * rows), (biases, np.float32, c.size * rows), (dists, np.float32, c.size * rows),
+                           (n_found, np.int32, c.size)):
+            if a.dtype != t or a.size != size or not a.flags.c_contiguous:
+                raise ValueError(f"a contiguous {np.dtype(t).name} array of {size} elements")
+        self._call(name, c.ctypes.data_as(_ip), c.size, k, ids.ctypes.data_as(_ip), biases.ctypes.data_as(_fp), dists.ctypes.data_as(_fp),
+                   n_found.ctypes.data_as(_ip))
+        return ids, biases, dists, n_found
+
+    def search_intra(self, curs, k, ids=None, biases=None, dists=None, n_found=None):
+        """the k best of this robot's keyframes [0, cur - num_exclude_recent) for every local index of curs, every column shift scored
+        against the whole set, without dist_thres: (ids (count, k) int32 LOCAL, biases (count, k) float32, dists (count, k) float32,
+        n_found int32); entries past n_found[i] are (-1, 0, +inf).  ids / biases / dists / n_found: arrays to fill (left untouched
+        when the call fails)"""
+        return self._search("search_intra", curs, k, ids, biases, dists, n_found)
+
+    def search_inter(self, curs, k, ids=None, biases=None, dists=None, n_found=None):
+        """the k best of the set detect_inter searches, for every global key of curs: (ids (count, k) int32 GLOBAL, biases, dists, n_found)"""
+        return self._search("search_inter", curs, k, ids, biases, dists, n_found)
 
     def get_image(self, key):
         img = np.empty((self.rows, self.cols), np.uint8); k = np.empty(self.rows, np.float32)
