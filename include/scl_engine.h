@@ -305,7 +305,10 @@ int  scl_ransac_correspondences(scl_engine *e, const void *src, int n_src, const
                                 int max_iterations, double inlier_threshold, uint64_t seed,
                                 int *inlier_mask, int *n_inliers, int *best_hypothesis, float T_model[16]);
 /* The compute core of geometricVerificationService, DM.h:1211-1243: NN correspondences -> RANSAC ->
- * SVD transform on the inliers -> gate `inliers >= inlier_ratio * correspondences` (inlierTreshold DM.h:189). */
+ * SVD transform on the inliers -> gate `inliers >= inlier_ratio * correspondences` (inlierTreshold DM.h:189).
+ * Only a source point whose search found a neighbour is a correspondence (one with a NaN or infinite coordinate finds
+ * none): they are kept in source order, *n_correspondences is their count, and RANSAC samples from, scores and gates
+ * on that count.  Fewer than three: T = identity, *success = 0, the count reported. */
 int  scl_geometric_verification(scl_engine *e, const void *src, int n_src, const void *tgt, int n_tgt,
                                 int stride_bytes, int ransac_iterations, double inlier_threshold,
                                 double inlier_ratio, uint64_t seed, float T[16], int *success,

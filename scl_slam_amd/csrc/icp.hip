@@ -62,8 +62,8 @@ struct IcpState {
 };
 
 enum Buf { B_SRC = 0, B_TGT, B_WORK, B_TSORT, B_CSTART, B_CFILL, B_NNI, B_NND, B_PART, B_STATE, B_BBOX, B_SI, B_TI, B_OUT, B_MASK, B_HYP, B_PROB,
-           B_NNQ, B_PERM, B_SORT, B_FLAG };
-static_assert(B_FLAG < (int)(sizeof(IcpWorkspace::buf) / sizeof(void *)), "IcpWorkspace::buf is too short");
+           B_NNQ, B_PERM, B_SORT, B_FLAG, B_PAIR };
+static_assert(B_PAIR < (int)(sizeof(IcpWorkspace::buf) / sizeof(void *)), "IcpWorkspace::buf is too short");
 constexpr int B_NORM = B_OUT;             // target normals share the slot of the raw-transform output (never live together)
 
 int ensure(IcpWorkspace *ws, int k, size_t bytes, std::string *err)
@@ -1227,10 +1227,18 @@ __global__ __launch_bounds__(256) void ransac_mask_kernel(const unsigned char *s
         mask[i] = ransac_inlier(sT, load_xyz(src, si[i], stride), load_xyz(tgt, ti[i], stride), thr2) ? 1 : 0;
 }
 
-__global__ void iota_pairs_kernel(const int *nn, int n, int *si, int *ti)
+// The pairs of the verification path: every source whose search found a neighbour (nn[i] >= 0; a source with a non-finite
+// coordinate finds none), in source order.  found[i] = 1 for such a source; rank = the inclusive prefix sum of found.
+__global__ void pair_found_kernel(const int *nn, int n, int *found)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { si[i] = i; ti[i] = nn[i]; }
+    if (i < n) found[i] = nn[i] >= 0 ? 1 : 0;
+}
+
+__global__ void iota_pairs_kernel(const int *nn, const int *rank, int n, int *si, int *ti)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && nn[i] >= 0) { const int k = rank[i] - 1; si[k] = i; ti[k] = nn[i]; }
 }
 
 // ---- batched forms: one launch serves the same step of many alignments (blockIdx.y = alignment) -------------------
@@ -2600,7 +2608,7 @@ int icp_geometric_verification(IcpWorkspace *ws, hipStream_t stream, int num_cu,
     (void)num_cu;
     int rc = check_cloud_args(n_src, n_tgt, stride, err);
     if (rc) return rc;
-    if (n_src >= 3 && n_tgt >= 1) {
+    if (n_src >= 1 && n_tgt >= 1) {                                  // (fewer than three sources still have their pairs counted)
         if ((rc = upload(ws, B_SRC, src, (size_t)n_src * stride, stream, err))) return rc;
         if ((rc = upload(ws, B_TGT, tgt, (size_t)n_tgt * stride, stream, err))) return rc;
     }
@@ -2620,35 +2628,50 @@ int icp_geometric_verification_staged(IcpWorkspace *ws, hipStream_t stream, int 
     if (success) *success = 0;
     if (n_corr_out) *n_corr_out = 0;
     if (n_inliers_out) *n_inliers_out = 0;
-    if (n_src < 3 || n_tgt < 1) return SCL_OK;
-    if (ransac_iterations < 1 || ransac_iterations > (1 << 20)) { if (err) *err = "ransac iterations out of range"; return SCL_ERR_INVALID_ARG; }
+    if (n_src < 1 || n_tgt < 1) return SCL_OK;                                                    // no pair at all
+    if (n_src >= 3 && (ransac_iterations < 1 || ransac_iterations > (1 << 20))) { if (err) *err = "ransac iterations out of range"; return SCL_ERR_INVALID_ARG; }
+    // found flags, their ranks (both padded to 16 bytes for the scan) and the scan's scratch share one buffer
+    const size_t slots = ((size_t)n_src + 3) / 4 * 4;
     if ((rc = ensure(ws, B_WORK, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
     if ((rc = ensure(ws, B_NNI, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
     if ((rc = ensure(ws, B_NND, sizeof(float) * (size_t)(n_src + 1), err))) return rc;
     if ((rc = ensure(ws, B_SI, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
     if ((rc = ensure(ws, B_TI, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
+    if ((rc = ensure(ws, B_PAIR, sizeof(int) * 2 * slots + scan_scratch_bytes((size_t)n_src), err))) return rc;
     if ((rc = ensure(ws, B_PART, sizeof(double) * kNSum * kRedBlocks, err))) return rc;
+    if ((rc = pinned(ws, sizeof(IcpState) + 256, err))) return rc;
     if ((rc = build_grid(ws, stream, n_tgt, stride, err))) return rc;
     IcpState *st = static_cast<IcpState *>(ws->buf[B_STATE]);
+    int *found = static_cast<int *>(ws->buf[B_PAIR]), *rank = found + slots;
     const int pb = (n_src + 255) / 256;
     hipLaunchKernelGGL(work_init_kernel, dim3(pb), dim3(256), 0, stream, (const unsigned char *)ws->buf[B_SRC], n_src, stride,
                        (float4 *)ws->buf[B_WORK]);
     launch_nn_search(stream, (float4 *)ws->buf[B_WORK], n_src, st,
                        (const int *)ws->buf[B_CSTART], (const float4 *)ws->buf[B_TSORT], (int *)ws->buf[B_NNI],
                        (float *)ws->buf[B_NND], 0, -1, (const unsigned char *)ws->buf[B_TGT], stride, 0);   // DM.h:1211-1215
-    hipLaunchKernelGGL(iota_pairs_kernel, dim3(pb), dim3(256), 0, stream, (const int *)ws->buf[B_NNI], n_src,
+    // only the sources that found a neighbour are pairs (a non-finite source finds none), in source order
+    hipLaunchKernelGGL(pair_found_kernel, dim3(pb), dim3(256), 0, stream, (const int *)ws->buf[B_NNI], n_src, found);
+    ICP_HIP(prefix_sum_i32(rank + slots, found, rank, n_src, true, stream));
+    hipLaunchKernelGGL(iota_pairs_kernel, dim3(pb), dim3(256), 0, stream, (const int *)ws->buf[B_NNI], (const int *)rank, n_src,
                        (int *)ws->buf[B_SI], (int *)ws->buf[B_TI]);
+    ICP_HIP(hipGetLastError());
+    int *h_count = static_cast<int *>(ws->pinned);
+    ICP_HIP(hipMemcpyAsync(h_count, rank + (n_src - 1), sizeof(int), hipMemcpyDeviceToHost, stream));
+    ICP_HIP(hipStreamSynchronize(stream));
+    const int n_corr = *h_count;
+    if (n_corr < 0 || n_corr > n_src) { if (err) *err = "geometric verification: pair count out of range"; return SCL_ERR_HIP; }
+    if (n_corr_out) *n_corr_out = n_corr;
+    if (n_corr < 3) return SCL_OK;                                                                 // nothing to sample from
     int best2[2];
-    if ((rc = ransac_device(ws, stream, stride, (const int *)ws->buf[B_SI], (const int *)ws->buf[B_TI], n_src,
+    if ((rc = ransac_device(ws, stream, stride, (const int *)ws->buf[B_SI], (const int *)ws->buf[B_TI], n_corr,
                             ransac_iterations, inlier_threshold, seed, best2, nullptr, err))) return rc;   // DM.h:1218-1225
     const int n_inl = best2[1];
-    if (n_corr_out) *n_corr_out = n_src;
     if (n_inliers_out) *n_inliers_out = n_inl;
     if (n_inl >= 3) {                                                                              // DM.h:1228-1230
-        int rb = (n_src + 255) / 256; rb = rb < 1 ? 1 : (rb > kRedBlocks ? kRedBlocks : rb);
+        int rb = (n_corr + 255) / 256; rb = rb < 1 ? 1 : (rb > kRedBlocks ? kRedBlocks : rb);
         hipLaunchKernelGGL(state_init_kernel, dim3(1), dim3(64), 0, stream, st);
         LAUNCH_REDUCE(rb, stream, (const float4 *)nullptr, (const unsigned char *)ws->buf[B_SRC],
-                      (const unsigned char *)ws->buf[B_TGT], stride, n_src, (const int *)ws->buf[B_MASK],
+                      (const unsigned char *)ws->buf[B_TGT], stride, n_corr, (const int *)ws->buf[B_MASK],
                       (const float *)nullptr, 0.f, (const int *)ws->buf[B_SI], (const int *)ws->buf[B_TI], 1, st,
                       (double *)ws->buf[B_PART], 0);
         hipLaunchKernelGGL(icp_solve_kernel, dim3(1), dim3(64), 0, stream, st, (const double *)ws->buf[B_PART], rb, 1, 0, 0.0, 0.0);
@@ -2658,7 +2681,7 @@ int icp_geometric_verification_staged(IcpWorkspace *ws, hipStream_t stream, int 
         ICP_HIP(hipStreamSynchronize(stream));
         std::memcpy(T, h->final_T, sizeof(float) * 16);
     }
-    if (success) *success = !((double)n_inl < inlier_ratio * (double)n_src);                      // DM.h:1238
+    if (success) *success = !((double)n_inl < inlier_ratio * (double)n_corr);                     // DM.h:1238
     return SCL_OK;
 }
 
