@@ -1586,10 +1586,11 @@ __device__ __forceinline__ void build_rotq(const unsigned int *q_kmask, uint4 *r
 }
 
 // one pair (scan qi of the batch, position ci of its range): returns its contribution to the launch's smallest d~.
-// In two steps: everything the pair reads from memory is REQUESTED first (one batch: the keyframe's mask, the first shift, the partial
-// sums, the keyframe's tiled ring key), then -- in the workgroup form behind the barrier that publishes the scan's rotated masks --
-// the distances are formed.  Written as one step the compiler waited for the loads two at a time: six memory round trips behind each
-// other in a kernel that is nothing but round trips (2.4 waves per SIMD, all resident at once).
+// In two steps: everything the pair reads from memory is REQUESTED first (one batch: the keyframe's tiled ring key, its mask, the
+// first shift, the partial sums; the scan's own ring key goes through LDS, once per workgroup: sc_screen2_finish_body), then -- in
+// the workgroup form behind the barrier that publishes the scan's rotated masks and its key -- the distances are formed.  Written
+// as one step the compiler waited for the loads two at a time: six memory round trips behind each other in a kernel that is
+// nothing but round trips (2.4 waves per SIMD, all resident at once).
 template <int RG, int S, int W, bool D2 = true>
 struct FinishLoads {
     static constexpr int NPA = S2Cfg<RG, S, W>::NP <= 3 ? S2Cfg<RG, S, W>::NP : 3;   // ring parts whose sums are requested up front (registers: the others follow
@@ -1606,6 +1607,13 @@ __device__ __forceinline__ FinishLoads<RG, S, W, D2> sc_screen2_finish_request(c
     using L = FinishLoads<RG, S, W, D2>;
     const ScreenBatchArgs &ab = fa.prod;
     L l;
+    // the ring key and the mask first: the launch's scans of a chunk follow each other on one XCD (finish_block_of), so these are hits
+    // in its L2 for every scan but the first; the partial sums, which nobody else reads, come from HBM and are asked for last
+    if constexpr (D2 && L::kRingUpFront) {
+        const int slot = a.slot_base + ci;
+#pragma unroll
+        for (int r = 0; r < RG; ++r) l.bk[r] = a.rkey4[(size_t)r * a.rk_cap + slot];
+    }
     const unsigned int *kp = a.kmask + (size_t)(a.slot_base + ci) * 8;
 #pragma unroll
     for (int i = 0; i < L::MW; ++i) l.km[i] = *reinterpret_cast<const uint4 *>(kp + 4 * i);
@@ -1618,11 +1626,6 @@ __device__ __forceinline__ FinishLoads<RG, S, W, D2> sc_screen2_finish_request(c
 #pragma unroll
     for (int i = 0; i < L::NPF; ++i) l.pv[i] = pp[i];
     l.rest = pp + L::NPF;
-    if constexpr (D2 && L::kRingUpFront) {
-        const int slot = a.slot_base + ci;
-#pragma unroll
-        for (int r = 0; r < RG; ++r) l.bk[r] = a.rkey4[(size_t)r * a.rk_cap + slot];
-    }
     return l;
 }
 // MASKS = false: an instance for launches that ask for no shift masks (the 64 x 120 stream's tail launch): no per-shift interval ends
@@ -1631,7 +1634,7 @@ __device__ __forceinline__ FinishLoads<RG, S, W, D2> sc_screen2_finish_request(c
 // front of its top-k, on the side stream): sixteen float4 loads and sixty-four registers per pair that the stream's tail launch
 // neither waits for nor holds
 template <int RG, int S, int W, bool MASKS = true, bool D2 = true>
-__device__ __forceinline__ float sc_screen2_finish_compute(const ScreenArgs &a, const int ci, const uint4 *rotq, const bool q_bad, const float q_err, FinishLoads<RG, S, W, D2> &l, float &pair_eps)
+__device__ __forceinline__ float sc_screen2_finish_compute(const ScreenArgs &a, const int ci, const uint4 *rotq, const float4 *qkey, const bool q_bad, const float q_err, FinishLoads<RG, S, W, D2> &l, float &pair_eps)
 {
     using C = S2Cfg<RG, S, W>;
     using L = FinishLoads<RG, S, W, D2>;
@@ -1726,7 +1729,8 @@ __device__ __forceinline__ float sc_screen2_finish_compute(const ScreenArgs &a, 
         a.out_smask[ci] = b_open ? 0u : m;
     }
     // nanoflann's metric (nanoflann.hpp:383-408) for the ring-key top-k: four dimensions per step, fp32, groups accumulated in
-    // order -- the arithmetic of sc_align_role, here with consecutive threads on consecutive slots of the tiled key table
+    // order -- the arithmetic of sc_align_role, here with consecutive threads on consecutive slots of the tiled key table; the scan's
+    // own key comes from LDS (qkey: staged once per workgroup, every lane reads the same sixteen bytes)
     if constexpr (D2) {
         const int slot = a.slot_base + ci;
         float result = 0.0f;
@@ -1734,7 +1738,7 @@ __device__ __forceinline__ float sc_screen2_finish_compute(const ScreenArgs &a, 
         for (int r = 0; r < RG; ++r) {
             float4 bk;
             if constexpr (L::kRingUpFront) bk = l.bk[r]; else bk = a.rkey4[(size_t)r * a.rk_cap + slot];
-            const float4 qk = *reinterpret_cast<const float4 *>(a.q_rkey + 4 * r);
+            const float4 qk = qkey[r];
             const float d0 = qk.x - bk.x, d1 = qk.y - bk.y, d2 = qk.z - bk.z, d3 = qk.w - bk.w;
             const float grp = d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
             result += grp;
@@ -1751,15 +1755,23 @@ __device__ __forceinline__ void sc_screen2_finish_body(const Screen2Args &fa, co
     const ScreenArgs a = screen_args_of(ab, qi);
     __shared__ uint4 rotq[S * MW];
     __shared__ float wmin[4], wmax[4];
+    __shared__ float4 qkey[D2 ? RG : 1];                                     // the scan's ring key: one 16-byte load per thread of the first RG, once per workgroup
     const int ci = (int)(chunk * blockDim.x + threadIdx.x);
     const bool live = ci < a.n;
+    float4 qk_mine = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if constexpr (D2) { if (threadIdx.x < RG) qk_mine = reinterpret_cast<const float4 *>(a.q_rkey)[threadIdx.x]; }   // (requested in front of the batch: its wait is for this load alone)
     FinishLoads<RG, S, W, D2> ld = sc_screen2_finish_request<RG, S, W, D2>(fa, a, qi, live ? ci : 0);   // (a.n >= 1 where a workgroup was launched for the scan)
     build_rotq<S>(a.q_kmask, rotq, (int)threadIdx.x, (int)blockDim.x);
     const bool q_bad = a.q_kmask[7] != 0;
+    if constexpr (D2) { if (threadIdx.x < RG) qkey[threadIdx.x] = qk_mine; }
     __syncthreads();
+    // (every float of the partial sums counts as used from here: the last tile rows of a pass are no shifts, and the registers of
+    //  their floats, free in the allocator's eyes, went to build_rotq's loop -- which then waited for the loads that fill them)
+#pragma unroll
+    for (int i = 0; i < FinishLoads<RG, S, W, D2>::NPF; ++i) asm("" : "+v"(ld.pv[i]));
     const float kInf = __int_as_float(0x7f800000);
     float contrib = kInf, peps = 0.0f;
-    if (live) contrib = sc_screen2_finish_compute<RG, S, W, MASKS, D2>(a, ci, rotq, q_bad, __uint_as_float(a.q_kmask[6]), ld, peps);
+    if (live) contrib = sc_screen2_finish_compute<RG, S, W, MASKS, D2>(a, ci, rotq, qkey, q_bad, __uint_as_float(a.q_kmask[6]), ld, peps);
     // (wave minimum / maximum by DPP row exchanges: twelve ds_bpermute round trips per thread otherwise)
     contrib = -wave_max_f32_dpp(-contrib);
     peps = wave_max_f32_dpp(peps);
@@ -1773,10 +1785,26 @@ __device__ __forceinline__ void sc_screen2_finish_body(const Screen2Args &fa, co
     }
 }
 
-template <int RG, int S, int W>
-__global__ __launch_bounds__(256) void sc_screen2_finish_kernel(Screen2Args fa)
+// The order of the finishing workgroups.  Workgroups b and b + 8 are observed to share an XCD (and its L2); the workgroups that read
+// the same 256 keyframes' ring keys and masks -- one chunk, every scan of the launch -- follow each other in ONE such class:
+// fb = 8 (nq (chunk / 8) + qi) + chunk % 8.  The grid is rounded up to whole groups of eight chunks (finish_blocks); a workgroup
+// behind the last chunk has nothing to do and leaves in front of every barrier.  Placement is a matter of speed only: each
+// (scan, chunk) is covered exactly once whichever XCD runs it, and an alignment role in front of the finishing whose workgroup
+// count is no multiple of eight only rotates the classes.
+__device__ __forceinline__ bool finish_block_of(const int fb, const int nq, const int chunks, int &qi, int &chunk)
 {
-    sc_screen2_finish_body<RG, S, W>(fa, (int)blockIdx.y, (int)blockIdx.x);
+    const int x = fb & 7, s = fb >> 3, g = s / nq;
+    chunk = 8 * g + x; qi = s - g * nq;
+    return chunk < chunks;
+}
+static int finish_blocks(int chunks, int nq) { return 8 * ((chunks + 7) / 8) * nq; }
+
+template <int RG, int S, int W>
+__global__ __launch_bounds__(256) void sc_screen2_finish_kernel(Screen2Args fa, int chunks)
+{
+    int qi, chunk;
+    if (!finish_block_of((int)blockIdx.x, fa.prod.nq, chunks, qi, chunk)) return;
+    sc_screen2_finish_body<RG, S, W>(fa, qi, chunk);
 }
 
 // The tail of a launch group in ONE launch: the alignment of the NEXT batch (workgroups [0, align_blocks): latency bound, a third
@@ -1788,8 +1816,9 @@ __global__ __launch_bounds__(kScreenWaves * kWave, 2) void sc_screen2_tail_kerne
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_tail[];
     const int b = (int)blockIdx.x;
     if (b < align_blocks) { sc_align_role<RG, S, W>(nb, b, smem_tail); return; }
-    const int fb = b - align_blocks;
-    sc_screen2_finish_body<RG, S, W>(fa, fb / chunks, fb - (fb / chunks) * chunks);
+    int qi, chunk;
+    if (!finish_block_of(b - align_blocks, fa.prod.nq, chunks, qi, chunk)) return;
+    sc_screen2_finish_body<RG, S, W>(fa, qi, chunk);
 }
 
 // ... with the alignment in its second form (one keyframe against the next batch's scans per wave)
@@ -1809,8 +1838,9 @@ __global__ __launch_bounds__(kScreenWaves * kWave, Align2Cfg<S>::OCC) void sc_sc
         sc_align2_role<S, W>(nb, halign, u_lo, u_n, b * kScreenWaves + wave, align_blocks * kScreenWaves, smem_tail2 + (size_t)wave * Align2Cfg<S>::LDS_WAVE);
         return;
     }
-    const int fb = b - align_blocks;
-    sc_screen2_finish_body<RG, S, W, MASKS, D2>(fa, fb / chunks, fb - (fb / chunks) * chunks);
+    int qi, chunk;
+    if (!finish_block_of(b - align_blocks, fa.prod.nq, chunks, qi, chunk)) return;
+    sc_screen2_finish_body<RG, S, W, MASKS, D2>(fa, qi, chunk);
 }
 
 static bool screen_second_form()
@@ -1970,9 +2000,10 @@ static hipError_t launch_screen_grid(const DbView &db, const ScreenBatch &sb, in
         // the products, it measured 0.67 / 0.51 G pairs/s against 1.45 G in line: the two event hops between the queues per launch cost
         // more than the alignment itself.  As extra waves of the products' workgroups: one launch of 81-87 us against 47.8 + 26.9.
         // Both removed)
-        const dim3 fgrid((nmax + 255) / 256, sb.nq), ablock(kScreenWaves * kWave);
+        const int chunks = (nmax + 255) / 256;                                 // finishing workgroups per scan
+        const dim3 fgrid(finish_blocks(chunks, sb.nq)), ablock(kScreenWaves * kWave);
         if (!next) {
-            hipLaunchKernelGGL((sc_screen2_finish_kernel<RG, S, W>), fgrid, dim3(256), 0, stream, f2);
+            hipLaunchKernelGGL((sc_screen2_finish_kernel<RG, S, W>), fgrid, dim3(256), 0, stream, f2, chunks);
             return hipGetLastError();
         }
         // the next batch's argument block and the grid of its alignment
@@ -1998,8 +2029,7 @@ static hipError_t launch_screen_grid(const DbView &db, const ScreenBatch &sb, in
         static const int tail_env = scl_lab_int("SCL_SCREEN_TAIL", 1);   // 0: finish and alignment as two launches
         if (tail_env) {
             // one launch: the alignment's workgroups in front, this batch's finishing behind them
-            const int chunks = (nmax + 255) / 256;
-            const dim3 tgrid(ablocks + chunks * sb.nq);
+            const dim3 tgrid(ablocks + finish_blocks(chunks, sb.nq));
             const bool d2 = !sb.no_ring_metric;                       // (left to the exact pass of the range: kernels.hpp)
             if (!next_v2) hipLaunchKernelGGL((sc_screen2_tail_kernel<RG, S, W>), tgrid, ablock, lds0, stream, f2, nb, ablocks, chunks);
             else if (sb.smask && d2) hipLaunchKernelGGL((sc_screen2_tail2_kernel<RG, S, W, true, true>), tgrid, ablock, lds_a2, stream, f2, nb, db.halign, ulo, un, ablocks, chunks);
@@ -2008,7 +2038,7 @@ static hipError_t launch_screen_grid(const DbView &db, const ScreenBatch &sb, in
             else hipLaunchKernelGGL((sc_screen2_tail2_kernel<RG, S, W, false, false>), tgrid, ablock, lds_a2, stream, f2, nb, db.halign, ulo, un, ablocks, chunks);
             return hipGetLastError();
         }
-        hipLaunchKernelGGL((sc_screen2_finish_kernel<RG, S, W>), fgrid, dim3(256), 0, stream, f2);
+        hipLaunchKernelGGL((sc_screen2_finish_kernel<RG, S, W>), fgrid, dim3(256), 0, stream, f2, chunks);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if (next_v2) hipLaunchKernelGGL((sc_align2_kernel<RG, S, W>), dim3(ablocks), ablock, lds_a2, stream, nb, db.halign, ulo, un);
         else hipLaunchKernelGGL((sc_align_kernel<RG, S, W>), dim3(ablocks), ablock, lds0, stream, nb);
