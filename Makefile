@@ -12,6 +12,8 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-f
             -fhip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-result -Iinclude -I$(CSRC) $(EXTRA)
 SRCS    := $(CSRC)/engine.hip $(CSRC)/sc_distance.hip $(CSRC)/ringkey_topk.hip $(CSRC)/make_sc.hip $(CSRC)/icp.hip $(CSRC)/voxel.hip $(CSRC)/sharded_front.hip $(CSRC)/sc_screen.hip $(CSRC)/sc_masked.hip $(CSRC)/sc_matrix.hip $(CSRC)/messages.hip $(CSRC)/iris.hip $(CSRC)/device_sort.hip $(CSRC)/m2dp.hip $(CSRC)/fpfh.hip $(CSRC)/grsd.hip
 OBJS    := $(SRCS:.hip=.o)
+# the adapter template the M2DP, FPFH and GRSD adapters derive from, and the batch declarations their C headers share
+VP_ADAPTER := include/scl/vector_plugin_hip_descriptor.hpp include/scl_plugin_batch.h
 
 all: $(LIBDIR)/libscl_engine.so oracle tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/grsd_adapter_check tests/cpp/plugin_batch_check tests/cpp/plugin_topk_check tests/cpp/iris_batch_check tests/cpp/iris_search_check tests/cpp/libfpfh_checker.so tests/cpp/libgrsd_checker.so tests/cpp/libmock_rccl.so
 
@@ -31,23 +33,23 @@ tests/cpp/adapter_check: tests/cpp/adapter_check.cpp tests/cpp/pcl_types_for_ada
 	g++ -std=c++14 -O2 -Wall -Iinclude -Itests/cpp -o $@ tests/cpp/adapter_check.cpp -L$(LIBDIR) -lscl_engine -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
 # the M2DP adapter (include/scl/m2dp_hip_descriptor.hpp) against the C ABI; runs on the GPU box (tests/test_gpu_m2dp.py)
-tests/cpp/m2dp_adapter_check: tests/cpp/m2dp_adapter_check.cpp tests/cpp/pcl_types_for_adapter_check.h include/scl/m2dp_hip_descriptor.hpp include/scl_m2dp.h $(LIBDIR)/libscl_engine.so
+tests/cpp/m2dp_adapter_check: tests/cpp/m2dp_adapter_check.cpp tests/cpp/pcl_types_for_adapter_check.h include/scl/m2dp_hip_descriptor.hpp $(VP_ADAPTER) include/scl_m2dp.h $(LIBDIR)/libscl_engine.so
 	g++ -std=c++14 -O2 -Wall -Iinclude -Itests/cpp -o $@ tests/cpp/m2dp_adapter_check.cpp -L$(LIBDIR) -lscl_engine -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
 # the FPFH adapter (include/scl/fpfh_hip_descriptor.hpp) against the C ABI; runs on the GPU box (tests/test_gpu_fpfh.py)
-tests/cpp/fpfh_adapter_check: tests/cpp/fpfh_adapter_check.cpp tests/cpp/pcl_types_for_adapter_check.h include/scl/fpfh_hip_descriptor.hpp include/scl_fpfh.h $(LIBDIR)/libscl_engine.so
+tests/cpp/fpfh_adapter_check: tests/cpp/fpfh_adapter_check.cpp tests/cpp/pcl_types_for_adapter_check.h include/scl/fpfh_hip_descriptor.hpp $(VP_ADAPTER) include/scl_fpfh.h $(LIBDIR)/libscl_engine.so
 	g++ -std=c++14 -O2 -Wall -Iinclude -Itests/cpp -o $@ tests/cpp/fpfh_adapter_check.cpp -L$(LIBDIR) -lscl_engine -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
 # the GRSD adapter (include/scl/grsd_hip_descriptor.hpp) against the C ABI; runs on the GPU box (tests/test_gpu_grsd.py)
-tests/cpp/grsd_adapter_check: tests/cpp/grsd_adapter_check.cpp tests/cpp/pcl_types_for_adapter_check.h include/scl/grsd_hip_descriptor.hpp include/scl_grsd.h $(LIBDIR)/libscl_engine.so
+tests/cpp/grsd_adapter_check: tests/cpp/grsd_adapter_check.cpp tests/cpp/pcl_types_for_adapter_check.h include/scl/grsd_hip_descriptor.hpp $(VP_ADAPTER) include/scl_grsd.h $(LIBDIR)/libscl_engine.so
 	g++ -std=c++14 -O2 -Wall -Iinclude -Itests/cpp -o $@ tests/cpp/grsd_adapter_check.cpp -L$(LIBDIR) -lscl_engine -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
 # the batch forms of the M2DP, FPFH and GRSD adapters against loops over the virtuals; runs on the GPU box (tests/test_gpu_plugin_batch_adapter.py)
-tests/cpp/plugin_batch_check: tests/cpp/plugin_batch_check.cpp tests/cpp/pcl_types_for_adapter_check.h include/scl/m2dp_hip_descriptor.hpp include/scl/fpfh_hip_descriptor.hpp include/scl/grsd_hip_descriptor.hpp include/scl_m2dp.h include/scl_fpfh.h include/scl_grsd.h include/scl_plugin_batch.h $(LIBDIR)/libscl_engine.so
+tests/cpp/plugin_batch_check: tests/cpp/plugin_batch_check.cpp tests/cpp/pcl_types_for_adapter_check.h include/scl/m2dp_hip_descriptor.hpp include/scl/fpfh_hip_descriptor.hpp include/scl/grsd_hip_descriptor.hpp $(VP_ADAPTER) include/scl_m2dp.h include/scl_fpfh.h include/scl_grsd.h include/scl_plugin_batch.h $(LIBDIR)/libscl_engine.so
 	g++ -std=c++14 -O2 -Wall -Iinclude -Itests/cpp -o $@ tests/cpp/plugin_batch_check.cpp -L$(LIBDIR) -lscl_engine -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
 # the candidate lists of the M2DP, FPFH and GRSD adapters against the C calls; runs on the GPU box (tests/test_gpu_plugin_topk_adapter.py)
-tests/cpp/plugin_topk_check: tests/cpp/plugin_topk_check.cpp tests/cpp/pcl_types_for_adapter_check.h include/scl/m2dp_hip_descriptor.hpp include/scl/fpfh_hip_descriptor.hpp include/scl/grsd_hip_descriptor.hpp include/scl_m2dp.h include/scl_fpfh.h include/scl_grsd.h include/scl_plugin_batch.h $(LIBDIR)/libscl_engine.so
+tests/cpp/plugin_topk_check: tests/cpp/plugin_topk_check.cpp tests/cpp/pcl_types_for_adapter_check.h include/scl/m2dp_hip_descriptor.hpp include/scl/fpfh_hip_descriptor.hpp include/scl/grsd_hip_descriptor.hpp $(VP_ADAPTER) include/scl_m2dp.h include/scl_fpfh.h include/scl_grsd.h include/scl_plugin_batch.h $(LIBDIR)/libscl_engine.so
 	g++ -std=c++14 -O2 -Wall -Iinclude -Itests/cpp -o $@ tests/cpp/plugin_topk_check.cpp -L$(LIBDIR) -lscl_engine -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
 # the batch forms of the LiDAR-Iris adapter against loops over its six virtuals; runs on the GPU box (tests/test_gpu_iris_batch_adapter.py)

@@ -13,213 +13,36 @@
 //     distThres -- 0.3 is a PLACEHOLDER, not validated on real data; the second member of the pair is the distance;
 //   * saveDescriptorAndKey reads all 192 floats makeAndSaveDescriptorAndKey emits (the reference reads 128);
 //   * the PCA axes follow a sign rule (PCL's are unpinned), which makes the signature rotation invariant.
+// The class itself, member by member: vector_plugin_hip_descriptor.hpp.  The descriptor is the 192 floats [u, v]
+// (descriptor.h:1820-1863; saveDescriptorAndKey 1989-1995; the detections 1998-2001 and 2003-2006; getIndex 2008-2011; getSize
+// 2013-2016).
 // Errors are written to stderr and mapped to "no loop" / empty results, as the reference only logs.
 // Lifetime: as for scan_context_hip_descriptor -- scan_descriptor has no virtual destructor, call close() before
 // dropping the object if the host re-creates descriptors.
 #pragma once
 
-#include <cstdint>
-#include <cstdio>
-#include <utility>
-#include <vector>
-
 #include "scl_m2dp.h"
+#include "vector_plugin_hip_descriptor.hpp"
 
-class m2dp_hip_descriptor : public scan_descriptor
+struct m2dp_hip_plugin {
+    typedef scl_m2dp handle;
+    typedef scl_m2dp_config config;
+    enum { DIM = SCL_M2DP_DIM };
+    static const char *name() { return "m2dp_hip_descriptor"; }
+    static const scl_vector_plugin_api<scl_m2dp, scl_m2dp_config> &api()
+    {
+        static const scl_vector_plugin_api<scl_m2dp, scl_m2dp_config> a = SCL_VECTOR_PLUGIN_API(scl_m2dp);
+        return a;
+    }
+};
+
+class m2dp_hip_descriptor : public vector_plugin_hip_descriptor<m2dp_hip_plugin>
 {
 public:
     m2dp_hip_descriptor(double distThres = 0.3, int numExcludeRecent = 30, int robotNum = 1, int thisID = 0, int device = 0)
     {
-        scl_m2dp_config cfg;
-        scl_m2dp_default_config(&cfg);
-        cfg.dist_thres = distThres; cfg.num_exclude_recent = numExcludeRecent; cfg.robot_num = robotNum; cfg.this_id = thisID;
-        cfg.device = device;
-        const int rc = scl_m2dp_create(&cfg, &m2dp_);
-        if (rc != SCL_OK) {
-            std::fprintf(stderr, "[m2dp_hip_descriptor] engine creation failed: %s\n", scl_status_string(rc));
-            m2dp_ = nullptr;
-        }
+        scl_m2dp_config cfg = defaults(robotNum, thisID, device);
+        cfg.dist_thres = distThres; cfg.num_exclude_recent = numExcludeRecent;
+        init(cfg);
     }
-
-    ~m2dp_hip_descriptor() { close(); }
-    void close()
-    {
-        if (m2dp_) scl_m2dp_destroy(m2dp_);
-        m2dp_ = nullptr;
-    }
-    m2dp_hip_descriptor(const m2dp_hip_descriptor &) = delete;
-    m2dp_hip_descriptor &operator=(const m2dp_hip_descriptor &) = delete;
-
-    // descriptor.h:25 / 1820-1863: the 192 floats [u, v]
-    std::vector<float> makeAndSaveDescriptorAndKey(const pcl::PointCloud<pcl::PointXYZI> &scan,
-                                                   const int8_t robot, const int index) override
-    {
-        std::vector<float> v(SCL_M2DP_DIM, 0.0f);
-        report(scl_m2dp_make_and_save(m2dp_, scan.points.data(), static_cast<int>(scan.points.size()),
-                                      static_cast<int>(sizeof(pcl::PointXYZI)), robot, index, v.data()),
-               "makeAndSaveDescriptorAndKey");
-        return v;
-    }
-
-    // the batch form: scans[i] appended as (robots[i], indexs[i]); returns scans.size() * 192 floats
-    std::vector<float> makeAndSaveDescriptorsAndKeys(const std::vector<const pcl::PointCloud<pcl::PointXYZI> *> &scans,
-                                                     const std::vector<int8_t> &robots, const std::vector<int> &indexs)
-    {
-        std::vector<float> v(scans.size() * SCL_M2DP_DIM, 0.0f);
-        if (robots.size() != scans.size() || indexs.size() != scans.size()) {
-            std::fprintf(stderr, "[m2dp_hip_descriptor] makeAndSaveDescriptorsAndKeys: %zu scans, %zu robots, %zu indexs\n",
-                         scans.size(), robots.size(), indexs.size());
-            return v;
-        }
-        std::vector<const void *> ptrs(scans.size());
-        std::vector<int> counts(scans.size());
-        for (size_t i = 0; i < scans.size(); ++i) { ptrs[i] = scans[i]->points.data(); counts[i] = static_cast<int>(scans[i]->points.size()); }
-        report(scl_m2dp_make_and_save_many(m2dp_, ptrs.data(), counts.data(), static_cast<int>(sizeof(pcl::PointXYZI)), robots.data(),
-                                           indexs.data(), static_cast<int>(scans.size()), v.data()),
-               "makeAndSaveDescriptorsAndKeys");
-        return v;
-    }
-
-    // the batch forms (scl_m2dp.h "THE BATCH FORMS"): what the single calls in the same order return, one device wait per call.
-    // {local index of the loop keyframe or -1, distance} per entry of curPtrs; on an error every entry is {-1, 0}
-    std::vector<std::pair<int, float>> detectIntraLoopClosureIDs(const std::vector<int> &curPtrs)
-    {
-        std::vector<int> loops(curPtrs.size(), -1);
-        std::vector<float> dists(curPtrs.size(), 0.0f);
-        const bool ok = report(scl_m2dp_detect_intra_many(m2dp_, curPtrs.data(), static_cast<int>(curPtrs.size()), loops.data(), dists.data()),
-                               "detectIntraLoopClosureIDs");
-        return pairs(loops, dists, ok);
-    }
-
-    // {global key of the loop keyframe or -1, distance} per entry of curPtrs
-    std::vector<std::pair<int, float>> detectInterLoopClosureIDs(const std::vector<int> &curPtrs)
-    {
-        std::vector<int> loops(curPtrs.size(), -1);
-        std::vector<float> dists(curPtrs.size(), 0.0f);
-        const bool ok = report(scl_m2dp_detect_inter_many(m2dp_, curPtrs.data(), static_cast<int>(curPtrs.size()), loops.data(), dists.data()),
-                               "detectInterLoopClosureIDs");
-        return pairs(loops, dists, ok);
-    }
-
-    // the candidate lists (scl_plugin_batch.h "THE CANDIDATE LISTS"): per entry of curPtrs the up to k nearest of the set the
-    // detection searches, nearest first, as {local index, distance}, without the threshold -- for a verifier (ICP, RANSAC) to judge.
-    // The inner vectors hold n_found pairs (fewer than k when the set is smaller); on an error every one is empty
-    std::vector<std::vector<std::pair<int, float>>> detectIntraLoopCandidates(const std::vector<int> &curPtrs, int k)
-    {
-        return candidates(curPtrs, k, scl_m2dp_detect_intra_topk, "detectIntraLoopCandidates");
-    }
-
-    // the same for the inter detection: {global key, distance}
-    std::vector<std::vector<std::pair<int, float>>> detectInterLoopCandidates(const std::vector<int> &curPtrs, int k)
-    {
-        return candidates(curPtrs, k, scl_m2dp_detect_inter_topk, "detectInterLoopCandidates");
-    }
-
-    // scans[i] appended as (robots[i], indexs[i]), then the intra detection of every new keyframe of this robot in the same call:
-    // {local index of the loop keyframe or -1, distance} per scan ({-1, +inf} for another robot's); descriptors: lastDescriptors()
-    std::vector<std::pair<int, float>> makeSaveAndDetect(const std::vector<const pcl::PointCloud<pcl::PointXYZI> *> &scans,
-                                                         const std::vector<int8_t> &robots, const std::vector<int> &indexs)
-    {
-        std::vector<int> loops(scans.size(), -1);
-        std::vector<float> dists(scans.size(), 0.0f);
-        last_.assign(scans.size() * SCL_M2DP_DIM, 0.0f);
-        if (robots.size() != scans.size() || indexs.size() != scans.size()) {
-            std::fprintf(stderr, "[m2dp_hip_descriptor] makeSaveAndDetect: %zu scans, %zu robots, %zu indexs\n", scans.size(), robots.size(),
-                         indexs.size());
-            return pairs(loops, dists, false);
-        }
-        std::vector<const void *> ptrs(scans.size());
-        std::vector<int> counts(scans.size());
-        for (size_t i = 0; i < scans.size(); ++i) { ptrs[i] = scans[i]->points.data(); counts[i] = static_cast<int>(scans[i]->points.size()); }
-        const bool ok = report(scl_m2dp_make_save_and_detect(m2dp_, ptrs.data(), counts.data(), static_cast<int>(sizeof(pcl::PointXYZI)),
-                                                          robots.data(), indexs.data(), static_cast<int>(scans.size()), loops.data(),
-                                                          dists.data(), last_.data()),
-                               "makeSaveAndDetect");
-        return pairs(loops, dists, ok);
-    }
-
-    // the descriptors of the last makeSaveAndDetect: scans.size() * 192 floats
-    const std::vector<float> &lastDescriptors() const { return last_; }
-
-    // descriptor.h:27 / 1989-1995, all 192 floats
-    void saveDescriptorAndKey(const float *m2dpVec, const int8_t robot, const int index) override
-    {
-        report(scl_m2dp_save_from_wire(m2dp_, m2dpVec, robot, index), "saveDescriptorAndKey");
-    }
-
-    // descriptor.h:29 / 1998-2001 (empty there): {local index of the loop keyframe or -1, distance}
-    std::pair<int, float> detectIntraLoopClosureID(const int curPtr) override
-    {
-        int loop_id = -1; float dist = 0.0f;
-        if (!report(scl_m2dp_detect_intra(m2dp_, curPtr, &loop_id, &dist), "detectIntraLoopClosureID"))
-            return std::pair<int, float>(-1, 0.0f);
-        return std::pair<int, float>(loop_id, dist);
-    }
-
-    // descriptor.h:31 / 2003-2006 (empty there): {global key of the loop keyframe or -1, distance}
-    std::pair<int, float> detectInterLoopClosureID(const int curPtr) override
-    {
-        int loop_id = -1; float dist = 0.0f;
-        if (!report(scl_m2dp_detect_inter(m2dp_, curPtr, &loop_id, &dist), "detectInterLoopClosureID"))
-            return std::pair<int, float>(-1, 0.0f);
-        return std::pair<int, float>(loop_id, dist);
-    }
-
-    // descriptor.h:33 / 2008-2011
-    std::pair<int8_t, int> getIndex(const int key) override
-    {
-        int8_t robot = 0; int index = -1;
-        report(scl_m2dp_get_index(m2dp_, key, &robot, &index), "getIndex");
-        return std::pair<int8_t, int>(robot, index);
-    }
-
-    // descriptor.h:35 / 2013-2016
-    int getSize(const int idIn = -1) override
-    {
-        if (!m2dp_) return 0;
-        const int n = scl_m2dp_get_size_of(m2dp_, idIn);
-        return n < 0 ? 0 : n;
-    }
-
-    scl_m2dp *engine() { return m2dp_; }
-
-private:
-    bool report(int rc, const char *where) const
-    {
-        if (!m2dp_) {
-            std::fprintf(stderr, "[m2dp_hip_descriptor] %s: no engine (creation failed or close() was called)\n", where);
-            return false;
-        }
-        if (rc == SCL_OK) return true;
-        std::fprintf(stderr, "[m2dp_hip_descriptor] %s: %s (%s)\n", where, scl_status_string(rc), scl_m2dp_last_error(m2dp_));
-        return false;
-    }
-
-    scl_m2dp *m2dp_ = nullptr;
-
-    std::vector<std::vector<std::pair<int, float>>> candidates(const std::vector<int> &curPtrs, int k,
-                                                               int (*call)(scl_m2dp *, const int *, int, int, int *, float *, int *),
-                                                               const char *where)
-    {
-        std::vector<std::vector<std::pair<int, float>>> out(curPtrs.size());
-        if (k < 1 || k > SCL_PLUGIN_TOPK_MAX) {
-            std::fprintf(stderr, "[m2dp_hip_descriptor] %s: k = %d outside [1, %d]\n", where, k, SCL_PLUGIN_TOPK_MAX);
-            return out;
-        }
-        std::vector<int> ids(curPtrs.size() * static_cast<size_t>(k), -1), found(curPtrs.size(), 0);
-        std::vector<float> dists(ids.size(), 0.0f);
-        if (!report(call(m2dp_, curPtrs.data(), static_cast<int>(curPtrs.size()), k, ids.data(), dists.data(), found.data()), where)) return out;
-        for (size_t i = 0; i < curPtrs.size(); ++i)
-            for (int j = 0; j < found[i]; ++j) out[i].push_back(std::pair<int, float>(ids[i * k + j], dists[i * k + j]));
-        return out;
-    }
-
-    static std::vector<std::pair<int, float>> pairs(const std::vector<int> &loops, const std::vector<float> &dists, bool ok)
-    {
-        std::vector<std::pair<int, float>> out(loops.size(), std::pair<int, float>(-1, 0.0f));
-        for (size_t i = 0; ok && i < loops.size(); ++i) out[i] = std::pair<int, float>(loops[i], dists[i]);
-        return out;
-    }
-
-    std::vector<float> last_;
 };

@@ -377,17 +377,9 @@ __global__ __launch_bounds__(kThreads) void fpfh_acosf_blocks_kernel(int first_b
 
 }  // namespace
 
-struct scl_fpfh {
+struct __attribute__((visibility("hidden"))) scl_fpfh : scl::VectorPlugin<kDim> {
+    static constexpr int kGroup = ::kGroup;
     scl_fpfh_config cfg;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    mutable std::mutex mu;
-    mutable std::string last_error;
-    scl::KeyframeRegistry reg;
-    scl::FloatRows<kDim> db;
-    // the reference's inter detection state: the call counter and the snapshot [0, snap_n) taken at the last rebuild
-    int tree_counter = 0, snap_n = 0;
     // the launch group's workspace (per point, per cell, per scan)
     unsigned char *d_pts = nullptr; size_t pts_cap = 0;
     size_t pt_cap = 0, cell_cap = 0, sort_cap = 0;
@@ -400,18 +392,20 @@ struct scl_fpfh {
     FpGrid *d_grids = nullptr;
     int *d_bad = nullptr;
     unsigned int *d_counts = nullptr;
-    unsigned long long *d_cand = nullptr, *d_best = nullptr;
-    int *d_list = nullptr; size_t list_cap = 0;
-    scl::NnManyWork many;                    // the batched detections' work buffers
-    scl::NnTopkWork topk;                    // the candidate lists' work buffers
+    unsigned long long *d_cand = nullptr;
     int *d_nbr = nullptr; float *d_nbr_d2 = nullptr; size_t nbr_cap = 0;
     unsigned long long points = 0;
-    double kernel_us = 0.0;
+
+    int report_dims() const { return cfg.report_dims; }
+    bool inter_snapshot() const { return cfg.inter_mode == 0; }
+    int snapshot_period() const { return cfg.tree_making_period; }
+    int reported_distance(int a, int b, float d2, float *dist);
+    static int check_layout(scl_fpfh *h, const void *points, int n_points, int stride);
+    static int run_group_locked(scl_fpfh *h, const void *const *clouds, const int *n_points, int stride, int G, int slot0, int *any_bad,
+                                bool want_nbr = false);
 };
 
-namespace {
-
-int check_layout(scl_fpfh *h, const void *points, int n_points, int stride)
+int scl_fpfh::check_layout(scl_fpfh *h, const void *points, int n_points, int stride)
 {
     if (stride < 12 || (stride & 3)) return fail(h, SCL_ERR_INVALID_ARG, "bad point layout (stride_bytes >= 12, multiple of 4)");
     if (n_points < 3) return fail(h, SCL_ERR_INVALID_ARG, "FPFH needs at least 3 points (N - 2 pairs)");
@@ -421,7 +415,7 @@ int check_layout(scl_fpfh *h, const void *points, int n_points, int stride)
 }
 
 // the workspace for a group of `pts` points, `cells` cell starts and `bytes` bytes of input
-int reserve(scl_fpfh *h, size_t pts, size_t cells, size_t bytes)
+static int reserve(scl_fpfh *h, size_t pts, size_t cells, size_t bytes)
 {
     int rc;
     if (bytes > h->pts_cap) {
@@ -454,8 +448,8 @@ int reserve(scl_fpfh *h, size_t pts, size_t cells, size_t bytes)
 
 // One launch group (G <= 16 clouds): descriptors into database rows slot0 .. slot0 + G - 1 (capacity ensured by the caller).
 // *any_bad = 1 if a cloud has a non-finite coordinate.  want_nbr: the neighbour hook (G == 1, d_nbr / d_nbr_d2 sized by the caller).
-int run_group_locked(scl_fpfh *h, const void *const *clouds, const int *n_points, int stride, int G, int slot0, int *any_bad,
-                     bool want_nbr = false)
+int scl_fpfh::run_group_locked(scl_fpfh *h, const void *const *clouds, const int *n_points, int stride, int G, int slot0, int *any_bad,
+                                bool want_nbr)
 {
     FpScan scans[kGroup];
     unsigned long long bytes = 0;
@@ -512,13 +506,13 @@ int run_group_locked(scl_fpfh *h, const void *const *clouds, const int *n_points
 }
 
 // the reported distance between keys a and b: sqrtf of the squared L2 over the first report_dims floats, nanoflann's order
-int report_distance_locked(scl_fpfh *h, int a, int b, float *dist)
+int scl_fpfh::reported_distance(int a, int b, float, float *dist)
 {
     float va[kDim], vb[kDim];
-    SCL_HIP(h, hipMemcpyAsync(va, h->db.row(a), sizeof va, hipMemcpyDeviceToHost, h->stream));
-    SCL_HIP(h, hipMemcpyAsync(vb, h->db.row(b), sizeof vb, hipMemcpyDeviceToHost, h->stream));
-    SCL_HIP(h, hipStreamSynchronize(h->stream));
-    const int D = h->cfg.report_dims;
+    SCL_HIP(this, hipMemcpyAsync(va, db.row(a), sizeof va, hipMemcpyDeviceToHost, stream));
+    SCL_HIP(this, hipMemcpyAsync(vb, db.row(b), sizeof vb, hipMemcpyDeviceToHost, stream));
+    SCL_HIP(this, hipStreamSynchronize(stream));
+    const int D = cfg.report_dims;
     float s = 0.0f;
     int k = 0;
     for (; k + 4 <= D; k += 4) {
@@ -530,24 +524,6 @@ int report_distance_locked(scl_fpfh *h, int a, int b, float *dist)
     return SCL_OK;
 }
 
-// a single cloud through the chain (test hooks): rows slot h->reg.n (scratch, not committed)
-int run_single_locked(scl_fpfh *h, const void *points, int n_points, int stride, bool want_nbr)
-{
-    int rc = check_layout(h, points, n_points, stride), bad = 0;
-    if (rc) return rc;
-    if ((rc = h->db.grow(h, h->reg.n + 1))) return rc;
-    if (want_nbr && (size_t)n_points * kK > h->nbr_cap) {
-        const size_t c = (size_t)n_points * kK;
-        if ((rc = dev_regrow(h, &h->d_nbr, c)) || (rc = dev_regrow(h, &h->d_nbr_d2, c))) return rc;
-        h->nbr_cap = c;
-    }
-    if ((rc = run_group_locked(h, &points, &n_points, stride, 1, h->reg.n, &bad, want_nbr))) return rc;
-    if (bad) return fail(h, SCL_ERR_INVALID_ARG, "non-finite coordinate");
-    return SCL_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int scl_fpfh_default_config(scl_fpfh_config *c)
@@ -558,33 +534,19 @@ int scl_fpfh_default_config(scl_fpfh_config *c)
     return SCL_OK;
 }
 
-const char *scl_fpfh_last_error(const scl_fpfh *h) { return h ? h->last_error.c_str() : "null handle"; }
-
 int scl_fpfh_create(const scl_fpfh_config *cfg, scl_fpfh **out)
 {
     if (!cfg || !out) return SCL_ERR_INVALID_ARG;
     *out = nullptr;
-    if (cfg->robot_num < 1 || cfg->robot_num > 127 || cfg->this_id < 0 || cfg->this_id >= cfg->robot_num || cfg->num_exclude_recent < 0 ||
-        cfg->tree_making_period < 1 || cfg->report_dims < 1 || cfg->report_dims > kDim || (cfg->inter_mode != 0 && cfg->inter_mode != 1) ||
-        !(cfg->dist_thres == cfg->dist_thres))
+    if (cfg->tree_making_period < 1 || cfg->report_dims < 1 || cfg->report_dims > kDim || (cfg->inter_mode != 0 && cfg->inter_mode != 1))
         return SCL_ERR_INVALID_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SCL_ERR_NO_DEVICE;
-    if (cfg->device < 0 || cfg->device >= ndev) return SCL_ERR_INVALID_ARG;
-    scl_fpfh *h = new (std::nothrow) scl_fpfh();
-    if (!h) return SCL_ERR_NOMEM;
-    h->cfg = *cfg; h->device = cfg->device;
-    h->reg.init(cfg->robot_num);
+    scl_fpfh *h = nullptr;
+    int rc = open_plugin(cfg, &h);
+    if (rc) return rc;
     auto bail = [&](int code) { scl_fpfh_destroy(h); return code; };
-    if (hipSetDevice(h->device) != hipSuccess) return bail(SCL_ERR_HIP);
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(SCL_ERR_HIP);
-    if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return bail(SCL_ERR_HIP);
-    int rc;
     if ((rc = dev_alloc(h, &h->d_scans, kGroup)) || (rc = dev_alloc(h, &h->d_grids, kGroup)) || (rc = dev_alloc(h, &h->d_bad, kGroup)) ||
-        (rc = dev_alloc(h, &h->d_counts, (size_t)kGroup * kCounts)) || (rc = dev_alloc(h, &h->d_cand, 1)) ||
-        (rc = dev_alloc(h, &h->d_best, 1)))
+        (rc = dev_alloc(h, &h->d_counts, (size_t)kGroup * kCounts)) || (rc = dev_alloc(h, &h->d_cand, 1)))
         return bail(rc);
-    if ((rc = h->db.grow(h, 1))) return bail(rc);
     if (hipMemset(h->d_cand, 0, sizeof(unsigned long long)) != hipSuccess) return bail(SCL_ERR_HIP);
     *out = h;
     return SCL_OK;
@@ -593,183 +555,24 @@ int scl_fpfh_create(const scl_fpfh_config *cfg, scl_fpfh **out)
 int scl_fpfh_destroy(scl_fpfh *h)
 {
     if (!h) return SCL_OK;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void *p : {(void *)h->db.d_db, (void *)h->d_pts, (void *)h->d_pos, (void *)h->d_sp, (void *)h->d_normals, (void *)h->d_keys0,
-                    (void *)h->d_keys1, (void *)h->d_vals0, (void *)h->d_vals1, h->d_sort, (void *)h->d_starts, (void *)h->d_scans,
-                    (void *)h->d_grids, (void *)h->d_bad, (void *)h->d_counts, (void *)h->d_cand, (void *)h->d_best, (void *)h->d_list,
-                    (void *)h->d_nbr, (void *)h->d_nbr_d2})
-        if (p) (void)hipFree(p);
-    h->many.release();
-    h->topk.release();
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-    return SCL_OK;
-}
-
-int scl_fpfh_make(scl_fpfh *h, const void *points, int n_points, int stride_bytes, float *out_values)
-{
-    if (!h || !out_values) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    int rc = run_single_locked(h, points, n_points, stride_bytes, false);
-    if (rc) return rc;
-    return h->db.read(h, h->reg.n, 1, out_values);
-}
-
-int scl_fpfh_make_and_save_many(scl_fpfh *h, const void *const *clouds, const int *n_points, int stride_bytes,
-                                const int8_t *robots, const int *indexs, int count, float *out_values)
-{
-    if (!h || count < 0 || (count > 0 && (!clouds || !n_points || !robots || !indexs))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    auto run = [&](const void *const *c, const int *np, int G, int slot0, int *bad) { return run_group_locked(h, c, np, stride_bytes, G, slot0, bad); };
-    return make_and_save_many_locked(h, clouds, n_points, stride_bytes, robots, indexs, count, out_values, kGroup, check_layout, run);
-}
-
-int scl_fpfh_make_and_save(scl_fpfh *h, const void *points, int n_points, int stride_bytes, int8_t robot, int index, float *out_values)
-{
-    return scl_fpfh_make_and_save_many(h, &points, &n_points, stride_bytes, &robot, &index, 1, out_values);
-}
-
-int scl_fpfh_save_from_wire(scl_fpfh *h, const float *values, int8_t robot, int index)
-{
-    if (!h || !values) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    int rc;
-    if ((rc = check_robot(h, robot, SCL_ERR_INVALID_ARG)) || (rc = h->db.grow(h, h->reg.n + 1)) || (rc = h->db.write(h, h->reg.n, values))) return rc;
-    h->reg.commit(robot, index);
-    return SCL_OK;
-}
-
-int scl_fpfh_get_size(const scl_fpfh *h) { return get_size(h); }
-int scl_fpfh_get_size_of(const scl_fpfh *h, int id) { return get_size_of(h, id); }
-int scl_fpfh_get_index(const scl_fpfh *h, int key, int8_t *robot, int *index) { return get_index(h, key, robot, index); }
-int scl_fpfh_local_to_global(const scl_fpfh *h, int robot, int local, int *key) { return local_to_global(h, robot, local, key); }
-
-int scl_fpfh_get_signature(scl_fpfh *h, int key, float *values)
-{
-    if (!h || !values) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    if (key < 0 || key >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "key out of range");
-    return h->db.read(h, key, 1, values);
-}
-
-int scl_fpfh_detect_intra(scl_fpfh *h, int cur, int *loop_id, float *dist)
-{
-    if (!h || !loop_id) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    *loop_id = -1;
-    if (dist) *dist = INFINITY;
-    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
-    if (cur < 0 || cur >= (int)mine.size()) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_intra: no such keyframe of this robot");
-    const int history = cur - h->cfg.num_exclude_recent;
-    if (history <= 0) return SCL_OK;
-    int pos; float d2, d;
-    int rc = nearest_locked(h, mine[(size_t)cur], mine.data(), history, &pos, &d2);     // ascending keys: position = local index
-    if (rc) return rc;
-    if (std::isnan(d2)) { if (dist) *dist = d2; return SCL_OK; }           // every 33-D distance NaN: nothing is nearest
-    if ((rc = report_distance_locked(h, mine[(size_t)cur], mine[(size_t)pos], &d))) return rc;
-    if (dist) *dist = d;
-    if ((double)d < h->cfg.dist_thres) *loop_id = pos;
-    return SCL_OK;
-}
-
-int scl_fpfh_detect_inter(scl_fpfh *h, int cur, int *loop_id, float *dist)
-{
-    if (!h || !loop_id) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    *loop_id = -1;
-    if (dist) *dist = INFINITY;
-    if (cur < 0 || cur >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter: key out of range");
-    int pos = -1, rc;
-    float d2;
-    if (h->cfg.inter_mode == 0) {                                 // D.h:381-428
-        if (h->reg.n < h->cfg.num_exclude_recent + 1) { if (dist) *dist = 0.0f; return SCL_OK; }
-        if (h->tree_counter % h->cfg.tree_making_period == 0) h->snap_n = h->reg.n - h->cfg.num_exclude_recent;
-        h->tree_counter += 1;
-        if ((rc = nearest_locked(h, cur, nullptr, h->snap_n, &pos, &d2))) return rc;
-    } else {
-        std::vector<int> list = h->reg.inter_candidates(cur, h->cfg.this_id);
-        std::sort(list.begin(), list.end());                      // ties go to the lowest key
-        if ((rc = nearest_locked(h, cur, list.data(), (int)list.size(), &pos, &d2))) return rc;
-        if (pos < 0) return SCL_OK;
-        pos = list[(size_t)pos];
-    }
-    if (std::isnan(d2)) { if (dist) *dist = d2; return SCL_OK; }  // every 33-D distance NaN: nothing is nearest
-    float d;
-    if ((rc = report_distance_locked(h, cur, pos, &d))) return rc;
-    if (dist) *dist = d;
-    if ((double)d < h->cfg.dist_thres) *loop_id = pos;
-    return SCL_OK;
-}
-
-int scl_fpfh_detect_intra_many(scl_fpfh *h, const int *curs, int count, int *loop_ids, float *dists)
-{
-    if (!h || count < 0 || (count > 0 && (!curs || !loop_ids))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    return detect_intra_many_locked(h, curs, count, h->cfg.report_dims, loop_ids, dists);
-}
-
-int scl_fpfh_detect_inter_many(scl_fpfh *h, const int *curs, int count, int *loop_ids, float *dists)
-{
-    if (!h || count < 0 || (count > 0 && (!curs || !loop_ids))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    if (h->cfg.inter_mode == 0) return detect_inter_snapshot_many_locked(h, curs, count, h->cfg.report_dims, loop_ids, dists);
-    return detect_inter_lists_many_locked(h, curs, count, h->cfg.report_dims, loop_ids, dists);
-}
-
-int scl_fpfh_detect_intra_topk(scl_fpfh *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
-{
-    if (!h || count < 0 || (count > 0 && (!curs || !cand_ids))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    return detect_intra_topk_locked(h, curs, count, k, h->cfg.report_dims, cand_ids, cand_dists, n_found);
-}
-
-int scl_fpfh_detect_inter_topk(scl_fpfh *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
-{
-    if (!h || count < 0 || (count > 0 && (!curs || !cand_ids))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    if (h->cfg.inter_mode == 0) return detect_inter_snapshot_topk_locked(h, curs, count, k, h->cfg.report_dims, cand_ids, cand_dists, n_found);
-    return detect_inter_lists_topk_locked(h, curs, count, k, h->cfg.report_dims, cand_ids, cand_dists, n_found);
-}
-
-int scl_fpfh_save_from_wire_many(scl_fpfh *h, const float *values, const int8_t *robots, const int *indexs, int count)
-{
-    if (!h || count < 0 || (count > 0 && (!values || !robots || !indexs))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    return save_from_wire_many_locked(h, values, robots, indexs, count);
-}
-
-int scl_fpfh_make_save_and_detect(scl_fpfh *h, const void *const *clouds, const int *n_points, int stride_bytes, const int8_t *robots,
-                               const int *indexs, int count, int *loop_ids, float *dists, float *out_values)
-{
-    if (!h || count < 0 || (count > 0 && (!clouds || !n_points || !robots || !indexs || !loop_ids))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    auto run = [&](const void *const *c, const int *np, int G, int slot0, int *bad) { return run_group_locked(h, c, np, stride_bytes, G, slot0, bad); };
-    return make_save_and_detect_locked(h, clouds, n_points, stride_bytes, robots, indexs, count, h->cfg.report_dims, loop_ids, dists, out_values, kGroup,
-                                       check_layout, run);
+    return close_plugin(h, {h->d_pts, h->d_pos, h->d_sp, h->d_normals, h->d_keys0, h->d_keys1, h->d_vals0, h->d_vals1, h->d_sort, h->d_starts,
+                            h->d_scans, h->d_grids, h->d_bad, h->d_counts, h->d_cand, h->d_nbr, h->d_nbr_d2});
 }
 
 int scl_fpfh_neighbors(scl_fpfh *h, const void *points, int n_points, int stride_bytes, int32_t *idx, float *d2)
 {
     if (!h) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    int rc = run_single_locked(h, points, n_points, stride_bytes, true);
+    Entered<scl_fpfh> in(h);
+    int rc = scl_fpfh::check_layout(h, points, n_points, stride_bytes), bad = 0;
     if (rc) return rc;
+    if ((rc = h->db.grow(h, h->reg.n + 1))) return rc;
+    if ((size_t)n_points * kK > h->nbr_cap) {
+        const size_t c = (size_t)n_points * kK;
+        if ((rc = dev_regrow(h, &h->d_nbr, c)) || (rc = dev_regrow(h, &h->d_nbr_d2, c))) return rc;
+        h->nbr_cap = c;
+    }
+    if ((rc = scl_fpfh::run_group_locked(h, &points, &n_points, stride_bytes, 1, h->reg.n, &bad, true))) return rc;     // row n: scratch
+    if (bad) return fail(h, SCL_ERR_INVALID_ARG, "non-finite coordinate");
     const size_t cnt = (size_t)n_points * (size_t)std::min(n_points, kK);
     if (idx) SCL_HIP(h, hipMemcpyAsync(idx, h->d_nbr, sizeof(int) * cnt, hipMemcpyDeviceToHost, h->stream));
     if (d2) SCL_HIP(h, hipMemcpyAsync(d2, h->d_nbr_d2, sizeof(float) * cnt, hipMemcpyDeviceToHost, h->stream));
@@ -780,9 +583,8 @@ int scl_fpfh_neighbors(scl_fpfh *h, const void *points, int n_points, int stride
 int scl_fpfh_normals(scl_fpfh *h, const void *points, int n_points, int stride_bytes, float *normals)
 {
     if (!h) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    int rc = run_single_locked(h, points, n_points, stride_bytes, false);
+    Entered<scl_fpfh> in(h);
+    int rc = run_single_locked(h, points, n_points, stride_bytes);
     if (rc) return rc;
     if (normals) {
         std::vector<float4> nv((size_t)n_points);
@@ -796,9 +598,8 @@ int scl_fpfh_normals(scl_fpfh *h, const void *points, int n_points, int stride_b
 int scl_fpfh_counts(scl_fpfh *h, const void *points, int n_points, int stride_bytes, uint32_t *counts, uint32_t *skipped)
 {
     if (!h) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    int rc = run_single_locked(h, points, n_points, stride_bytes, false);
+    Entered<scl_fpfh> in(h);
+    int rc = run_single_locked(h, points, n_points, stride_bytes);
     if (rc) return rc;
     uint32_t c[kCounts];
     SCL_HIP(h, hipMemcpyAsync(c, h->d_counts, sizeof c, hipMemcpyDeviceToHost, h->stream));
@@ -818,8 +619,7 @@ int scl_fpfh_values(const uint32_t *counts, int n, float hist_incr, float *out)
 int scl_fpfh_acosf_blocks(scl_fpfh *h, int first_block, int n_blocks, uint64_t *checksums)
 {
     if (!h || !checksums || first_block < 0 || n_blocks < 1 || first_block + n_blocks > 256) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
+    Entered<scl_fpfh> in(h);
     unsigned long long *d = nullptr;
     int rc = dev_alloc(h, &d, (size_t)n_blocks);
     if (rc) return rc;
@@ -839,8 +639,7 @@ int scl_fpfh_acosf_blocks(scl_fpfh *h, int first_block, int n_blocks, uint64_t *
 int scl_fpfh_stats(const scl_fpfh *h, unsigned long long *points, unsigned long long *candidates, double *kernel_us)
 {
     if (!h) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
+    Entered<scl_fpfh> in(h);
     unsigned long long c = 0;
     SCL_HIP(h, hipMemcpy(&c, h->d_cand, sizeof(c), hipMemcpyDeviceToHost));
     if (points) *points = h->points;
@@ -850,3 +649,5 @@ int scl_fpfh_stats(const scl_fpfh *h, unsigned long long *points, unsigned long 
 }
 
 }  // extern "C"
+
+SCL_VECTOR_PLUGIN_ENTRY_POINTS(scl_fpfh)

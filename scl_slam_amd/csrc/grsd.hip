@@ -432,18 +432,10 @@ __global__ __launch_bounds__(64) void grsd_finish_kernel(const GrScan *scans, co
 
 }  // namespace
 
-struct scl_grsd {
+struct __attribute__((visibility("hidden"))) scl_grsd : scl::VectorPlugin<kDim> {
+    static constexpr int kGroup = ::kGroup;
     scl_grsd_config cfg;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    mutable std::mutex mu;
-    mutable std::string last_error;
-    scl::KeyframeRegistry reg;
-    scl::FloatRows<kDim> db;
     GrParams prm;
-    // the reference's inter detection state: the call counter and the snapshot [0, snap_n) taken at the last rebuild
-    int tree_counter = 0, snap_n = 0;
     // the launch group's workspace (per point -- a group has at most as many voxels as points -- and per scan)
     unsigned char *d_pts = nullptr; size_t pts_cap = 0;
     size_t pt_cap = 0, sort_cap = 0;
@@ -457,18 +449,21 @@ struct scl_grsd {
     GrGrid *d_grids = nullptr;
     int *d_bad = nullptr, *d_nvox = nullptr;
     unsigned int *d_T = nullptr;
-    unsigned long long *d_best = nullptr;
-    int *d_list = nullptr; size_t list_cap = 0;
-    scl::NnManyWork many;                    // the batched detections' work buffers
-    scl::NnTopkWork topk;                    // the candidate lists' work buffers
     int last_voxels = 0;                     // voxels of the last launch group (the hooks read one cloud's)
     unsigned long long points = 0, voxels = 0;
-    double kernel_us = 0.0;
+
+    bool inter_snapshot() const { return cfg.inter_mode == 0; }
+    int snapshot_period() const { return cfg.tree_making_period; }
+    const char *bad_cloud(int bad) const
+    {
+        return bad == 2 ? "GRSD: the voxel index range of the cloud overflows int32: nothing of the call was stored"
+                        : "non-finite coordinate: nothing of the call was stored";
+    }
+    static int check_layout(scl_grsd *h, const void *points, int n_points, int stride);
+    static int run_group_locked(scl_grsd *h, const void *const *clouds, const int *n_points, int stride, int G, int slot0, int *any_bad);
 };
 
-namespace {
-
-int check_layout(scl_grsd *h, const void *points, int n_points, int stride)
+int scl_grsd::check_layout(scl_grsd *h, const void *points, int n_points, int stride)
 {
     if (stride < 12 || (stride & 3)) return fail(h, SCL_ERR_INVALID_ARG, "bad point layout (stride_bytes >= 12, multiple of 4)");
     if (n_points < 1) return fail(h, SCL_ERR_INVALID_ARG, "GRSD needs at least 1 point");
@@ -478,7 +473,7 @@ int check_layout(scl_grsd *h, const void *points, int n_points, int stride)
 }
 
 // the workspace for a group of `pts` points and `bytes` bytes of input
-int reserve(scl_grsd *h, size_t pts, size_t bytes)
+static int reserve(scl_grsd *h, size_t pts, size_t bytes)
 {
     int rc;
     if (bytes > h->pts_cap) {
@@ -510,7 +505,7 @@ int reserve(scl_grsd *h, size_t pts, size_t bytes)
 
 // One launch group (G <= 16 clouds): descriptors into database rows slot0 .. slot0 + G - 1 (capacity ensured by the caller).
 // *any_bad = 1 if a cloud has a non-finite coordinate, 2 if its voxel index range overflows int32.
-int run_group_locked(scl_grsd *h, const void *const *clouds, const int *n_points, int stride, int G, int slot0, int *any_bad)
+int scl_grsd::run_group_locked(scl_grsd *h, const void *const *clouds, const int *n_points, int stride, int G, int slot0, int *any_bad)
 {
     GrScan scans[kGroup];
     unsigned long long bytes = 0;
@@ -574,34 +569,6 @@ int run_group_locked(scl_grsd *h, const void *const *clouds, const int *n_points
     return SCL_OK;
 }
 
-int bad_cloud(scl_grsd *h, int bad)
-{
-    return fail(h, SCL_ERR_INVALID_ARG, bad == 2 ? "GRSD: the voxel index range of the cloud overflows int32: nothing of the call was stored"
-                                                 : "non-finite coordinate: nothing of the call was stored");
-}
-
-// a single cloud through the chain (make and the test hooks): row slot h->reg.n (scratch, not committed)
-int run_single_locked(scl_grsd *h, const void *points, int n_points, int stride)
-{
-    int rc = check_layout(h, points, n_points, stride), bad = 0;
-    if (rc) return rc;
-    if ((rc = h->db.grow(h, h->reg.n + 1))) return rc;
-    if ((rc = run_group_locked(h, &points, &n_points, stride, 1, h->reg.n, &bad))) return rc;
-    if (bad) return bad_cloud(h, bad);
-    return SCL_OK;
-}
-
-// a detection's answer from the 1-NN's squared distance: *dist = sqrtf(d2), the loop when it is below the threshold
-void report_locked(const scl_grsd *h, int id, float d2, int *loop_id, float *dist)
-{
-    if (std::isnan(d2)) { if (dist) *dist = d2; return; }          // every distance NaN: nothing is nearest
-    const float d = sqrtf(d2);
-    if (dist) *dist = d;
-    if ((double)d < h->cfg.dist_thres) *loop_id = id;
-}
-
-}  // namespace
-
 extern "C" {
 
 int scl_grsd_default_config(scl_grsd_config *c)
@@ -612,38 +579,27 @@ int scl_grsd_default_config(scl_grsd_config *c)
     return SCL_OK;
 }
 
-const char *scl_grsd_last_error(const scl_grsd *h) { return h ? h->last_error.c_str() : "null handle"; }
-
 int scl_grsd_create(const scl_grsd_config *cfg, scl_grsd **out)
 {
     if (!cfg || !out) return SCL_ERR_INVALID_ARG;
     *out = nullptr;
     // ne_radius <= 1: |q| <= 2^20 (1 + 2^-23) + 1/2 per axis, a product below 2^40.1, a sum over 2^22 points below 2^62.1 (scl_grsd.h)
-    if (cfg->robot_num < 1 || cfg->robot_num > 127 || cfg->this_id < 0 || cfg->this_id >= cfg->robot_num || cfg->num_exclude_recent < 0 ||
-        cfg->tree_making_period < 1 || (cfg->inter_mode != 0 && cfg->inter_mode != 1) || !(cfg->dist_thres == cfg->dist_thres) ||
-        !(cfg->ne_radius > 0.0 && cfg->ne_radius <= 1.0) || !(cfg->grsd_radius > 0.0 && cfg->grsd_radius <= 1.0e6) ||
-        !((float)cfg->grsd_radius > 0.0f) || !((float)(cfg->ne_radius * cfg->ne_radius) > 0.0f))
+    if (cfg->tree_making_period < 1 || (cfg->inter_mode != 0 && cfg->inter_mode != 1) || !(cfg->ne_radius > 0.0 && cfg->ne_radius <= 1.0) ||
+        !(cfg->grsd_radius > 0.0 && cfg->grsd_radius <= 1.0e6) || !((float)cfg->grsd_radius > 0.0f) ||
+        !((float)(cfg->ne_radius * cfg->ne_radius) > 0.0f))
         return SCL_ERR_INVALID_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SCL_ERR_NO_DEVICE;
-    if (cfg->device < 0 || cfg->device >= ndev) return SCL_ERR_INVALID_ARG;
-    scl_grsd *h = new (std::nothrow) scl_grsd();
-    if (!h) return SCL_ERR_NOMEM;
-    h->cfg = *cfg; h->device = cfg->device;
-    h->reg.init(cfg->robot_num);
+    scl_grsd *h = nullptr;
+    int rc = open_plugin(cfg, &h);
+    if (rc) return rc;
     h->prm.inv_leaf = 1.0f / (float)cfg->grsd_radius;
     h->prm.ne_r2 = (float)(cfg->ne_radius * cfg->ne_radius); h->prm.ne_rw = (float)(cfg->ne_radius * 1.00001);
     h->prm.rsd_r2 = (float)(cfg->grsd_radius * cfg->grsd_radius); h->prm.rsd_rw = (float)(cfg->grsd_radius * 1.00001);
     h->prm.max_dist = cfg->grsd_radius;
-    auto bail = [&](int code) { scl_grsd_destroy(h); return code; };
-    if (hipSetDevice(h->device) != hipSuccess) return bail(SCL_ERR_HIP);
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(SCL_ERR_HIP);
-    if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return bail(SCL_ERR_HIP);
-    int rc;
     if ((rc = dev_alloc(h, &h->d_scans, kGroup)) || (rc = dev_alloc(h, &h->d_grids, kGroup)) || (rc = dev_alloc(h, &h->d_bad, kGroup)) ||
-        (rc = dev_alloc(h, &h->d_T, (size_t)kGroup * kT)) || (rc = dev_alloc(h, &h->d_nvox, 1)) || (rc = dev_alloc(h, &h->d_best, 1)))
-        return bail(rc);
-    if ((rc = h->db.grow(h, 1))) return bail(rc);
+        (rc = dev_alloc(h, &h->d_T, (size_t)kGroup * kT)) || (rc = dev_alloc(h, &h->d_nvox, 1))) {
+        scl_grsd_destroy(h);
+        return rc;
+    }
     *out = h;
     return SCL_OK;
 }
@@ -651,176 +607,15 @@ int scl_grsd_create(const scl_grsd_config *cfg, scl_grsd **out)
 int scl_grsd_destroy(scl_grsd *h)
 {
     if (!h) return SCL_OK;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void *p : {(void *)h->db.d_db, (void *)h->d_pts, (void *)h->d_pos, (void *)h->d_sp, (void *)h->d_normals, (void *)h->d_nsp,
-                    (void *)h->d_cent, (void *)h->d_keys0, (void *)h->d_keys1, (void *)h->d_vals0, (void *)h->d_vals1, (void *)h->d_vkey,
-                    (void *)h->d_head, (void *)h->d_vid, (void *)h->d_vstart, (void *)h->d_vend, (void *)h->d_vscan, (void *)h->d_cls,
-                    (void *)h->d_rmin, (void *)h->d_rmax, h->d_sort, (void *)h->d_scans, (void *)h->d_grids, (void *)h->d_bad,
-                    (void *)h->d_nvox, (void *)h->d_T, (void *)h->d_best, (void *)h->d_list})
-        if (p) (void)hipFree(p);
-    h->many.release();
-    h->topk.release();
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-    return SCL_OK;
-}
-
-int scl_grsd_make(scl_grsd *h, const void *points, int n_points, int stride_bytes, float *out_values)
-{
-    if (!h || !out_values) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    int rc = run_single_locked(h, points, n_points, stride_bytes);
-    if (rc) return rc;
-    return h->db.read(h, h->reg.n, 1, out_values);
-}
-
-int scl_grsd_make_and_save_many(scl_grsd *h, const void *const *clouds, const int *n_points, int stride_bytes,
-                                const int8_t *robots, const int *indexs, int count, float *out_values)
-{
-    if (!h || count < 0 || (count > 0 && (!clouds || !n_points || !robots || !indexs))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    auto run = [&](const void *const *c, const int *np, int G, int slot0, int *bad) { return run_group_locked(h, c, np, stride_bytes, G, slot0, bad); };
-    return make_and_save_many_locked(h, clouds, n_points, stride_bytes, robots, indexs, count, out_values, kGroup, check_layout, run);
-}
-
-int scl_grsd_make_and_save(scl_grsd *h, const void *points, int n_points, int stride_bytes, int8_t robot, int index, float *out_values)
-{
-    return scl_grsd_make_and_save_many(h, &points, &n_points, stride_bytes, &robot, &index, 1, out_values);
-}
-
-int scl_grsd_save_from_wire(scl_grsd *h, const float *values, int8_t robot, int index)
-{
-    if (!h || !values) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    int rc;
-    if ((rc = check_robot(h, robot, SCL_ERR_INVALID_ARG)) || (rc = h->db.grow(h, h->reg.n + 1)) || (rc = h->db.write(h, h->reg.n, values))) return rc;
-    h->reg.commit(robot, index);
-    return SCL_OK;
-}
-
-int scl_grsd_get_size(const scl_grsd *h) { return get_size(h); }
-int scl_grsd_get_size_of(const scl_grsd *h, int id) { return get_size_of(h, id); }
-int scl_grsd_get_index(const scl_grsd *h, int key, int8_t *robot, int *index) { return get_index(h, key, robot, index); }
-int scl_grsd_local_to_global(const scl_grsd *h, int robot, int local, int *key) { return local_to_global(h, robot, local, key); }
-
-int scl_grsd_get_signature(scl_grsd *h, int key, float *values)
-{
-    if (!h || !values) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    if (key < 0 || key >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "key out of range");
-    return h->db.read(h, key, 1, values);
-}
-
-int scl_grsd_detect_intra(scl_grsd *h, int cur, int *loop_id, float *dist)
-{
-    if (!h || !loop_id) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    *loop_id = -1;
-    if (dist) *dist = INFINITY;
-    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
-    if (cur < 0 || cur >= (int)mine.size()) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_intra: no such keyframe of this robot");
-    const int history = cur - h->cfg.num_exclude_recent;
-    if (history <= 0) return SCL_OK;
-    int pos; float d2;
-    int rc = nearest_locked(h, mine[(size_t)cur], mine.data(), history, &pos, &d2);     // ascending keys: position = local index
-    if (rc) return rc;
-    report_locked(h, pos, d2, loop_id, dist);
-    return SCL_OK;
-}
-
-int scl_grsd_detect_inter(scl_grsd *h, int cur, int *loop_id, float *dist)
-{
-    if (!h || !loop_id) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    *loop_id = -1;
-    if (dist) *dist = INFINITY;
-    if (cur < 0 || cur >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter: key out of range");
-    int pos = -1, rc;
-    float d2;
-    if (h->cfg.inter_mode == 0) {                                 // D.h:116-167
-        if (h->reg.n < h->cfg.num_exclude_recent + 1) { if (dist) *dist = 0.0f; return SCL_OK; }
-        if (h->tree_counter % h->cfg.tree_making_period == 0) h->snap_n = h->reg.n - h->cfg.num_exclude_recent;
-        h->tree_counter += 1;
-        if ((rc = nearest_locked(h, cur, nullptr, h->snap_n, &pos, &d2))) return rc;
-        if (pos < 0) return SCL_OK;
-    } else {
-        std::vector<int> list = h->reg.inter_candidates(cur, h->cfg.this_id);
-        std::sort(list.begin(), list.end());                      // ties go to the lowest key
-        if ((rc = nearest_locked(h, cur, list.data(), (int)list.size(), &pos, &d2))) return rc;
-        if (pos < 0) return SCL_OK;
-        pos = list[(size_t)pos];
-    }
-    report_locked(h, pos, d2, loop_id, dist);
-    return SCL_OK;
-}
-
-int scl_grsd_detect_intra_many(scl_grsd *h, const int *curs, int count, int *loop_ids, float *dists)
-{
-    if (!h || count < 0 || (count > 0 && (!curs || !loop_ids))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    return detect_intra_many_locked(h, curs, count, kDim, loop_ids, dists);
-}
-
-int scl_grsd_detect_inter_many(scl_grsd *h, const int *curs, int count, int *loop_ids, float *dists)
-{
-    if (!h || count < 0 || (count > 0 && (!curs || !loop_ids))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    if (h->cfg.inter_mode == 0) return detect_inter_snapshot_many_locked(h, curs, count, kDim, loop_ids, dists);
-    return detect_inter_lists_many_locked(h, curs, count, kDim, loop_ids, dists);
-}
-
-int scl_grsd_detect_intra_topk(scl_grsd *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
-{
-    if (!h || count < 0 || (count > 0 && (!curs || !cand_ids))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    return detect_intra_topk_locked(h, curs, count, k, kDim, cand_ids, cand_dists, n_found);
-}
-
-int scl_grsd_detect_inter_topk(scl_grsd *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
-{
-    if (!h || count < 0 || (count > 0 && (!curs || !cand_ids))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    if (h->cfg.inter_mode == 0) return detect_inter_snapshot_topk_locked(h, curs, count, k, kDim, cand_ids, cand_dists, n_found);
-    return detect_inter_lists_topk_locked(h, curs, count, k, kDim, cand_ids, cand_dists, n_found);
-}
-
-int scl_grsd_save_from_wire_many(scl_grsd *h, const float *values, const int8_t *robots, const int *indexs, int count)
-{
-    if (!h || count < 0 || (count > 0 && (!values || !robots || !indexs))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    return save_from_wire_many_locked(h, values, robots, indexs, count);
-}
-
-int scl_grsd_make_save_and_detect(scl_grsd *h, const void *const *clouds, const int *n_points, int stride_bytes, const int8_t *robots,
-                               const int *indexs, int count, int *loop_ids, float *dists, float *out_values)
-{
-    if (!h || count < 0 || (count > 0 && (!clouds || !n_points || !robots || !indexs || !loop_ids))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    auto run = [&](const void *const *c, const int *np, int G, int slot0, int *bad) { return run_group_locked(h, c, np, stride_bytes, G, slot0, bad); };
-    return make_save_and_detect_locked(h, clouds, n_points, stride_bytes, robots, indexs, count, kDim, loop_ids, dists, out_values, kGroup,
-                                       check_layout, run);
+    return close_plugin(h, {h->d_pts, h->d_pos, h->d_sp, h->d_normals, h->d_nsp, h->d_cent, h->d_keys0, h->d_keys1, h->d_vals0, h->d_vals1,
+                            h->d_vkey, h->d_head, h->d_vid, h->d_vstart, h->d_vend, h->d_vscan, h->d_cls, h->d_rmin, h->d_rmax, h->d_sort,
+                            h->d_scans, h->d_grids, h->d_bad, h->d_nvox, h->d_T});
 }
 
 int scl_grsd_normals(scl_grsd *h, const void *points, int n_points, int stride_bytes, float *normals, uint8_t *valid)
 {
     if (!h) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
+    Entered<scl_grsd> in(h);
     int rc = run_single_locked(h, points, n_points, stride_bytes);
     if (rc) return rc;
     std::vector<float4> nv((size_t)n_points);
@@ -837,8 +632,7 @@ int scl_grsd_voxels(scl_grsd *h, const void *points, int n_points, int stride_by
                     float *r_max, int32_t *classes)
 {
     if (!h) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
+    Entered<scl_grsd> in(h);
     int rc = run_single_locked(h, points, n_points, stride_bytes);
     if (rc) return rc;
     const size_t nv = (size_t)h->last_voxels;
@@ -857,8 +651,7 @@ int scl_grsd_voxels(scl_grsd *h, const void *points, int n_points, int stride_by
 int scl_grsd_transitions(scl_grsd *h, const void *points, int n_points, int stride_bytes, uint32_t *counters)
 {
     if (!h) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
+    Entered<scl_grsd> in(h);
     int rc = run_single_locked(h, points, n_points, stride_bytes);
     if (rc) return rc;
     if (counters) {
@@ -879,3 +672,5 @@ int scl_grsd_stats(const scl_grsd *h, unsigned long long *points, unsigned long 
 }
 
 }  // extern "C"
+
+SCL_VECTOR_PLUGIN_ENTRY_POINTS(scl_grsd)

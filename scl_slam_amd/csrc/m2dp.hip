@@ -369,15 +369,9 @@ __global__ __launch_bounds__(kThreads) void m2dp_signature_kernel(const M2Scan *
 
 }  // namespace
 
-struct scl_m2dp {
+struct __attribute__((visibility("hidden"))) scl_m2dp : scl::VectorPlugin<SCL_M2DP_DIM> {
+    static constexpr int kGroup = ::kGroup;
     scl_m2dp_config cfg;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    mutable std::mutex mu;
-    mutable std::string last_error;
-    scl::KeyframeRegistry reg;
-    scl::FloatRows<SCL_M2DP_DIM> db;
     // the launch group's workspace
     unsigned char *d_pts = nullptr; size_t pts_cap = 0;
     M2Scan *d_scans = nullptr;
@@ -385,17 +379,15 @@ struct scl_m2dp {
     float *d_framef = nullptr, *d_frame_out = nullptr;
     unsigned int *d_max_rho = nullptr, *d_counts = nullptr;
     int *d_bad = nullptr;
-    unsigned long long *d_exact = nullptr, *d_best = nullptr;
-    int *d_list = nullptr; size_t list_cap = 0;
-    scl::NnManyWork many;                    // the batched detections' work buffers
-    scl::NnTopkWork topk;                    // the candidate lists' work buffers
+    unsigned long long *d_exact = nullptr;
     unsigned long long decisions = 0;
-    double kernel_us = 0.0;
+
+    static int check_layout(scl_m2dp *h, const void *points, int n_points, int stride);
+    static int run_group_locked(scl_m2dp *h, const void *const *clouds, const int *n_points, int stride, int G, int slot0, int *any_bad,
+                                uint32_t *counts_out = nullptr, float *frame_out = nullptr, float *max_rho_out = nullptr);
 };
 
-namespace {
-
-int check_layout(scl_m2dp *h, const void *points, int n_points, int stride)
+int scl_m2dp::check_layout(scl_m2dp *h, const void *points, int n_points, int stride)
 {
     if (stride < 12 || (stride & 3)) return fail(h, SCL_ERR_INVALID_ARG, "bad point layout (stride_bytes >= 12, multiple of 4)");
     if (n_points < 3) return fail(h, SCL_ERR_INVALID_ARG, "M2DP needs at least 3 points (PCA)");
@@ -405,8 +397,8 @@ int check_layout(scl_m2dp *h, const void *points, int n_points, int stride)
 
 // One launch group (G <= 16 clouds): signatures into database rows slot0 .. slot0 + G - 1 (capacity ensured by the caller).
 // *any_bad = 1 if a cloud has a non-finite coordinate.  counts_out / frame_out / max_rho_out: the test hook (G == 1).
-int run_group_locked(scl_m2dp *h, const void *const *clouds, const int *n_points, int stride, int G, int slot0, int *any_bad,
-                     uint32_t *counts_out = nullptr, float *frame_out = nullptr, float *max_rho_out = nullptr)
+int scl_m2dp::run_group_locked(scl_m2dp *h, const void *const *clouds, const int *n_points, int stride, int G, int slot0, int *any_bad,
+                                uint32_t *counts_out, float *frame_out, float *max_rho_out)
 {
     M2Scan scans[kGroup];
     unsigned long long bytes = 0;
@@ -455,8 +447,6 @@ int run_group_locked(scl_m2dp *h, const void *const *clouds, const int *n_points
     return SCL_OK;
 }
 
-}  // namespace
-
 extern "C" {
 
 int scl_m2dp_default_config(scl_m2dp_config *c)
@@ -466,35 +456,21 @@ int scl_m2dp_default_config(scl_m2dp_config *c)
     return SCL_OK;
 }
 
-const char *scl_m2dp_last_error(const scl_m2dp *h) { return h ? h->last_error.c_str() : "null handle"; }
-
 int scl_m2dp_create(const scl_m2dp_config *cfg, scl_m2dp **out)
 {
     if (!cfg || !out) return SCL_ERR_INVALID_ARG;
     *out = nullptr;
-    if (cfg->robot_num < 1 || cfg->robot_num > 127 || cfg->this_id < 0 || cfg->this_id >= cfg->robot_num || cfg->num_exclude_recent < 0 ||
-        !(cfg->dist_thres == cfg->dist_thres))
-        return SCL_ERR_INVALID_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SCL_ERR_NO_DEVICE;
-    if (cfg->device < 0 || cfg->device >= ndev) return SCL_ERR_INVALID_ARG;
-    scl_m2dp *h = new (std::nothrow) scl_m2dp();
-    if (!h) return SCL_ERR_NOMEM;
-    h->cfg = *cfg; h->device = cfg->device;
-    h->reg.init(cfg->robot_num);
+    scl_m2dp *h = nullptr;
+    int rc = open_plugin(cfg, &h);
+    if (rc) return rc;
     auto bail = [&](int code) { scl_m2dp_destroy(h); return code; };
-    if (hipSetDevice(h->device) != hipSuccess) return bail(SCL_ERR_HIP);
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(SCL_ERR_HIP);
-    if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return bail(SCL_ERR_HIP);
-    int rc;
     if ((rc = dev_alloc(h, &h->d_scans, kGroup)) || (rc = dev_alloc(h, &h->d_part, (size_t)kGroup * kParts * 9)) ||
         (rc = dev_alloc(h, &h->d_cube, (size_t)kGroup * kParts * 2)) || (rc = dev_alloc(h, &h->d_planes, 6 * SCL_M2DP_ROWS)) ||
         (rc = dev_alloc(h, &h->d_theta, 17)) || (rc = dev_alloc(h, &h->d_framef, (size_t)kGroup * kFrame)) ||
         (rc = dev_alloc(h, &h->d_frame_out, (size_t)kGroup * kFrame)) || (rc = dev_alloc(h, &h->d_max_rho, kGroup)) ||
         (rc = dev_alloc(h, &h->d_counts, (size_t)kGroup * kBins)) || (rc = dev_alloc(h, &h->d_bad, kGroup)) ||
-        (rc = dev_alloc(h, &h->d_exact, 1)) || (rc = dev_alloc(h, &h->d_best, 1)))
+        (rc = dev_alloc(h, &h->d_exact, 1)))
         return bail(rc);
-    if ((rc = h->db.grow(h, 1))) return bail(rc);
     // the planes with the host's libm, as the reference computes them (D.h:1808-1818, 1885-1906; Eigen's cross product)
     std::vector<double> pl(6 * SCL_M2DP_ROWS);
     for (int i = 0; i < SCL_M2DP_NUM_P; ++i) {
@@ -522,176 +498,21 @@ int scl_m2dp_create(const scl_m2dp_config *cfg, scl_m2dp **out)
 int scl_m2dp_destroy(scl_m2dp *h)
 {
     if (!h) return SCL_OK;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void *p : {(void *)h->db.d_db, (void *)h->d_pts, (void *)h->d_scans, (void *)h->d_part, (void *)h->d_cube,
-                    (void *)h->d_planes, (void *)h->d_theta, (void *)h->d_framef, (void *)h->d_frame_out, (void *)h->d_max_rho,
-                    (void *)h->d_counts, (void *)h->d_bad, (void *)h->d_exact, (void *)h->d_best, (void *)h->d_list})
-        if (p) (void)hipFree(p);
-    h->many.release();
-    h->topk.release();
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-    return SCL_OK;
-}
-
-int scl_m2dp_make(scl_m2dp *h, const void *points, int n_points, int stride_bytes, float *out_values)
-{
-    if (!h || !out_values) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    int rc = check_layout(h, points, n_points, stride_bytes), bad = 0;
-    if (rc) return rc;
-    if ((rc = h->db.grow(h, h->reg.n + 1))) return rc;
-    if ((rc = run_group_locked(h, &points, &n_points, stride_bytes, 1, h->reg.n, &bad))) return rc;     // row n: scratch, not committed
-    if (bad) return fail(h, SCL_ERR_INVALID_ARG, "non-finite coordinate");
-    return h->db.read(h, h->reg.n, 1, out_values);
-}
-
-int scl_m2dp_make_and_save_many(scl_m2dp *h, const void *const *clouds, const int *n_points, int stride_bytes,
-                                const int8_t *robots, const int *indexs, int count, float *out_values)
-{
-    if (!h || count < 0 || (count > 0 && (!clouds || !n_points || !robots || !indexs))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    auto run = [&](const void *const *c, const int *np, int G, int slot0, int *bad) { return run_group_locked(h, c, np, stride_bytes, G, slot0, bad); };
-    return make_and_save_many_locked(h, clouds, n_points, stride_bytes, robots, indexs, count, out_values, kGroup, check_layout, run);
-}
-
-int scl_m2dp_make_and_save(scl_m2dp *h, const void *points, int n_points, int stride_bytes, int8_t robot, int index, float *out_values)
-{
-    return scl_m2dp_make_and_save_many(h, &points, &n_points, stride_bytes, &robot, &index, 1, out_values);
-}
-
-int scl_m2dp_save_from_wire(scl_m2dp *h, const float *values, int8_t robot, int index)
-{
-    if (!h || !values) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    int rc;
-    if ((rc = check_robot(h, robot, SCL_ERR_INVALID_ARG)) || (rc = h->db.grow(h, h->reg.n + 1)) || (rc = h->db.write(h, h->reg.n, values))) return rc;
-    h->reg.commit(robot, index);
-    return SCL_OK;
-}
-
-int scl_m2dp_get_size(const scl_m2dp *h) { return get_size(h); }
-int scl_m2dp_get_size_of(const scl_m2dp *h, int id) { return get_size_of(h, id); }
-int scl_m2dp_get_index(const scl_m2dp *h, int key, int8_t *robot, int *index) { return get_index(h, key, robot, index); }
-int scl_m2dp_local_to_global(const scl_m2dp *h, int robot, int local, int *key) { return local_to_global(h, robot, local, key); }
-
-int scl_m2dp_get_signature(scl_m2dp *h, int key, float *values)
-{
-    if (!h || !values) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    if (key < 0 || key >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "key out of range");
-    return h->db.read(h, key, 1, values);
-}
-
-int scl_m2dp_detect_intra(scl_m2dp *h, int cur, int *loop_id, float *dist)
-{
-    if (!h || !loop_id) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    *loop_id = -1;
-    if (dist) *dist = INFINITY;
-    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
-    if (cur < 0 || cur >= (int)mine.size()) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_intra: no such keyframe of this robot");
-    const int history = cur - h->cfg.num_exclude_recent;
-    if (history <= 0) return SCL_OK;
-    int pos; float d2;
-    int rc = nearest_locked(h, mine[(size_t)cur], mine.data(), history, &pos, &d2);     // ascending keys: position = local index
-    if (rc) return rc;
-    const float d = sqrtf(d2);
-    if (dist) *dist = d;
-    if (pos >= 0 && (double)d < h->cfg.dist_thres) *loop_id = pos;
-    return SCL_OK;
-}
-
-int scl_m2dp_detect_inter(scl_m2dp *h, int cur, int *loop_id, float *dist)
-{
-    if (!h || !loop_id) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    *loop_id = -1;
-    if (dist) *dist = INFINITY;
-    if (cur < 0 || cur >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter: key out of range");
-    std::vector<int> list = h->reg.inter_candidates(cur, h->cfg.this_id);
-    std::sort(list.begin(), list.end());                                   // ties go to the lowest key
-    int pos; float d2;
-    int rc = nearest_locked(h, cur, list.data(), (int)list.size(), &pos, &d2);
-    if (rc) return rc;
-    const float d = sqrtf(d2);
-    if (dist) *dist = d;
-    if (pos >= 0 && (double)d < h->cfg.dist_thres) *loop_id = list[(size_t)pos];
-    return SCL_OK;
-}
-
-int scl_m2dp_detect_intra_many(scl_m2dp *h, const int *curs, int count, int *loop_ids, float *dists)
-{
-    if (!h || count < 0 || (count > 0 && (!curs || !loop_ids))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    return detect_intra_many_locked(h, curs, count, SCL_M2DP_DIM, loop_ids, dists);
-}
-
-int scl_m2dp_detect_inter_many(scl_m2dp *h, const int *curs, int count, int *loop_ids, float *dists)
-{
-    if (!h || count < 0 || (count > 0 && (!curs || !loop_ids))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    return detect_inter_lists_many_locked(h, curs, count, SCL_M2DP_DIM, loop_ids, dists);
-}
-
-int scl_m2dp_detect_intra_topk(scl_m2dp *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
-{
-    if (!h || count < 0 || (count > 0 && (!curs || !cand_ids))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    return detect_intra_topk_locked(h, curs, count, k, SCL_M2DP_DIM, cand_ids, cand_dists, n_found);
-}
-
-int scl_m2dp_detect_inter_topk(scl_m2dp *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
-{
-    if (!h || count < 0 || (count > 0 && (!curs || !cand_ids))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    return detect_inter_lists_topk_locked(h, curs, count, k, SCL_M2DP_DIM, cand_ids, cand_dists, n_found);
-}
-
-int scl_m2dp_save_from_wire_many(scl_m2dp *h, const float *values, const int8_t *robots, const int *indexs, int count)
-{
-    if (!h || count < 0 || (count > 0 && (!values || !robots || !indexs))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    return save_from_wire_many_locked(h, values, robots, indexs, count);
-}
-
-int scl_m2dp_make_save_and_detect(scl_m2dp *h, const void *const *clouds, const int *n_points, int stride_bytes, const int8_t *robots,
-                               const int *indexs, int count, int *loop_ids, float *dists, float *out_values)
-{
-    if (!h || count < 0 || (count > 0 && (!clouds || !n_points || !robots || !indexs || !loop_ids))) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    auto run = [&](const void *const *c, const int *np, int G, int slot0, int *bad) { return run_group_locked(h, c, np, stride_bytes, G, slot0, bad); };
-    return make_save_and_detect_locked(h, clouds, n_points, stride_bytes, robots, indexs, count, SCL_M2DP_DIM, loop_ids, dists, out_values, kGroup,
-                                       check_layout, run);
+    return close_plugin(h, {h->d_pts, h->d_scans, h->d_part, h->d_cube, h->d_planes, h->d_theta, h->d_framef, h->d_frame_out, h->d_max_rho,
+                            h->d_counts, h->d_bad, h->d_exact});
 }
 
 int scl_m2dp_signature_matrix(scl_m2dp *h, const void *points, int n_points, int stride_bytes, uint32_t *counts,
                               float *mean, float *axes, float *max_rho)
 {
     if (!h) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
-    int rc = check_layout(h, points, n_points, stride_bytes), bad = 0;
+    Entered<scl_m2dp> in(h);
+    int rc = scl_m2dp::check_layout(h, points, n_points, stride_bytes), bad = 0;
     if (rc) return rc;
     if ((rc = h->db.grow(h, h->reg.n + 1))) return rc;
     float fr[kFrame], mr = 0.0f;
     std::vector<uint32_t> c(kBins);
-    if ((rc = run_group_locked(h, &points, &n_points, stride_bytes, 1, h->reg.n, &bad, c.data(), fr, &mr))) return rc;
+    if ((rc = scl_m2dp::run_group_locked(h, &points, &n_points, stride_bytes, 1, h->reg.n, &bad, c.data(), fr, &mr))) return rc;
     if (bad) return fail(h, SCL_ERR_INVALID_ARG, "non-finite coordinate");
     if (counts) std::memcpy(counts, c.data(), sizeof(uint32_t) * kBins);
     if (mean) std::memcpy(mean, fr, sizeof(float) * 3);
@@ -703,8 +524,7 @@ int scl_m2dp_signature_matrix(scl_m2dp *h, const void *points, int n_points, int
 int scl_m2dp_stats(const scl_m2dp *h, unsigned long long *decisions, unsigned long long *exact, double *kernel_us)
 {
     if (!h) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->device);
+    Entered<scl_m2dp> in(h);
     unsigned long long e = 0;
     SCL_HIP(h, hipMemcpy(&e, h->d_exact, sizeof(e), hipMemcpyDeviceToHost));
     if (decisions) *decisions = h->decisions;
@@ -714,3 +534,5 @@ int scl_m2dp_stats(const scl_m2dp *h, unsigned long long *decisions, unsigned lo
 }
 
 }  // extern "C"
+
+SCL_VECTOR_PLUGIN_ENTRY_POINTS(scl_m2dp)

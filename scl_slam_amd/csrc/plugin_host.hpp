@@ -1,17 +1,14 @@
 // plugin_host.hpp -- the host layer the descriptor plugins share (iris.hip, m2dp.hip, fpfh.hip, grsd.hip; engine.hip and sharded_front.hip
 // take the error helpers): the HIP-check macro and error helpers, the keyframe registry behind the get_size / get_index / local_to_global
-// entry points and the inter-detection candidate rule, and for the vector plugins (M2DP, FPFH, GRSD) the float-row database, the
-// make_and_save_many driver, the 1-NN search and its batched form with the *_many detections built on it.  No descriptor logic
-// lives here.
+// entry points and the inter-detection candidate rule, and for the vector plugins (M2DP, FPFH, GRSD) everything but their kernels: the
+// float-row database, the 1-NN search with its batched and k-nearest forms, the handle base (scl::VectorPlugin), the C entry points as
+// function templates and the macro that defines the extern "C" functions from them.  No descriptor logic lives here.
 //
 // Every helper that touches a handle assumes its lock is held (the `_locked` convention; std::mutex is not recursive), except
-// the registry's C entry points below, which take it once.  A handle provides `mutable std::mutex mu`, `mutable std::string
-// last_error`, `hipStream_t stream` and `scl::KeyframeRegistry reg`; a vector plugin's also `scl::FloatRows<DIM> db`,
-// `int *d_list`, `size_t list_cap`, `unsigned long long *d_best` (one element), `scl::NnManyWork many` (the batched search) and
-// `scl::NnTopkWork topk` (the candidate lists: nn_l2_topk_kernel, nn_topk_merge_kernel and the *_topk detections).
-// Included from .hip files only (nn_l2_kernel and nn_l2_many_kernel are device code).  Everything here has internal linkage (the
-// unnamed namespace): the
-// library exports its C ABI and nothing of this layer.
+// the entry points, which take it once.  A handle provides `mutable std::mutex mu`, `mutable std::string last_error`,
+// `hipStream_t stream` and `scl::KeyframeRegistry reg`; a vector plugin's derives from scl::VectorPlugin<DIM> and adds `cfg`.
+// Included from .hip files only (the search kernels are device code).  Everything here has internal linkage (the unnamed namespace)
+// and the vector plugins' handles are marked hidden: the library exports its C ABI and nothing of this layer.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -20,7 +17,9 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -175,29 +174,40 @@ template <int DIM> struct FloatRows {
     }
 };
 
-// make_and_save_many of a vector plugin: every cloud (check(h, points, n_points, stride)) and robot id validated first, then
-// launch groups of up to max_group clouds into rows n .. n + count - 1 (run(clouds, n_points, G, slot0, &bad)); the first
-// group with a non-finite coordinate ends the call, and nothing of the call is committed
-template <class H, class Check, class Run>
+// make_and_save_many of a vector plugin: every cloud (H::check_layout) and robot id validated first, then launch groups of up to
+// H::kGroup clouds into rows n .. n + count - 1 (H::run_group_locked); the first group with an invalid cloud ends the call, and
+// nothing of the call is committed
+template <class H>
 int make_and_save_many_locked(H *h, const void *const *clouds, const int *n_points, int stride, const int8_t *robots,
-                              const int *indexs, int count, float *out_values, int max_group, Check check, Run run)
+                              const int *indexs, int count, float *out_values)
 {
     for (int i = 0; i < count; ++i) {
-        int rc = check(h, clouds[i], n_points[i], stride);
+        int rc = H::check_layout(h, clouds[i], n_points[i], stride);
         if (rc) return rc;
         if ((rc = check_robot(h, robots[i], SCL_ERR_INVALID_ARG))) return rc;
     }
     if (count == 0) return SCL_OK;
     int rc = h->db.grow(h, h->reg.n + count);
     if (rc) return rc;
-    for (int s = 0; s < count; s += max_group) {
-        const int G = std::min(max_group, count - s);
+    for (int s = 0; s < count; s += H::kGroup) {
+        const int G = std::min((int)H::kGroup, count - s);
         int bad = 0;
-        if ((rc = run(clouds + s, n_points + s, G, h->reg.n + s, &bad))) return rc;
+        if ((rc = H::run_group_locked(h, clouds + s, n_points + s, stride, G, h->reg.n + s, &bad))) return rc;
         if (bad) return fail(h, SCL_ERR_INVALID_ARG, "non-finite coordinate: nothing of the call was stored");
     }
     if (out_values && (rc = h->db.read(h, h->reg.n, count, out_values))) return rc;
     for (int i = 0; i < count; ++i) h->reg.commit(robots[i], indexs[i]);
+    return SCL_OK;
+}
+
+// one cloud through the chain into row reg.n (scratch, not committed): make and the test hooks
+template <class H> int run_single_locked(H *h, const void *points, int n_points, int stride)
+{
+    int rc = H::check_layout(h, points, n_points, stride), bad = 0;
+    if (rc) return rc;
+    if ((rc = h->db.grow(h, h->reg.n + 1))) return rc;
+    if ((rc = H::run_group_locked(h, &points, &n_points, stride, 1, h->reg.n, &bad))) return rc;
+    if (bad) return fail(h, SCL_ERR_INVALID_ARG, h->bad_cloud(bad));
     return SCL_OK;
 }
 
@@ -575,6 +585,39 @@ struct NnList {
     int n;
 };
 
+// ---- what every vector plugin's handle holds: scl_m2dp, scl_fpfh and scl_grsd derive from it and add `cfg` (device, dist_thres,
+// num_exclude_recent, robot_num, this_id and the plugin's own fields), their workspace and their counters.  The plugin's rules are
+// members of the derived handle; the ones below are the defaults, hidden by a plugin that differs:
+//   report_dims()           the floats a reported distance is taken over (FPFH: cfg.report_dims);
+//   inter_snapshot()        detect_inter is the reference's (every key below a snapshot taken each snapshot_period() calls), not
+//                           M2DP's rule (the sorted keys of the other robots) -- FPFH and GRSD: cfg.inter_mode == 0;
+//   reported_distance()     the distance a single detection reports for the winner (FPFH: over report_dims floats, on the host);
+//   bad_cloud()             the message of a single cloud the kernels flagged;
+// and the launch group has no default: static int check_layout(H *, points, n_points, stride), static int run_group_locked(H *,
+// clouds, n_points, stride, G, slot0, &any_bad) and kGroup, the clouds of one group.
+template <int DIM> struct VectorPlugin {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;                 // around a launch group's kernels: kernel_us
+    mutable std::mutex mu;
+    mutable std::string last_error;
+    KeyframeRegistry reg;
+    FloatRows<DIM> db;
+    unsigned long long *d_best = nullptr;
+    int *d_list = nullptr; size_t list_cap = 0;
+    NnManyWork many;                                         // the batched detections' work buffers
+    NnTopkWork topk;                                         // the candidate lists' work buffers
+    double kernel_us = 0.0;
+    // the reference's inter detection state: the call counter and the snapshot [0, snap_n) taken at the last rebuild
+    int tree_counter = 0, snap_n = 0;
+
+    int report_dims() const { return DIM; }
+    bool inter_snapshot() const { return false; }
+    int snapshot_period() const { return 1; }
+    int reported_distance(int, int, float d2, float *dist) { *dist = sqrtf(d2); return SCL_OK; }
+    const char *bad_cloud(int) const { return "non-finite coordinate"; }
+};
+
 // `count` queries in one call: query i is row qkey[i] against the prefix [0, limit[i]) of lists[which[i]] (limit[i] <= its n).
 // The queries are grouped by list and run in groups of 16 back to back on the stream, then the finishing kernel; ONE device-to-host
 // copy and ONE synchronisation for the whole call.  out[i]: as NnManyResult says, in the caller's order.
@@ -663,7 +706,7 @@ template <class H> void report_many(const H *h, const NnManyResult *res, int cou
 }
 
 // detect_intra for curs[0 .. count): every cur validated first, then one batched search over this robot's keys
-template <class H> int detect_intra_many_locked(H *h, const int *curs, int count, int report_dims, int *loop_ids, float *dists)
+template <class H> int detect_intra_many_locked(H *h, const int *curs, int count, int *loop_ids, float *dists)
 {
     const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
     for (int i = 0; i < count; ++i)
@@ -675,7 +718,7 @@ template <class H> int detect_intra_many_locked(H *h, const int *curs, int count
     }
     const NnList lists[2] = {{mine.data(), (int)mine.size()}, {nullptr, 0}};       // ascending keys: position = local index
     std::vector<NnManyResult> res((size_t)count);
-    int rc = nearest_many_locked(h, qkey.data(), limit.data(), which.data(), lists, count, report_dims, res.data());
+    int rc = nearest_many_locked(h, qkey.data(), limit.data(), which.data(), lists, count, h->report_dims(), res.data());
     if (rc) return rc;
     report_many(h, res.data(), count, true, loop_ids, dists);
     return SCL_OK;
@@ -683,7 +726,7 @@ template <class H> int detect_intra_many_locked(H *h, const int *curs, int count
 
 // detect_inter by M2DP's rule (inter_mode 1 of FPFH and GRSD) for curs[0 .. count): a keyframe of this robot searches the sorted
 // keys of every other robot, a received keyframe searches this robot's
-template <class H> int detect_inter_lists_many_locked(H *h, const int *curs, int count, int report_dims, int *loop_ids, float *dists)
+template <class H> int detect_inter_lists_many_locked(H *h, const int *curs, int count, int *loop_ids, float *dists)
 {
     for (int i = 0; i < count; ++i)
         if (curs[i] < 0 || curs[i] >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter: key out of range");
@@ -699,7 +742,7 @@ template <class H> int detect_inter_lists_many_locked(H *h, const int *curs, int
         limit[(size_t)i] = lists[which[(size_t)i]].n;
     }
     std::vector<NnManyResult> res((size_t)count);
-    int rc = nearest_many_locked(h, curs, limit.data(), which.data(), lists, count, report_dims, res.data());
+    int rc = nearest_many_locked(h, curs, limit.data(), which.data(), lists, count, h->report_dims(), res.data());
     if (rc) return rc;
     report_many(h, res.data(), count, false, loop_ids, dists);
     return SCL_OK;
@@ -708,7 +751,7 @@ template <class H> int detect_inter_lists_many_locked(H *h, const int *curs, int
 // detect_inter of the reference (inter_mode 0 of FPFH and GRSD) for curs[0 .. count), the handle's tree_counter and snap_n walked
 // as `count` single calls in order would: before num_exclude_recent + 1 keyframes (-1, 0) and the counter stays; else the snapshot
 // [0, snap_n) is retaken when tree_counter % tree_making_period == 0 and the counter advances.  Both are committed on success only
-template <class H> int detect_inter_snapshot_many_locked(H *h, const int *curs, int count, int report_dims, int *loop_ids, float *dists)
+template <class H> int detect_inter_snapshot_many_locked(H *h, const int *curs, int count, int *loop_ids, float *dists)
 {
     for (int i = 0; i < count; ++i)
         if (curs[i] < 0 || curs[i] >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter: key out of range");
@@ -719,13 +762,13 @@ template <class H> int detect_inter_snapshot_many_locked(H *h, const int *curs, 
     int counter = h->tree_counter, snap_n = h->snap_n;
     std::vector<int> limit((size_t)count), which((size_t)count, 0);
     for (int i = 0; i < count; ++i) {
-        if (counter % h->cfg.tree_making_period == 0) snap_n = h->reg.n - h->cfg.num_exclude_recent;
+        if (counter % h->snapshot_period() == 0) snap_n = h->reg.n - h->cfg.num_exclude_recent;
         counter += 1;
         limit[(size_t)i] = snap_n;
     }
     const NnList lists[2] = {{nullptr, h->reg.n}, {nullptr, 0}};
     std::vector<NnManyResult> res((size_t)count);
-    int rc = nearest_many_locked(h, curs, limit.data(), which.data(), lists, count, report_dims, res.data());
+    int rc = nearest_many_locked(h, curs, limit.data(), which.data(), lists, count, h->report_dims(), res.data());
     if (rc) return rc;
     h->tree_counter = counter; h->snap_n = snap_n;
     report_many(h, res.data(), count, false, loop_ids, dists);
@@ -843,7 +886,7 @@ inline bool topk_ok(int k) { return k >= 1 && k <= kTopkMax; }
 
 // the candidate list of detect_intra for curs[0 .. count): the search sets of detect_intra_many_locked
 template <class H>
-int detect_intra_topk_locked(H *h, const int *curs, int count, int k, int report_dims, int *cand_ids, float *cand_dists, int *n_found)
+int detect_intra_topk_locked(H *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
 {
     if (!topk_ok(k)) return fail(h, SCL_ERR_INVALID_ARG, "detect_intra_topk: k outside [1, SCL_PLUGIN_TOPK_MAX]");
     const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
@@ -856,7 +899,7 @@ int detect_intra_topk_locked(H *h, const int *curs, int count, int k, int report
     }
     const NnList lists[2] = {{mine.data(), (int)mine.size()}, {nullptr, 0}};       // ascending keys: position = local index
     std::vector<NnTopkEntry> res((size_t)count * k);
-    int rc = nearest_topk_many_locked(h, qkey.data(), limit.data(), which.data(), lists, count, k, report_dims, res.data());
+    int rc = nearest_topk_many_locked(h, qkey.data(), limit.data(), which.data(), lists, count, k, h->report_dims(), res.data());
     if (rc) return rc;
     report_topk(res.data(), count, k, true, cand_ids, cand_dists, n_found);
     return SCL_OK;
@@ -864,7 +907,7 @@ int detect_intra_topk_locked(H *h, const int *curs, int count, int k, int report
 
 // the candidate list of detect_inter by M2DP's rule (inter_mode 1 of FPFH and GRSD): the search sets of detect_inter_lists_many_locked
 template <class H>
-int detect_inter_lists_topk_locked(H *h, const int *curs, int count, int k, int report_dims, int *cand_ids, float *cand_dists, int *n_found)
+int detect_inter_lists_topk_locked(H *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
 {
     if (!topk_ok(k)) return fail(h, SCL_ERR_INVALID_ARG, "detect_inter_topk: k outside [1, SCL_PLUGIN_TOPK_MAX]");
     for (int i = 0; i < count; ++i)
@@ -881,7 +924,7 @@ int detect_inter_lists_topk_locked(H *h, const int *curs, int count, int k, int 
         limit[(size_t)i] = lists[which[(size_t)i]].n;
     }
     std::vector<NnTopkEntry> res((size_t)count * k);
-    int rc = nearest_topk_many_locked(h, curs, limit.data(), which.data(), lists, count, k, report_dims, res.data());
+    int rc = nearest_topk_many_locked(h, curs, limit.data(), which.data(), lists, count, k, h->report_dims(), res.data());
     if (rc) return rc;
     report_topk(res.data(), count, k, false, cand_ids, cand_dists, n_found);
     return SCL_OK;
@@ -891,7 +934,7 @@ int detect_inter_lists_topk_locked(H *h, const int *curs, int count, int k, int 
 // detect_inter_snapshot_many_locked and are committed on success only; before num_exclude_recent + 1 keyframes every list is empty
 // and the counter stays
 template <class H>
-int detect_inter_snapshot_topk_locked(H *h, const int *curs, int count, int k, int report_dims, int *cand_ids, float *cand_dists, int *n_found)
+int detect_inter_snapshot_topk_locked(H *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
 {
     if (!topk_ok(k)) return fail(h, SCL_ERR_INVALID_ARG, "detect_inter_topk: k outside [1, SCL_PLUGIN_TOPK_MAX]");
     for (int i = 0; i < count; ++i)
@@ -904,13 +947,13 @@ int detect_inter_snapshot_topk_locked(H *h, const int *curs, int count, int k, i
     int counter = h->tree_counter, snap_n = h->snap_n;
     std::vector<int> limit((size_t)count), which((size_t)count, 0);
     for (int i = 0; i < count; ++i) {
-        if (counter % h->cfg.tree_making_period == 0) snap_n = h->reg.n - h->cfg.num_exclude_recent;
+        if (counter % h->snapshot_period() == 0) snap_n = h->reg.n - h->cfg.num_exclude_recent;
         counter += 1;
         limit[(size_t)i] = snap_n;
     }
     const NnList lists[2] = {{nullptr, h->reg.n}, {nullptr, 0}};
     std::vector<NnTopkEntry> res((size_t)count * k);
-    int rc = nearest_topk_many_locked(h, curs, limit.data(), which.data(), lists, count, k, report_dims, res.data());
+    int rc = nearest_topk_many_locked(h, curs, limit.data(), which.data(), lists, count, k, h->report_dims(), res.data());
     if (rc) return rc;
     h->tree_counter = counter; h->snap_n = snap_n;
     report_topk(res.data(), count, k, false, cand_ids, cand_dists, n_found);
@@ -934,23 +977,247 @@ template <class H> int save_from_wire_many_locked(H *h, const float *values, con
 
 // make_and_save_many, then on the same stream the intra detection of every new keyframe of this robot; entries of other robots
 // answer (-1, +inf).  An invalid cloud: nothing stored, nothing detected, the outputs untouched
-template <class H, class Check, class Run>
+template <class H>
 int make_save_and_detect_locked(H *h, const void *const *clouds, const int *n_points, int stride, const int8_t *robots, const int *indexs,
-                                int count, int report_dims, int *loop_ids, float *dists, float *out_values, int max_group, Check check, Run run)
+                                int count, int *loop_ids, float *dists, float *out_values)
 {
     const int first = (int)h->reg.keys_of(h->cfg.this_id).size();
-    int rc = make_and_save_many_locked(h, clouds, n_points, stride, robots, indexs, count, out_values, max_group, check, run);
+    int rc = make_and_save_many_locked(h, clouds, n_points, stride, robots, indexs, count, out_values);
     if (rc) return rc;
     std::vector<int> curs, at;
     for (int i = 0; i < count; ++i)
         if (robots[i] == h->cfg.this_id) { curs.push_back(first + (int)curs.size()); at.push_back(i); }
     std::vector<int> loops(curs.size());
     std::vector<float> ds(curs.size());
-    if ((rc = detect_intra_many_locked(h, curs.data(), (int)curs.size(), report_dims, loops.data(), ds.data()))) return rc;
+    if ((rc = detect_intra_many_locked(h, curs.data(), (int)curs.size(), loops.data(), ds.data()))) return rc;
     for (int i = 0; i < count; ++i) { loop_ids[i] = -1; if (dists) dists[i] = INFINITY; }
     for (size_t j = 0; j < at.size(); ++j) { loop_ids[at[j]] = loops[j]; if (dists) dists[at[j]] = ds[j]; }
     return SCL_OK;
 }
 
+// ---- the vector plugins' C entry points, written once: SCL_VECTOR_PLUGIN_ENTRY_POINTS(scl_X) below forwards scl_X_<name> to
+// <name> here.  Each is the argument check, the handle's lock with its device made current, and the body
+
+// a call on a handle: its lock held and its device current for the scope
+template <class H> struct Entered {
+    std::lock_guard<std::mutex> lk;
+    explicit Entered(const H *h) : lk(h->mu) { (void)hipSetDevice(h->device); }
+};
+
+// the common half of destroy: the stream drained, the plugin's own device buffers (`own`) and the base's freed, the handle deleted
+template <class H> int close_plugin(H *h, std::initializer_list<void *> own)
+{
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    for (void *p : own)
+        if (p) (void)hipFree(p);
+    for (void *p : {(void *)h->db.d_db, (void *)h->d_best, (void *)h->d_list})
+        if (p) (void)hipFree(p);
+    h->many.release();
+    h->topk.release();
+    if (h->ev0) (void)hipEventDestroy(h->ev0);
+    if (h->ev1) (void)hipEventDestroy(h->ev1);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+    return SCL_OK;
+}
+
+// the common half of create, after the plugin's own config checks: the shared checks, the device, then a new handle with its config,
+// registry, stream, events, d_best and a database of one row.  On an error nothing is left behind
+template <class H, class C> int open_plugin(const C *cfg, H **out)
+{
+    *out = nullptr;
+    if (cfg->robot_num < 1 || cfg->robot_num > 127 || cfg->this_id < 0 || cfg->this_id >= cfg->robot_num || cfg->num_exclude_recent < 0 ||
+        !(cfg->dist_thres == cfg->dist_thres))
+        return SCL_ERR_INVALID_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SCL_ERR_NO_DEVICE;
+    if (cfg->device < 0 || cfg->device >= ndev) return SCL_ERR_INVALID_ARG;
+    H *h = new (std::nothrow) H();
+    if (!h) return SCL_ERR_NOMEM;
+    h->cfg = *cfg; h->device = cfg->device;
+    h->reg.init(cfg->robot_num);
+    int rc = SCL_OK;
+    if (hipSetDevice(h->device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess)
+        rc = SCL_ERR_HIP;
+    else if (!(rc = dev_alloc(h, &h->d_best, 1)))
+        rc = h->db.grow(h, 1);
+    if (rc) { close_plugin(h, {}); return rc; }
+    *out = h;
+    return SCL_OK;
+}
+
+template <class H> const char *last_error(const H *h) { return h ? h->last_error.c_str() : "null handle"; }
+
+template <class H> int make(H *h, const void *points, int n_points, int stride, float *out_values)
+{
+    if (!h || !out_values) return SCL_ERR_INVALID_ARG;
+    Entered<H> in(h);
+    int rc = run_single_locked(h, points, n_points, stride);
+    return rc ? rc : h->db.read(h, h->reg.n, 1, out_values);
+}
+
+template <class H>
+int make_and_save_many(H *h, const void *const *clouds, const int *n_points, int stride, const int8_t *robots, const int *indexs, int count,
+                       float *out_values)
+{
+    if (!h || count < 0 || (count > 0 && (!clouds || !n_points || !robots || !indexs))) return SCL_ERR_INVALID_ARG;
+    Entered<H> in(h);
+    return make_and_save_many_locked(h, clouds, n_points, stride, robots, indexs, count, out_values);
+}
+
+template <class H> int save_from_wire(H *h, const float *values, int8_t robot, int index)
+{
+    if (!h || !values) return SCL_ERR_INVALID_ARG;
+    Entered<H> in(h);
+    int rc;
+    if ((rc = check_robot(h, robot, SCL_ERR_INVALID_ARG)) || (rc = h->db.grow(h, h->reg.n + 1)) || (rc = h->db.write(h, h->reg.n, values))) return rc;
+    h->reg.commit(robot, index);
+    return SCL_OK;
+}
+
+template <class H> int save_from_wire_many(H *h, const float *values, const int8_t *robots, const int *indexs, int count)
+{
+    if (!h || count < 0 || (count > 0 && (!values || !robots || !indexs))) return SCL_ERR_INVALID_ARG;
+    Entered<H> in(h);
+    return save_from_wire_many_locked(h, values, robots, indexs, count);
+}
+
+template <class H> int get_signature(H *h, int key, float *values)
+{
+    if (!h || !values) return SCL_ERR_INVALID_ARG;
+    Entered<H> in(h);
+    if (key < 0 || key >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "key out of range");
+    return h->db.read(h, key, 1, values);
+}
+
+// a single detection's answer by report_many's rule.  *loop_id = -1 and *dist = +inf on entry (nothing searched); the winner of row
+// `q` is row `key` at squared distance d2 and would be reported as `loop`: a NaN d2 -> (-1, that NaN), else the reported distance,
+// and the loop when it is below dist_thres, compared in double
+template <class H> int report_one_locked(H *h, int q, int key, int loop, float d2, int *loop_id, float *dist)
+{
+    if (std::isnan(d2)) { if (dist) *dist = d2; return SCL_OK; }          // every distance NaN: nothing is nearest
+    float d;
+    int rc = h->reported_distance(q, key, d2, &d);
+    if (rc) return rc;
+    if (dist) *dist = d;
+    if ((double)d < h->cfg.dist_thres) *loop_id = loop;
+    return SCL_OK;
+}
+
+template <class H> int detect_intra(H *h, int cur, int *loop_id, float *dist)
+{
+    if (!h || !loop_id) return SCL_ERR_INVALID_ARG;
+    Entered<H> in(h);
+    *loop_id = -1;
+    if (dist) *dist = INFINITY;
+    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
+    if (cur < 0 || cur >= (int)mine.size()) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_intra: no such keyframe of this robot");
+    int pos; float d2;                                            // ascending keys: position = local index
+    int rc = nearest_locked(h, mine[(size_t)cur], mine.data(), cur - h->cfg.num_exclude_recent, &pos, &d2);
+    if (rc || pos < 0) return rc;
+    return report_one_locked(h, mine[(size_t)cur], mine[(size_t)pos], pos, d2, loop_id, dist);
+}
+
+template <class H> int detect_inter(H *h, int cur, int *loop_id, float *dist)
+{
+    if (!h || !loop_id) return SCL_ERR_INVALID_ARG;
+    Entered<H> in(h);
+    *loop_id = -1;
+    if (dist) *dist = INFINITY;
+    if (cur < 0 || cur >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter: key out of range");
+    int pos = -1, rc;
+    float d2;
+    if (h->inter_snapshot()) {                                    // the reference's detection (FPFH: D.h:381-428, GRSD: D.h:116-167)
+        if (h->reg.n < h->cfg.num_exclude_recent + 1) { if (dist) *dist = 0.0f; return SCL_OK; }
+        if (h->tree_counter % h->snapshot_period() == 0) h->snap_n = h->reg.n - h->cfg.num_exclude_recent;
+        h->tree_counter += 1;
+        if ((rc = nearest_locked(h, cur, nullptr, h->snap_n, &pos, &d2)) || pos < 0) return rc;
+    } else {
+        std::vector<int> list = h->reg.inter_candidates(cur, h->cfg.this_id);
+        std::sort(list.begin(), list.end());                      // ties go to the lowest key
+        if ((rc = nearest_locked(h, cur, list.data(), (int)list.size(), &pos, &d2)) || pos < 0) return rc;
+        pos = list[(size_t)pos];
+    }
+    return report_one_locked(h, cur, pos, pos, d2, loop_id, dist);
+}
+
+template <class H> int detect_intra_many(H *h, const int *curs, int count, int *loop_ids, float *dists)
+{
+    if (!h || count < 0 || (count > 0 && (!curs || !loop_ids))) return SCL_ERR_INVALID_ARG;
+    Entered<H> in(h);
+    return detect_intra_many_locked(h, curs, count, loop_ids, dists);
+}
+
+template <class H> int detect_inter_many(H *h, const int *curs, int count, int *loop_ids, float *dists)
+{
+    if (!h || count < 0 || (count > 0 && (!curs || !loop_ids))) return SCL_ERR_INVALID_ARG;
+    Entered<H> in(h);
+    if (h->inter_snapshot()) return detect_inter_snapshot_many_locked(h, curs, count, loop_ids, dists);
+    return detect_inter_lists_many_locked(h, curs, count, loop_ids, dists);
+}
+
+template <class H> int detect_intra_topk(H *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
+{
+    if (!h || count < 0 || (count > 0 && (!curs || !cand_ids))) return SCL_ERR_INVALID_ARG;
+    Entered<H> in(h);
+    return detect_intra_topk_locked(h, curs, count, k, cand_ids, cand_dists, n_found);
+}
+
+template <class H> int detect_inter_topk(H *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
+{
+    if (!h || count < 0 || (count > 0 && (!curs || !cand_ids))) return SCL_ERR_INVALID_ARG;
+    Entered<H> in(h);
+    if (h->inter_snapshot()) return detect_inter_snapshot_topk_locked(h, curs, count, k, cand_ids, cand_dists, n_found);
+    return detect_inter_lists_topk_locked(h, curs, count, k, cand_ids, cand_dists, n_found);
+}
+
+template <class H>
+int make_save_and_detect(H *h, const void *const *clouds, const int *n_points, int stride, const int8_t *robots, const int *indexs, int count,
+                         int *loop_ids, float *dists, float *out_values)
+{
+    if (!h || count < 0 || (count > 0 && (!clouds || !n_points || !robots || !indexs || !loop_ids))) return SCL_ERR_INVALID_ARG;
+    Entered<H> in(h);
+    return make_save_and_detect_locked(h, clouds, n_points, stride, robots, indexs, count, loop_ids, dists, out_values);
+}
+
 }  // namespace
 }  // namespace scl
+
+// The extern "C" definitions of a vector plugin whose handle type and prefix are P, the counterpart of the declarations in scl_P.h
+// and of SCL_PLUGIN_BATCH_API / SCL_PLUGIN_TOPK_API: every one a forward to its template above.  default_config, create, destroy,
+// stats and the test hooks stay in the plugin's own file
+#define SCL_VECTOR_PLUGIN_ENTRY_POINTS(P)                                                                                              \
+    extern "C" {                                                                                                                       \
+    const char *P##_last_error(const P *h) { return scl::last_error(h); }                                                              \
+    int P##_make(P *h, const void *points, int n_points, int stride_bytes, float *out_values)                                          \
+    { return scl::make(h, points, n_points, stride_bytes, out_values); }                                                               \
+    int P##_make_and_save_many(P *h, const void *const *clouds, const int *n_points, int stride_bytes, const int8_t *robots,           \
+                               const int *indexs, int count, float *out_values)                                                        \
+    { return scl::make_and_save_many(h, clouds, n_points, stride_bytes, robots, indexs, count, out_values); }                          \
+    int P##_make_and_save(P *h, const void *points, int n_points, int stride_bytes, int8_t robot, int index, float *out_values)        \
+    { return scl::make_and_save_many(h, &points, &n_points, stride_bytes, &robot, &index, 1, out_values); }                            \
+    int P##_save_from_wire(P *h, const float *values, int8_t robot, int index)                                                         \
+    { return scl::save_from_wire(h, values, robot, index); }                                                                           \
+    int P##_save_from_wire_many(P *h, const float *values, const int8_t *robots, const int *indexs, int count)                         \
+    { return scl::save_from_wire_many(h, values, robots, indexs, count); }                                                             \
+    int P##_get_size(const P *h) { return scl::get_size(h); }                                                                          \
+    int P##_get_size_of(const P *h, int id) { return scl::get_size_of(h, id); }                                                        \
+    int P##_get_index(const P *h, int key, int8_t *robot, int *index) { return scl::get_index(h, key, robot, index); }                 \
+    int P##_local_to_global(const P *h, int robot, int local, int *key) { return scl::local_to_global(h, robot, local, key); }         \
+    int P##_get_signature(P *h, int key, float *values) { return scl::get_signature(h, key, values); }                                 \
+    int P##_detect_intra(P *h, int cur, int *loop_id, float *dist) { return scl::detect_intra(h, cur, loop_id, dist); }                \
+    int P##_detect_inter(P *h, int cur, int *loop_id, float *dist) { return scl::detect_inter(h, cur, loop_id, dist); }                \
+    int P##_detect_intra_many(P *h, const int *curs, int count, int *loop_ids, float *dists)                                           \
+    { return scl::detect_intra_many(h, curs, count, loop_ids, dists); }                                                                \
+    int P##_detect_inter_many(P *h, const int *curs, int count, int *loop_ids, float *dists)                                           \
+    { return scl::detect_inter_many(h, curs, count, loop_ids, dists); }                                                                \
+    int P##_detect_intra_topk(P *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)                 \
+    { return scl::detect_intra_topk(h, curs, count, k, cand_ids, cand_dists, n_found); }                                               \
+    int P##_detect_inter_topk(P *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)                 \
+    { return scl::detect_inter_topk(h, curs, count, k, cand_ids, cand_dists, n_found); }                                               \
+    int P##_make_save_and_detect(P *h, const void *const *clouds, const int *n_points, int stride_bytes, const int8_t *robots,         \
+                                 const int *indexs, int count, int *loop_ids, float *dists, float *out_values)                         \
+    { return scl::make_save_and_detect(h, clouds, n_points, stride_bytes, robots, indexs, count, loop_ids, dists, out_values); }       \
+    }
