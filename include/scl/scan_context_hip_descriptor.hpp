@@ -188,6 +188,31 @@ public:
         return out;
     }
 
+    // Not part of scan_descriptor: one listed keyframe of the ranked search -- database key, ring shift as float (as detectIntraLoopClosureID
+    // returns it) and the fp64 SC distance
+    struct LoopCandidate { int id; float shift; double dist; };
+
+    // the ranked search (scl_engine.h "THE RANKED SEARCH"): per entry of curPtrs the up to k best keyframes of the whole set
+    // [0, curPtr - NUM_EXCLUDE_RECENT) (descriptor.h:1627) by SC distance, ascending, SC_DIST_THRES not applied -- for a verifier that
+    // takes several candidates (scl_loop_icp_batch_from_store).  On an error (k outside [1, SCL_SC_SEARCH_MAX], an entry out of range)
+    // every list is empty
+    std::vector<std::vector<LoopCandidate>> searchLoopClosureIDs(const std::vector<int> &curPtrs, int k)
+    {
+        std::vector<std::vector<LoopCandidate>> out(curPtrs.size());
+        if (k < 1 || k > SCL_SC_SEARCH_MAX) {
+            std::fprintf(stderr, "[scan_context_hip_descriptor] searchLoopClosureIDs: k = %d outside [1, %d]\n", k, SCL_SC_SEARCH_MAX);
+            return out;
+        }
+        std::vector<int> ids(curPtrs.size() * static_cast<size_t>(k), -1), shifts(ids.size(), 0), found(curPtrs.size(), 0);
+        std::vector<double> dists(ids.size(), 1e7);
+        if (!report(scl_sc_search(engine_, curPtrs.data(), static_cast<int>(curPtrs.size()), k, ids.data(), shifts.data(), dists.data(), found.data()),
+                    "searchLoopClosureIDs"))
+            return out;
+        for (size_t i = 0; i < curPtrs.size(); ++i)
+            for (int j = 0; j < found[i]; ++j) out[i].push_back(LoopCandidate{ids[i * k + j], static_cast<float>(shifts[i * k + j]), dists[i * k + j]});
+        return out;
+    }
+
 private:
     void init(int numRing, int numSector, int numCandidates, double distThres, double lidarHeight, double maxRadius,
               int numExcludeRecent, int treeMakingPeriod, double searchRatio, float knnExcludeEps,

@@ -216,6 +216,46 @@ int  scl_sc_distance_batch(scl_engine *e, int query, const int *cand, int n,
  * SCL_MATRIX_PLAIN=1 evaluates every shift of every pair.  Several rows share a launch and a launch's results travel to the
  * host while the next one runs. */
 int  scl_sc_distance_matrix(scl_engine *e, const int *queries, int nq, int lo, int hi, double *dist, int *shift);
+/*
+ * THE RANKED SEARCH.  scl_detect_full* reports the one arg-min of a scan's search set and scl_topk_with_distance ranks by RING KEY
+ * (the reference's pre-selection) before it scores; these two calls score a query against its WHOLE search set with the distance
+ * that decides and return the k best, ranked, for a verifier that takes several candidates (scl_loop_icp_batch_from_store's
+ * keys_pre; BASELINE C3: 25 ICP verifications per query) or for rank statistics.  Shape and conventions are those of
+ * scl_iris_search_* (scl_iris.h) and SCL_PLUGIN_TOPK_API (scl_plugin_batch.h): cand_ids, cand_shifts and cand_dists hold
+ * n_queries * k elements, row i for query i; n_found holds n_queries elements; cand_shifts, cand_dists and n_found may be NULL;
+ * n_queries == 0 is SCL_OK.
+ *   * Search set of query i.  scl_sc_search_range: keyframe queries[i] (or a staged query, -1 - slot, as scl_sc_distance_matrix
+ *     takes it) against the keyframes lo[i] .. hi[i]-1.  scl_sc_search: the set of scl_detect_full, keyframe curs[i] against
+ *     [0, curs[i] - num_exclude_recent) (D.h:1627; empty when that is <= 0).  ids are database slots, which are global keys; the
+ *     query itself is listed like any other keyframe when it lies in its range.
+ *   * Score of a pair: distanceBtnScanContext (D.h:1538-1569) with its arg-min shift -- bit for bit the fp64 value and the shift
+ *     of scl_sc_distance_matrix and scl_sc_distance_batch (the same kernels produce it; the screened grids evaluate the open
+ *     shifts only, as there).
+ *   * The list: the k smallest scores in ascending (distance compared as doubles with <, position in the range) order -- equal
+ *     distances go to the lower keyframe, by value and not by bit pattern (-0.0 ties with 0.0).  A pair is listed only if its
+ *     distance is < 10000000.0, the rule of the engine's arg-min: an empty descriptor scores exactly 10000000.0 and is never listed,
+ *     NaN is never listed.  n_found[i] = min(k, listable pairs); entries j >= n_found[i] are id -1, shift 0, distance 10000000.0,
+ *     the engine's "no winner" values.
+ *   * No threshold, no loop decision: the caller applies dist_thres.  The result does not depend on num_candidates, dist_thres,
+ *     knn_exclude_eps or tree_making_period, and the calls change nothing a later call can see (the periodic tree's counter of
+ *     scl_detect_inter included).
+ *   * k < 1 or k > SCL_SC_SEARCH_MAX or a NULL required pointer: SCL_ERR_INVALID_ARG.  A query out of range (for scl_sc_search
+ *     every cur < 0 too): SCL_ERR_OUT_OF_RANGE; a staged slot that holds nothing: SCL_ERR_INVALID_ARG; a range with lo < 0,
+ *     hi > size or hi < lo: SCL_ERR_OUT_OF_RANGE -- the matrix's rule, not the clipping of scl_detect_full_range.  All of it before
+ *     anything runs: no output written, no state changed.
+ * The rows come from the distance matrix's own launches, queries in call order in groups of 4 (16 on the screened grids); the
+ * selection of a group runs on the device behind its rows, and rows x k records travel to the host instead of 12 bytes per pair.
+ * A group's matrix runs over the union [min lo, max hi) of its queries' ranges and each list is cut from its own range: widely
+ * different ranges in one group cost the union.  The host waits for the device once per call.  On a scl_create_sharded engine
+ * every query runs once per shard over the shard's slots of its range and the shards' lists are merged on the host by (distance,
+ * global key), whatever the exchange: the same lists, bit for bit.
+ */
+#define SCL_SC_SEARCH_MAX 32     /* the longest list; = SCL_PLUGIN_TOPK_MAX, SCL_IRIS_SEARCH_MAX */
+
+int  scl_sc_search_range(scl_engine *e, const int *queries, const int *lo, const int *hi, int n_queries, int k,
+                         int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found);
+int  scl_sc_search(scl_engine *e, const int *curs, int count, int k,
+                   int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found);
 /* BASELINE "full-DB" mode: ring-key top-k AND the shifted SC distance against
  * every eligible slot [0, hi) with hi = cur - num_exclude_recent (D.h:1627), then
  * the global arg-min (ties -> lowest slot).  nn_idx/shift/dist describe the best

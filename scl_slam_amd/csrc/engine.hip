@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
+#include <climits>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -679,6 +680,10 @@ int scl_destroy(scl_engine *e)
     dev_free(e->d_smask);
     if (e->d_mat_dist) (void)hipFree(e->d_mat_dist);
     if (e->d_mat_shift) (void)hipFree(e->d_mat_shift);
+    if (e->d_rank_key) (void)hipFree(e->d_rank_key);
+    if (e->d_rank_pos) (void)hipFree(e->d_rank_pos);
+    if (e->d_rank_out) (void)hipFree(e->d_rank_out);
+    if (e->h_rank_out) (void)hipHostFree(e->h_rank_out);
     if (e->h_mat) (void)hipHostFree(e->h_mat);
     for (auto &ev : e->ev_mat_k) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : e->ev_mat_c) if (ev) (void)hipEventDestroy(ev);
@@ -1018,7 +1023,63 @@ int scl_sc_distance_batch(scl_engine *e, int query, const int *cand, int n, doub
     return sync(e);
 }
 
-namespace { int matrix_screened_locked(scl_engine *e, const int *slots, int nq, int lo, int n, double *dist, int *shift); }
+namespace {
+
+// The group loops of the distance matrix (matrix_plain_locked, matrix_screened_locked) produce the rows group by group into the halves
+// d_mat_dist / d_mat_shift; what happens to a finished group is the consumer's: scl_sc_distance_matrix copies the rows to the host
+// (MatrixToHost), the ranked search selects on the device and copies the lists (RankGroups).
+struct MatrixGroup {
+    int g, h, r0, rows, rb;                  // group, its half, its first row of the call, its rows, rows a half holds
+    size_t cap;                              // entries per row of the halves: row r of the group at (h * rb + r) * cap
+    int lo, n;                               // the group's keyframes [lo, lo + n)
+    hipStream_t ks;                          // the stream the group's exact kernel was enqueued on
+    int set0, sets;                          // the screening's buffer sets the group went through (sets == 0: no screening pass)
+};
+struct MatrixConsumer {
+    virtual int enqueued(const MatrixGroup &m) = 0;   // the group's launches are on m.ks: enqueue what takes its rows out of the half
+    virtual int retire(int g) = 0;                     // the loop is about to move on: group g's half will be written again by group g + 2
+protected:
+    ~MatrixConsumer() = default;
+};
+
+bool matrix_is_screened(const scl_engine *e) { return e->screen && sc_masked_supported(db_view(e), e->SR) && !scl_lab_int("SCL_MATRIX_PLAIN", 0); }
+int matrix_group_rows(const scl_engine *e) { return matrix_is_screened(e) ? sc_screen_max_batch(db_view(e), e->SR) : kMaxQueryBatch; }
+int matrix_screened_locked(scl_engine *e, const int *slots, int nq, const int *grp_lo, const int *grp_n, MatrixConsumer &out);
+int matrix_plain_locked(scl_engine *e, const int *slots, int nq, const int *grp_lo, const int *grp_n, MatrixConsumer &out);
+
+// scl_sc_distance_matrix's consumer: a group's rows travel to the pinned halves on the second stream and from there to the caller
+struct MatrixToHost final : MatrixConsumer {
+    scl_engine *e; int nq, n, per_group; double *dist; int *shift;
+    int rb = 0; size_t cap = 0;
+    MatrixToHost(scl_engine *e_, int nq_, int n_, int per_group_, double *dist_, int *shift_) : e(e_), nq(nq_), n(n_), per_group(per_group_), dist(dist_), shift(shift_) {}
+    int enqueued(const MatrixGroup &m) override
+    {
+        rb = m.rb; cap = m.cap;
+        double *h_dist = static_cast<double *>(e->h_mat);
+        int *h_shift = reinterpret_cast<int *>(h_dist + (size_t)2 * rb * cap);
+        const int h = m.h, rows = m.rows;
+        SCL_HIP(e, hipEventRecord(e->ev_mat_k[h], m.ks));
+        SCL_HIP(e, hipStreamWaitEvent(e->stream2, e->ev_mat_k[h], 0));
+        SCL_HIP(e, hipMemcpyAsync(h_dist + (size_t)h * rb * cap, e->d_mat_dist + (size_t)h * rb * cap, sizeof(double) * (size_t)rows * cap, hipMemcpyDeviceToHost, e->stream2));
+        SCL_HIP(e, hipMemcpyAsync(h_shift + (size_t)h * rb * cap, e->d_mat_shift + (size_t)h * rb * cap, sizeof(int) * (size_t)rows * cap, hipMemcpyDeviceToHost, e->stream2));
+        SCL_HIP(e, hipEventRecord(e->ev_mat_c[h], e->stream2));
+        return SCL_OK;
+    }
+    int retire(int g) override                                             // group g's rows: pinned half -> the caller's arrays
+    {
+        const int h = g & 1, r0 = g * per_group, rows = nq - r0 < per_group ? nq - r0 : per_group;
+        const double *h_dist = static_cast<const double *>(e->h_mat);
+        const int *h_shift = reinterpret_cast<const int *>(h_dist + (size_t)2 * rb * cap);
+        SCL_HIP(e, hipEventSynchronize(e->ev_mat_c[h]));
+        for (int r = 0; r < rows; ++r) {
+            std::memcpy(dist + (size_t)(r0 + r) * n, h_dist + ((size_t)h * rb + r) * cap, sizeof(double) * (size_t)n);
+            std::memcpy(shift + (size_t)(r0 + r) * n, h_shift + ((size_t)h * rb + r) * cap, sizeof(int) * (size_t)n);
+        }
+        return SCL_OK;
+    }
+};
+
+}  // namespace
 
 /* The exact distance matrix (north_star: "the column-shifted SC distance matrix over the keyframe database"): rows = queries,
  * columns = keyframes lo .. hi-1, every entry the reference's distanceBtnScanContext (D.h:1538-1569) in fp64 with its shift.
@@ -1042,10 +1103,25 @@ int scl_sc_distance_matrix(scl_engine *e, const int *queries, int nq, int lo, in
         if (q < 0 && !e->staged[-1 - q]) return fail(e, SCL_ERR_INVALID_ARG, "no staged query in that slot");
         slots[(size_t)i] = q >= 0 ? q : e->cap + (-1 - q);
     }
-    // the screened grids: alignment + screening of 16 rows at a time, then the exact evaluation of the shifts still open (sc_masked.hip)
-    if (e->screen && sc_masked_supported(db_view(e), e->SR) && !scl_lab_int("SCL_MATRIX_PLAIN", 0)) return matrix_screened_locked(e, slots.data(), nq, lo, n, dist, shift);
+    // (the screened grids: alignment + screening of 16 rows at a time, then the exact evaluation of the shifts still open, sc_masked.hip)
+    const int per_group = matrix_group_rows(e), groups = (nq + per_group - 1) / per_group;
+    const std::vector<int> grp_lo((size_t)groups, lo), grp_n((size_t)groups, n);
+    MatrixToHost out(e, nq, n, per_group, dist, shift);
+    if (matrix_is_screened(e)) return matrix_screened_locked(e, slots.data(), nq, grp_lo.data(), grp_n.data(), out);
+    return matrix_plain_locked(e, slots.data(), nq, grp_lo.data(), grp_n.data(), out);
+}
+
+namespace {
+
+// The matrix on the grids without a screening pass: kMaxQueryBatch rows per launch of the wave program, group g into half g & 1.
+// Group g covers the keyframes [grp_lo[g], grp_lo[g] + grp_n[g]) (a group of no keyframes launches nothing).
+int matrix_plain_locked(scl_engine *e, const int *slots, int nq, const int *grp_lo, const int *grp_n, MatrixConsumer &out)
+{
     constexpr int RB = kMaxQueryBatch;                                     // rows per launch
-    const size_t row = ((size_t)n + 63) & ~(size_t)63;
+    const int groups = (nq + RB - 1) / RB;
+    int max_n = 0;
+    for (int g = 0; g < groups; ++g) max_n = grp_n[g] > max_n ? grp_n[g] : max_n;
+    const size_t row = ((size_t)max_n + 63) & ~(size_t)63;
     if (e->mat_cap < row) {
         if (e->d_mat_dist) (void)hipFree(e->d_mat_dist);
         if (e->d_mat_shift) (void)hipFree(e->d_mat_shift);
@@ -1062,38 +1138,153 @@ int scl_sc_distance_matrix(scl_engine *e, const int *queries, int nq, int lo, in
         }
     }
     const size_t cap = e->mat_cap;
-    double *h_dist = static_cast<double *>(e->h_mat);
-    int *h_shift = reinterpret_cast<int *>(h_dist + 2 * RB * cap);
-    const int groups = (nq + RB - 1) / RB;
-    auto deliver = [&](int g) -> int {                                     // group g's rows: pinned half -> the caller's arrays
-        const int h = g & 1, r0 = g * RB, rows = nq - r0 < RB ? nq - r0 : RB;
-        SCL_HIP(e, hipEventSynchronize(e->ev_mat_c[h]));
-        for (int r = 0; r < rows; ++r) {
-            std::memcpy(dist + (size_t)(r0 + r) * n, h_dist + ((size_t)h * RB + r) * cap, sizeof(double) * (size_t)n);
-            std::memcpy(shift + (size_t)(r0 + r) * n, h_shift + ((size_t)h * RB + r) * cap, sizeof(int) * (size_t)n);
-        }
-        return SCL_OK;
-    };
     int rc = SCL_OK;
     for (int g = 0; g < groups; ++g) {
         const int h = g & 1, r0 = g * RB, rows = nq - r0 < RB ? nq - r0 : RB;
-        if (g >= 2 && (rc = deliver(g - 2))) return rc;                    // (also: half h of the device buffers has been copied out)
-        {
+        const int lo = grp_lo[g], n = grp_n[g];
+        if (g >= 2 && (rc = out.retire(g - 2))) return rc;                 // (also: half h of the device buffers has been copied out)
+        if (n > 0) {
             ProfScope ps(e, P_SC);
-            SCL_HIP(e, launch_sc_distance_matrix(db_view(e), slots.data() + r0, rows, lo, n, e->SR, e->d_mat_dist + (size_t)h * RB * cap,
+            SCL_HIP(e, launch_sc_distance_matrix(db_view(e), slots + r0, rows, lo, n, e->SR, e->d_mat_dist + (size_t)h * RB * cap,
                                                  e->d_mat_shift + (size_t)h * RB * cap, cap, e->num_cu, e->stream));
             if (ps.active()) e->prof.sc_distance_pairs += (uint64_t)rows * (uint64_t)n;
         }
-        SCL_HIP(e, hipEventRecord(e->ev_mat_k[h], e->stream));
-        SCL_HIP(e, hipStreamWaitEvent(e->stream2, e->ev_mat_k[h], 0));
-        SCL_HIP(e, hipMemcpyAsync(h_dist + (size_t)h * RB * cap, e->d_mat_dist + (size_t)h * RB * cap, sizeof(double) * (size_t)rows * cap, hipMemcpyDeviceToHost, e->stream2));
-        SCL_HIP(e, hipMemcpyAsync(h_shift + (size_t)h * RB * cap, e->d_mat_shift + (size_t)h * RB * cap, sizeof(int) * (size_t)rows * cap, hipMemcpyDeviceToHost, e->stream2));
-        SCL_HIP(e, hipEventRecord(e->ev_mat_c[h], e->stream2));
+        if ((rc = out.enqueued({g, h, r0, rows, RB, cap, lo, n, e->stream, 0, 0}))) return rc;
     }
     for (int g = groups >= 2 ? groups - 2 : 0; g < groups; ++g)
-        if ((rc = deliver(g))) return rc;
+        if ((rc = out.retire(g))) return rc;
     if (e->prof_on) collect_profile(e);
     return SCL_OK;
+}
+
+}  // namespace
+
+namespace {
+
+// The ranked search's consumer: behind a group's exact kernel, on the SAME stream, the selection (sc_rank.hip) and the copy of the
+// group's rows x k records to pinned memory.  The next group that writes this half (g + 2) runs on that stream too -- both groups of a
+// half share a lane on 80 x 180 --, so a half is never written before its ranking has read it, and the host waits for nothing here.
+struct RankGroups final : MatrixConsumer {
+    scl_engine *e; int k; const int *qlo, *qhi; size_t part_half; bool used_alt = false;
+    RankGroups(scl_engine *e_, int k_, const int *qlo_, const int *qhi_, size_t part_half_) : e(e_), k(k_), qlo(qlo_), qhi(qhi_), part_half(part_half_) {}
+    int enqueued(const MatrixGroup &m) override
+    {
+        ScRankArgs a{};
+        a.dist = e->d_mat_dist + (size_t)m.h * m.rb * m.cap; a.shift = e->d_mat_shift + (size_t)m.h * m.rb * m.cap; a.row_stride = m.cap;
+        a.rows = m.rows; a.n = m.n; a.base = m.lo; a.k = k;
+        for (int r = 0; r < m.rows; ++r) {                                  // the row covers the group's union; the list its own range
+            const int l = qlo[m.r0 + r], h = qhi[m.r0 + r];
+            a.plo[r] = h > l ? l - m.lo : 0; a.phi[r] = h > l ? h - m.lo : 0;
+        }
+        a.part_key = e->d_rank_key + (size_t)m.h * part_half; a.part_pos = e->d_rank_pos + (size_t)m.h * part_half;
+        ScRankRecord *d_out = static_cast<ScRankRecord *>(e->d_rank_out) + (size_t)m.r0 * k;
+        a.out = d_out;
+        SCL_HIP(e, launch_sc_rank(a, m.ks));
+        if (m.sets > 0) {
+            // The group's screening launches left the smallest screened distance of every row in its buffer set's t_min word (and the
+            // launch's largest bound behind it), which only the exact pass of a full-database detection re-arms -- the matrix's kernels
+            // do not read them.  Left as they are, a later scl_detect_full* through these sets would select its survivors against
+            // another scan's minimum; a search leaves no trace, so the words go back to their initial state here.
+            SCL_HIP(e, hipMemsetAsync(e->d_tmin + m.set0, 0xff, sizeof(unsigned int) * (size_t)m.sets, m.ks));
+            SCL_HIP(e, hipMemsetAsync(e->d_tmin + kTminEpsOffset + m.set0, 0, sizeof(unsigned int) * (size_t)m.sets, m.ks));
+        }
+        SCL_HIP(e, hipMemcpyAsync(static_cast<ScRankRecord *>(e->h_rank_out) + (size_t)m.r0 * k, d_out, sizeof(ScRankRecord) * (size_t)m.rows * k, hipMemcpyDeviceToHost, m.ks));
+        used_alt |= m.ks == e->stream_alt;
+        return SCL_OK;
+    }
+    int retire(int) override { return SCL_OK; }
+};
+
+// scl_sc_search_range behind the locks; everything is validated before anything is sized or launched
+int sc_search_locked(scl_engine *e, const int *queries, const int *lo, const int *hi, int nq, int k,
+                     int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found)
+{
+    std::vector<int> slots((size_t)nq);
+    for (int i = 0; i < nq; ++i) {
+        const int q = queries[i];
+        if (q >= e->n || q < -e->stage_rows) return fail(e, SCL_ERR_OUT_OF_RANGE, "query keyframe out of range");
+        if (q < 0 && !e->staged[-1 - q]) return fail(e, SCL_ERR_INVALID_ARG, "no staged query in that slot");
+        if (lo[i] < 0 || hi[i] > e->n || hi[i] < lo[i]) return fail(e, SCL_ERR_OUT_OF_RANGE, "keyframe range out of the database");
+        slots[(size_t)i] = q >= 0 ? q : e->cap + (-1 - q);
+    }
+    // a group's matrix runs over the union of its queries' ranges
+    const int per_group = matrix_group_rows(e), groups = (nq + per_group - 1) / per_group;
+    std::vector<int> grp_lo((size_t)groups, 0), grp_n((size_t)groups, 0);
+    int max_n = 0;
+    for (int g = 0; g < groups; ++g) {
+        int l = INT_MAX, h = 0;
+        for (int i = g * per_group; i < nq && i < (g + 1) * per_group; ++i)
+            if (hi[i] > lo[i]) { l = lo[i] < l ? lo[i] : l; h = hi[i] > h ? hi[i] : h; }
+        if (h > l) { grp_lo[(size_t)g] = l; grp_n[(size_t)g] = h - l; }
+        max_n = grp_n[(size_t)g] > max_n ? grp_n[(size_t)g] : max_n;
+    }
+    // work buffers: the tiles' lists of two groups in flight, grown like the matrix halves; the call's records and their pinned copy
+    const size_t part_half = sc_rank_part_entries(per_group, max_n, k);
+    if (e->rank_part_cap < part_half) {
+        dev_free(e->d_rank_key); dev_free(e->d_rank_pos); e->rank_part_cap = 0;
+        if (hipMalloc((void **)&e->d_rank_key, sizeof(unsigned long long) * 2 * part_half) != hipSuccess ||
+            hipMalloc((void **)&e->d_rank_pos, sizeof(unsigned int) * 2 * part_half) != hipSuccess)
+            return fail(e, SCL_ERR_NOMEM, "ranked search: work buffers");
+        e->rank_part_cap = part_half;
+    }
+    const size_t recs = (size_t)nq * (size_t)k;
+    if (e->rank_out_cap < recs) {
+        if (e->d_rank_out) (void)hipFree(e->d_rank_out);
+        if (e->h_rank_out) (void)hipHostFree(e->h_rank_out);
+        e->d_rank_out = nullptr; e->h_rank_out = nullptr; e->rank_out_cap = 0;
+        if (hipMalloc(&e->d_rank_out, sizeof(ScRankRecord) * recs) != hipSuccess ||
+            hipHostMalloc(&e->h_rank_out, sizeof(ScRankRecord) * recs, hipHostMallocDefault) != hipSuccess)
+            return fail(e, SCL_ERR_NOMEM, "ranked search: result buffers");
+        e->rank_out_cap = recs;
+    }
+    RankGroups out(e, k, lo, hi, part_half);
+    int rc = matrix_is_screened(e) ? matrix_screened_locked(e, slots.data(), nq, grp_lo.data(), grp_n.data(), out)
+                                   : matrix_plain_locked(e, slots.data(), nq, grp_lo.data(), grp_n.data(), out);
+    if (rc) return rc;
+    if (out.used_alt) SCL_HIP(e, hipStreamSynchronize(e->stream_alt));     // the one wait of the call (one per lane)
+    if ((rc = sync(e))) return rc;
+    const ScRankRecord *h = static_cast<const ScRankRecord *>(e->h_rank_out);
+    for (int i = 0; i < nq; ++i) {
+        int found = 0;
+        for (int j = 0; j < k; ++j) {
+            const ScRankRecord &r = h[(size_t)i * k + j];
+            cand_ids[(size_t)i * k + j] = r.id;
+            if (cand_shifts) cand_shifts[(size_t)i * k + j] = r.shift;
+            if (cand_dists) cand_dists[(size_t)i * k + j] = r.dist;
+            found += r.id >= 0;
+        }
+        if (n_found) n_found[i] = found;
+    }
+    return SCL_OK;
+}
+
+}  // namespace
+
+/* The ranked search: the distance matrix's rows, group by group, with the selection of the k best behind each group on the device
+ * (sc_rank.hip); include/scl_engine.h, THE RANKED SEARCH, has the contract. */
+int scl_sc_search_range(scl_engine *e, const int *queries, const int *lo, const int *hi, int n_queries, int k,
+                        int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found)
+{
+    if (!e || n_queries < 0 || k < 1 || k > SCL_SC_SEARCH_MAX || (n_queries > 0 && (!queries || !lo || !hi || !cand_ids))) return SCL_ERR_INVALID_ARG;
+    if (n_queries == 0) return SCL_OK;
+    if (e->front) return front_sc_search_range(e, queries, lo, hi, n_queries, k, cand_ids, cand_shifts, cand_dists, n_found);
+    std::lock_guard<std::mutex> pk(e->pass_mu);
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    return sc_search_locked(e, queries, lo, hi, n_queries, k, cand_ids, cand_shifts, cand_dists, n_found);
+}
+
+int scl_sc_search(scl_engine *e, const int *curs, int count, int k, int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found)
+{
+    if (!e || count < 0 || k < 1 || k > SCL_SC_SEARCH_MAX || (count > 0 && (!curs || !cand_ids))) return SCL_ERR_INVALID_ARG;
+    if (count == 0) return SCL_OK;
+    std::vector<int> lo((size_t)count, 0), hi((size_t)count, 0);
+    for (int i = 0; i < count; ++i) {
+        if (curs[i] < 0) return SCL_ERR_OUT_OF_RANGE;                      // (a staged query has no place in the database: scl_sc_search_range)
+        const int h = curs[i] - e->cfg.num_exclude_recent;                 /* D.h:1627 */
+        hi[(size_t)i] = h > 0 ? h : 0;
+    }
+    return scl_sc_search_range(e, curs, lo.data(), hi.data(), count, k, cand_ids, cand_shifts, cand_dists, n_found);
 }
 
 namespace {
@@ -1246,12 +1437,15 @@ static int matrix_kr()
 // products and finishing -- which leaves, per pair, the first shift and the mask of the shifts within 2 eps of the pair's smallest
 // screened distance -- then sc_masked_kernel evaluates exactly those shifts in fp64.  Every entry is the reference's distance and
 // shift, bit for bit; the results of a group travel to the host while the next group runs.
-int matrix_screened_locked(scl_engine *e, const int *slots, int nq, int lo, int n, double *dist, int *shift)
+int matrix_screened_locked(scl_engine *e, const int *slots, int nq, const int *grp_lo, const int *grp_n, MatrixConsumer &out)
 {
     const int mb = sc_screen_max_batch(db_view(e), e->SR);
     const bool wide = sc_screen_is_wide(db_view(e), e->SR);
     const int v2_min = wide ? 2 : 4;                                        // smaller batches take the first form, which leaves no masks: padded
-    int rc = ensure_sets(e, (size_t)n);
+    const int groups = (nq + mb - 1) / mb;
+    int max_n = 0;
+    for (int g = 0; g < groups; ++g) max_n = grp_n[g] > max_n ? grp_n[g] : max_n;
+    int rc = ensure_sets(e, (size_t)max_n);
     if (rc) return rc;
     const size_t need = e->set_stride * scl_engine::kScreenSets;
     if (e->smask_cap < need) {
@@ -1259,7 +1453,7 @@ int matrix_screened_locked(scl_engine *e, const int *slots, int nq, int lo, int 
         if ((rc = dev_alloc(e, &e->d_smask, need))) return rc;
         e->smask_cap = need;
     }
-    const size_t row = ((size_t)n + 63) & ~(size_t)63;
+    const size_t row = ((size_t)max_n + 63) & ~(size_t)63;
     const int RB = kMaxScreenBatch;
     if (e->mat_cap < row * (size_t)(RB / kMaxQueryBatch)) {                  // (the plain form sizes the halves for kMaxQueryBatch rows)
         if (e->d_mat_dist) (void)hipFree(e->d_mat_dist);
@@ -1278,18 +1472,6 @@ int matrix_screened_locked(scl_engine *e, const int *slots, int nq, int lo, int 
         }
     }
     const size_t cap = row;
-    double *h_dist = static_cast<double *>(e->h_mat);
-    int *h_shift = reinterpret_cast<int *>(h_dist + (size_t)2 * RB * cap);
-    const int groups = (nq + mb - 1) / mb;
-    auto deliver = [&](int g) -> int {
-        const int h = g & 1, r0 = g * mb, rows = nq - r0 < mb ? nq - r0 : mb;
-        SCL_HIP(e, hipEventSynchronize(e->ev_mat_c[h]));
-        for (int r = 0; r < rows; ++r) {
-            std::memcpy(dist + (size_t)(r0 + r) * n, h_dist + ((size_t)h * RB + r) * cap, sizeof(double) * (size_t)n);
-            std::memcpy(shift + (size_t)(r0 + r) * n, h_shift + ((size_t)h * RB + r) * cap, sizeof(int) * (size_t)n);
-        }
-        return SCL_OK;
-    };
     // Consecutive groups alternate between the engine's stream and its second lane (buffer sets, partial sums and output halves of their
     // own) on the 80 x 180 grid: a group is alignment, products and finishing -- launches that each ramp up and drain -- in front of the exact
     // kernel, and on one stream the chip went through them with nothing beside them; now they run under the group before's exact kernel:
@@ -1297,9 +1479,10 @@ int matrix_screened_locked(scl_engine *e, const int *slots, int nq, int lo, int 
     // lives off its keyframes staying in the XCDs' L2s (sc_matrix.hip), which a products launch beside it streams the database through.
     for (int g = 0; g < groups; ++g) {
         const int h = g & 1, r0 = g * mb, rows = nq - r0 < mb ? nq - r0 : mb;
+        const int lo = grp_lo[g], n = grp_n[g];
         const int lane = (groups > 1 && wide) ? h : 0, set0 = lane * mb;   // (64 x 120: one lane -- see above)
         hipStream_t ks = lane ? e->stream_alt : e->stream;
-        if (lane && e->alt_seen_version != e->db_version) {                  // descriptors written on `stream` since the last pass on the second lane
+        if (n > 0 && lane && e->alt_seen_version != e->db_version) {                  // descriptors written on `stream` since the last pass on the second lane
             SCL_HIP(e, hipEventRecord(e->ev_db, e->stream));
             SCL_HIP(e, hipStreamWaitEvent(e->stream_alt, e->ev_db, 0));
             e->alt_seen_version = e->db_version;
@@ -1307,7 +1490,7 @@ int matrix_screened_locked(scl_engine *e, const int *slots, int nq, int lo, int 
         int qs[kMaxScreenBatch], los[kMaxScreenBatch], ns[kMaxScreenBatch];
         const int padded = rows < v2_min ? v2_min : rows;                   // (the padding rows repeat the last one; their results are dropped)
         for (int j = 0; j < padded; ++j) { qs[j] = slots[r0 + (j < rows ? j : rows - 1)]; los[j] = lo; ns[j] = n; }
-        {
+        if (n > 0) {
             ProfScope ps(e, P_SC, ks);
             ScreenGroup grp{qs, los, ns, padded, set0};
             grp.masks = true; grp.part_half = lane;
@@ -1334,16 +1517,12 @@ int matrix_screened_locked(scl_engine *e, const int *slots, int nq, int lo, int 
             }
             if (ps.active()) e->prof.sc_distance_pairs += (uint64_t)rows * (uint64_t)n;
         }
-        SCL_HIP(e, hipEventRecord(e->ev_mat_k[h], ks));
-        SCL_HIP(e, hipStreamWaitEvent(e->stream2, e->ev_mat_k[h], 0));
-        SCL_HIP(e, hipMemcpyAsync(h_dist + (size_t)h * RB * cap, e->d_mat_dist + (size_t)h * RB * cap, sizeof(double) * (size_t)rows * cap, hipMemcpyDeviceToHost, e->stream2));
-        SCL_HIP(e, hipMemcpyAsync(h_shift + (size_t)h * RB * cap, e->d_mat_shift + (size_t)h * RB * cap, sizeof(int) * (size_t)rows * cap, hipMemcpyDeviceToHost, e->stream2));
-        SCL_HIP(e, hipEventRecord(e->ev_mat_c[h], e->stream2));
+        if ((rc = out.enqueued({g, h, r0, rows, RB, cap, lo, n, ks, set0, n > 0 ? padded : 0}))) return rc;
         // group g is enqueued: hand over group g - 1 now (its copy ends while g runs; the half it leaves is g + 1's) -- only the last
         // group's copy and hand-over are left behind the last kernel
-        if (g >= 1 && (rc = deliver(g - 1))) return rc;
+        if (g >= 1 && (rc = out.retire(g - 1))) return rc;
     }
-    if ((rc = deliver(groups - 1))) return rc;
+    if ((rc = out.retire(groups - 1))) return rc;
     if (e->prof_on) collect_profile(e);
     return SCL_OK;
 }

@@ -136,6 +136,10 @@ struct scl_engine {
     // scl_sc_distance_matrix: two halves of (rows of a launch) x (row length) device results and their pinned copies
     double *d_mat_dist = nullptr; int *d_mat_shift = nullptr; void *h_mat = nullptr; size_t mat_cap = 0;
     hipEvent_t ev_mat_k[2] = {nullptr, nullptr}, ev_mat_c[2] = {nullptr, nullptr};
+    // scl_sc_search: the tiles' lists of the ranking (sc_rank.hip), two halves of rank_part_cap entries like the matrix halves, and the
+    // records of a call (queries x k) on the device with their pinned copy
+    unsigned long long *d_rank_key = nullptr; unsigned int *d_rank_pos = nullptr; size_t rank_part_cap = 0;
+    void *d_rank_out = nullptr; void *h_rank_out = nullptr; size_t rank_out_cap = 0;
 
     // inter-robot tree bookkeeping (descriptor.h:1691-1703, counter initialised: see DESIGN.md)
     int tree_counter = 0, tree_n = 0;
@@ -217,6 +221,8 @@ int front_profile_enable(scl_engine *e, int on);
 int front_profile_reset(scl_engine *e);
 int front_profile_get(scl_engine *e, scl_profile *out);
 int front_sc_distance_matrix(scl_engine *e, const int *queries, int nq, int lo, int hi, double *dist, int *shift);
+int front_sc_search_range(scl_engine *e, const int *queries, const int *lo, const int *hi, int n_queries, int k,
+                          int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found);
 int front_alignment_stats(scl_engine *e, uint64_t *pairs, uint64_t *fallbacks, int reset);
 int front_survivor_stats(scl_engine *e, uint64_t *queries, uint64_t *survivors, uint64_t *max_survivors, int reset);
 scl_engine *front_primary(const scl_engine *e);            // the shard that runs unsharded work (geometry, keyframe store)

@@ -144,6 +144,22 @@ struct MaskedArgs { const float4 *desc; const double *norm; int nq, parts, sprea
 bool sc_matrix_supported(const struct DbView &db, int SR);
 hipError_t launch_sc_matrix(const struct DbView &db, int SR, const int *qslots, int nq, int lo, int n, const int *starts, const unsigned int *smask,
                             size_t set_stride, double *out_dist, int *out_shift, size_t row_stride, int kr, hipStream_t stream);
+// ---- the ranked search (sc_rank.hip): the k <= kScRankMaxK smallest listable entries (distance < kBigDist) of each of rows <= 16 finished
+// rows of the distance matrix -- row r at r * row_stride, n entries, entry p = keyframe base + p --, among the positions [plo[r], phi[r])
+// of the row, ascending by (distance as a double, position); record j of row r at out[r * k + j], {kBigDist, -1, 0} behind the listed
+// ones.  part_key / part_pos: sc_rank_part_entries(rows, n, k) entries of scratch.  Two launches (tiles, merge) on `stream`; n == 0:
+// the merge alone, which writes the empty lists.
+constexpr int kScRankMaxK = 32;
+struct ScRankRecord { double dist; int id; int shift; };
+struct ScRankArgs {
+    const double *dist; const int *shift; unsigned long long row_stride;
+    int rows, n, base, k, tiles;                                              // (tiles: filled by the launcher)
+    int plo[16], phi[16];
+    unsigned long long *part_key; unsigned int *part_pos;
+    ScRankRecord *out;
+};
+size_t sc_rank_part_entries(int rows, int n, int k);
+hipError_t launch_sc_rank(const ScRankArgs &args, hipStream_t stream);
 // ---- the exact pass of a small batch of screened scans (sc_masked.hip: sc_small_exact_kernel) -- one workgroup per scan lists the
 // keyframes within the margin of the smallest screened distance, scores them at their open shifts, forms the ring-key top-k and writes
 // the winner {distance, position in the range or -1, shift} to out3 (pinned).  list: scratch of n ints; t_min is re-armed.

@@ -627,6 +627,54 @@ int front_sc_distance_matrix(scl_engine *e, const int *queries, int nq, int lo, 
     return SCL_OK;
 }
 
+// The ranked search on a sharded database: per query one scl_sc_search_range per shard over the shard's slots of the global range
+// (keyframe g = slot g / G of shard g mod G, so position order within a shard is global-key order), the slots translated to global
+// keys and the G lists merged on the host by (distance, global key): the list one database gives, bit for bit.  No collective.
+int front_sc_search_range(scl_engine *e, const int *queries, const int *lo, const int *hi, int n_queries, int k,
+                          int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found)
+{
+    std::lock_guard<std::mutex> lk(e->mu);
+    ShardedFront *f = e->front;
+    for (int i = 0; i < n_queries; ++i) {                                  // everything is checked before anything runs
+        if (queries[i] >= f->n || queries[i] < SCL_QUERY_STAGED) return fail(e, SCL_ERR_OUT_OF_RANGE, "query keyframe out of range");
+        if (queries[i] == SCL_QUERY_STAGED && !f->staged0) return fail(e, SCL_ERR_INVALID_ARG, "no staged query (call scl_stage_query first)");
+        if (lo[i] < 0 || hi[i] > f->n || hi[i] < lo[i]) return fail(e, SCL_ERR_OUT_OF_RANGE, "keyframe range out of the database");
+    }
+    struct Rec { double dist; int g; int shift; };
+    std::vector<Rec> all;
+    std::vector<int> ids((size_t)k), shifts((size_t)k); std::vector<double> dists((size_t)k);
+    std::vector<int> out_ids((size_t)n_queries * k, -1), out_shifts((size_t)n_queries * k, 0); std::vector<double> out_dists((size_t)n_queries * k, kBigDist);
+    for (int i = 0; i < n_queries; ++i) {
+        int qid[kMaxShards];
+        int rc = place_query(e, queries[i], 1 + kFrontSlots, qid);         // the staging slot of blocking calls
+        if (rc) return rc;
+        all.clear();
+        for (int c = 0; c < f->G; ++c) {
+            const int l = local_count(lo[i], c, f->G), h = local_count(hi[i], c, f->G);
+            int found = 0;
+            rc = scl_sc_search_range(f->sh[c], &qid[c], &l, &h, 1, k, ids.data(), shifts.data(), dists.data(), &found);
+            if (rc) return child_fail(e, f->sh[c], rc, "ranked search on shard");
+            for (int j = 0; j < found; ++j) all.push_back({dists[(size_t)j], ids[(size_t)j] * f->G + c, shifts[(size_t)j]});
+        }
+        std::sort(all.begin(), all.end(), [](const Rec &a, const Rec &b) { return a.dist < b.dist || (a.dist == b.dist && a.g < b.g); });
+        for (size_t j = 0; j < all.size() && j < (size_t)k; ++j) {
+            out_ids[(size_t)i * k + j] = all[j].g; out_shifts[(size_t)i * k + j] = all[j].shift; out_dists[(size_t)i * k + j] = all[j].dist;
+        }
+    }
+    for (int i = 0; i < n_queries; ++i) {                                  // the outputs are written once every shard has answered
+        int found = 0;
+        for (int j = 0; j < k; ++j) {
+            const size_t o = (size_t)i * k + j;
+            cand_ids[o] = out_ids[o];
+            if (cand_shifts) cand_shifts[o] = out_shifts[o];
+            if (cand_dists) cand_dists[o] = out_dists[o];
+            found += out_ids[o] >= 0;
+        }
+        if (n_found) n_found[i] = found;
+    }
+    return SCL_OK;
+}
+
 // ---- full-DB detection --------------------------------------------------------------------------------------------------
 
 namespace {

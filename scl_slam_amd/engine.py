@@ -94,6 +94,8 @@ def _bind(lib):
         "scl_ringkey_topk": (c_int, [P, c_int, c_int, c_int, c_int, ip, fp, ip]),
         "scl_sc_distance_batch": (c_int, [P, c_int, ip, c_int, dp, ip]),
         "scl_sc_distance_matrix": (c_int, [P, ip, c_int, c_int, c_int, dp, ip]),
+        "scl_sc_search_range": (c_int, [P, ip, ip, ip, c_int, c_int, ip, ip, dp, ip]),
+        "scl_sc_search": (c_int, [P, ip, c_int, c_int, ip, ip, dp, ip]),
         "scl_detect_full": (c_int, [P, c_int, ip, ip, ip, dp]),
         "scl_detect_full_range": (c_int, [P, c_int, c_int, c_int, ip, ip, dp]),
         "scl_get_last_topk": (c_int, [P, c_int, ip, fp]),
@@ -482,6 +484,35 @@ class ScanContextEngine:
         self._check(self._lib.scl_sc_distance_matrix(self._h, _ptr(q, c_int), q.size, int(lo), int(hi), _ptr(dist, c_double), _ptr(shift, c_int)),
                     "scl_sc_distance_matrix")
         return dist, shift
+
+    @staticmethod
+    def _search_out(n, k, out):
+        if out is not None:
+            return out
+        return (np.empty((n, k), dtype=np.int32), np.empty((n, k), dtype=np.int32), np.empty((n, k), dtype=np.float64),
+                np.empty(n, dtype=np.int32))
+
+    def sc_search_range(self, queries, lo, hi, k, out=None):
+        """the ranked search (scl_engine.h, THE RANKED SEARCH): query i = keyframe queries[i] (or a staged query, -1 - slot) against the
+        keyframes lo[i] .. hi[i]-1, the k best by SC distance: (ids int32 [n,k], shifts int32 [n,k], dists float64 [n,k], n_found
+        int32 [n]); entries behind n_found are (-1, 0, 1e7).  lo / hi: one value for all queries or one per query.  out: four
+        C-contiguous arrays of those shapes to write into instead of new ones (an error leaves them as they are)."""
+        q = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1)
+        n = q.size
+        lo_ = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.int32), (n,)))
+        hi_ = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.int32), (n,)))
+        ids, shifts, dists, found = self._search_out(n, max(int(k), 0), out)
+        self._check(self._lib.scl_sc_search_range(self._h, _ptr(q, c_int), _ptr(lo_, c_int), _ptr(hi_, c_int), n, int(k), _ptr(ids, c_int),
+                                                  _ptr(shifts, c_int), _ptr(dists, c_double), _ptr(found, c_int)), "scl_sc_search_range")
+        return ids, shifts, dists, found
+
+    def sc_search(self, curs, k, out=None):
+        """... over the search set of detect_full: query i = keyframe curs[i] against [0, curs[i] - num_exclude_recent)"""
+        q = np.ascontiguousarray(curs, dtype=np.int32).reshape(-1)
+        ids, shifts, dists, found = self._search_out(q.size, max(int(k), 0), out)
+        self._check(self._lib.scl_sc_search(self._h, _ptr(q, c_int), q.size, int(k), _ptr(ids, c_int), _ptr(shifts, c_int),
+                                            _ptr(dists, c_double), _ptr(found, c_int)), "scl_sc_search")
+        return ids, shifts, dists, found
 
     def detect_full(self, cur):
         lid, nn, sh, d = c_int(), c_int(), c_int(), c_double()
