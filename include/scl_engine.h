@@ -421,6 +421,41 @@ int  scl_geometric_verification_from_store(scl_engine *e, const void *src, int n
                                            float T[16], int *success, int *n_src_filtered, int *n_tgt,
                                            int *n_correspondences, int *n_inliers);
 
+/*
+ * THE BATCHED VERIFICATION.  scl_sc_search, scl_iris_search_* and scl_X_detect_*_topk hand a robot up to 32 ranked candidates per
+ * query; scl_loop_icp_batch_from_store verifies such a list on the intra-robot side.  These two calls are the inter-robot side:
+ * geometricVerificationService (DM.h:1189-1268) for ONE received scan against n candidates, where scl_geometric_verification and
+ * scl_geometric_verification_from_store take one candidate per call (about fifteen short launches, three waits of the host, and
+ * the received cloud filtered and uploaded again every time).
+ *   * Arguments.  scl_geometric_verification_batch: tgts[c] / n_tgts[c] = candidate c's cloud on the host, every cloud with the
+ *     source's stride.  scl_geometric_verification_batch_from_store: candidate c = submap(keys_pre[c], search_num) from the
+ *     keyframe store, its window of 2 * search_num + 1 poses at poses_pre + c * (2 * search_num + 1) * 16 (the layout of
+ *     scl_loop_icp_batch_from_store).  One seed serves every candidate.
+ *   * Outputs.  T: n x 16 floats; success, n_correspondences, n_inliers and n_tgts: n entries each, any of them may be NULL;
+ *     n_src_filtered: one int (may be NULL).  Entry c is, bit for bit, what the single call answers for candidate c with the same
+ *     arguments -- T, success, the pair count and the inlier count; the size gate (a gated candidate keeps T = identity, success
+ *     0, counts 0, its n_tgts reported), fewer than three pairs and fewer than three inliers included.
+ *   * Errors.  A NULL required pointer, n < 0, a bad stride, a stride other than the store's, a NULL target with points,
+ *     ransac_iterations outside 1 .. 2^20 when n_src >= 3 (the received cloud's size BEFORE its filter in the store form), a key
+ *     whose window holds a keyframe that was never stored: the status the single call returns, before anything runs, no output
+ *     written.  n == 0 is SCL_OK; the store form still filters the received cloud and reports n_src_filtered.
+ *   * How it runs.  Candidates go in rounds of 32.  The received cloud is filtered and placed on the device once per call.  A
+ *     round is one chain on the engine's stream -- submaps (the batched voxel filter), search grids, one cold neighbour search,
+ *     pairs, RANSAC scoring / pick / mask, masked covariance, solve -- every step one launch over all candidates of the round, a
+ *     candidate's pair count staying on the device; the host waits once per round behind the submaps' sizes.  On a
+ *     scl_create_sharded engine the calls run on the shard that owns the keyframe store, like the other store calls.
+ */
+int  scl_geometric_verification_batch(scl_engine *e, const void *src, int n_src,
+                                      const void *const *tgts, const int *n_tgts, int n_targets, int stride_bytes,
+                                      int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
+                                      float *T, int *success, int *n_correspondences, int *n_inliers);
+int  scl_geometric_verification_batch_from_store(scl_engine *e, const void *src, int n_src, int stride_bytes, float src_leaf,
+                                                 int robot, int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                                                 int min_src_points, int min_tgt_points,
+                                                 int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
+                                                 float *T, int *success, int *n_src_filtered, int *n_tgts,
+                                                 int *n_correspondences, int *n_inliers);
+
 /* ---- measurement ----------------------------------------------------------- */
 int  scl_profile_enable(scl_engine *e, int on);   /* 0 off, 1 every kernel family, 2 SC distance only,
                                                      3 SC distance only, sampled: one launch in thirteen -- in the stream form one

@@ -504,7 +504,7 @@ const char *scl_status_string(int status)
 
 const char *scl_last_error(const scl_engine *e) { return e ? e->last_error.c_str() : "null engine"; }
 
-int scl_abi_version(void) { return 5; }
+int scl_abi_version(void) { return 6; }
 
 int scl_default_config(scl_config *c)
 {
@@ -3347,6 +3347,144 @@ int scl_geometric_verification_from_store(scl_engine *e, const void *src, int n_
                                            inlier_ratio, (unsigned long long)seed, T, success, n_correspondences, n_inliers, &err);
     if (rc) e->last_error = err;
     return rc;
+}
+
+/* ---- geometric verification of one received scan against k candidates ----------- */
+
+namespace {
+
+// one round (at most kIcpBatch candidates, entries first .. first + m - 1 of the outputs) of a verification batch: the source
+// staged in icp_batch_ctl, target c on the device at d_tgts[c]; a candidate that is gated or has no point keeps what the caller
+// wrote (identity, zeros), the others go through icp_geometric_verification_batch in one chain
+int verification_round(scl_engine *e, int first, int m, int ns, const void *const *d_tgts, const int *n_tgts, const bool *gated, int stride,
+                       int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
+                       float *T, int *success, int *n_correspondences, int *n_inliers)
+{
+    IcpWorkspace *wss[scl_engine::kIcpBatch]; int which[scl_engine::kIcpBatch]; int live = 0;
+    const void *tg[scl_engine::kIcpBatch]; int tn[scl_engine::kIcpBatch];
+    for (int c = 0; c < m; ++c) {
+        if (gated[c] || ns < 1 || n_tgts[c] < 1) continue;                  // (no pair at all: scl_geometric_verification's early answer)
+        wss[live] = &e->icp_batch_ws[c]; which[live] = first + c; tg[live] = d_tgts[c]; tn[live] = n_tgts[c]; ++live;
+    }
+    if (live == 0) return SCL_OK;
+    float Tl[16 * scl_engine::kIcpBatch]; int ok[scl_engine::kIcpBatch], nc[scl_engine::kIcpBatch], ni[scl_engine::kIcpBatch];
+    std::string err;
+    int rc = icp_geometric_verification_batch(wss, live, &e->icp_batch_ctl, e->stream, ns, tg, tn, stride, ransac_iterations,
+                                              inlier_threshold, inlier_ratio, (unsigned long long)seed, Tl, ok, nc, ni, &err);
+    if (rc) { e->last_error = err; return rc; }
+    for (int j = 0; j < live; ++j) {
+        std::memcpy(T + 16 * (size_t)which[j], Tl + 16 * (size_t)j, 16 * sizeof(float));
+        if (success) success[which[j]] = ok[j];
+        if (n_correspondences) n_correspondences[which[j]] = nc[j];
+        if (n_inliers) n_inliers[which[j]] = ni[j];
+    }
+    return SCL_OK;
+}
+
+void verification_clear(int n, float *T, int *success, int *n_tgts, int *n_correspondences, int *n_inliers)
+{
+    for (int c = 0; c < n; ++c) {
+        for (int i = 0; i < 16; ++i) T[16 * (size_t)c + i] = (i % 5 == 0) ? 1.0f : 0.0f;
+        if (success) success[c] = 0;
+        if (n_tgts) n_tgts[c] = 0;
+        if (n_correspondences) n_correspondences[c] = 0;
+        if (n_inliers) n_inliers[c] = 0;
+    }
+}
+
+}  // namespace
+
+int scl_geometric_verification_batch(scl_engine *e, const void *src, int n_src,
+                                     const void *const *tgts, const int *n_tgts, int n_targets, int stride_bytes,
+                                     int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
+                                     float *T, int *success, int *n_correspondences, int *n_inliers)
+{
+    if (!e || n_targets < 0 || (!src && n_src > 0) || (n_targets > 0 && (!tgts || !n_tgts || !T))) return SCL_ERR_INVALID_ARG;
+    if (e->front) e = front_primary(e);
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (n_src < 0 || stride_bytes < 12 || (stride_bytes & 3)) return fail(e, SCL_ERR_INVALID_ARG, "geometric_verification_batch: bad cloud layout");
+    for (int c = 0; c < n_targets; ++c)
+        if (n_tgts[c] < 0 || (!tgts[c] && n_tgts[c] > 0)) return fail(e, SCL_ERR_INVALID_ARG, "geometric_verification_batch: bad target");
+    if (n_src >= 3 && (ransac_iterations < 1 || ransac_iterations > (1 << 20))) return fail(e, SCL_ERR_INVALID_ARG, "ransac iterations out of range");
+    if (n_targets == 0) return SCL_OK;
+    (void)hipSetDevice(e->device);
+    verification_clear(n_targets, T, success, nullptr, n_correspondences, n_inliers);
+    if (n_src < 1) return SCL_OK;                                          // no pair at all
+    std::string err;
+    int rc = icp_stage_cloud_host(&e->icp_batch_ctl, e->stream, false, src, n_src, stride_bytes, &err);   // once per call
+    if (rc) { e->last_error = err; return rc; }
+    for (int first = 0; first < n_targets; first += scl_engine::kIcpBatch) {
+        const int m = n_targets - first < scl_engine::kIcpBatch ? n_targets - first : scl_engine::kIcpBatch;
+        const void *d_tgts[scl_engine::kIcpBatch]; bool gated[scl_engine::kIcpBatch];
+        for (int c = 0; c < m; ++c) {
+            gated[c] = false; d_tgts[c] = nullptr;
+            if (n_tgts[first + c] < 1) continue;
+            rc = icp_stage_cloud_host(&e->icp_batch_ws[c], e->stream, true, tgts[first + c], n_tgts[first + c], stride_bytes, &err);
+            if (rc) { e->last_error = err; return rc; }
+            d_tgts[c] = icp_staged_cloud(&e->icp_batch_ws[c], true);
+        }
+        rc = verification_round(e, first, m, n_src, d_tgts, n_tgts + first, gated, stride_bytes, ransac_iterations, inlier_threshold,
+                                inlier_ratio, seed, T, success, n_correspondences, n_inliers);
+        if (rc) return rc;
+    }
+    return SCL_OK;
+}
+
+int scl_geometric_verification_batch_from_store(scl_engine *e, const void *src, int n_src, int stride_bytes, float src_leaf,
+                                                int robot, int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                                                int min_src_points, int min_tgt_points,
+                                                int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
+                                                float *T, int *success, int *n_src_filtered, int *n_tgts,
+                                                int *n_correspondences, int *n_inliers)
+{
+    if (!e || n_candidates < 0 || (!src && n_src > 0) || (n_candidates > 0 && (!keys_pre || !poses_pre || !T))) return SCL_ERR_INVALID_ARG;
+    if (e->front) e = front_primary(e);
+    std::lock_guard<std::mutex> lk(e->mu);
+    const int stride = e->kf_stride ? e->kf_stride : stride_bytes;
+    if (stride != stride_bytes) return fail(e, SCL_ERR_INVALID_ARG, "geometric_verification_batch_from_store: stride differs from the store's");
+    if (n_src < 0 || stride < 12 || (stride & 3) || !(src_leaf > 0.f) || !(leaf > 0.f)) return fail(e, SCL_ERR_INVALID_ARG, "geometric_verification_batch_from_store: bad arguments");
+    // (the received cloud's size before the filter: what is left of it is known only after something has run)
+    if (n_src >= 3 && (ransac_iterations < 1 || ransac_iterations > (1 << 20))) return fail(e, SCL_ERR_INVALID_ARG, "ransac iterations out of range");
+    // every candidate's window (DM.h:1202) before anything runs: an unstored keyframe inside one fails the call with no output written
+    const int win = 2 * search_num + 1;
+    std::vector<const void *> clouds, cl_all; std::vector<int> counts, cn_all, first_of; std::vector<float> Tw, tw_all;
+    int rc;
+    first_of.push_back(0);
+    for (int c = 0; c < n_candidates; ++c) {
+        if ((rc = kf_window(e, robot, keys_pre[c], search_num, poses_pre + (size_t)c * win * 16, &clouds, &counts, &Tw))) return rc;
+        cl_all.insert(cl_all.end(), clouds.begin(), clouds.end()); cn_all.insert(cn_all.end(), counts.begin(), counts.end()); tw_all.insert(tw_all.end(), Tw.begin(), Tw.end());
+        first_of.push_back((int)cl_all.size());
+    }
+    (void)hipSetDevice(e->device);
+    std::string err;
+    int ns = 0;
+    const void *d_res = nullptr;
+    // received cloud: downSizeFilterICP (DM.h:1199-1201), filtered and placed once per call; it stays on the device
+    rc = voxel_grid_to_device(&e->vox_ws, e->stream, src, n_src, stride, src_leaf, &d_res, &ns, &err);
+    if (!rc) rc = icp_stage_cloud(&e->icp_batch_ctl, e->stream, false, d_res, ns, stride, &err);
+    if (rc) { e->last_error = err; return rc; }
+    if (n_src_filtered) *n_src_filtered = ns;
+    verification_clear(n_candidates, T, success, n_tgts, n_correspondences, n_inliers);
+    for (int first = 0; first < n_candidates; first += scl_engine::kIcpBatch) {
+        const int m = n_candidates - first < scl_engine::kIcpBatch ? n_candidates - first : scl_engine::kIcpBatch;
+        // the round's submaps, every step of the voxel filter one launch over all of them (voxel.hip, assemble_submaps_batch); they
+        // stay in the filter's workspace and are read there
+        const int p0 = first_of[(size_t)first];
+        std::vector<int> first_rel((size_t)m + 1);
+        for (int c = 0; c <= m; ++c) first_rel[(size_t)c] = first_of[(size_t)(first + c)] - p0;
+        const void *d_sub[scl_engine::kIcpBatch]; int n_sub[scl_engine::kIcpBatch]; bool gated[scl_engine::kIcpBatch];
+        rc = assemble_submaps_batch(&e->vox_ws, e->stream, cl_all.data() + p0, cn_all.data() + p0, tw_all.data() + 16 * (size_t)p0, first_rel.data(), m,
+                                    stride, leaf, d_sub, n_sub, &err);
+        if (rc) { e->last_error = err; return rc; }
+        for (int c = 0; c < m; ++c) {
+            if (n_tgts) n_tgts[first + c] = n_sub[c];
+            gated[c] = ns < min_src_points || n_sub[c] < min_tgt_points;   // DM.h:1204: clouds too small
+        }
+        rc = verification_round(e, first, m, ns, d_sub, n_sub, gated, stride, ransac_iterations, inlier_threshold, inlier_ratio, seed,
+                                T, success, n_correspondences, n_inliers);
+        if (rc) return rc;
+    }
+    return SCL_OK;
 }
 
 /* ---- measurement ------------------------------------------------------------- */

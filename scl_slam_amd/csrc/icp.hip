@@ -427,13 +427,16 @@ __device__ __forceinline__ void corr_reduce_kernel_body(const float4 *work, cons
                                                           const unsigned char *tgt_raw, int stride, int n,
                                                           const int *nn_idx, const float *nn_d2, float maxd2,
                                                           const int *si, const int *ti, int mode,
-                                                          const IcpState *st, double *partials, int check_done)
+                                                          const IcpState *st, double *partials, int check_done,
+                                                          int block, int nblocks)
 {
+    // (block, nblocks): this workgroup's place among those that share the n correspondences -- blockIdx.x of gridDim.x in a launch
+    //  of its own; the batched verification gives every candidate a count of its own (verify_reduce_batch_kernel)
     if (check_done && st->done) return;
     double acc[kNSum];
 #pragma unroll
     for (int k = 0; k < kNSum; ++k) acc[k] = 0.0;
-    const int r_i0 = (int)(blockIdx.x * blockDim.x), r_step = (int)(gridDim.x * blockDim.x), r_i1 = n;
+    const int r_i0 = (int)(block * blockDim.x), r_step = (int)(nblocks * blockDim.x), r_i1 = n;
     for (int i = r_i0 + (int)threadIdx.x; i < r_i1; i += r_step) {
         float3 p, q;
         float d2 = 0.f;
@@ -467,7 +470,7 @@ __device__ __forceinline__ void corr_reduce_kernel_body(const float4 *work, cons
     if ((threadIdx.x & 63) == 0) for (int k = 0; k < kNSum; ++k) s[wv][k] = acc[k];
     __syncthreads();
     if (threadIdx.x < kNSum)
-        partials[blockIdx.x * kNSum + threadIdx.x] = ((s[0][threadIdx.x] + s[1][threadIdx.x]) + s[2][threadIdx.x]) + s[3][threadIdx.x];
+        partials[block * kNSum + threadIdx.x] = ((s[0][threadIdx.x] + s[1][threadIdx.x]) + s[2][threadIdx.x]) + s[3][threadIdx.x];
 }
 
 __global__ __launch_bounds__(256) void corr_reduce_kernel(const float4 *work, const unsigned char *src_raw,
@@ -476,7 +479,7 @@ __global__ __launch_bounds__(256) void corr_reduce_kernel(const float4 *work, co
                                                           const int *si, const int *ti, int mode,
                                                           const IcpState *st, double *partials, int check_done)
 {
-    corr_reduce_kernel_body(work, src_raw, tgt_raw, stride, n, nn_idx, nn_d2, maxd2, si, ti, mode, st, partials, check_done);
+    corr_reduce_kernel_body(work, src_raw, tgt_raw, stride, n, nn_idx, nn_d2, maxd2, si, ti, mode, st, partials, check_done, blockIdx.x, gridDim.x);
 }
 
 // MFMA form of K5.  v_mfma_f64_4x4x4_4b_f64 computes, in each of its four 16-lane blocks,
@@ -489,12 +492,13 @@ __device__ __forceinline__ void corr_reduce_mfma_kernel_body(const float4 *work,
                                                                const unsigned char *tgt_raw, int stride, int n,
                                                                const int *nn_idx, const float *nn_d2, float maxd2,
                                                                const int *si, const int *ti, int mode,
-                                                               const IcpState *st, double *partials, int check_done)
+                                                               const IcpState *st, double *partials, int check_done,
+                                                               int block, int nblocks)
 {
     if (check_done && st->done) return;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int k = lane >> 4, blk = (lane >> 2) & 3, comp = lane & 3;
-    const int wave_global = blockIdx.x * 4 + wv, nwaves = gridDim.x * 4;
+    const int wave_global = block * 4 + wv, nwaves = nblocks * 4;
     double acc0 = 0.0, acc1 = 0.0;
     double sum_d2 = 0.0;
     const int b_first = wave_global * 32, b_step = nwaves * 32, b_end = n;
@@ -535,7 +539,7 @@ __device__ __forceinline__ void corr_reduce_mfma_kernel_body(const float4 *work,
     if (lane == 0) s[wv][16] = sum_d2;
     __syncthreads();
     if (threadIdx.x < kNSum)
-        partials[blockIdx.x * kNSum + threadIdx.x] = ((s[0][threadIdx.x] + s[1][threadIdx.x]) + s[2][threadIdx.x]) + s[3][threadIdx.x];
+        partials[block * kNSum + threadIdx.x] = ((s[0][threadIdx.x] + s[1][threadIdx.x]) + s[2][threadIdx.x]) + s[3][threadIdx.x];
 }
 
 __global__ __launch_bounds__(256) void corr_reduce_mfma_kernel(const float4 *work, const unsigned char *src_raw,
@@ -544,7 +548,7 @@ __global__ __launch_bounds__(256) void corr_reduce_mfma_kernel(const float4 *wor
                                                                const int *si, const int *ti, int mode,
                                                                const IcpState *st, double *partials, int check_done)
 {
-    corr_reduce_mfma_kernel_body(work, src_raw, tgt_raw, stride, n, nn_idx, nn_d2, maxd2, si, ti, mode, st, partials, check_done);
+    corr_reduce_mfma_kernel_body(work, src_raw, tgt_raw, stride, n, nn_idx, nn_d2, maxd2, si, ti, mode, st, partials, check_done, blockIdx.x, gridDim.x);
 }
 
 // ---- K5b ---------------------------------------------------------------------------
@@ -1160,9 +1164,9 @@ __device__ __forceinline__ bool ransac_inlier(const double *T, float3 p, float3 
     return (dx * dx + dy * dy) + dz * dz < thr2;
 }
 
-__global__ __launch_bounds__(256) void ransac_score_kernel(const unsigned char *src, const unsigned char *tgt, int stride,
-                                                           const int *si, const int *ti, int n, unsigned long long seed,
-                                                           int n_hyp, double thr2, int *counts)
+__device__ __forceinline__ void ransac_score_body(const unsigned char *src, const unsigned char *tgt, int stride,
+                                                  const int *si, const int *ti, int n, unsigned long long seed,
+                                                  int n_hyp, double thr2, int *counts)
 {
     __shared__ double sT[kHypPerBlock][12];
     __shared__ int scnt[kHypPerBlock];
@@ -1191,9 +1195,15 @@ __global__ __launch_bounds__(256) void ransac_score_kernel(const unsigned char *
     __syncthreads();
     if (threadIdx.x < kHypPerBlock && h0 + (int)threadIdx.x < n_hyp) counts[h0 + threadIdx.x] = scnt[threadIdx.x];
 }
+__global__ __launch_bounds__(256) void ransac_score_kernel(const unsigned char *src, const unsigned char *tgt, int stride,
+                                                           const int *si, const int *ti, int n, unsigned long long seed,
+                                                           int n_hyp, double thr2, int *counts)
+{
+    ransac_score_body(src, tgt, stride, si, ti, n, seed, n_hyp, thr2, counts);
+}
 
 // best hypothesis (most inliers, ties -> lowest index), its model, and the inlier mask
-__global__ void ransac_pick_kernel(const int *counts, int n_hyp, int *best /*[2]: h, count*/)
+__device__ __forceinline__ void ransac_pick_body(const int *counts, int n_hyp, int *best /*[2]: h, count*/)
 {
     __shared__ long long sk[16];
     long long key = -1;                                  // (count << 32) | (0x7fffffff - h): max = most inliers, lowest h
@@ -1211,20 +1221,27 @@ __global__ void ransac_pick_kernel(const int *counts, int n_hyp, int *best /*[2]
         best[1] = key < 0 ? 0 : (int)(key >> 32);
     }
 }
+__global__ void ransac_pick_kernel(const int *counts, int n_hyp, int *best) { ransac_pick_body(counts, n_hyp, best); }
 
-__global__ __launch_bounds__(256) void ransac_mask_kernel(const unsigned char *src, const unsigned char *tgt, int stride,
-                                                          const int *si, const int *ti, int n, unsigned long long seed,
-                                                          const int *best, double thr2, int *mask, double *T_out)
+__device__ __forceinline__ void ransac_mask_body(const unsigned char *src, const unsigned char *tgt, int stride,
+                                                 const int *si, const int *ti, int n, unsigned long long seed,
+                                                 const int *best, double thr2, int *mask, double *T_out /* may be nullptr */)
 {
     __shared__ double sT[12];
     if (threadIdx.x == 0) {
         if (best[0] >= 0) ransac_model(src, tgt, stride, si, ti, n, seed, best[0], sT);
         else for (int k = 0; k < 12; ++k) sT[k] = (k % 5 == 0) ? 1.0 : 0.0;
-        if (blockIdx.x == 0) for (int k = 0; k < 12; ++k) T_out[k] = sT[k];
+        if (T_out && blockIdx.x == 0) for (int k = 0; k < 12; ++k) T_out[k] = sT[k];
     }
     __syncthreads();
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
         mask[i] = ransac_inlier(sT, load_xyz(src, si[i], stride), load_xyz(tgt, ti[i], stride), thr2) ? 1 : 0;
+}
+__global__ __launch_bounds__(256) void ransac_mask_kernel(const unsigned char *src, const unsigned char *tgt, int stride,
+                                                          const int *si, const int *ti, int n, unsigned long long seed,
+                                                          const int *best, double thr2, int *mask, double *T_out)
+{
+    ransac_mask_body(src, tgt, stride, si, ti, n, seed, best, thr2, mask, T_out);
 }
 
 // The pairs of the verification path: every source whose search found a neighbour (nn[i] >= 0; a source with a non-finite
@@ -1939,6 +1956,122 @@ __global__ void gather_states_kernel(const IcpProblem *pr, int nprob, IcpState *
 }
 
 
+// ---- the verification tail for the candidates of ONE received scan at once (blockIdx.y = candidate) ----------------------------
+// geometricVerificationService (DM.h:1211-1243) for one candidate is about fifteen short launches and three waits of the host (pair
+// count, best hypothesis, state), and its one heavy launch, the scoring, is iterations / kHypPerBlock workgroups: half the chip
+// at 1 000 hypotheses.  The candidates of a ranked list are independent, so here every step is one launch over all of them, a
+// candidate's pair count stays on the device (every kernel reads it, clamped to n_src, and leaves below 3) and the host waits once.
+// Every value comes from the single path's bodies over the single path's partition of the pairs: candidate c's answer is the
+// single call's, bit for bit.
+struct VerifyJob {
+    const unsigned char *tgt; IcpState *st; const int *nni;
+    int *si, *ti, *mask;                                     // pairs in source order and their inlier flags (n_src entries each)
+    int *counts, *best, *n_corr;                             // inliers per hypothesis, {best hypothesis, its inliers}, pairs
+    double *part;                                            // kRedBlocks records of the masked covariance
+};
+struct VerifyOut { int n_corr, n_inl; float T[16]; };
+
+__device__ __forceinline__ int verify_pairs(const VerifyJob &j, int n_src)
+{
+    const int n = *j.n_corr;
+    return n < 0 ? 0 : (n > n_src ? n_src : n);
+}
+
+// pair_found + prefix sum + iota_pairs of one candidate in one workgroup: 4 096 sources per trip, the count carried along (as
+// grid_scan_batch_kernel sums a target's cells)
+__global__ __launch_bounds__(1024) void verify_pairs_batch_kernel(const VerifyJob *jobs, int n_src)
+{
+    const VerifyJob j = jobs[blockIdx.x];
+    __shared__ int s_wave[16];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    int carry = 0;
+    for (int base = 0; base < n_src; base += 4096) {
+        const int i0 = base + 4 * t;
+        int v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = i0 + u < n_src ? j.nni[i0 + u] : -1;
+        const int mine = ((v[0] >= 0) + (v[1] >= 0)) + ((v[2] >= 0) + (v[3] >= 0));
+        int incl = mine;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off, kWave); if (lane >= off) incl += o; }
+        if (lane == 63) s_wave[wv] = incl;
+        __syncthreads();
+        int before = carry, total = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) { const int x = s_wave[w]; before += w < wv ? x : 0; total += x; }
+        int k = before + incl - mine;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) if (v[u] >= 0) { j.si[k] = i0 + u; j.ti[k] = v[u]; ++k; }   // (k < n_src: one slot per source that found)
+        carry += total;
+        __syncthreads();
+    }
+    if (t == 0) *j.n_corr = carry;
+}
+
+__global__ __launch_bounds__(256) void ransac_score_batch_kernel(const VerifyJob *jobs, const unsigned char *src, int stride, int n_src,
+                                                                 unsigned long long seed, int n_hyp, double thr2)
+{
+    const VerifyJob j = jobs[blockIdx.y];
+    const int n = verify_pairs(j, n_src);
+    if (n < 3) return;
+    ransac_score_body(src, j.tgt, stride, j.si, j.ti, n, seed, n_hyp, thr2, j.counts);
+}
+
+__global__ __launch_bounds__(256) void ransac_pick_batch_kernel(const VerifyJob *jobs, int n_src, int n_hyp)
+{
+    const VerifyJob j = jobs[blockIdx.x];
+    if (verify_pairs(j, n_src) < 3) return;
+    ransac_pick_body(j.counts, n_hyp, j.best);
+}
+
+// (the grid is sized for n_src pairs: a candidate's surplus workgroups leave before they form the model)
+__global__ __launch_bounds__(256) void ransac_mask_batch_kernel(const VerifyJob *jobs, const unsigned char *src, int stride, int n_src,
+                                                                unsigned long long seed, double thr2)
+{
+    const VerifyJob j = jobs[blockIdx.y];
+    const int n = verify_pairs(j, n_src);
+    if (n < 3 || (long long)blockIdx.x * blockDim.x >= n) return;
+    ransac_mask_body(src, j.tgt, stride, j.si, j.ti, n, seed, j.best, thr2, j.mask, nullptr);
+}
+
+// The masked covariance of a candidate's inliers (DM.h:1228-1230).  Its sums depend on how many workgroups share the pairs: the
+// single path launches rb = clamp(ceil(n_corr / 256), 1, kRedBlocks); here the grid is that bound for n_src pairs, every candidate
+// forms its own rb from its own count and only its first rb workgroups work, as (block, rb) of the same body.
+__device__ __forceinline__ int verify_red_blocks(int n)
+{
+    const int rb = (n + 255) / 256;
+    return rb < 1 ? 1 : (rb > kRedBlocks ? kRedBlocks : rb);
+}
+
+template <bool MFMA>
+__global__ __launch_bounds__(256) void verify_reduce_batch_kernel(const VerifyJob *jobs, const unsigned char *src, int stride, int n_src)
+{
+    const VerifyJob j = jobs[blockIdx.y];
+    const int n = verify_pairs(j, n_src);
+    if (n < 3 || j.best[1] < 3) return;
+    const int rb = verify_red_blocks(n);
+    if ((int)blockIdx.x >= rb) return;
+    if (MFMA) corr_reduce_mfma_kernel_body(nullptr, src, j.tgt, stride, n, j.mask, nullptr, 0.f, j.si, j.ti, 1, j.st, j.part, 0, (int)blockIdx.x, rb);
+    else corr_reduce_kernel_body(nullptr, src, j.tgt, stride, n, j.mask, nullptr, 0.f, j.si, j.ti, 1, j.st, j.part, 0, (int)blockIdx.x, rb);
+}
+
+// state, one-shot solve over the candidate's rb records (T stays the identity below three inliers) and the candidate's answer
+__global__ __launch_bounds__(64) void verify_solve_batch_kernel(const VerifyJob *jobs, int n_src, VerifyOut *out)
+{
+    const VerifyJob j = jobs[blockIdx.x];
+    const int n = verify_pairs(j, n_src);
+    int n_inl = n >= 3 ? j.best[1] : 0;
+    n_inl = n_inl < 0 ? 0 : (n_inl > n ? n : n_inl);
+    state_init_body(j.st);
+    if (n_inl >= 3) icp_solve_kernel_body(j.st, j.part, verify_red_blocks(n), 1, 0, 0.0, 0.0);
+    if (threadIdx.x == 0) {
+        VerifyOut &o = out[blockIdx.x];
+        o.n_corr = n; o.n_inl = n_inl;
+        for (int k = 0; k < 16; ++k) o.T[k] = j.st->final_T[k];
+    }
+}
+
+
 // ---- host helpers -------------------------------------------------------------------
 // partial-sum records of an iteration: one per workgroup of the tile search (point to point), kRedBlocks of the plane reduction
 static size_t part_bytes(int n_src)
@@ -2175,39 +2308,28 @@ int icp_batch_prepare(IcpWorkspace *ws, hipStream_t stream, const void *d_src, i
     return SCL_OK;
 }
 
-// icp_batch_prepare for n alignments at once, their targets already on the device (d_tgts[c], n_tgts[c] points: read in place, not
-// copied): every step one launch over all of them, on one stream.  ctl keeps the table of the jobs.
-int icp_batch_prepare_all(IcpWorkspace *const *wss, int n, IcpWorkspace *ctl, hipStream_t stream, int n_src, const void *const *d_tgts,
-                          const int *n_tgts, int stride, const scl_icp_params &p, std::string *err)
+// The search grids of n targets that are already on the device (d_tgts[c], n_tgts[c] points: read in place, not copied): buffers,
+// the table of the jobs (ctl, B_PROB; *jobs_out) and the box, set-up, zero, count, scan and scatter launches, each over all targets.
+static int grid_build_batch(IcpWorkspace *const *wss, int n, IcpWorkspace *ctl, hipStream_t stream, const void *const *d_tgts,
+                            const int *n_tgts, int stride, bool normals, const GridJob **jobs_out, int *max_n_out, std::string *err)
 {
-    if (n <= 0) return SCL_OK;
-    if (p.estimator != 0 && p.estimator != 1) { if (err) *err = "unknown estimator"; return SCL_ERR_INVALID_ARG; }
-    if (p.estimator == 1 && !(p.normal_radius > 0.0)) { if (err) *err = "normal_radius must be > 0"; return SCL_ERR_INVALID_ARG; }
-    if (p.max_iterations < 1) { if (err) *err = "max_iterations < 1"; return SCL_ERR_INVALID_ARG; }
     int rc, max_n = 0;
     std::vector<GridJob> jobs((size_t)n);
     for (int c = 0; c < n; ++c) {
         IcpWorkspace *ws = wss[c];
         const int n_tgt = n_tgts[c];
-        if ((rc = check_cloud_args(n_src, n_tgt, stride, err))) return rc;
-        if ((rc = ensure(ws, B_WORK, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
-        if ((rc = ensure(ws, B_NNQ, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
-        if ((rc = ensure(ws, B_FLAG, sizeof(int) * ((size_t)(n_src > n_tgt ? n_src : n_tgt) / kTileQ + 2), err))) return rc;
-        if ((rc = ensure(ws, B_NNI, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
-        if ((rc = ensure(ws, B_NND, sizeof(float) * (size_t)(n_src + 1), err))) return rc;
-        if ((rc = ensure(ws, B_PART, part_bytes(n_src), err))) return rc;
         if ((rc = ensure(ws, B_TSORT, sizeof(float4) * (size_t)(n_tgt + 1), err))) return rc;
         if ((rc = ensure(ws, B_CSTART, sizeof(int) * (size_t)(kMaxCells + 2), err))) return rc;
         if ((rc = ensure(ws, B_CFILL, sizeof(int) * (size_t)(kMaxCells + 2), err))) return rc;
         if ((rc = ensure(ws, B_BBOX, sizeof(float) * 6 * 256, err))) return rc;
         if ((rc = ensure(ws, B_STATE, sizeof(IcpState), err))) return rc;
-        if (p.estimator == 1 && (rc = ensure(ws, B_NORM, sizeof(float4) * (size_t)(n_tgt + 1), err))) return rc;
+        if (normals && (rc = ensure(ws, B_NORM, sizeof(float4) * (size_t)(n_tgt + 1), err))) return rc;
         ws->ext_tgt = d_tgts[c];
         ws->n_tgt = n_tgt;
         GridJob &j = jobs[(size_t)c];
         j.tgt = static_cast<const unsigned char *>(d_tgts[c]); j.n = n_tgt; j.st = (IcpState *)ws->buf[B_STATE];
         j.cstart = (int *)ws->buf[B_CSTART]; j.cfill = (int *)ws->buf[B_CFILL]; j.tsort = (float4 *)ws->buf[B_TSORT];
-        j.bbox = (float *)ws->buf[B_BBOX]; j.normals = p.estimator == 1 ? (float4 *)ws->buf[B_NORM] : nullptr;
+        j.bbox = (float *)ws->buf[B_BBOX]; j.normals = normals ? (float4 *)ws->buf[B_NORM] : nullptr;
         max_n = n_tgt > max_n ? n_tgt : max_n;
     }
     if ((rc = ensure(ctl, B_PROB, sizeof(GridJob) * (size_t)n, err))) return rc;
@@ -2220,6 +2342,34 @@ int icp_batch_prepare_all(IcpWorkspace *const *wss, int n, IcpWorkspace *ctl, hi
     hipLaunchKernelGGL(grid_count_batch_kernel, dim3(gb, n), dim3(256), 0, stream, dj, stride);
     hipLaunchKernelGGL(grid_scan_batch_kernel, dim3(n), dim3(1024), 0, stream, dj);
     hipLaunchKernelGGL(grid_scatter_batch_kernel, dim3(gb, n), dim3(256), 0, stream, dj, stride);
+    *jobs_out = dj;
+    *max_n_out = max_n;
+    return SCL_OK;
+}
+
+// icp_batch_prepare for n alignments at once, their targets already on the device (d_tgts[c], n_tgts[c] points: read in place, not
+// copied): every step one launch over all of them, on one stream.  ctl keeps the table of the jobs.
+int icp_batch_prepare_all(IcpWorkspace *const *wss, int n, IcpWorkspace *ctl, hipStream_t stream, int n_src, const void *const *d_tgts,
+                          const int *n_tgts, int stride, const scl_icp_params &p, std::string *err)
+{
+    if (n <= 0) return SCL_OK;
+    if (p.estimator != 0 && p.estimator != 1) { if (err) *err = "unknown estimator"; return SCL_ERR_INVALID_ARG; }
+    if (p.estimator == 1 && !(p.normal_radius > 0.0)) { if (err) *err = "normal_radius must be > 0"; return SCL_ERR_INVALID_ARG; }
+    if (p.max_iterations < 1) { if (err) *err = "max_iterations < 1"; return SCL_ERR_INVALID_ARG; }
+    int rc, max_n = 0;
+    for (int c = 0; c < n; ++c) {
+        IcpWorkspace *ws = wss[c];
+        const int n_tgt = n_tgts[c];
+        if ((rc = check_cloud_args(n_src, n_tgt, stride, err))) return rc;
+        if ((rc = ensure(ws, B_WORK, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
+        if ((rc = ensure(ws, B_NNQ, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
+        if ((rc = ensure(ws, B_FLAG, sizeof(int) * ((size_t)(n_src > n_tgt ? n_src : n_tgt) / kTileQ + 2), err))) return rc;
+        if ((rc = ensure(ws, B_NNI, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
+        if ((rc = ensure(ws, B_NND, sizeof(float) * (size_t)(n_src + 1), err))) return rc;
+        if ((rc = ensure(ws, B_PART, part_bytes(n_src), err))) return rc;
+    }
+    const GridJob *dj = nullptr;
+    if ((rc = grid_build_batch(wss, n, ctl, stream, d_tgts, n_tgts, stride, p.estimator == 1, &dj, &max_n, err))) return rc;
     // the normals (point to plane) are first needed by the plane reduction behind the cold search: icp_batch_run launches them beside
     // the cold searches of its parts
     ctl->normals_pending = p.estimator == 1 && max_n > 0;
@@ -2682,6 +2832,99 @@ int icp_geometric_verification_staged(IcpWorkspace *ws, hipStream_t stream, int 
         std::memcpy(T, h->final_T, sizeof(float) * 16);
     }
     if (success) *success = !((double)n_inl < inlier_ratio * (double)n_corr);                     // DM.h:1238
+    return SCL_OK;
+}
+
+const void *icp_staged_cloud(const IcpWorkspace *ws, bool target) { return ws->buf[target ? B_TGT : B_SRC]; }
+
+// geometricVerificationService's core for m candidates of one source: the source staged in ctl (icp_stage_cloud*), the targets on
+// the device and read in place, every candidate with at least one point (and n_src >= 1): the caller answers the others itself.
+// One chain of launches over all candidates, one wait.  Outputs have m entries, none may be nullptr.
+int icp_geometric_verification_batch(IcpWorkspace *const *wss, int m, IcpWorkspace *ctl, hipStream_t stream, int n_src,
+                                     const void *const *d_tgts, const int *n_tgts, int stride, int ransac_iterations,
+                                     double inlier_threshold, double inlier_ratio, unsigned long long seed, float *T, int *success,
+                                     int *n_corr_out, int *n_inliers_out, std::string *err)
+{
+    if (m <= 0) return SCL_OK;
+    int rc;
+    if (n_src < 1) { if (err) *err = "geometric verification batch: no source"; return SCL_ERR_INVALID_ARG; }
+    for (int c = 0; c < m; ++c) {
+        if ((rc = check_cloud_args(n_src, n_tgts[c], stride, err))) return rc;
+        if (n_tgts[c] < 1 || !d_tgts[c]) { if (err) *err = "geometric verification batch: empty target"; return SCL_ERR_INVALID_ARG; }
+    }
+    const bool sample = n_src >= 3;                              // (below three sources no candidate has three pairs: the pairs are only counted)
+    if (sample && (ransac_iterations < 1 || ransac_iterations > (1 << 20))) { if (err) *err = "ransac iterations out of range"; return SCL_ERR_INVALID_ARG; }
+    const int n_hyp = sample ? ransac_iterations : 0;
+    const GridJob *dj = nullptr;
+    int max_n = 0;
+    if ((rc = ensure(ctl, B_WORK, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
+    if ((rc = ensure(ctl, B_MASK, sizeof(IcpProblem) * (size_t)m, err))) return rc;
+    if ((rc = ensure(ctl, B_PAIR, (sizeof(VerifyJob) + sizeof(VerifyOut)) * (size_t)m, err))) return rc;
+    if ((rc = pinned(ctl, sizeof(VerifyOut) * (size_t)m, err))) return rc;
+    for (int c = 0; c < m; ++c) {
+        IcpWorkspace *ws = wss[c];
+        if ((rc = ensure(ws, B_NNI, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
+        if ((rc = ensure(ws, B_NND, sizeof(float) * (size_t)(n_src + 1), err))) return rc;
+        if ((rc = ensure(ws, B_SI, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
+        if ((rc = ensure(ws, B_TI, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
+        if ((rc = ensure(ws, B_MASK, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
+        if ((rc = ensure(ws, B_HYP, sizeof(int) * (size_t)(n_hyp + 8), err))) return rc;
+        if ((rc = ensure(ws, B_PART, sizeof(double) * kNSum * kRedBlocks, err))) return rc;
+    }
+    const unsigned char *d_src = static_cast<const unsigned char *>(ctl->buf[B_SRC]);
+    float4 *work = static_cast<float4 *>(ctl->buf[B_WORK]);
+    const int pb = (n_src + 255) / 256;
+    // the working cloud in SOURCE order (the pairs are defined in it), one for all candidates: the cold search only reads it
+    hipLaunchKernelGGL(work_init_kernel, dim3(pb), dim3(256), 0, stream, d_src, n_src, stride, work);
+    if ((rc = grid_build_batch(wss, m, ctl, stream, d_tgts, n_tgts, stride, false, &dj, &max_n, err))) return rc;
+    std::vector<IcpProblem> hp((size_t)m);
+    std::vector<VerifyJob> hj((size_t)m);
+    for (int c = 0; c < m; ++c) {
+        IcpWorkspace *ws = wss[c];
+        IcpProblem &p = hp[(size_t)c];
+        std::memset(&p, 0, sizeof(p));
+        p.work = work; p.st = (IcpState *)ws->buf[B_STATE]; p.cell_start = (const int *)ws->buf[B_CSTART];
+        p.sorted = (const float4 *)ws->buf[B_TSORT]; p.nni = (int *)ws->buf[B_NNI]; p.nnd = (float *)ws->buf[B_NND];
+        p.tgt = static_cast<const unsigned char *>(d_tgts[c]); p.n_tgt = n_tgts[c];
+        VerifyJob &j = hj[(size_t)c];
+        j.tgt = p.tgt; j.st = p.st; j.nni = p.nni;
+        j.si = (int *)ws->buf[B_SI]; j.ti = (int *)ws->buf[B_TI]; j.mask = (int *)ws->buf[B_MASK];
+        j.counts = (int *)ws->buf[B_HYP]; j.best = j.counts + n_hyp + 2; j.n_corr = j.counts + n_hyp + 4;
+        j.part = (double *)ws->buf[B_PART];
+    }
+    VerifyJob *djobs = static_cast<VerifyJob *>(ctl->buf[B_PAIR]);
+    VerifyOut *dout = reinterpret_cast<VerifyOut *>(djobs + m);
+    const IcpProblem *dp = static_cast<const IcpProblem *>(ctl->buf[B_MASK]);
+    ICP_HIP(hipMemcpyAsync(ctl->buf[B_MASK], hp.data(), sizeof(IcpProblem) * (size_t)m, hipMemcpyHostToDevice, stream));   // (pageable: staged before the call returns)
+    ICP_HIP(hipMemcpyAsync(djobs, hj.data(), sizeof(VerifyJob) * (size_t)m, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(nn_search_batch_kernel<kNnGroup>, dim3((unsigned)(((long long)n_src * kNnGroup + 255) / 256), m), dim3(256), 0, stream,
+                       dp, n_src, 0, -1, stride, 0);                                               // DM.h:1211-1215, cold
+    hipLaunchKernelGGL(verify_pairs_batch_kernel, dim3(m), dim3(1024), 0, stream, djobs, n_src);
+    if (sample) {
+        const double thr2 = inlier_threshold * inlier_threshold;
+        const int hb = (n_hyp + kHypPerBlock - 1) / kHypPerBlock;
+        int mb = pb > 1024 ? 1024 : pb;
+        hipLaunchKernelGGL(ransac_score_batch_kernel, dim3(hb, m), dim3(256), 0, stream, djobs, d_src, stride, n_src, seed, n_hyp, thr2);   // DM.h:1218-1225
+        hipLaunchKernelGGL(ransac_pick_batch_kernel, dim3(m), dim3(256), 0, stream, djobs, n_src, n_hyp);
+        hipLaunchKernelGGL(ransac_mask_batch_kernel, dim3(mb, m), dim3(256), 0, stream, djobs, d_src, stride, n_src, seed, thr2);
+        const int rb = pb > kRedBlocks ? kRedBlocks : pb;
+        if (use_mfma_reduce()) hipLaunchKernelGGL(verify_reduce_batch_kernel<true>, dim3(rb, m), dim3(256), 0, stream, djobs, d_src, stride, n_src);   // DM.h:1228-1230
+        else hipLaunchKernelGGL(verify_reduce_batch_kernel<false>, dim3(rb, m), dim3(256), 0, stream, djobs, d_src, stride, n_src);
+    }
+    hipLaunchKernelGGL(verify_solve_batch_kernel, dim3(m), dim3(64), 0, stream, djobs, n_src, dout);
+    ICP_HIP(hipGetLastError());
+    VerifyOut *h = static_cast<VerifyOut *>(ctl->pinned);
+    ICP_HIP(hipMemcpyAsync(h, dout, sizeof(VerifyOut) * (size_t)m, hipMemcpyDeviceToHost, stream));
+    ICP_HIP(hipStreamSynchronize(stream));
+    for (int c = 0; c < m; ++c) {
+        const int n_corr = h[c].n_corr, n_inl = h[c].n_inl;
+        for (int k = 0; k < 16; ++k) T[16 * (size_t)c + k] = (k % 5 == 0) ? 1.f : 0.f;
+        success[c] = 0; n_corr_out[c] = n_corr; n_inliers_out[c] = 0;
+        if (n_corr < 3) continue;                                                                  // nothing to sample from
+        n_inliers_out[c] = n_inl;
+        if (n_inl >= 3) std::memcpy(T + 16 * (size_t)c, h[c].T, sizeof(float) * 16);
+        success[c] = !((double)n_inl < inlier_ratio * (double)n_corr);                             // DM.h:1238
+    }
     return SCL_OK;
 }
 

@@ -73,6 +73,17 @@ int icp_geometric_verification_staged(IcpWorkspace *ws, hipStream_t stream, int 
                                       unsigned long long seed, float T[16], int *success, int *n_corr_out,
                                       int *n_inliers_out, std::string *err);
 
+// the same for m candidates of ONE source, every step one launch over all of them and one wait (icp.hip): the source staged in ctl
+// (icp_stage_cloud / icp_stage_cloud_host, once per call), the targets on the device and read in place (d_tgts[c], n_tgts[c] >= 1
+// points; n_src >= 1), wss[c] the candidates' workspaces.  Entry c of every output (m entries each, none nullptr) is what
+// icp_geometric_verification_staged answers for candidate c, bit for bit.
+int icp_geometric_verification_batch(IcpWorkspace *const *wss, int m, IcpWorkspace *ctl, hipStream_t stream, int n_src,
+                                     const void *const *d_tgts, const int *n_tgts, int stride, int ransac_iterations,
+                                     double inlier_threshold, double inlier_ratio, unsigned long long seed, float *T, int *success,
+                                     int *n_corr_out, int *n_inliers_out, std::string *err);
+// where icp_stage_cloud / icp_stage_cloud_host left a cloud
+const void *icp_staged_cloud(const IcpWorkspace *ws, bool target);
+
 // voxel.hip (a separate workspace instance is used: buffer slots differ from icp.hip's)
 int voxel_grid(IcpWorkspace *ws, hipStream_t stream, const void *in, int n, int stride, float leaf,
                void *out, int out_capacity, int *n_out, std::string *err);

@@ -128,6 +128,10 @@ def _bind(lib):
                                                   fp, fp, ip, ip, ip, ip]),
         "scl_geometric_verification_from_store": (c_int, [P, P, c_int, c_int, c_float, c_int, c_int, c_int, fp, c_float, c_int, c_int,
                                                           c_int, c_double, c_double, c_uint64, fp, ip, ip, ip, ip, ip]),
+        "scl_geometric_verification_batch": (c_int, [P, P, c_int, POINTER(c_void_p), ip, c_int, c_int, c_int, c_double, c_double, c_uint64,
+                                                     fp, ip, ip, ip]),
+        "scl_geometric_verification_batch_from_store": (c_int, [P, P, c_int, c_int, c_float, c_int, c_int, ip, c_int, fp, c_float, c_int, c_int,
+                                                                c_int, c_double, c_double, c_uint64, fp, ip, ip, ip, ip, ip]),
         "scl_profile_enable": (c_int, [P, c_int]),
         "scl_profile_reset": (c_int, [P]),
         "scl_profile_get": (c_int, [P, POINTER(SclProfile)]),
@@ -789,6 +793,40 @@ class ScanContextEngine:
             min_src_points, min_tgt_points, ransac_iterations, inlier_threshold, inlier_ratio, seed,
             _ptr(T, c_float), byref(ok), byref(ns), byref(nt), byref(nc), byref(ni)), "scl_geometric_verification_from_store")
         return T.reshape(4, 4), bool(ok.value), ns.value, nt.value, nc.value, ni.value
+
+    def geometric_verification_batch(self, src, tgts, ransac_iterations=1000, inlier_threshold=0.25, inlier_ratio=0.45, seed=1):
+        """geometric_verification of one source against every cloud of `tgts`, every step one launch over all of them; returns
+        (T[m,4,4], success[m], n_correspondences[m], n_inliers[m]), entry c equal to geometric_verification(src, tgts[c], ...)"""
+        s, ns, stride = _cloud(src)
+        arrs, ptrs, counts, m, stride_t = self._cloud_list(tgts)
+        if m and stride != stride_t:
+            raise ValueError("source and targets must share a record layout")
+        k = max(m, 1)
+        T = np.empty((k, 16), np.float32); ok = np.zeros(k, np.int32); nc = np.zeros(k, np.int32); ni = np.zeros(k, np.int32)
+        self._check(self._lib.scl_geometric_verification_batch(self._h, s.ctypes.data_as(c_void_p), ns, ptrs, _ptr(counts, c_int), m, stride,
+                                                               ransac_iterations, inlier_threshold, inlier_ratio, seed,
+                                                               _ptr(T, c_float), _ptr(ok, c_int), _ptr(nc, c_int), _ptr(ni, c_int)),
+                    "scl_geometric_verification_batch")
+        return T[:m].reshape(m, 4, 4), ok[:m].astype(bool), nc[:m], ni[:m]
+
+    def geometric_verification_batch_from_store(self, src, src_leaf, robot, keys_pre, search_num, poses_pre, leaf,
+                                                ransac_iterations=1000, inlier_threshold=0.25, inlier_ratio=0.45, seed=1,
+                                                min_src_points=300, min_tgt_points=1000):
+        """geometricVerificationService (DM.h:1189-1268) for one received scan against the submaps of keys_pre (a peer's ranked
+        list): returns (T[m,4,4], success[m], n_src_filtered, n_tgts[m], n_correspondences[m], n_inliers[m]), entry c equal to
+        geometric_verification_from_store(src, src_leaf, robot, keys_pre[c], search_num, poses_pre[c], leaf, ...)"""
+        a, n, stride = _cloud(src)
+        keys = np.ascontiguousarray(keys_pre, dtype=np.int32); m = keys.size
+        Tp = _f32(np.asarray(poses_pre)).reshape(m, 2 * search_num + 1, 16)
+        k = max(m, 1)
+        T = np.empty((k, 16), np.float32); ok = np.zeros(k, np.int32); ns = c_int(); nt = np.zeros(k, np.int32)
+        nc = np.zeros(k, np.int32); ni = np.zeros(k, np.int32)
+        self._check(self._lib.scl_geometric_verification_batch_from_store(
+            self._h, a.ctypes.data_as(c_void_p), n, stride, src_leaf, robot, m, _ptr(keys, c_int), search_num, _ptr(Tp, c_float), leaf,
+            min_src_points, min_tgt_points, ransac_iterations, inlier_threshold, inlier_ratio, seed,
+            _ptr(T, c_float), _ptr(ok, c_int), byref(ns), _ptr(nt, c_int), _ptr(nc, c_int), _ptr(ni, c_int)),
+            "scl_geometric_verification_batch_from_store")
+        return T[:m].reshape(m, 4, 4), ok[:m].astype(bool), ns.value, nt[:m], nc[:m], ni[:m]
 
     # -- measurement ------------------------------------------------------------
     def profile_enable(self, on=True):
