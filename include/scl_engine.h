@@ -369,6 +369,16 @@ int  scl_matrix_to_pose(const float T[16], float *x, float *y, float *z, float *
  * quaternion x, y, z, w (w >= 0) -- the fields of loop_info.betPose / poseBetween --, between_rpy (optional) =
  * roll, pitch, yaw of the same rotation. */
 int  scl_loop_pose_between(const float T_icp[16], const float pose_cur[6], const float pose_pre[6], double between_xyz_q[7], double between_rpy[3]);
+/* The initial guess of an inter-robot verification from a Scan Context match; host-side helper, no engine.  shift = the ring shift
+ * the search reported for (query = the received keyframe, candidate) -- scl_sc_search's cand_shifts --, num_sector = the grid's,
+ * pose_cur / pose_pre = x, y, z, roll, pitch, yaw of the received keyframe in its robot's world frame (the received cloud is in that
+ * frame, DM.h:1333) and of the candidate keyframe in the other robot's.  G = M(pose_pre) * Rz(yaw) * M(pose_cur)^-1, M the matrix of
+ * scl_pose_to_matrix, M^-1 the rigid inverse [R^T | -R^T t]: the received cloud back in its sensor frame, turned by the descriptor's
+ * yaw, placed at the candidate keyframe's pose.  distanceBtnScanContext shifts the CANDIDATE's columns right by `shift` (D.h:1376-1378,
+ * 1559), so the query turns by yaw = -shift * 2 pi / num_sector (shift taken modulo num_sector).  Built in double from the float
+ * inputs, rounded to float once.  The shift resolves the yaw to half a sector only.  num_sector < 1, a NULL pointer or a non-finite
+ * pose: SCL_ERR_INVALID_ARG. */
+int  scl_loop_guess_from_shift(int shift, int num_sector, const float pose_cur[6], const float pose_pre[6], float G[16]);
 /* loopFindNearKeyframes, DM.h:1163-1186: concatenation of transformPointCloud(cloud_i, T_i) (DM.h:234-253)
  * followed by the voxel filter.  transforms = n_clouds row-major 4x4 matrices. */
 int  scl_assemble_submap(scl_engine *e, const void *const *clouds, const int *counts, const float *transforms,
@@ -455,6 +465,43 @@ int  scl_geometric_verification_batch_from_store(scl_engine *e, const void *src,
                                                  int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
                                                  float *T, int *success, int *n_src_filtered, int *n_tgts,
                                                  int *n_correspondences, int *n_inliers);
+
+/*
+ * THE BATCHED VERIFICATION WITH INITIAL GUESSES.  Nearest-neighbour pairs mean something only between clouds that are nearly aligned,
+ * and two robots' world frames are not: the ranked search reports a ring shift per candidate (scl_loop_guess_from_shift turns it and
+ * the two keyframe poses into a motion), and these two calls take one such motion per candidate.
+ *   * Arguments.  Those of the pair above, and guesses: n x 16 floats, candidate c's G_c = guesses + 16 * c, a row-major 4x4 whose
+ *     first three rows are read (the last is taken as 0, 0, 0, 1).  Candidate c's source is the received cloud moved by G_c with the
+ *     arithmetic of scl_transform_cloud (DM.h:247-249); fields other than x, y, z play no part.  In the store form the received cloud
+ *     is voxel-filtered FIRST, once, with src_leaf, and the filtered cloud is moved per candidate.
+ *   * Outputs.  T_fit (n x 16, may be NULL), success, n_correspondences, n_inliers: entry c is, bit for bit, what
+ *     scl_geometric_verification answers for (scl_transform_cloud(src, G_c), tgts[c]) with the same arguments -- in the store form
+ *     for (scl_transform_cloud(scl_voxel_grid(src, src_leaf), G_c), scl_submap_from_store(keys_pre[c], ...)) behind the size gate of
+ *     the store form above, which looks at the filtered size (no guess changes it); a gated candidate keeps T = T_fit = identity,
+ *     success 0, counts 0, its n_tgts reported.  T (n x 16, required): the whole motion received cloud -> candidate, T_fit[c] * G_c,
+ *     every entry formed on the host in double as ((a0 b0 + a1 b1) + a2 b2) + a3 b3 and rounded to float once; where T_fit[c] is the
+ *     identity because there were fewer than three pairs or inliers, T[c] is G_c with the last row 0, 0, 0, 1.  The other optional
+ *     outputs as above.
+ *   * Errors.  Whatever the pair above refuses, with the same status; then guesses == NULL with n > 0, or a non-finite entry in the
+ *     first three rows of any guess: SCL_ERR_INVALID_ARG.  All before anything runs, no output written.  n == 0 is SCL_OK (guesses
+ *     may then be NULL); the store form still reports n_src_filtered.
+ *   * How it runs.  The chain of the pair above on the engine's stream, one wait per round, with one more launch per round: a
+ *     (blocks, candidates) grid writes every candidate's moved source as a float4 cloud, which the cold search and the RANSAC / mask /
+ *     covariance steps of that candidate read in place of the shared one.  Memory: 16 bytes x n_src per candidate of a round (at
+ *     most 32), in the candidates' grow-only workspaces; a later call without guesses does not read them.  Sharded engines: as above.
+ */
+int  scl_geometric_verification_batch_guess(scl_engine *e, const void *src, int n_src,
+                                            const void *const *tgts, const int *n_tgts, int n_targets, int stride_bytes,
+                                            const float *guesses,
+                                            int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
+                                            float *T, float *T_fit, int *success, int *n_correspondences, int *n_inliers);
+int  scl_geometric_verification_batch_from_store_guess(scl_engine *e, const void *src, int n_src, int stride_bytes, float src_leaf,
+                                                       int robot, int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                                                       const float *guesses,
+                                                       int min_src_points, int min_tgt_points,
+                                                       int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
+                                                       float *T, float *T_fit, int *success, int *n_src_filtered, int *n_tgts,
+                                                       int *n_correspondences, int *n_inliers);
 
 /* ---- measurement ----------------------------------------------------------- */
 int  scl_profile_enable(scl_engine *e, int on);   /* 0 off, 1 every kernel family, 2 SC distance only,

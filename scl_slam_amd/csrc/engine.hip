@@ -504,7 +504,7 @@ const char *scl_status_string(int status)
 
 const char *scl_last_error(const scl_engine *e) { return e ? e->last_error.c_str() : "null engine"; }
 
-int scl_abi_version(void) { return 6; }
+int scl_abi_version(void) { return 7; }
 
 int scl_default_config(scl_config *c)
 {
@@ -3009,6 +3009,35 @@ int scl_pose_to_matrix(float x, float y, float z, float roll, float pitch, float
     return SCL_OK;
 }
 
+int scl_loop_guess_from_shift(int shift, int num_sector, const float pose_cur[6], const float pose_pre[6], float G[16])
+{
+    if (!pose_cur || !pose_pre || !G || num_sector < 1) return SCL_ERR_INVALID_ARG;
+    for (int k = 0; k < 6; ++k) if (!std::isfinite(pose_cur[k]) || !std::isfinite(pose_pre[k])) return SCL_ERR_INVALID_ARG;
+    auto pose_matrix = [](const float p[6], double R[9], double t[3]) {      /* scl_pose_to_matrix's entries, in double */
+        const double A = std::cos((double)p[5]), B = std::sin((double)p[5]), C = std::cos((double)p[4]), D = std::sin((double)p[4]);
+        const double E = std::cos((double)p[3]), F = std::sin((double)p[3]);
+        R[0] = A * C; R[1] = A * D * F - B * E; R[2] = B * F + A * D * E;
+        R[3] = B * C; R[4] = A * E + B * D * F; R[5] = B * D * E - A * F;
+        R[6] = -D;    R[7] = C * F;             R[8] = C * E;
+        t[0] = (double)p[0]; t[1] = (double)p[1]; t[2] = (double)p[2];
+    };
+    double Rc[9], tc[3], Rp[9], tp[3];
+    pose_matrix(pose_cur, Rc, tc);
+    pose_matrix(pose_pre, Rp, tp);
+    /* the candidate's columns shifted right by `shift` look like the query (D.h:1376-1378, 1559): the query turns by -shift sectors */
+    const int sh = ((shift % num_sector) + num_sector) % num_sector;
+    const double yaw = -(double)sh * 6.283185307179586476925286766559 / (double)num_sector;
+    const double cz = std::cos(yaw), sz = std::sin(yaw);
+    const double Rz[9] = {cz, -sz, 0.0, sz, cz, 0.0, 0.0, 0.0, 1.0};
+    double A[9], R[9], t[3];                                                 /* A = Rp * Rz, R = A * Rc^T, t = tp - R * tc */
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) A[3 * r + c] = (Rp[3 * r] * Rz[c] + Rp[3 * r + 1] * Rz[3 + c]) + Rp[3 * r + 2] * Rz[6 + c];
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) R[3 * r + c] = (A[3 * r] * Rc[3 * c] + A[3 * r + 1] * Rc[3 * c + 1]) + A[3 * r + 2] * Rc[3 * c + 2];
+    for (int r = 0; r < 3; ++r) t[r] = tp[r] - ((R[3 * r] * tc[0] + R[3 * r + 1] * tc[1]) + R[3 * r + 2] * tc[2]);
+    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) G[4 * r + c] = (float)R[3 * r + c]; G[4 * r + 3] = (float)t[r]; }
+    G[12] = 0.f; G[13] = 0.f; G[14] = 0.f; G[15] = 1.f;
+    return SCL_OK;
+}
+
 int scl_assemble_submap(scl_engine *e, const void *const *clouds, const int *counts, const float *transforms,
                         int n_clouds, int stride_bytes, float leaf, void *out, int out_capacity, int *n_out)
 {
@@ -3357,7 +3386,7 @@ namespace {
 // staged in icp_batch_ctl, target c on the device at d_tgts[c]; a candidate that is gated or has no point keeps what the caller
 // wrote (identity, zeros), the others go through icp_geometric_verification_batch in one chain
 int verification_round(scl_engine *e, int first, int m, int ns, const void *const *d_tgts, const int *n_tgts, const bool *gated, int stride,
-                       int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
+                       const float *guesses /* nullptr, or the call's n x 16 */, int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
                        float *T, int *success, int *n_correspondences, int *n_inliers)
 {
     IcpWorkspace *wss[scl_engine::kIcpBatch]; int which[scl_engine::kIcpBatch]; int live = 0;
@@ -3368,8 +3397,10 @@ int verification_round(scl_engine *e, int first, int m, int ns, const void *cons
     }
     if (live == 0) return SCL_OK;
     float Tl[16 * scl_engine::kIcpBatch]; int ok[scl_engine::kIcpBatch], nc[scl_engine::kIcpBatch], ni[scl_engine::kIcpBatch];
+    float g12[12 * scl_engine::kIcpBatch];                               // rows 0 .. 2 of the live candidates' guesses
+    if (guesses) for (int j = 0; j < live; ++j) std::memcpy(g12 + 12 * (size_t)j, guesses + 16 * (size_t)which[j], 12 * sizeof(float));
     std::string err;
-    int rc = icp_geometric_verification_batch(wss, live, &e->icp_batch_ctl, e->stream, ns, tg, tn, stride, ransac_iterations,
+    int rc = icp_geometric_verification_batch(wss, live, &e->icp_batch_ctl, e->stream, ns, tg, tn, stride, guesses ? g12 : nullptr, ransac_iterations,
                                               inlier_threshold, inlier_ratio, (unsigned long long)seed, Tl, ok, nc, ni, &err);
     if (rc) { e->last_error = err; return rc; }
     for (int j = 0; j < live; ++j) {
@@ -3392,12 +3423,98 @@ void verification_clear(int n, float *T, int *success, int *n_tgts, int *n_corre
     }
 }
 
+// the guessed calls' last checks (after everything the unguessed calls refuse) -> nullptr or the message
+const char *verification_guesses_bad(const float *guesses, int n)
+{
+    if (n > 0 && !guesses) return "guesses is NULL";
+    for (size_t k = 0; k < 16 * (size_t)n; ++k)
+        if ((k & 15) < 12 && !std::isfinite(guesses[k])) return "a guess has a non-finite entry in its first three rows";
+    return nullptr;
+}
+
+// T[c] = T_fit[c] * G_c with G_c's last row taken as (0, 0, 0, 1): the whole motion received cloud -> candidate.  Every entry in double,
+// ((a0 b0 + a1 b1) + a2 b2) + a3 b3, rounded once; no contraction (an fma would round differently).  T may be T_fit's own storage.
+void verification_compose(int n, const float *T_fit, const float *guesses, const char *skip, float *T)
+{
+#pragma clang fp contract(off)
+    for (int c = 0; c < n; ++c) {
+        const float *A = T_fit + 16 * (size_t)c, *G = guesses + 16 * (size_t)c;
+        float out[16];
+        for (int r = 0; r < 4; ++r)
+            for (int k = 0; k < 4; ++k) {
+                const double a0 = A[4 * r], a1 = A[4 * r + 1], a2 = A[4 * r + 2], a3 = A[4 * r + 3];
+                const double b0 = G[k], b1 = G[4 + k], b2 = G[8 + k], b3 = k == 3 ? 1.0 : 0.0;
+                const double p0 = a0 * b0, p1 = a1 * b1, p2 = a2 * b2, p3 = a3 * b3;
+                out[4 * r + k] = (float)(((p0 + p1) + p2) + p3);
+            }
+        std::memcpy(T + 16 * (size_t)c, skip && skip[c] ? A : out, sizeof out);
+    }
+}
+
+int verification_batch_host(scl_engine *e, const void *src, int n_src,
+                            const void *const *tgts, const int *n_tgts, int n_targets, int stride_bytes, const float *guesses, bool guessed,
+                            int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
+                            float *T, float *T_fit, int *success, int *n_correspondences, int *n_inliers);
+int verification_batch_store(scl_engine *e, const void *src, int n_src, int stride_bytes, float src_leaf,
+                             int robot, int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                             const float *guesses, bool guessed, int min_src_points, int min_tgt_points,
+                             int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
+                             float *T, float *T_fit, int *success, int *n_src_filtered, int *n_tgts,
+                             int *n_correspondences, int *n_inliers);
+
 }  // namespace
 
 int scl_geometric_verification_batch(scl_engine *e, const void *src, int n_src,
                                      const void *const *tgts, const int *n_tgts, int n_targets, int stride_bytes,
                                      int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
                                      float *T, int *success, int *n_correspondences, int *n_inliers)
+{
+    return verification_batch_host(e, src, n_src, tgts, n_tgts, n_targets, stride_bytes, nullptr, false, ransac_iterations, inlier_threshold,
+                                   inlier_ratio, seed, T, nullptr, success, n_correspondences, n_inliers);
+}
+
+int scl_geometric_verification_batch_guess(scl_engine *e, const void *src, int n_src,
+                                           const void *const *tgts, const int *n_tgts, int n_targets, int stride_bytes,
+                                           const float *guesses,
+                                           int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
+                                           float *T, float *T_fit, int *success, int *n_correspondences, int *n_inliers)
+{
+    return verification_batch_host(e, src, n_src, tgts, n_tgts, n_targets, stride_bytes, guesses, true, ransac_iterations, inlier_threshold,
+                                   inlier_ratio, seed, T, T_fit, success, n_correspondences, n_inliers);
+}
+
+int scl_geometric_verification_batch_from_store(scl_engine *e, const void *src, int n_src, int stride_bytes, float src_leaf,
+                                                int robot, int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                                                int min_src_points, int min_tgt_points,
+                                                int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
+                                                float *T, int *success, int *n_src_filtered, int *n_tgts,
+                                                int *n_correspondences, int *n_inliers)
+{
+    return verification_batch_store(e, src, n_src, stride_bytes, src_leaf, robot, n_candidates, keys_pre, search_num, poses_pre, leaf, nullptr, false,
+                                    min_src_points, min_tgt_points, ransac_iterations, inlier_threshold, inlier_ratio, seed,
+                                    T, nullptr, success, n_src_filtered, n_tgts, n_correspondences, n_inliers);
+}
+
+int scl_geometric_verification_batch_from_store_guess(scl_engine *e, const void *src, int n_src, int stride_bytes, float src_leaf,
+                                                      int robot, int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                                                      const float *guesses,
+                                                      int min_src_points, int min_tgt_points,
+                                                      int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
+                                                      float *T, float *T_fit, int *success, int *n_src_filtered, int *n_tgts,
+                                                      int *n_correspondences, int *n_inliers)
+{
+    return verification_batch_store(e, src, n_src, stride_bytes, src_leaf, robot, n_candidates, keys_pre, search_num, poses_pre, leaf, guesses, true,
+                                    min_src_points, min_tgt_points, ransac_iterations, inlier_threshold, inlier_ratio, seed,
+                                    T, T_fit, success, n_src_filtered, n_tgts, n_correspondences, n_inliers);
+}
+
+namespace {
+
+// scl_geometric_verification_batch (guessed == false: guesses and T_fit are not looked at) and scl_geometric_verification_batch_guess
+int verification_batch_host(scl_engine *e, const void *src, int n_src,
+                            const void *const *tgts, const int *n_tgts, int n_targets, int stride_bytes, const float *guesses, bool guessed,
+                            int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
+                            float *T, float *T_fit, int *success, int *n_correspondences, int *n_inliers)
 {
     if (!e || n_targets < 0 || (!src && n_src > 0) || (n_targets > 0 && (!tgts || !n_tgts || !T))) return SCL_ERR_INVALID_ARG;
     if (e->front) e = front_primary(e);
@@ -3406,14 +3523,15 @@ int scl_geometric_verification_batch(scl_engine *e, const void *src, int n_src,
     for (int c = 0; c < n_targets; ++c)
         if (n_tgts[c] < 0 || (!tgts[c] && n_tgts[c] > 0)) return fail(e, SCL_ERR_INVALID_ARG, "geometric_verification_batch: bad target");
     if (n_src >= 3 && (ransac_iterations < 1 || ransac_iterations > (1 << 20))) return fail(e, SCL_ERR_INVALID_ARG, "ransac iterations out of range");
+    if (guessed) if (const char *bad = verification_guesses_bad(guesses, n_targets)) return fail(e, SCL_ERR_INVALID_ARG, (std::string("geometric_verification_batch_guess: ") + bad).c_str());
     if (n_targets == 0) return SCL_OK;
     (void)hipSetDevice(e->device);
     verification_clear(n_targets, T, success, nullptr, n_correspondences, n_inliers);
-    if (n_src < 1) return SCL_OK;                                          // no pair at all
     std::string err;
-    int rc = icp_stage_cloud_host(&e->icp_batch_ctl, e->stream, false, src, n_src, stride_bytes, &err);   // once per call
+    int rc = SCL_OK;
+    if (n_src >= 1) rc = icp_stage_cloud_host(&e->icp_batch_ctl, e->stream, false, src, n_src, stride_bytes, &err);   // once per call (none: no pair at all)
     if (rc) { e->last_error = err; return rc; }
-    for (int first = 0; first < n_targets; first += scl_engine::kIcpBatch) {
+    for (int first = 0; n_src >= 1 && first < n_targets; first += scl_engine::kIcpBatch) {
         const int m = n_targets - first < scl_engine::kIcpBatch ? n_targets - first : scl_engine::kIcpBatch;
         const void *d_tgts[scl_engine::kIcpBatch]; bool gated[scl_engine::kIcpBatch];
         for (int c = 0; c < m; ++c) {
@@ -3423,19 +3541,24 @@ int scl_geometric_verification_batch(scl_engine *e, const void *src, int n_src,
             if (rc) { e->last_error = err; return rc; }
             d_tgts[c] = icp_staged_cloud(&e->icp_batch_ws[c], true);
         }
-        rc = verification_round(e, first, m, n_src, d_tgts, n_tgts + first, gated, stride_bytes, ransac_iterations, inlier_threshold,
-                                inlier_ratio, seed, T, success, n_correspondences, n_inliers);
+        rc = verification_round(e, first, m, n_src, d_tgts, n_tgts + first, gated, stride_bytes, guessed ? guesses : nullptr, ransac_iterations,
+                                inlier_threshold, inlier_ratio, seed, T, success, n_correspondences, n_inliers);
         if (rc) return rc;
+    }
+    if (guessed) {                                                         // the chain answered the fits: T = fit * guess, on the host
+        if (T_fit) std::memcpy(T_fit, T, sizeof(float) * 16 * (size_t)n_targets);
+        verification_compose(n_targets, T, guesses, nullptr, T);
     }
     return SCL_OK;
 }
 
-int scl_geometric_verification_batch_from_store(scl_engine *e, const void *src, int n_src, int stride_bytes, float src_leaf,
-                                                int robot, int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
-                                                int min_src_points, int min_tgt_points,
-                                                int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
-                                                float *T, int *success, int *n_src_filtered, int *n_tgts,
-                                                int *n_correspondences, int *n_inliers)
+// scl_geometric_verification_batch_from_store (guessed == false) and scl_geometric_verification_batch_from_store_guess
+int verification_batch_store(scl_engine *e, const void *src, int n_src, int stride_bytes, float src_leaf,
+                             int robot, int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                             const float *guesses, bool guessed, int min_src_points, int min_tgt_points,
+                             int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
+                             float *T, float *T_fit, int *success, int *n_src_filtered, int *n_tgts,
+                             int *n_correspondences, int *n_inliers)
 {
     if (!e || n_candidates < 0 || (!src && n_src > 0) || (n_candidates > 0 && (!keys_pre || !poses_pre || !T))) return SCL_ERR_INVALID_ARG;
     if (e->front) e = front_primary(e);
@@ -3455,11 +3578,14 @@ int scl_geometric_verification_batch_from_store(scl_engine *e, const void *src, 
         cl_all.insert(cl_all.end(), clouds.begin(), clouds.end()); cn_all.insert(cn_all.end(), counts.begin(), counts.end()); tw_all.insert(tw_all.end(), Tw.begin(), Tw.end());
         first_of.push_back((int)cl_all.size());
     }
+    if (guessed) if (const char *bad = verification_guesses_bad(guesses, n_candidates)) return fail(e, SCL_ERR_INVALID_ARG, (std::string("geometric_verification_batch_from_store_guess: ") + bad).c_str());
     (void)hipSetDevice(e->device);
     std::string err;
     int ns = 0;
     const void *d_res = nullptr;
-    // received cloud: downSizeFilterICP (DM.h:1199-1201), filtered and placed once per call; it stays on the device
+    std::vector<char> gated_all((size_t)n_candidates + 1, 0);
+    // received cloud: downSizeFilterICP (DM.h:1199-1201), filtered and placed once per call; it stays on the device (a guess moves
+    // the filtered cloud, per candidate)
     rc = voxel_grid_to_device(&e->vox_ws, e->stream, src, n_src, stride, src_leaf, &d_res, &ns, &err);
     if (!rc) rc = icp_stage_cloud(&e->icp_batch_ctl, e->stream, false, d_res, ns, stride, &err);
     if (rc) { e->last_error = err; return rc; }
@@ -3478,14 +3604,20 @@ int scl_geometric_verification_batch_from_store(scl_engine *e, const void *src, 
         if (rc) { e->last_error = err; return rc; }
         for (int c = 0; c < m; ++c) {
             if (n_tgts) n_tgts[first + c] = n_sub[c];
-            gated[c] = ns < min_src_points || n_sub[c] < min_tgt_points;   // DM.h:1204: clouds too small
+            gated_all[(size_t)(first + c)] = gated[c] = ns < min_src_points || n_sub[c] < min_tgt_points;   // DM.h:1204: clouds too small
         }
-        rc = verification_round(e, first, m, ns, d_sub, n_sub, gated, stride, ransac_iterations, inlier_threshold, inlier_ratio, seed,
-                                T, success, n_correspondences, n_inliers);
+        rc = verification_round(e, first, m, ns, d_sub, n_sub, gated, stride, guessed ? guesses : nullptr, ransac_iterations, inlier_threshold,
+                                inlier_ratio, seed, T, success, n_correspondences, n_inliers);
         if (rc) return rc;
+    }
+    if (guessed) {                                                         // (a gated candidate keeps T = T_fit = identity)
+        if (T_fit) std::memcpy(T_fit, T, sizeof(float) * 16 * (size_t)n_candidates);
+        verification_compose(n_candidates, T, guesses, gated_all.data(), T);
     }
     return SCL_OK;
 }
+
+}  // namespace
 
 /* ---- measurement ------------------------------------------------------------- */
 

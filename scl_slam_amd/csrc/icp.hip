@@ -423,7 +423,7 @@ __global__ __launch_bounds__(256) void nn_search_kernel_t(float4 *work, int n_sr
 // ---- K5 ----------------------------------------------------------------------------
 // sums of [p;1][q;1]^T (16) and of d2 over the accepted correspondences.
 // mode 0: pairs (i, nn_idx[i]) with d2 <= maxd2, p from `work`;  mode 1: explicit pairs (si[k], ti[k]).
-__device__ __forceinline__ void corr_reduce_kernel_body(const float4 *work, const unsigned char *src_raw,
+__device__ __forceinline__ void corr_reduce_kernel_body(const float4 *work, const unsigned char *src_raw, int sstride,
                                                           const unsigned char *tgt_raw, int stride, int n,
                                                           const int *nn_idx, const float *nn_d2, float maxd2,
                                                           const int *si, const int *ti, int mode,
@@ -431,7 +431,9 @@ __device__ __forceinline__ void corr_reduce_kernel_body(const float4 *work, cons
                                                           int block, int nblocks)
 {
     // (block, nblocks): this workgroup's place among those that share the n correspondences -- blockIdx.x of gridDim.x in a launch
-    //  of its own; the batched verification gives every candidate a count of its own (verify_reduce_batch_kernel)
+    //  of its own; the batched verification gives every candidate a count of its own (verify_reduce_batch_kernel).
+    // sstride: the record size of src_raw (mode 1), `stride` everywhere but in the guessed verification batch, whose sources are
+    //  float4 working clouds
     if (check_done && st->done) return;
     double acc[kNSum];
 #pragma unroll
@@ -449,7 +451,7 @@ __device__ __forceinline__ void corr_reduce_kernel_body(const float4 *work, cons
             q = load_xyz(tgt_raw, j, stride);
         } else {
             if (nn_idx && nn_idx[i] == 0) continue;          // mode 1: nn_idx doubles as an optional inlier mask
-            p = load_xyz(src_raw, si[i], stride);
+            p = load_xyz(src_raw, si[i], sstride);
             q = load_xyz(tgt_raw, ti[i], stride);
         }
         const double pv[4] = {(double)p.x, (double)p.y, (double)p.z, 1.0};
@@ -479,7 +481,7 @@ __global__ __launch_bounds__(256) void corr_reduce_kernel(const float4 *work, co
                                                           const int *si, const int *ti, int mode,
                                                           const IcpState *st, double *partials, int check_done)
 {
-    corr_reduce_kernel_body(work, src_raw, tgt_raw, stride, n, nn_idx, nn_d2, maxd2, si, ti, mode, st, partials, check_done, blockIdx.x, gridDim.x);
+    corr_reduce_kernel_body(work, src_raw, stride, tgt_raw, stride, n, nn_idx, nn_d2, maxd2, si, ti, mode, st, partials, check_done, blockIdx.x, gridDim.x);
 }
 
 // MFMA form of K5.  v_mfma_f64_4x4x4_4b_f64 computes, in each of its four 16-lane blocks,
@@ -488,7 +490,7 @@ __global__ __launch_bounds__(256) void corr_reduce_kernel(const float4 *work, co
 // [q;1] for correspondence k of the block, one instruction adds the augmented outer products of 16
 // correspondences: cross-covariance, both centroids and the count at once.  Operand layout (probed):
 // A[i][k] of block b sits in lane 16k + 4b + i, B[k][j] in lane 16k + 4b + j, D[i][j] in lane 16i + 4b + j.
-__device__ __forceinline__ void corr_reduce_mfma_kernel_body(const float4 *work, const unsigned char *src_raw,
+__device__ __forceinline__ void corr_reduce_mfma_kernel_body(const float4 *work, const unsigned char *src_raw, int sstride,
                                                                const unsigned char *tgt_raw, int stride, int n,
                                                                const int *nn_idx, const float *nn_d2, float maxd2,
                                                                const int *si, const int *ti, int mode,
@@ -518,7 +520,7 @@ __device__ __forceinline__ void corr_reduce_mfma_kernel_body(const float4 *work,
                     if (comp == 3) { pc = 1.0f; qc = 1.0f; }
                     else {
                         pc = mode == 0 ? reinterpret_cast<const float *>(work + pi)[comp]
-                                       : reinterpret_cast<const float *>(src_raw + (size_t)pi * stride)[comp];
+                                       : reinterpret_cast<const float *>(src_raw + (size_t)pi * sstride)[comp];
                         qc = reinterpret_cast<const float *>(tgt_raw + (size_t)qi * stride)[comp];
                     }
                     av = (double)pc; bv = (double)qc;
@@ -548,7 +550,7 @@ __global__ __launch_bounds__(256) void corr_reduce_mfma_kernel(const float4 *wor
                                                                const int *si, const int *ti, int mode,
                                                                const IcpState *st, double *partials, int check_done)
 {
-    corr_reduce_mfma_kernel_body(work, src_raw, tgt_raw, stride, n, nn_idx, nn_d2, maxd2, si, ti, mode, st, partials, check_done, blockIdx.x, gridDim.x);
+    corr_reduce_mfma_kernel_body(work, src_raw, stride, tgt_raw, stride, n, nn_idx, nn_d2, maxd2, si, ti, mode, st, partials, check_done, blockIdx.x, gridDim.x);
 }
 
 // ---- K5b ---------------------------------------------------------------------------
@@ -1037,6 +1039,13 @@ __global__ void work_init_kernel(const unsigned char *src, int n, int stride, fl
     if (i < n) { const float3 p = load_xyz(src, i, stride); work[i] = make_float4(p.x, p.y, p.z, 0.f); }
 }
 
+// paramsServer::transformPointCloud's arithmetic on one point (DM.h:247-249), rows 0 .. 2 of a row-major 4x4: the one body of
+// raw_transform_kernel and guess_move_batch_kernel, whose values must agree bit for bit
+__device__ __forceinline__ float3 transform_xyz(const float *T, float x, float y, float z)
+{
+    return make_float3(T[0] * x + T[1] * y + T[2] * z + T[3], T[4] * x + T[5] * y + T[6] * z + T[7], T[8] * x + T[9] * y + T[10] * z + T[11]);
+}
+
 __global__ void raw_transform_kernel(const unsigned char *in, unsigned char *out, int n, int stride, const float *T)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1047,9 +1056,8 @@ __global__ void raw_transform_kernel(const unsigned char *in, unsigned char *out
     const float x = f[0], y = f[1], z = f[2];
     float *o = reinterpret_cast<float *>(po);
     for (int k = 3; k < stride / 4; ++k) o[k] = f[k];                        // intensity & padding copied (DM.h:250)
-    o[0] = T[0] * x + T[1] * y + T[2] * z + T[3];
-    o[1] = T[4] * x + T[5] * y + T[6] * z + T[7];
-    o[2] = T[8] * x + T[9] * y + T[10] * z + T[11];
+    const float3 q = transform_xyz(T, x, y, z);
+    o[0] = q.x; o[1] = q.y; o[2] = q.z;
 }
 
 __device__ __forceinline__ void state_init_body(IcpState *st)
@@ -1125,7 +1133,7 @@ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x)
     return x ^ (x >> 31);
 }
 
-__device__ void ransac_model(const unsigned char *src, const unsigned char *tgt, int stride, const int *si, const int *ti,
+__device__ void ransac_model(const unsigned char *src, int sstride, const unsigned char *tgt, int stride, const int *si, const int *ti,
                              int n, unsigned long long seed, int h, double T[12])
 {
     int idx[3];
@@ -1140,7 +1148,7 @@ __device__ void ransac_model(const unsigned char *src, const unsigned char *tgt,
     }
     double pm[3] = {0, 0, 0}, qm[3] = {0, 0, 0}, P[3][3], Q[3][3];
     for (int i = 0; i < 3; ++i) {
-        const float3 p = load_xyz(src, si[idx[i]], stride), q = load_xyz(tgt, ti[idx[i]], stride);
+        const float3 p = load_xyz(src, si[idx[i]], sstride), q = load_xyz(tgt, ti[idx[i]], stride);
         P[i][0] = p.x; P[i][1] = p.y; P[i][2] = p.z; Q[i][0] = q.x; Q[i][1] = q.y; Q[i][2] = q.z;
         for (int a = 0; a < 3; ++a) { pm[a] += P[i][a]; qm[a] += Q[i][a]; }
     }
@@ -1164,7 +1172,7 @@ __device__ __forceinline__ bool ransac_inlier(const double *T, float3 p, float3 
     return (dx * dx + dy * dy) + dz * dz < thr2;
 }
 
-__device__ __forceinline__ void ransac_score_body(const unsigned char *src, const unsigned char *tgt, int stride,
+__device__ __forceinline__ void ransac_score_body(const unsigned char *src, int sstride, const unsigned char *tgt, int stride,
                                                   const int *si, const int *ti, int n, unsigned long long seed,
                                                   int n_hyp, double thr2, int *counts)
 {
@@ -1173,7 +1181,7 @@ __device__ __forceinline__ void ransac_score_body(const unsigned char *src, cons
     const int h0 = blockIdx.x * kHypPerBlock;
     if (threadIdx.x < kHypPerBlock) {
         scnt[threadIdx.x] = 0;
-        if (h0 + (int)threadIdx.x < n_hyp) ransac_model(src, tgt, stride, si, ti, n, seed, h0 + threadIdx.x, sT[threadIdx.x]);
+        if (h0 + (int)threadIdx.x < n_hyp) ransac_model(src, sstride, tgt, stride, si, ti, n, seed, h0 + threadIdx.x, sT[threadIdx.x]);
         else for (int k = 0; k < 12; ++k) sT[threadIdx.x][k] = 0.0;
     }
     __syncthreads();
@@ -1181,7 +1189,7 @@ __device__ __forceinline__ void ransac_score_body(const unsigned char *src, cons
 #pragma unroll
     for (int u = 0; u < kHypPerBlock; ++u) cnt[u] = 0;
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const float3 p = load_xyz(src, si[i], stride), q = load_xyz(tgt, ti[i], stride);
+        const float3 p = load_xyz(src, si[i], sstride), q = load_xyz(tgt, ti[i], stride);
 #pragma unroll
         for (int u = 0; u < kHypPerBlock; ++u) cnt[u] += ransac_inlier(sT[u], p, q, thr2) ? 1 : 0;
     }
@@ -1199,7 +1207,7 @@ __global__ __launch_bounds__(256) void ransac_score_kernel(const unsigned char *
                                                            const int *si, const int *ti, int n, unsigned long long seed,
                                                            int n_hyp, double thr2, int *counts)
 {
-    ransac_score_body(src, tgt, stride, si, ti, n, seed, n_hyp, thr2, counts);
+    ransac_score_body(src, stride, tgt, stride, si, ti, n, seed, n_hyp, thr2, counts);
 }
 
 // best hypothesis (most inliers, ties -> lowest index), its model, and the inlier mask
@@ -1223,25 +1231,25 @@ __device__ __forceinline__ void ransac_pick_body(const int *counts, int n_hyp, i
 }
 __global__ void ransac_pick_kernel(const int *counts, int n_hyp, int *best) { ransac_pick_body(counts, n_hyp, best); }
 
-__device__ __forceinline__ void ransac_mask_body(const unsigned char *src, const unsigned char *tgt, int stride,
+__device__ __forceinline__ void ransac_mask_body(const unsigned char *src, int sstride, const unsigned char *tgt, int stride,
                                                  const int *si, const int *ti, int n, unsigned long long seed,
                                                  const int *best, double thr2, int *mask, double *T_out /* may be nullptr */)
 {
     __shared__ double sT[12];
     if (threadIdx.x == 0) {
-        if (best[0] >= 0) ransac_model(src, tgt, stride, si, ti, n, seed, best[0], sT);
+        if (best[0] >= 0) ransac_model(src, sstride, tgt, stride, si, ti, n, seed, best[0], sT);
         else for (int k = 0; k < 12; ++k) sT[k] = (k % 5 == 0) ? 1.0 : 0.0;
         if (T_out && blockIdx.x == 0) for (int k = 0; k < 12; ++k) T_out[k] = sT[k];
     }
     __syncthreads();
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-        mask[i] = ransac_inlier(sT, load_xyz(src, si[i], stride), load_xyz(tgt, ti[i], stride), thr2) ? 1 : 0;
+        mask[i] = ransac_inlier(sT, load_xyz(src, si[i], sstride), load_xyz(tgt, ti[i], stride), thr2) ? 1 : 0;
 }
 __global__ __launch_bounds__(256) void ransac_mask_kernel(const unsigned char *src, const unsigned char *tgt, int stride,
                                                           const int *si, const int *ti, int n, unsigned long long seed,
                                                           const int *best, double thr2, int *mask, double *T_out)
 {
-    ransac_mask_body(src, tgt, stride, si, ti, n, seed, best, thr2, mask, T_out);
+    ransac_mask_body(src, stride, tgt, stride, si, ti, n, seed, best, thr2, mask, T_out);
 }
 
 // The pairs of the verification path: every source whose search found a neighbour (nn[i] >= 0; a source with a non-finite
@@ -1964,6 +1972,7 @@ __global__ void gather_states_kernel(const IcpProblem *pr, int nprob, IcpState *
 // Every value comes from the single path's bodies over the single path's partition of the pairs: candidate c's answer is the
 // single call's, bit for bit.
 struct VerifyJob {
+    const unsigned char *src; int sstride;                   // the candidate's source: the staged cloud (its stride), or with a guess its own moved float4 cloud (16)
     const unsigned char *tgt; IcpState *st; const int *nni;
     int *si, *ti, *mask;                                     // pairs in source order and their inlier flags (n_src entries each)
     int *counts, *best, *n_corr;                             // inliers per hypothesis, {best hypothesis, its inliers}, pairs
@@ -2008,13 +2017,13 @@ __global__ __launch_bounds__(1024) void verify_pairs_batch_kernel(const VerifyJo
     if (t == 0) *j.n_corr = carry;
 }
 
-__global__ __launch_bounds__(256) void ransac_score_batch_kernel(const VerifyJob *jobs, const unsigned char *src, int stride, int n_src,
+__global__ __launch_bounds__(256) void ransac_score_batch_kernel(const VerifyJob *jobs, int stride, int n_src,
                                                                  unsigned long long seed, int n_hyp, double thr2)
 {
     const VerifyJob j = jobs[blockIdx.y];
     const int n = verify_pairs(j, n_src);
     if (n < 3) return;
-    ransac_score_body(src, j.tgt, stride, j.si, j.ti, n, seed, n_hyp, thr2, j.counts);
+    ransac_score_body(j.src, j.sstride, j.tgt, stride, j.si, j.ti, n, seed, n_hyp, thr2, j.counts);
 }
 
 __global__ __launch_bounds__(256) void ransac_pick_batch_kernel(const VerifyJob *jobs, int n_src, int n_hyp)
@@ -2025,13 +2034,13 @@ __global__ __launch_bounds__(256) void ransac_pick_batch_kernel(const VerifyJob 
 }
 
 // (the grid is sized for n_src pairs: a candidate's surplus workgroups leave before they form the model)
-__global__ __launch_bounds__(256) void ransac_mask_batch_kernel(const VerifyJob *jobs, const unsigned char *src, int stride, int n_src,
+__global__ __launch_bounds__(256) void ransac_mask_batch_kernel(const VerifyJob *jobs, int stride, int n_src,
                                                                 unsigned long long seed, double thr2)
 {
     const VerifyJob j = jobs[blockIdx.y];
     const int n = verify_pairs(j, n_src);
     if (n < 3 || (long long)blockIdx.x * blockDim.x >= n) return;
-    ransac_mask_body(src, j.tgt, stride, j.si, j.ti, n, seed, j.best, thr2, j.mask, nullptr);
+    ransac_mask_body(j.src, j.sstride, j.tgt, stride, j.si, j.ti, n, seed, j.best, thr2, j.mask, nullptr);
 }
 
 // The masked covariance of a candidate's inliers (DM.h:1228-1230).  Its sums depend on how many workgroups share the pairs: the
@@ -2044,15 +2053,15 @@ __device__ __forceinline__ int verify_red_blocks(int n)
 }
 
 template <bool MFMA>
-__global__ __launch_bounds__(256) void verify_reduce_batch_kernel(const VerifyJob *jobs, const unsigned char *src, int stride, int n_src)
+__global__ __launch_bounds__(256) void verify_reduce_batch_kernel(const VerifyJob *jobs, int stride, int n_src)
 {
     const VerifyJob j = jobs[blockIdx.y];
     const int n = verify_pairs(j, n_src);
     if (n < 3 || j.best[1] < 3) return;
     const int rb = verify_red_blocks(n);
     if ((int)blockIdx.x >= rb) return;
-    if (MFMA) corr_reduce_mfma_kernel_body(nullptr, src, j.tgt, stride, n, j.mask, nullptr, 0.f, j.si, j.ti, 1, j.st, j.part, 0, (int)blockIdx.x, rb);
-    else corr_reduce_kernel_body(nullptr, src, j.tgt, stride, n, j.mask, nullptr, 0.f, j.si, j.ti, 1, j.st, j.part, 0, (int)blockIdx.x, rb);
+    if (MFMA) corr_reduce_mfma_kernel_body(nullptr, j.src, j.sstride, j.tgt, stride, n, j.mask, nullptr, 0.f, j.si, j.ti, 1, j.st, j.part, 0, (int)blockIdx.x, rb);
+    else corr_reduce_kernel_body(nullptr, j.src, j.sstride, j.tgt, stride, n, j.mask, nullptr, 0.f, j.si, j.ti, 1, j.st, j.part, 0, (int)blockIdx.x, rb);
 }
 
 // state, one-shot solve over the candidate's rb records (T stays the identity below three inliers) and the candidate's answer
@@ -2069,6 +2078,24 @@ __global__ __launch_bounds__(64) void verify_solve_batch_kernel(const VerifyJob 
         o.n_corr = n; o.n_inl = n_inl;
         for (int k = 0; k < 16; ++k) o.T[k] = j.st->final_T[k];
     }
+}
+
+// The guessed batch: candidate blockIdx.y's source is the staged cloud moved by its own initial guess (guesses: 12 floats per
+// candidate, rows 0 .. 2 of G_c), written as a float4 working cloud in SOURCE order.  The cold search reads it as p.work, the
+// RANSAC and covariance bodies as records of 16 bytes through load_xyz.  A streaming kernel: one point per thread, one 16-byte
+// store; the guess is uniform over the workgroup and sits in scalar registers.
+__global__ __launch_bounds__(256) void guess_move_batch_kernel(const IcpProblem *__restrict__ pr, const unsigned char *__restrict__ src,
+                                                               int n, int stride, const float *__restrict__ guesses)
+{
+    float4 *__restrict__ work = pr[blockIdx.y].work;
+    float g[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) g[k] = guesses[12 * blockIdx.y + k];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float3 p = load_xyz(src, i, stride);
+    const float3 q = transform_xyz(g, p.x, p.y, p.z);
+    work[i] = make_float4(q.x, q.y, q.z, 0.f);
 }
 
 
@@ -2840,8 +2867,11 @@ const void *icp_staged_cloud(const IcpWorkspace *ws, bool target) { return ws->b
 // geometricVerificationService's core for m candidates of one source: the source staged in ctl (icp_stage_cloud*), the targets on
 // the device and read in place, every candidate with at least one point (and n_src >= 1): the caller answers the others itself.
 // One chain of launches over all candidates, one wait.  Outputs have m entries, none may be nullptr.
+// guesses (nullptr: none) = 12 floats per candidate, rows 0 .. 2 of its initial guess: candidate c's source is then the staged cloud
+// moved by it (scl_transform_cloud's values), a float4 working cloud of its own in wss[c] (16 bytes x n_src per candidate); without
+// guesses the one working cloud in ctl serves all and the raw staged cloud is every candidate's source.
 int icp_geometric_verification_batch(IcpWorkspace *const *wss, int m, IcpWorkspace *ctl, hipStream_t stream, int n_src,
-                                     const void *const *d_tgts, const int *n_tgts, int stride, int ransac_iterations,
+                                     const void *const *d_tgts, const int *n_tgts, int stride, const float *guesses, int ransac_iterations,
                                      double inlier_threshold, double inlier_ratio, unsigned long long seed, float *T, int *success,
                                      int *n_corr_out, int *n_inliers_out, std::string *err)
 {
@@ -2857,9 +2887,9 @@ int icp_geometric_verification_batch(IcpWorkspace *const *wss, int m, IcpWorkspa
     const int n_hyp = sample ? ransac_iterations : 0;
     const GridJob *dj = nullptr;
     int max_n = 0;
-    if ((rc = ensure(ctl, B_WORK, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
+    if (!guesses && (rc = ensure(ctl, B_WORK, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
     if ((rc = ensure(ctl, B_MASK, sizeof(IcpProblem) * (size_t)m, err))) return rc;
-    if ((rc = ensure(ctl, B_PAIR, (sizeof(VerifyJob) + sizeof(VerifyOut)) * (size_t)m, err))) return rc;
+    if ((rc = ensure(ctl, B_PAIR, (sizeof(VerifyJob) + sizeof(VerifyOut) + (guesses ? sizeof(float) * 12 : 0)) * (size_t)m, err))) return rc;
     if ((rc = pinned(ctl, sizeof(VerifyOut) * (size_t)m, err))) return rc;
     for (int c = 0; c < m; ++c) {
         IcpWorkspace *ws = wss[c];
@@ -2870,12 +2900,13 @@ int icp_geometric_verification_batch(IcpWorkspace *const *wss, int m, IcpWorkspa
         if ((rc = ensure(ws, B_MASK, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
         if ((rc = ensure(ws, B_HYP, sizeof(int) * (size_t)(n_hyp + 8), err))) return rc;
         if ((rc = ensure(ws, B_PART, sizeof(double) * kNSum * kRedBlocks, err))) return rc;
+        if (guesses && (rc = ensure(ws, B_WORK, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
     }
     const unsigned char *d_src = static_cast<const unsigned char *>(ctl->buf[B_SRC]);
-    float4 *work = static_cast<float4 *>(ctl->buf[B_WORK]);
+    float4 *work = guesses ? nullptr : static_cast<float4 *>(ctl->buf[B_WORK]);
     const int pb = (n_src + 255) / 256;
     // the working cloud in SOURCE order (the pairs are defined in it), one for all candidates: the cold search only reads it
-    hipLaunchKernelGGL(work_init_kernel, dim3(pb), dim3(256), 0, stream, d_src, n_src, stride, work);
+    if (!guesses) hipLaunchKernelGGL(work_init_kernel, dim3(pb), dim3(256), 0, stream, d_src, n_src, stride, work);
     if ((rc = grid_build_batch(wss, m, ctl, stream, d_tgts, n_tgts, stride, false, &dj, &max_n, err))) return rc;
     std::vector<IcpProblem> hp((size_t)m);
     std::vector<VerifyJob> hj((size_t)m);
@@ -2883,10 +2914,11 @@ int icp_geometric_verification_batch(IcpWorkspace *const *wss, int m, IcpWorkspa
         IcpWorkspace *ws = wss[c];
         IcpProblem &p = hp[(size_t)c];
         std::memset(&p, 0, sizeof(p));
-        p.work = work; p.st = (IcpState *)ws->buf[B_STATE]; p.cell_start = (const int *)ws->buf[B_CSTART];
+        p.work = guesses ? static_cast<float4 *>(ws->buf[B_WORK]) : work; p.st = (IcpState *)ws->buf[B_STATE]; p.cell_start = (const int *)ws->buf[B_CSTART];
         p.sorted = (const float4 *)ws->buf[B_TSORT]; p.nni = (int *)ws->buf[B_NNI]; p.nnd = (float *)ws->buf[B_NND];
         p.tgt = static_cast<const unsigned char *>(d_tgts[c]); p.n_tgt = n_tgts[c];
         VerifyJob &j = hj[(size_t)c];
+        j.src = guesses ? reinterpret_cast<const unsigned char *>(p.work) : d_src; j.sstride = guesses ? (int)sizeof(float4) : stride;
         j.tgt = p.tgt; j.st = p.st; j.nni = p.nni;
         j.si = (int *)ws->buf[B_SI]; j.ti = (int *)ws->buf[B_TI]; j.mask = (int *)ws->buf[B_MASK];
         j.counts = (int *)ws->buf[B_HYP]; j.best = j.counts + n_hyp + 2; j.n_corr = j.counts + n_hyp + 4;
@@ -2897,6 +2929,11 @@ int icp_geometric_verification_batch(IcpWorkspace *const *wss, int m, IcpWorkspa
     const IcpProblem *dp = static_cast<const IcpProblem *>(ctl->buf[B_MASK]);
     ICP_HIP(hipMemcpyAsync(ctl->buf[B_MASK], hp.data(), sizeof(IcpProblem) * (size_t)m, hipMemcpyHostToDevice, stream));   // (pageable: staged before the call returns)
     ICP_HIP(hipMemcpyAsync(djobs, hj.data(), sizeof(VerifyJob) * (size_t)m, hipMemcpyHostToDevice, stream));
+    if (guesses) {                                                                                 // every candidate's own source, one launch
+        float *dg = reinterpret_cast<float *>(dout + m);
+        ICP_HIP(hipMemcpyAsync(dg, guesses, sizeof(float) * 12 * (size_t)m, hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(guess_move_batch_kernel, dim3(pb, m), dim3(256), 0, stream, dp, d_src, n_src, stride, (const float *)dg);
+    }
     hipLaunchKernelGGL(nn_search_batch_kernel<kNnGroup>, dim3((unsigned)(((long long)n_src * kNnGroup + 255) / 256), m), dim3(256), 0, stream,
                        dp, n_src, 0, -1, stride, 0);                                               // DM.h:1211-1215, cold
     hipLaunchKernelGGL(verify_pairs_batch_kernel, dim3(m), dim3(1024), 0, stream, djobs, n_src);
@@ -2904,12 +2941,12 @@ int icp_geometric_verification_batch(IcpWorkspace *const *wss, int m, IcpWorkspa
         const double thr2 = inlier_threshold * inlier_threshold;
         const int hb = (n_hyp + kHypPerBlock - 1) / kHypPerBlock;
         int mb = pb > 1024 ? 1024 : pb;
-        hipLaunchKernelGGL(ransac_score_batch_kernel, dim3(hb, m), dim3(256), 0, stream, djobs, d_src, stride, n_src, seed, n_hyp, thr2);   // DM.h:1218-1225
+        hipLaunchKernelGGL(ransac_score_batch_kernel, dim3(hb, m), dim3(256), 0, stream, djobs, stride, n_src, seed, n_hyp, thr2);   // DM.h:1218-1225
         hipLaunchKernelGGL(ransac_pick_batch_kernel, dim3(m), dim3(256), 0, stream, djobs, n_src, n_hyp);
-        hipLaunchKernelGGL(ransac_mask_batch_kernel, dim3(mb, m), dim3(256), 0, stream, djobs, d_src, stride, n_src, seed, thr2);
+        hipLaunchKernelGGL(ransac_mask_batch_kernel, dim3(mb, m), dim3(256), 0, stream, djobs, stride, n_src, seed, thr2);
         const int rb = pb > kRedBlocks ? kRedBlocks : pb;
-        if (use_mfma_reduce()) hipLaunchKernelGGL(verify_reduce_batch_kernel<true>, dim3(rb, m), dim3(256), 0, stream, djobs, d_src, stride, n_src);   // DM.h:1228-1230
-        else hipLaunchKernelGGL(verify_reduce_batch_kernel<false>, dim3(rb, m), dim3(256), 0, stream, djobs, d_src, stride, n_src);
+        if (use_mfma_reduce()) hipLaunchKernelGGL(verify_reduce_batch_kernel<true>, dim3(rb, m), dim3(256), 0, stream, djobs, stride, n_src);   // DM.h:1228-1230
+        else hipLaunchKernelGGL(verify_reduce_batch_kernel<false>, dim3(rb, m), dim3(256), 0, stream, djobs, stride, n_src);
     }
     hipLaunchKernelGGL(verify_solve_batch_kernel, dim3(m), dim3(64), 0, stream, djobs, n_src, dout);
     ICP_HIP(hipGetLastError());

@@ -76,9 +76,10 @@ int icp_geometric_verification_staged(IcpWorkspace *ws, hipStream_t stream, int 
 // the same for m candidates of ONE source, every step one launch over all of them and one wait (icp.hip): the source staged in ctl
 // (icp_stage_cloud / icp_stage_cloud_host, once per call), the targets on the device and read in place (d_tgts[c], n_tgts[c] >= 1
 // points; n_src >= 1), wss[c] the candidates' workspaces.  Entry c of every output (m entries each, none nullptr) is what
-// icp_geometric_verification_staged answers for candidate c, bit for bit.
+// icp_geometric_verification_staged answers for candidate c, bit for bit.  guesses (may be nullptr) = 12 floats per candidate, rows
+// 0 .. 2 of its initial guess: candidate c is then answered for the staged source moved by it (icp_transform_cloud's values).
 int icp_geometric_verification_batch(IcpWorkspace *const *wss, int m, IcpWorkspace *ctl, hipStream_t stream, int n_src,
-                                     const void *const *d_tgts, const int *n_tgts, int stride, int ransac_iterations,
+                                     const void *const *d_tgts, const int *n_tgts, int stride, const float *guesses, int ransac_iterations,
                                      double inlier_threshold, double inlier_ratio, unsigned long long seed, float *T, int *success,
                                      int *n_corr_out, int *n_inliers_out, std::string *err);
 // where icp_stage_cloud / icp_stage_cloud_host left a cloud

@@ -132,6 +132,11 @@ def _bind(lib):
                                                      fp, ip, ip, ip]),
         "scl_geometric_verification_batch_from_store": (c_int, [P, P, c_int, c_int, c_float, c_int, c_int, ip, c_int, fp, c_float, c_int, c_int,
                                                                 c_int, c_double, c_double, c_uint64, fp, ip, ip, ip, ip, ip]),
+        "scl_geometric_verification_batch_guess": (c_int, [P, P, c_int, POINTER(c_void_p), ip, c_int, c_int, fp, c_int, c_double, c_double, c_uint64,
+                                                           fp, fp, ip, ip, ip]),
+        "scl_geometric_verification_batch_from_store_guess": (c_int, [P, P, c_int, c_int, c_float, c_int, c_int, ip, c_int, fp, c_float, fp, c_int, c_int,
+                                                                      c_int, c_double, c_double, c_uint64, fp, fp, ip, ip, ip, ip, ip]),
+        "scl_loop_guess_from_shift": (c_int, [c_int, c_int, fp, fp, fp]),
         "scl_profile_enable": (c_int, [P, c_int]),
         "scl_profile_reset": (c_int, [P]),
         "scl_profile_get": (c_int, [P, POINTER(SclProfile)]),
@@ -827,6 +832,54 @@ class ScanContextEngine:
             _ptr(T, c_float), _ptr(ok, c_int), byref(ns), _ptr(nt, c_int), _ptr(nc, c_int), _ptr(ni, c_int)),
             "scl_geometric_verification_batch_from_store")
         return T[:m].reshape(m, 4, 4), ok[:m].astype(bool), ns.value, nt[:m], nc[:m], ni[:m]
+
+    def geometric_verification_batch_guess(self, src, tgts, guesses, ransac_iterations=1000, inlier_threshold=0.25, inlier_ratio=0.45, seed=1):
+        """geometric_verification_batch with an initial guess per target (guesses[m,4,4]): entry c is answered for the source moved by
+        guesses[c]; returns (T[m,4,4] = T_fit @ guess, success[m], n_correspondences[m], n_inliers[m], T_fit[m,4,4])"""
+        s, ns, stride = _cloud(src)
+        arrs, ptrs, counts, m, stride_t = self._cloud_list(tgts)
+        if m and stride != stride_t:
+            raise ValueError("source and targets must share a record layout")
+        G = _f32(np.asarray(guesses)).reshape(m, 16)
+        k = max(m, 1)
+        T = np.empty((k, 16), np.float32); Tf = np.empty((k, 16), np.float32)
+        ok = np.zeros(k, np.int32); nc = np.zeros(k, np.int32); ni = np.zeros(k, np.int32)
+        self._check(self._lib.scl_geometric_verification_batch_guess(self._h, s.ctypes.data_as(c_void_p), ns, ptrs, _ptr(counts, c_int), m, stride,
+                                                                     _ptr(G, c_float), ransac_iterations, inlier_threshold, inlier_ratio, seed,
+                                                                     _ptr(T, c_float), _ptr(Tf, c_float), _ptr(ok, c_int), _ptr(nc, c_int), _ptr(ni, c_int)),
+                    "scl_geometric_verification_batch_guess")
+        return T[:m].reshape(m, 4, 4), ok[:m].astype(bool), nc[:m], ni[:m], Tf[:m].reshape(m, 4, 4)
+
+    def geometric_verification_batch_from_store_guess(self, src, src_leaf, robot, keys_pre, search_num, poses_pre, leaf, guesses,
+                                                      ransac_iterations=1000, inlier_threshold=0.25, inlier_ratio=0.45, seed=1,
+                                                      min_src_points=300, min_tgt_points=1000):
+        """geometric_verification_batch_from_store with an initial guess per candidate (guesses[m,4,4]), applied to the filtered received
+        cloud: returns (T[m,4,4] = T_fit @ guess, success[m], n_src_filtered, n_tgts[m], n_correspondences[m], n_inliers[m], T_fit[m,4,4])"""
+        a, n, stride = _cloud(src)
+        keys = np.ascontiguousarray(keys_pre, dtype=np.int32); m = keys.size
+        Tp = _f32(np.asarray(poses_pre)).reshape(m, 2 * search_num + 1, 16)
+        G = _f32(np.asarray(guesses)).reshape(m, 16)
+        k = max(m, 1)
+        T = np.empty((k, 16), np.float32); Tf = np.empty((k, 16), np.float32); ok = np.zeros(k, np.int32); ns = c_int(); nt = np.zeros(k, np.int32)
+        nc = np.zeros(k, np.int32); ni = np.zeros(k, np.int32)
+        self._check(self._lib.scl_geometric_verification_batch_from_store_guess(
+            self._h, a.ctypes.data_as(c_void_p), n, stride, src_leaf, robot, m, _ptr(keys, c_int), search_num, _ptr(Tp, c_float), leaf,
+            _ptr(G, c_float), min_src_points, min_tgt_points, ransac_iterations, inlier_threshold, inlier_ratio, seed,
+            _ptr(T, c_float), _ptr(Tf, c_float), _ptr(ok, c_int), byref(ns), _ptr(nt, c_int), _ptr(nc, c_int), _ptr(ni, c_int)),
+            "scl_geometric_verification_batch_from_store_guess")
+        return T[:m].reshape(m, 4, 4), ok[:m].astype(bool), ns.value, nt[:m], nc[:m], ni[:m], Tf[:m].reshape(m, 4, 4)
+
+    @staticmethod
+    def loop_guess_from_shift(shift, num_sector, pose_cur, pose_pre):
+        """the initial guess of an inter-robot verification from a Scan Context match (scl_loop_guess_from_shift): poses are
+        (x, y, z, roll, pitch, yaw) of the received and of the candidate keyframe; needs no engine"""
+        lib = load_library(); _bind(lib)
+        pc = _f32(np.asarray(pose_cur)).reshape(6); pp = _f32(np.asarray(pose_pre)).reshape(6)
+        G = np.empty(16, np.float32)
+        rc = lib.scl_loop_guess_from_shift(int(shift), int(num_sector), _ptr(pc, c_float), _ptr(pp, c_float), _ptr(G, c_float))
+        if rc != 0:
+            raise SclError(rc, "scl_loop_guess_from_shift")
+        return G.reshape(4, 4)
 
     # -- measurement ------------------------------------------------------------
     def profile_enable(self, on=True):
