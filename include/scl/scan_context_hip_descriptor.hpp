@@ -213,7 +213,41 @@ public:
         return out;
     }
 
+    // the ranked searches per robot (scl_engine.h "THE RANKED SEARCH PER ROBOT"; the names are those of lidar_iris_hip_descriptor).
+    // Intra: per entry of curPtrs the up to k best keyframes of the SAME robot whose index lies below the entry's own index -
+    // NUM_EXCLUDE_RECENT, wherever in the database they sit.  Inter: the up to k best keyframes of robotPre -- the list for
+    // scl_geometric_verification_batch_from_store*(robot = robotPre) --, or of every robot but the entry's own
+    // (SCL_SC_ANY_OTHER_ROBOT).  On an error (k outside [1, SCL_SC_SEARCH_MAX], an entry out of range, robotPre outside [-1, 127] or
+    // the robot of an entry) every list is empty
+    std::vector<std::vector<LoopCandidate>> searchIntraLoopClosureIDs(const std::vector<int> &curPtrs, int k)
+    {
+        return searchPerRobot(curPtrs, k, false, 0, "searchIntraLoopClosureIDs");
+    }
+
+    std::vector<std::vector<LoopCandidate>> searchInterLoopClosureIDs(const std::vector<int> &curPtrs, int k, int robotPre = SCL_SC_ANY_OTHER_ROBOT)
+    {
+        return searchPerRobot(curPtrs, k, true, robotPre, "searchInterLoopClosureIDs");
+    }
+
 private:
+    std::vector<std::vector<LoopCandidate>> searchPerRobot(const std::vector<int> &curPtrs, int k, bool inter, int robotPre, const char *where)
+    {
+        std::vector<std::vector<LoopCandidate>> out(curPtrs.size());
+        if (k < 1 || k > SCL_SC_SEARCH_MAX) {
+            std::fprintf(stderr, "[scan_context_hip_descriptor] %s: k = %d outside [1, %d]\n", where, k, SCL_SC_SEARCH_MAX);
+            return out;
+        }
+        std::vector<int> ids(curPtrs.size() * static_cast<size_t>(k), -1), shifts(ids.size(), 0), found(curPtrs.size(), 0);
+        std::vector<double> dists(ids.size(), 1e7);
+        const int n = static_cast<int>(curPtrs.size());
+        const int rc = inter ? scl_sc_search_inter(engine_, curPtrs.data(), n, robotPre, k, ids.data(), shifts.data(), dists.data(), found.data())
+                             : scl_sc_search_intra(engine_, curPtrs.data(), n, k, ids.data(), shifts.data(), dists.data(), found.data());
+        if (!report(rc, where)) return out;
+        for (size_t i = 0; i < curPtrs.size(); ++i)
+            for (int j = 0; j < found[i]; ++j) out[i].push_back(LoopCandidate{ids[i * k + j], static_cast<float>(shifts[i * k + j]), dists[i * k + j]});
+        return out;
+    }
+
     void init(int numRing, int numSector, int numCandidates, double distThres, double lidarHeight, double maxRadius,
               int numExcludeRecent, int treeMakingPeriod, double searchRatio, float knnExcludeEps,
               const int *devices, int n_devices, bool sharded)

@@ -256,6 +256,40 @@ int  scl_sc_search_range(scl_engine *e, const int *queries, const int *lo, const
                          int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found);
 int  scl_sc_search(scl_engine *e, const int *curs, int count, int k,
                    int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found);
+/*
+ * THE RANKED SEARCH PER ROBOT.  The database is one slot sequence for the whole team (the own robot's keyframes and every received
+ * one, DM.h:627 and DM.h:1002), and once two robots' keyframes interleave no slot range is "this robot's older keyframes" or "that
+ * robot's keyframes".  These two calls are scl_sc_search over search sets defined by the VALUE of each keyframe's (robot, index), the
+ * pair scl_get_index returns (robot 0 and index = slot for keyframes saved without them).  Output shape, optional pointers, k,
+ * count == 0, the score of a pair, the order, the < 10000000.0 rule and the fillers behind n_found are scl_sc_search's; ids are
+ * global slots, and equal distances go to the lower slot among the eligible ones.  curs[i] is a database key; let (r_i, x_i) be its
+ * robot and index.
+ *   * scl_sc_search_intra: every slot s with robot[s] == r_i and index[s] < x_i - num_exclude_recent (D.h:1627 on the robot's own
+ *     keyframe numbering, the rule of scl_iris_search_intra; the bound is formed in 64 bits).  Slot order plays no part: a keyframe
+ *     that arrived out of order, a duplicate (robot, index) and a slot behind curs[i] are judged by the rule like any other.  With
+ *     num_exclude_recent >= 0 the query is never in its own set.  In a one-robot database with index = slot the lists are
+ *     scl_sc_search's, bit for bit.
+ *   * scl_sc_search_inter, robot_pre == SCL_SC_ANY_OTHER_ROBOT: every slot with robot[s] != r_i.  No index rule: other robots'
+ *     keyframes are not temporal neighbours.  A keyframe stored with a negative robot id counts as another robot here.
+ *   * scl_sc_search_inter, robot_pre in 0 .. 127: every slot with robot[s] == robot_pre -- the list to hand to
+ *     scl_geometric_verification_batch_from_store*(robot = robot_pre) once scl_get_index has turned the ids into that robot's keys.
+ *     A negative robot id cannot be named.
+ *   * Errors, all before anything runs (no output written, no state changed): those of scl_sc_search -- a NULL required pointer,
+ *     count < 0, k outside [1, SCL_SC_SEARCH_MAX]: SCL_ERR_INVALID_ARG; a cur < 0 or >= size: SCL_ERR_OUT_OF_RANGE --, and
+ *     robot_pre < -1 or > 127, or robot_pre == r_i for any i (the intra set without its recency rule: a mistake):
+ *     SCL_ERR_INVALID_ARG.
+ *   * Not offered: staged (unsaved) queries -- the reference saves a received descriptor before it searches for it, DM.h:625-628.
+ * Like scl_sc_search the calls leave nothing a later call can see and do not depend on num_candidates, dist_thres, knn_exclude_eps or
+ * tree_making_period.  The rule is applied in the selection on the device, which reads a copy of (robot, index) per slot that a search
+ * brings up to date before its first launch.  A query's matrix runs over [its first eligible slot, its last eligible slot + 1) --
+ * a team map loaded in per-robot blocks does not score the other blocks --; inside that span ineligible keyframes are scored and then
+ * dropped.  On a scl_create_sharded engine: the same lists, bit for bit.
+ */
+#define SCL_SC_ANY_OTHER_ROBOT (-1)
+int  scl_sc_search_intra(scl_engine *e, const int *curs, int count, int k,
+                         int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found);
+int  scl_sc_search_inter(scl_engine *e, const int *curs, int count, int robot_pre, int k,
+                         int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found);
 /* BASELINE "full-DB" mode: ring-key top-k AND the shifted SC distance against
  * every eligible slot [0, hi) with hi = cur - num_exclude_recent (D.h:1627), then
  * the global arg-min (ties -> lowest slot).  nn_idx/shift/dist describe the best

@@ -504,7 +504,7 @@ const char *scl_status_string(int status)
 
 const char *scl_last_error(const scl_engine *e) { return e ? e->last_error.c_str() : "null engine"; }
 
-int scl_abi_version(void) { return 7; }
+int scl_abi_version(void) { return 8; }
 
 int scl_default_config(scl_config *c)
 {
@@ -684,6 +684,7 @@ int scl_destroy(scl_engine *e)
     if (e->d_rank_pos) (void)hipFree(e->d_rank_pos);
     if (e->d_rank_out) (void)hipFree(e->d_rank_out);
     if (e->h_rank_out) (void)hipHostFree(e->h_rank_out);
+    dev_free(e->d_meta_robot); dev_free(e->d_meta_index);
     if (e->h_mat) (void)hipHostFree(e->h_mat);
     for (auto &ev : e->ev_mat_k) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : e->ev_mat_c) if (ev) (void)hipEventDestroy(ev);
@@ -1165,8 +1166,9 @@ namespace {
 // group's rows x k records to pinned memory.  The next group that writes this half (g + 2) runs on that stream too -- both groups of a
 // half share a lane on 80 x 180 --, so a half is never written before its ranking has read it, and the host waits for nothing here.
 struct RankGroups final : MatrixConsumer {
-    scl_engine *e; int k; const int *qlo, *qhi; size_t part_half; bool used_alt = false;
-    RankGroups(scl_engine *e_, int k_, const int *qlo_, const int *qhi_, size_t part_half_) : e(e_), k(k_), qlo(qlo_), qhi(qhi_), part_half(part_half_) {}
+    scl_engine *e; int k; const int *qlo, *qhi; const ScRankRule *rules; size_t part_half; bool used_alt = false;
+    RankGroups(scl_engine *e_, int k_, const int *qlo_, const int *qhi_, const ScRankRule *rules_, size_t part_half_)
+        : e(e_), k(k_), qlo(qlo_), qhi(qhi_), rules(rules_), part_half(part_half_) {}
     int enqueued(const MatrixGroup &m) override
     {
         ScRankArgs a{};
@@ -1175,7 +1177,9 @@ struct RankGroups final : MatrixConsumer {
         for (int r = 0; r < m.rows; ++r) {                                  // the row covers the group's union; the list its own range
             const int l = qlo[m.r0 + r], h = qhi[m.r0 + r];
             a.plo[r] = h > l ? l - m.lo : 0; a.phi[r] = h > l ? h - m.lo : 0;
+            if (rules) a.rule[r] = rules[m.r0 + r];
         }
+        if (rules) { a.meta_robot = e->d_meta_robot; a.meta_index = e->d_meta_index; }   // (uploaded and waited for before the first group: both lanes see them)
         a.part_key = e->d_rank_key + (size_t)m.h * part_half; a.part_pos = e->d_rank_pos + (size_t)m.h * part_half;
         ScRankRecord *d_out = static_cast<ScRankRecord *>(e->d_rank_out) + (size_t)m.r0 * k;
         a.out = d_out;
@@ -1195,9 +1199,42 @@ struct RankGroups final : MatrixConsumer {
     int retire(int) override { return SCL_OK; }
 };
 
-// scl_sc_search_range behind the locks; everything is validated before anything is sized or launched
+// Is keyframe `s` in the search set of a rule?  (The host's copy of the selection's test, sc_rank.hip.)
+inline bool rule_admits(const scl_engine *e, const ScRankRule &u, int s)
+{
+    if (!(u.flags & kScRuleActive)) return true;
+    if (((int)e->robots[(size_t)s] == u.robot) == ((u.flags & kScRuleNotEqual) != 0)) return false;
+    return !(u.flags & kScRuleIndex) || e->indexs[(size_t)s] < u.bound;
+}
+
+// The device copy of (robots, indexs) the ruled selection reads, brought up to the database: new arrays when the database's arrays
+// have grown, then the slots behind the watermark.  The vectors are pageable and may move with the next append, so the copy is waited
+// for here -- which also puts it in front of whatever either lane launches afterwards.
+int meta_upload_locked(scl_engine *e)
+{
+    if (e->meta_cap != e->cap) {
+        dev_free(e->d_meta_robot); dev_free(e->d_meta_index); e->meta_cap = 0; e->meta_n = 0;
+        if (hipMalloc((void **)&e->d_meta_robot, sizeof(signed char) * (size_t)e->cap) != hipSuccess ||
+            hipMalloc((void **)&e->d_meta_index, sizeof(int) * (size_t)e->cap) != hipSuccess) {
+            dev_free(e->d_meta_robot); dev_free(e->d_meta_index);
+            return fail(e, SCL_ERR_NOMEM, "ranked search: (robot, index) arrays");
+        }
+        e->meta_cap = e->cap;
+    }
+    if (e->meta_n >= e->n) return SCL_OK;
+    const size_t o = (size_t)e->meta_n, m = (size_t)(e->n - e->meta_n);
+    SCL_HIP(e, hipMemcpyAsync(e->d_meta_robot + o, e->robots.data() + o, sizeof(signed char) * m, hipMemcpyHostToDevice, e->stream));
+    SCL_HIP(e, hipMemcpyAsync(e->d_meta_index + o, e->indexs.data() + o, sizeof(int) * m, hipMemcpyHostToDevice, e->stream));
+    SCL_HIP(e, hipStreamSynchronize(e->stream));
+    e->meta_n = e->n;
+    return SCL_OK;
+}
+
+// scl_sc_search_range behind the locks; everything is validated before anything is sized or launched.  rules != nullptr: the
+// robot-aware searches -- query i lists the keyframes of [lo[i], hi[i]) that satisfy rules[i], and its matrix range is narrowed to
+// [first such keyframe, last such keyframe + 1) (the lists do not depend on that: what the narrowing leaves out the rule excludes).
 int sc_search_locked(scl_engine *e, const int *queries, const int *lo, const int *hi, int nq, int k,
-                     int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found)
+                     int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found, const ScRankRule *rules = nullptr)
 {
     std::vector<int> slots((size_t)nq);
     for (int i = 0; i < nq; ++i) {
@@ -1206,6 +1243,19 @@ int sc_search_locked(scl_engine *e, const int *queries, const int *lo, const int
         if (q < 0 && !e->staged[-1 - q]) return fail(e, SCL_ERR_INVALID_ARG, "no staged query in that slot");
         if (lo[i] < 0 || hi[i] > e->n || hi[i] < lo[i]) return fail(e, SCL_ERR_OUT_OF_RANGE, "keyframe range out of the database");
         slots[(size_t)i] = q >= 0 ? q : e->cap + (-1 - q);
+    }
+    std::vector<int> nlo, nhi;
+    if (rules) {
+        int rc = meta_upload_locked(e);
+        if (rc) return rc;
+        nlo.assign((size_t)nq, 0); nhi.assign((size_t)nq, 0);
+        for (int i = 0; i < nq; ++i) {
+            int first = lo[i], last = hi[i];
+            while (first < last && !rule_admits(e, rules[i], first)) ++first;
+            while (last > first && !rule_admits(e, rules[i], last - 1)) --last;
+            if (last > first) { nlo[(size_t)i] = first; nhi[(size_t)i] = last; }      // (nothing eligible: the empty range [0, 0))
+        }
+        lo = nlo.data(); hi = nhi.data();
     }
     // a group's matrix runs over the union of its queries' ranges
     const int per_group = matrix_group_rows(e), groups = (nq + per_group - 1) / per_group;
@@ -1237,7 +1287,7 @@ int sc_search_locked(scl_engine *e, const int *queries, const int *lo, const int
             return fail(e, SCL_ERR_NOMEM, "ranked search: result buffers");
         e->rank_out_cap = recs;
     }
-    RankGroups out(e, k, lo, hi, part_half);
+    RankGroups out(e, k, lo, hi, rules, part_half);
     int rc = matrix_is_screened(e) ? matrix_screened_locked(e, slots.data(), nq, grp_lo.data(), grp_n.data(), out)
                                    : matrix_plain_locked(e, slots.data(), nq, grp_lo.data(), grp_n.data(), out);
     if (rc) return rc;
@@ -1285,6 +1335,49 @@ int scl_sc_search(scl_engine *e, const int *curs, int count, int k, int *cand_id
         hi[(size_t)i] = h > 0 ? h : 0;
     }
     return scl_sc_search_range(e, curs, lo.data(), hi.data(), count, k, cand_ids, cand_shifts, cand_dists, n_found);
+}
+
+namespace {
+
+// both calls behind their argument checks
+int sc_search_robot(scl_engine *e, const int *curs, int count, bool inter, int robot_pre, int k,
+                    int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found)
+{
+    std::lock_guard<std::mutex> pk(e->pass_mu);
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    for (int i = 0; i < count; ++i)
+        if (curs[i] < 0 || curs[i] >= e->n) return fail(e, SCL_ERR_OUT_OF_RANGE, "query keyframe out of range");
+    std::vector<ScRankRule> rules((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        const int r = e->robots[(size_t)curs[i]], x = e->indexs[(size_t)curs[i]];
+        if (inter && robot_pre != SCL_SC_ANY_OTHER_ROBOT && robot_pre == r) return fail(e, SCL_ERR_INVALID_ARG, "robot_pre is the query's own robot: that is scl_sc_search_intra's set");
+        rules[(size_t)i] = inter ? sc_inter_rule(r, robot_pre) : sc_intra_rule(r, x, e->cfg.num_exclude_recent);
+    }
+    const std::vector<int> lo((size_t)count, 0), hi((size_t)count, e->n);
+    return sc_search_locked(e, curs, lo.data(), hi.data(), count, k, cand_ids, cand_shifts, cand_dists, n_found, rules.data());
+}
+
+}  // namespace
+
+/* The robot-aware ranked searches: scl_sc_search's lists over the search sets a multi-robot caller needs, defined by the VALUE of each
+ * keyframe's (robot, index) and not by its slot; include/scl_engine.h, THE RANKED SEARCH, has the contract. */
+int scl_sc_search_intra(scl_engine *e, const int *curs, int count, int k, int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found)
+{
+    if (!e || count < 0 || k < 1 || k > SCL_SC_SEARCH_MAX || (count > 0 && (!curs || !cand_ids))) return SCL_ERR_INVALID_ARG;
+    if (count == 0) return SCL_OK;
+    if (e->front) return front_sc_search_intra(e, curs, count, k, cand_ids, cand_shifts, cand_dists, n_found);
+    return sc_search_robot(e, curs, count, false, 0, k, cand_ids, cand_shifts, cand_dists, n_found);
+}
+
+int scl_sc_search_inter(scl_engine *e, const int *curs, int count, int robot_pre, int k, int *cand_ids, int *cand_shifts, double *cand_dists,
+                        int *n_found)
+{
+    if (!e || count < 0 || k < 1 || k > SCL_SC_SEARCH_MAX || (count > 0 && (!curs || !cand_ids))) return SCL_ERR_INVALID_ARG;
+    if (robot_pre < SCL_SC_ANY_OTHER_ROBOT || robot_pre > 127) return SCL_ERR_INVALID_ARG;
+    if (count == 0) return SCL_OK;
+    if (e->front) return front_sc_search_inter(e, curs, count, robot_pre, k, cand_ids, cand_shifts, cand_dists, n_found);
+    return sc_search_robot(e, curs, count, true, robot_pre, k, cand_ids, cand_shifts, cand_dists, n_found);
 }
 
 namespace {
@@ -3784,6 +3877,18 @@ bool eng_would_regrow(const scl_engine *e, int count)
     return e->n + count > e->cap;
 }
 
+int eng_sc_search_ruled(scl_engine *e, const int *queries, const int *lo, const int *hi, const ScRankRule *rules, int n_queries, int k,
+                        int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found)
+{
+    if (!e || e->front || n_queries < 0 || k < 1 || k > SCL_SC_SEARCH_MAX || (n_queries > 0 && (!queries || !lo || !hi || !rules || !cand_ids)))
+        return SCL_ERR_INVALID_ARG;
+    if (n_queries == 0) return SCL_OK;
+    std::lock_guard<std::mutex> pk(e->pass_mu);
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    return sc_search_locked(e, queries, lo, hi, n_queries, k, cand_ids, cand_shifts, cand_dists, n_found, rules);
+}
+
 // Drop the keyframes from n_keep on (the sharded front undoes a multi-shard append that failed on a later shard; the slots'
 // contents are simply overwritten by the next append).  Passes in flight must have been collected by the caller.
 int eng_truncate(scl_engine *e, int n_keep)
@@ -3792,6 +3897,7 @@ int eng_truncate(scl_engine *e, int n_keep)
     if (n_keep < 0 || n_keep > e->n) return SCL_ERR_INVALID_ARG;
     e->robots.resize((size_t)n_keep); e->indexs.resize((size_t)n_keep);
     e->n = n_keep;
+    if (e->meta_n > n_keep) e->meta_n = n_keep;              // the slots from n_keep on will hold other keyframes: uploaded again
     return SCL_OK;
 }
 

@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -140,6 +141,9 @@ struct scl_engine {
     // records of a call (queries x k) on the device with their pinned copy
     unsigned long long *d_rank_key = nullptr; unsigned int *d_rank_pos = nullptr; size_t rank_part_cap = 0;
     void *d_rank_out = nullptr; void *h_rank_out = nullptr; size_t rank_out_cap = 0;
+    // scl_sc_search_intra / _inter: the device copy of (robots, indexs) per slot that the selection's rules read, sized with `cap`
+    // (meta_cap != cap: new arrays) and filled lazily by a search up to the watermark meta_n -- appends do not touch it
+    signed char *d_meta_robot = nullptr; int *d_meta_index = nullptr; int meta_n = 0, meta_cap = 0;
 
     // inter-robot tree bookkeeping (descriptor.h:1691-1703, counter initialised: see DESIGN.md)
     int tree_counter = 0, tree_n = 0;
@@ -190,11 +194,32 @@ int eng_sync_streams(scl_engine *e);
 // true when appending `count` keyframes would move the database arrays
 bool eng_would_regrow(const scl_engine *e, int count);
 int eng_truncate(scl_engine *e, int n_keep);
+// the ranked search with a rule per query on the keyframes' (robot, index) (kernels.hpp: ScRankRule; scl_sc_search_intra / _inter are
+// built on it): query i -- a slot or a staged / mirror row, -1 - row -- against the keyframes of [lo[i], hi[i]) that satisfy rules[i];
+// the matrix runs over [first eligible slot, last eligible slot + 1) only.  Takes both locks; outputs as scl_sc_search_range.
+int eng_sc_search_ruled(scl_engine *e, const int *queries, const int *lo, const int *hi, const ScRankRule *rules, int n_queries, int k,
+                        int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found);
 // device-side exchange of full-DB winners: the pinned (device-visible) result record of a ticket, its range start,
 // the stream the pass runs on; release = free the ticket without reading it (the exchange has delivered it)
 const double *eng_ticket_record(const scl_engine *e, int ticket, int *slot_lo, bool *empty);
 hipStream_t eng_stream(const scl_engine *e);
 int eng_release_ticket(scl_engine *e, int ticket);
+
+// The search set of scl_sc_search_intra as a rule: robot r, index < x - num_exclude_recent (D.h:1627 on the robot's own numbering),
+// the bound formed in 64 bits and brought back into what an int32 index can be compared with.
+inline ScRankRule sc_intra_rule(int r, int x, int num_exclude_recent)
+{
+    const long long b = (long long)x - (long long)num_exclude_recent;
+    if (b > (long long)INT_MAX) return {r, kScRuleActive, 0};                         // every index is below it
+    return {r, kScRuleActive | kScRuleIndex, b < (long long)INT_MIN ? INT_MIN : (int)b};   // (INT_MIN: no index is below it)
+}
+
+// The search sets of scl_sc_search_inter: every robot but r, or robot_pre alone (robot_pre == r is refused by the callers).
+inline ScRankRule sc_inter_rule(int r, int robot_pre)
+{
+    if (robot_pre == SCL_SC_ANY_OTHER_ROBOT) return {r, kScRuleActive | kScRuleNotEqual, 0};
+    return {robot_pre, kScRuleActive, 0};
+}
 
 // the front's side of every public entry point (same arguments)
 int front_destroy(scl_engine *e);
@@ -222,6 +247,9 @@ int front_profile_reset(scl_engine *e);
 int front_profile_get(scl_engine *e, scl_profile *out);
 int front_sc_distance_matrix(scl_engine *e, const int *queries, int nq, int lo, int hi, double *dist, int *shift);
 int front_sc_search_range(scl_engine *e, const int *queries, const int *lo, const int *hi, int n_queries, int k,
+                          int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found);
+int front_sc_search_intra(scl_engine *e, const int *curs, int count, int k, int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found);
+int front_sc_search_inter(scl_engine *e, const int *curs, int count, int robot_pre, int k,
                           int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found);
 int front_alignment_stats(scl_engine *e, uint64_t *pairs, uint64_t *fallbacks, int reset);
 int front_survivor_stats(scl_engine *e, uint64_t *queries, uint64_t *survivors, uint64_t *max_survivors, int reset);

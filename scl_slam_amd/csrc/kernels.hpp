@@ -149,12 +149,20 @@ hipError_t launch_sc_matrix(const struct DbView &db, int SR, const int *qslots, 
 // of the row, ascending by (distance as a double, position); record j of row r at out[r * k + j], {kBigDist, -1, 0} behind the listed
 // ones.  part_key / part_pos: sc_rank_part_entries(rows, n, k) entries of scratch.  Two launches (tiles, merge) on `stream`; n == 0:
 // the merge alone, which writes the empty lists.
+// The robot-aware forms (scl_sc_search_intra / _inter) add a RULE per row on the keyframe's (robot, index): meta_robot / meta_index are
+// indexed by database slot (entry p of a row reads slot base + p), and an entry is listable only if it also satisfies its row's rule --
+// robot[slot] == rule.robot (kScRuleNotEqual: !=) and, with kScRuleIndex, index[slot] < rule.bound.  A row without kScRuleActive has no
+// rule; meta_robot == nullptr: no row has one (the launch of scl_sc_search / scl_sc_search_range).
 constexpr int kScRankMaxK = 32;
+constexpr int kScRuleActive = 1, kScRuleNotEqual = 2, kScRuleIndex = 4;
 struct ScRankRecord { double dist; int id; int shift; };
+struct ScRankRule { int robot, flags, bound; };
 struct ScRankArgs {
     const double *dist; const int *shift; unsigned long long row_stride;
     int rows, n, base, k, tiles;                                              // (tiles: filled by the launcher)
     int plo[16], phi[16];
+    const signed char *meta_robot; const int *meta_index;                     // both or neither
+    ScRankRule rule[16];
     unsigned long long *part_key; unsigned int *part_pos;
     ScRankRecord *out;
 };

@@ -1,9 +1,13 @@
-// sc_rank.hip -- the selection behind scl_sc_search / scl_sc_search_range: the k smallest entries of each row of a finished group of
-// the exact distance matrix (sc_distance.hip, sc_matrix.hip, sc_masked.hip write the rows; nothing here computes a distance).
+// sc_rank.hip -- the selection behind scl_sc_search / scl_sc_search_range / scl_sc_search_intra / _inter: the k smallest entries of
+// each row of a finished group of the exact distance matrix (sc_distance.hip, sc_matrix.hip, sc_masked.hip write the rows; nothing
+// here computes a distance).
 //
 // A row holds, per keyframe of the group's range, distanceBtnScanContext (descriptor.h:1538-1569) in fp64 and its shift.  The list of a
 // row is its k smallest entries in ascending (distance compared as doubles, position) order among the positions [plo, phi) of the
-// row's own query that are listable: distance < 1e7, argmin_kernel's rule (sc_distance.hip), which NaN fails by itself.
+// row's own query that are listable: distance < 1e7, argmin_kernel's rule (sc_distance.hip), which NaN fails by itself.  The robot-aware
+// searches (scl_sc_search_intra / _inter) add a rule per row on the (robot, index) of the entry's database slot (kernels.hpp: ScRankRule),
+// applied where the entry becomes a key: an entry that fails its row's rule is a filler like an unlistable one, so rows of different
+// rules share a launch and the merge knows nothing of rules.  Without the slot arrays no entry is filtered.
 //
 //   * The key of an entry is the pair (u64 image of the distance, u32 position).  The image keeps the order of the doubles: sign bit
 //     set -> every bit flipped, otherwise -> the sign bit set; -0.0 is keyed as +0.0, since the two compare equal and the position
@@ -55,7 +59,14 @@ __global__ __launch_bounds__(kRankTileWaves * kRankTile) void sc_rank_tile_kerne
     unsigned int pos = kRankNoPos;
     if (p >= plo && p < phi) {                                             // (phi <= n: inside the row)
         const double d = a.dist[(size_t)r * a.row_stride + (size_t)p];
-        if (d < kBigDist) { key = rank_key(d); pos = (unsigned int)p; }
+        bool listable = d < kBigDist;
+        if (a.meta_robot && (a.rule[r].flags & kScRuleActive)) {           // the row's rule on (robot, index) of slot base + p
+            const ScRankRule rule = a.rule[r];
+            const size_t s = (size_t)a.base + (size_t)p;
+            listable = listable && (((int)a.meta_robot[s] == rule.robot) != ((rule.flags & kScRuleNotEqual) != 0));
+            if (rule.flags & kScRuleIndex) listable = listable && a.meta_index[s] < rule.bound;
+        }
+        if (listable) { key = rank_key(d); pos = (unsigned int)p; }
     }
 #pragma unroll
     for (int k2 = 2; k2 <= kRankTile; k2 <<= 1)
@@ -127,6 +138,7 @@ hipError_t launch_sc_rank(const ScRankArgs &args, hipStream_t stream)
     if (args.n > 0 && (!args.dist || !args.shift || !args.part_key || !args.part_pos || args.row_stride < (unsigned long long)args.n)) return hipErrorInvalidValue;
     for (int r = 0; r < args.rows; ++r)
         if (args.plo[r] < 0 || args.phi[r] > args.n || args.phi[r] < args.plo[r]) return hipErrorInvalidValue;
+    if ((args.meta_robot != nullptr) != (args.meta_index != nullptr)) return hipErrorInvalidValue;
     ScRankArgs a = args;
     a.tiles = (a.n + kRankTile - 1) / kRankTile;
     if (a.tiles > 0) {

@@ -415,7 +415,11 @@ int front_save_bulk(scl_engine *e, const float *values, int count, const int8_t 
         const int c = f->n % f->G;
         int rc = quiesce_if_regrow(e, c, 1);
         if (rc) return rc;
-        rc = scl_save_bulk(f->sh[c], values, 1, robots, indexs);
+        // (explicit, as below: the shard's own default index would be its LOCAL slot, and the shards' (robot, index) are what the
+        // per-robot ranked searches read)
+        const int8_t r1 = robots ? robots[0] : (int8_t)0;
+        const int i1 = indexs ? indexs[0] : f->n;
+        rc = scl_save_bulk(f->sh[c], values, 1, &r1, &i1);
         if (rc) return child_fail(e, f->sh[c], rc, "save on shard");
     } else {
         std::vector<float> buf;
@@ -627,19 +631,18 @@ int front_sc_distance_matrix(scl_engine *e, const int *queries, int nq, int lo, 
     return SCL_OK;
 }
 
-// The ranked search on a sharded database: per query one scl_sc_search_range per shard over the shard's slots of the global range
-// (keyframe g = slot g / G of shard g mod G, so position order within a shard is global-key order), the slots translated to global
-// keys and the G lists merged on the host by (distance, global key): the list one database gives, bit for bit.  No collective.
-int front_sc_search_range(scl_engine *e, const int *queries, const int *lo, const int *hi, int n_queries, int k,
-                          int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found)
+namespace {
+
+// What the ranked searches of a sharded database share.  Per query: the query placed on every shard, one search per shard --
+// `on_shard(i, c, qid, ids, shifts, dists, &found)` runs query i (id `qid` on shard c) over the shard's slots and fills one list --, the
+// slots translated to global keys (keyframe g = slot g / G of shard g mod G, so position order within a shard is global-key order) and
+// the G lists merged on the host by (distance, global key): the list one database gives, bit for bit.  No collective.  The outputs
+// are written once every shard has answered.
+template <class OnShard>
+int front_ranked_merge(scl_engine *e, const int *queries, int n_queries, int k, OnShard on_shard,
+                       int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found)
 {
-    std::lock_guard<std::mutex> lk(e->mu);
     ShardedFront *f = e->front;
-    for (int i = 0; i < n_queries; ++i) {                                  // everything is checked before anything runs
-        if (queries[i] >= f->n || queries[i] < SCL_QUERY_STAGED) return fail(e, SCL_ERR_OUT_OF_RANGE, "query keyframe out of range");
-        if (queries[i] == SCL_QUERY_STAGED && !f->staged0) return fail(e, SCL_ERR_INVALID_ARG, "no staged query (call scl_stage_query first)");
-        if (lo[i] < 0 || hi[i] > f->n || hi[i] < lo[i]) return fail(e, SCL_ERR_OUT_OF_RANGE, "keyframe range out of the database");
-    }
     struct Rec { double dist; int g; int shift; };
     std::vector<Rec> all;
     std::vector<int> ids((size_t)k), shifts((size_t)k); std::vector<double> dists((size_t)k);
@@ -650,9 +653,8 @@ int front_sc_search_range(scl_engine *e, const int *queries, const int *lo, cons
         if (rc) return rc;
         all.clear();
         for (int c = 0; c < f->G; ++c) {
-            const int l = local_count(lo[i], c, f->G), h = local_count(hi[i], c, f->G);
             int found = 0;
-            rc = scl_sc_search_range(f->sh[c], &qid[c], &l, &h, 1, k, ids.data(), shifts.data(), dists.data(), &found);
+            rc = on_shard(i, c, qid[c], ids.data(), shifts.data(), dists.data(), &found);
             if (rc) return child_fail(e, f->sh[c], rc, "ranked search on shard");
             for (int j = 0; j < found; ++j) all.push_back({dists[(size_t)j], ids[(size_t)j] * f->G + c, shifts[(size_t)j]});
         }
@@ -661,7 +663,7 @@ int front_sc_search_range(scl_engine *e, const int *queries, const int *lo, cons
             out_ids[(size_t)i * k + j] = all[j].g; out_shifts[(size_t)i * k + j] = all[j].shift; out_dists[(size_t)i * k + j] = all[j].dist;
         }
     }
-    for (int i = 0; i < n_queries; ++i) {                                  // the outputs are written once every shard has answered
+    for (int i = 0; i < n_queries; ++i) {
         int found = 0;
         for (int j = 0; j < k; ++j) {
             const size_t o = (size_t)i * k + j;
@@ -673,6 +675,60 @@ int front_sc_search_range(scl_engine *e, const int *queries, const int *lo, cons
         if (n_found) n_found[i] = found;
     }
     return SCL_OK;
+}
+
+// The robot-aware ranked searches on a sharded database.  (r_i, x_i) come from the front's replicated vectors and everything is checked
+// first; then, per query, the ruled search of every shard over ALL of the shard's slots -- the rule is passed explicitly, since the
+// placed query (a staging or mirror row) has no (robot, index) on that shard, while the shard's own slots carry their global ones.
+int front_sc_search_robot(scl_engine *e, const int *curs, int count, bool inter, int robot_pre, int k,
+                          int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found)
+{
+    std::lock_guard<std::mutex> lk(e->mu);
+    ShardedFront *f = e->front;
+    for (int i = 0; i < count; ++i)
+        if (curs[i] < 0 || curs[i] >= f->n) return fail(e, SCL_ERR_OUT_OF_RANGE, "query keyframe out of range");
+    std::vector<ScRankRule> rules((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        const int r = f->robots[(size_t)curs[i]], x = f->indexs[(size_t)curs[i]];
+        if (inter && robot_pre != SCL_SC_ANY_OTHER_ROBOT && robot_pre == r)
+            return fail(e, SCL_ERR_INVALID_ARG, "robot_pre is the query's own robot: that is scl_sc_search_intra's set");
+        rules[(size_t)i] = inter ? sc_inter_rule(r, robot_pre) : sc_intra_rule(r, x, e->cfg.num_exclude_recent);
+    }
+    return front_ranked_merge(e, curs, count, k, [&](int i, int c, int qid, int *ids, int *shifts, double *dists, int *found) {
+        const int l = 0, h = local_count(f->n, c, f->G);
+        return eng_sc_search_ruled(f->sh[c], &qid, &l, &h, &rules[(size_t)i], 1, k, ids, shifts, dists, found);
+    }, cand_ids, cand_shifts, cand_dists, n_found);
+}
+
+}  // namespace
+
+// The ranked search on a sharded database: per query one scl_sc_search_range per shard over the shard's slots of the global range
+// (front_ranked_merge).
+int front_sc_search_range(scl_engine *e, const int *queries, const int *lo, const int *hi, int n_queries, int k,
+                          int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found)
+{
+    std::lock_guard<std::mutex> lk(e->mu);
+    ShardedFront *f = e->front;
+    for (int i = 0; i < n_queries; ++i) {                                  // everything is checked before anything runs
+        if (queries[i] >= f->n || queries[i] < SCL_QUERY_STAGED) return fail(e, SCL_ERR_OUT_OF_RANGE, "query keyframe out of range");
+        if (queries[i] == SCL_QUERY_STAGED && !f->staged0) return fail(e, SCL_ERR_INVALID_ARG, "no staged query (call scl_stage_query first)");
+        if (lo[i] < 0 || hi[i] > f->n || hi[i] < lo[i]) return fail(e, SCL_ERR_OUT_OF_RANGE, "keyframe range out of the database");
+    }
+    return front_ranked_merge(e, queries, n_queries, k, [&](int i, int c, int qid, int *ids, int *shifts, double *dists, int *found) {
+        const int l = local_count(lo[i], c, f->G), h = local_count(hi[i], c, f->G);
+        return scl_sc_search_range(f->sh[c], &qid, &l, &h, 1, k, ids, shifts, dists, found);
+    }, cand_ids, cand_shifts, cand_dists, n_found);
+}
+
+int front_sc_search_intra(scl_engine *e, const int *curs, int count, int k, int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found)
+{
+    return front_sc_search_robot(e, curs, count, false, 0, k, cand_ids, cand_shifts, cand_dists, n_found);
+}
+
+int front_sc_search_inter(scl_engine *e, const int *curs, int count, int robot_pre, int k,
+                          int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found)
+{
+    return front_sc_search_robot(e, curs, count, true, robot_pre, k, cand_ids, cand_shifts, cand_dists, n_found);
 }
 
 // ---- full-DB detection --------------------------------------------------------------------------------------------------

@@ -96,6 +96,8 @@ def _bind(lib):
         "scl_sc_distance_matrix": (c_int, [P, ip, c_int, c_int, c_int, dp, ip]),
         "scl_sc_search_range": (c_int, [P, ip, ip, ip, c_int, c_int, ip, ip, dp, ip]),
         "scl_sc_search": (c_int, [P, ip, c_int, c_int, ip, ip, dp, ip]),
+        "scl_sc_search_intra": (c_int, [P, ip, c_int, c_int, ip, ip, dp, ip]),
+        "scl_sc_search_inter": (c_int, [P, ip, c_int, c_int, c_int, ip, ip, dp, ip]),
         "scl_detect_full": (c_int, [P, c_int, ip, ip, ip, dp]),
         "scl_detect_full_range": (c_int, [P, c_int, c_int, c_int, ip, ip, dp]),
         "scl_get_last_topk": (c_int, [P, c_int, ip, fp]),
@@ -521,6 +523,25 @@ class ScanContextEngine:
         ids, shifts, dists, found = self._search_out(q.size, max(int(k), 0), out)
         self._check(self._lib.scl_sc_search(self._h, _ptr(q, c_int), q.size, int(k), _ptr(ids, c_int), _ptr(shifts, c_int),
                                             _ptr(dists, c_double), _ptr(found, c_int)), "scl_sc_search")
+        return ids, shifts, dists, found
+
+    def sc_search_intra(self, curs, k, out=None):
+        """... over this robot's older keyframes, by VALUE (scl_engine.h, THE RANKED SEARCH PER ROBOT): with (r, x) = get_index(curs[i]),
+        every keyframe of robot r whose index is < x - num_exclude_recent, wherever it sits in the database"""
+        q = np.ascontiguousarray(curs, dtype=np.int32).reshape(-1)
+        ids, shifts, dists, found = self._search_out(q.size, max(int(k), 0), out)
+        self._check(self._lib.scl_sc_search_intra(self._h, _ptr(q, c_int), q.size, int(k), _ptr(ids, c_int), _ptr(shifts, c_int),
+                                                  _ptr(dists, c_double), _ptr(found, c_int)), "scl_sc_search_intra")
+        return ids, shifts, dists, found
+
+    def sc_search_inter(self, curs, k, robot_pre=-1, out=None):
+        """... over the other robots' keyframes: robot_pre = -1 (SCL_SC_ANY_OTHER_ROBOT): every keyframe of a robot other than
+        curs[i]'s; robot_pre in 0 .. 127: the keyframes of that robot (which must not be the robot of a query) -- the list for
+        geometric_verification_batch_from_store*(robot=robot_pre) once get_index has turned the ids into that robot's keys"""
+        q = np.ascontiguousarray(curs, dtype=np.int32).reshape(-1)
+        ids, shifts, dists, found = self._search_out(q.size, max(int(k), 0), out)
+        self._check(self._lib.scl_sc_search_inter(self._h, _ptr(q, c_int), q.size, int(robot_pre), int(k), _ptr(ids, c_int), _ptr(shifts, c_int),
+                                                  _ptr(dists, c_double), _ptr(found, c_int)), "scl_sc_search_inter")
         return ids, shifts, dists, found
 
     def detect_full(self, cur):
