@@ -15,7 +15,7 @@ OBJS    := $(SRCS:.hip=.o)
 # the adapter template the M2DP, FPFH and GRSD adapters derive from, and the batch declarations their C headers share
 VP_ADAPTER := include/scl/vector_plugin_hip_descriptor.hpp include/scl_plugin_batch.h
 
-all: $(LIBDIR)/libscl_engine.so oracle tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/grsd_adapter_check tests/cpp/plugin_batch_check tests/cpp/plugin_topk_check tests/cpp/iris_batch_check tests/cpp/iris_search_check tests/cpp/sc_search_check tests/cpp/sc_search_robot_check tests/cpp/libfpfh_checker.so tests/cpp/libgrsd_checker.so tests/cpp/libmock_rccl.so
+all: $(LIBDIR)/libscl_engine.so oracle tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/grsd_adapter_check tests/cpp/plugin_batch_check tests/cpp/plugin_topk_check tests/cpp/iris_batch_check tests/cpp/iris_search_check tests/cpp/sc_search_check tests/cpp/sc_search_robot_check tests/cpp/nn_plan_check tests/cpp/libfpfh_checker.so tests/cpp/libgrsd_checker.so tests/cpp/libmock_rccl.so
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.hpp) include/scl_engine.h include/scl_m2dp.h include/scl_fpfh.h include/scl_grsd.h include/scl_iris.h include/scl_plugin_batch.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -67,6 +67,11 @@ tests/cpp/sc_search_check: tests/cpp/sc_search_check.cpp tests/cpp/pcl_types_for
 tests/cpp/sc_search_robot_check: tests/cpp/sc_search_robot_check.cpp tests/cpp/pcl_types_for_adapter_check.h include/scl/scan_context_hip_descriptor.hpp include/scl_engine.h $(LIBDIR)/libscl_engine.so
 	g++ -std=c++14 -O2 -Wall -Iinclude -Itests/cpp -o $@ tests/cpp/sc_search_robot_check.cpp -L$(LIBDIR) -lscl_engine -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
+# the plan of the vector plugins' batched search (nn_plan.hpp, host code only) under ASan + UBSan, a program of its own; runs without
+# a GPU (tests/test_nn_plan.py)
+tests/cpp/nn_plan_check: tests/cpp/nn_plan_check.cpp $(CSRC)/nn_plan.hpp
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -I$(CSRC) -o $@ tests/cpp/nn_plan_check.cpp
+
 # TEST INFRASTRUCTURE: the FPFH CPU checker (tests/fpfh_checker.py loads it); atan2f from oracle/liboracle.so.  No -march, no
 # contraction: every float operation is the one written
 tests/cpp/libfpfh_checker.so: tests/cpp/fpfh_checker.c | oracle
@@ -112,7 +117,7 @@ sanitize: tests/cpp/fuzz_host
 	@cat $(SAN_LOG)
 
 clean:
-	rm -f $(OBJS) $(LIBDIR)/libscl_engine.so tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/grsd_adapter_check tests/cpp/plugin_batch_check tests/cpp/plugin_topk_check tests/cpp/iris_batch_check tests/cpp/iris_search_check tests/cpp/sc_search_check tests/cpp/sc_search_robot_check tests/cpp/libfpfh_checker.so tests/cpp/libgrsd_checker.so tests/cpp/libmock_rccl.so
+	rm -f $(OBJS) $(LIBDIR)/libscl_engine.so tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/grsd_adapter_check tests/cpp/plugin_batch_check tests/cpp/plugin_topk_check tests/cpp/iris_batch_check tests/cpp/iris_search_check tests/cpp/sc_search_check tests/cpp/sc_search_robot_check tests/cpp/nn_plan_check tests/cpp/libfpfh_checker.so tests/cpp/libgrsd_checker.so tests/cpp/libmock_rccl.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean sanitize

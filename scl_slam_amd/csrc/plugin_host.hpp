@@ -21,8 +21,10 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
+#include "nn_plan.hpp"
 #include "scl_engine.h"
 #include "scl_plugin_batch.h"
 
@@ -59,6 +61,19 @@ template <class H, class T> int dev_regrow(H *h, T **p, size_t count)
     if (*p) (void)hipFree(*p);
     *p = nullptr;
     return dev_alloc(h, p, count);
+}
+
+// room for `need` elements (of `per` Ts each) in *p, whose capacity is *cap: past it the buffer is allocated again for need + need / 2
+// + 256 elements, nothing copied.  The capacity is zero while the pointer is invalid
+template <class H, class T> int dev_reserve(H *h, T **p, size_t *cap, size_t need, size_t per = 1)
+{
+    if (need <= *cap) return SCL_OK;
+    *cap = 0;
+    const size_t c = need + need / 2 + 256;
+    int rc = dev_regrow(h, p, per * c);
+    if (rc) return rc;
+    *cap = c;
+    return SCL_OK;
 }
 
 // ---- keyframe registry (the reference's plugin layer, D.h:501-509, 1055-1057): global key -> (robot, index), and per robot
@@ -261,13 +276,8 @@ template <class H> int nearest_locked(H *h, int q, const int *list, int n, int *
     constexpr int DIM = decltype(h->db)::kDim;
     *pos = -1; *d2 = INFINITY;
     if (n <= 0) return SCL_OK;
-    if (list && (size_t)n > h->list_cap) {
-        h->list_cap = 0;
-        const size_t c = (size_t)n + (size_t)n / 2 + 256;
-        int rc = dev_regrow(h, &h->d_list, c);
-        if (rc) return rc;
-        h->list_cap = c;
-    }
+    if (list)
+        if (int rc = dev_reserve(h, &h->d_list, &h->list_cap, (size_t)n)) return rc;
     if (list) SCL_HIP(h, hipMemcpyAsync(h->d_list, list, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, h->stream));
     SCL_HIP(h, hipMemsetAsync(h->d_best, 0xff, sizeof(unsigned long long), h->stream));
     hipLaunchKernelGGL(nn_l2_kernel<DIM>, dim3((unsigned)((n + kNnThreads - 1) / kNnThreads)), dim3(kNnThreads), 0, h->stream, h->db.d_db,
@@ -303,9 +313,11 @@ template <int DIM> struct NnManyShape {
     static_assert(DIM % kChunk == 0 && (kChunk % 4 == 0 || kChunk == DIM), "a chunk is whole groups of four, or the whole row");
 };
 
+// The body the 1-NN and the k-NN tile kernels share, so that both form the same floats: lane t's sums s[q] between candidate
+// blockIdx.x * kManyTile + t of the list and the group's queries.  Returns lim[] in LDS for the epilogue: limit[q], 0 for an absent query
 template <int DIM>
-__global__ __launch_bounds__(kManyTile) void nn_l2_many_kernel(const float *db, const int *list, int n, const int *qkey, const int *limit,
-                                                               int nq, unsigned long long *best)
+__device__ __forceinline__ const int *nn_tile_sums(const float *db, const int *list, int n, const int *qkey, const int *limit, int nq,
+                                                   float (&s)[kDetectGroup])
 {
     constexpr int KC = NnManyShape<DIM>::kChunk, P = NnManyShape<DIM>::kPitch;
     __shared__ alignas(16) float qs[kDetectGroup * DIM];               // rows of absent queries (q >= nq): zeros, their sums unused
@@ -319,7 +331,6 @@ __global__ __launch_bounds__(kManyTile) void nn_l2_many_kernel(const float *db, 
     }
     if (t < kDetectGroup) lim[t] = t < nq ? limit[t] : 0;
     if (t < rows) ks[t] = list ? list[i] : i;
-    float s[kDetectGroup];
 #pragma unroll
     for (int q = 0; q < kDetectGroup; ++q) s[q] = 0.0f;
     for (int k0 = 0; k0 < DIM; k0 += KC) {
@@ -352,6 +363,16 @@ __global__ __launch_bounds__(kManyTile) void nn_l2_many_kernel(const float *db, 
             }
         }
     }
+    return lim;
+}
+
+template <int DIM>
+__global__ __launch_bounds__(kManyTile) void nn_l2_many_kernel(const float *db, const int *list, int n, const int *qkey, const int *limit,
+                                                               int nq, unsigned long long *best)
+{
+    float s[kDetectGroup];
+    const int *lim = nn_tile_sums<DIM>(db, list, n, qkey, limit, nq, s);
+    const int t = threadIdx.x, i = blockIdx.x * kManyTile + t;
 #pragma unroll
     for (int q = 0; q < kDetectGroup; ++q) {
         unsigned long long key = i < lim[q] ? ((unsigned long long)__float_as_uint(s[q]) << 32) | (unsigned int)i : ~0ull;   // lim[q] <= n
@@ -363,15 +384,35 @@ __global__ __launch_bounds__(kManyTile) void nn_l2_many_kernel(const float *db, 
     }
 }
 
+// What a search reports for the candidate at position `pos` of a query's list (list_off: where the list starts in `list`, -1 for
+// keys 0 .. n - 1): its global key into *key, and sqrtf of the squared distance between its row and the query's row `a` (in global
+// memory or in LDS) over the first report_dims floats, in nanoflann's order
+template <int DIM>
+__device__ __forceinline__ float nn_reported(const float *db, const int *list, int list_off, int pos, const float *a, int report_dims, int *key)
+{
+    *key = list_off < 0 ? pos : list[list_off + pos];
+    const float *c = db + (size_t)*key * DIM;
+    float s = 0.0f;
+    int k = 0;
+    for (; k + 4 <= report_dims; k += 4) {
+        const float d0 = a[k] - c[k], d1 = a[k + 1] - c[k + 1], d2 = a[k + 2] - c[k + 2], d3 = a[k + 3] - c[k + 3];
+        s += ((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3;
+    }
+    for (; k < report_dims; ++k) {
+        const float d = a[k] - c[k];
+        s += d * d;
+    }
+    return sqrtf(s);
+}
+
 // what a batched search answers per query: the winner's position in its list and its global key (-1, -1: nothing reduced, an empty
-// prefix), the 1-NN's squared distance (+inf then) and sqrtf of the squared distance over the first report_dims floats (+inf then)
+// prefix), the 1-NN's squared distance (+inf then) and the reported distance (+inf then)
 struct NnManyResult {
     int pos, key;
     float d2, dist;
 };
 
-// the finishing step, one thread per query of the whole call: best[q] -> NnManyResult without the host in between.  list_off[q]:
-// where the query's list starts in `list`, -1 for keys 0 .. n - 1.  The distance over report_dims floats in nanoflann's order
+// the finishing step, one thread per query of the whole call: best[q] -> NnManyResult without the host in between
 template <int DIM>
 __global__ __launch_bounds__(kNnThreads) void nn_finish_many_kernel(const float *db, const int *list, const int *qkey, const int *list_off,
                                                                     const unsigned long long *best, int count,
@@ -383,42 +424,15 @@ __global__ __launch_bounds__(kNnThreads) void nn_finish_many_kernel(const float 
     const unsigned long long b = best[q];
     if (b != ~0ull) {
         r.pos = (int)(b & 0xffffffffu);
-        r.key = list_off[q] < 0 ? r.pos : list[list_off[q] + r.pos];
         r.d2 = __uint_as_float((unsigned int)(b >> 32));
-        const float *a = db + (size_t)qkey[q] * DIM, *c = db + (size_t)r.key * DIM;
-        float s = 0.0f;
-        int k = 0;
-        for (; k + 4 <= report_dims; k += 4) {
-            const float d0 = a[k] - c[k], d1 = a[k + 1] - c[k + 1], d2 = a[k + 2] - c[k + 2], d3 = a[k + 3] - c[k + 3];
-            s += ((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3;
-        }
-        for (; k < report_dims; ++k) {
-            const float d = a[k] - c[k];
-            s += d * d;
-        }
-        r.dist = sqrtf(s);
+        r.dist = nn_reported<DIM>(db, list, list_off[q], r.pos, db + (size_t)qkey[q] * DIM, report_dims, &r.key);
     }
     res[q] = r;
 }
 
-// the batched search's work buffers of a handle (`scl::NnManyWork many`; the lists share d_list): they grow like d_list
-struct NnManyWork {
-    int *d_q = nullptr;                          // qkey | limit | list_off, `count` elements each
-    unsigned long long *d_best = nullptr;
-    NnManyResult *d_res = nullptr;
-    size_t cap = 0;
-    void release()
-    {
-        for (void *p : {(void *)d_q, (void *)d_best, (void *)d_res})
-            if (p) (void)hipFree(p);
-        d_q = nullptr; d_best = nullptr; d_res = nullptr; cap = 0;
-    }
-};
-
-// ---- batched k-NN (the candidate lists, SCL_PLUGIN_TOPK_API): the sums of nn_l2_many_kernel -- same launch geometry, same staging,
-// same operation order, so bit for bit the same floats -- but instead of the atomic min every wave emits, per query, the
-// min(k, valid) smallest (sum bits << 32 | position) keys of its tile in ascending order into part[(q * tiles + tile) * k + j];
-// unused slots are ~0ull.  Valid: position < limit[q] and the sum not NaN (nanoflann's KNNResultSet admits dist < worst only; +inf
+// ---- batched k-NN (the candidate lists, SCL_PLUGIN_TOPK_API): the sums of nn_l2_many_kernel -- both kernels call nn_tile_sums, so
+// bit for bit the same floats -- but instead of the atomic min every wave emits, per query, the min(k, valid) smallest
+// (sum bits << 32 | position) keys of its tile in ascending order into part[(q * tiles + tile) * k + j]; unused slots are ~0ull.  Valid: position < limit[q] and the sum not NaN (nanoflann's KNNResultSet admits dist < worst only; +inf
 // is a distance like any other).  A tile at or past limit[q] writes nothing for q: the merge reads the tiles below the limit only.
 //
 // The selection is a bitonic sorting network over the wave's 64 keys, one per lane, through __shfl_xor: 21 compare-exchange stages
@@ -445,54 +459,12 @@ template <int DIM>
 __global__ __launch_bounds__(kManyTile) void nn_l2_topk_kernel(const float *db, const int *list, int n, const int *qkey, const int *limit,
                                                                int nq, int k, unsigned long long *part)
 {
-    constexpr int KC = NnManyShape<DIM>::kChunk, P = NnManyShape<DIM>::kPitch;
-    __shared__ alignas(16) float qs[kDetectGroup * DIM];               // rows of absent queries (q >= nq): zeros, their sums unused
-    __shared__ float cs[kManyTile * P];
-    __shared__ int ks[kManyTile], lim[kDetectGroup];
-    const int t = threadIdx.x, base = blockIdx.x * kManyTile, i = base + t;
-    const int rows = min(kManyTile, n - base);
-    for (int e = t; e < kDetectGroup * DIM; e += kManyTile) {
-        const int q = e / DIM;
-        qs[e] = q < nq ? db[(size_t)qkey[q] * DIM + (e - q * DIM)] : 0.0f;
-    }
-    if (t < kDetectGroup) lim[t] = t < nq ? limit[t] : 0;
-    if (t < rows) ks[t] = list ? list[i] : i;
     float s[kDetectGroup];
-#pragma unroll
-    for (int q = 0; q < kDetectGroup; ++q) s[q] = 0.0f;
-    for (int k0 = 0; k0 < DIM; k0 += KC) {
-        __syncthreads();                                               // ks / qs written; the previous chunk read
-        for (int e = t; e < rows * KC; e += kManyTile) {
-            const int c = e / KC, kk = e - c * KC;
-            cs[c * P + kk] = db[(size_t)ks[c] * DIM + k0 + kk];
-        }
-        __syncthreads();
-        if (t < rows) {
-            const float *c = cs + t * P;
-#pragma unroll
-            for (int kk = 0; kk + 4 <= KC; kk += 4) {
-                const float c0 = c[kk], c1 = c[kk + 1], c2 = c[kk + 2], c3 = c[kk + 3];
-#pragma unroll
-                for (int q = 0; q < kDetectGroup; ++q) {
-                    const float *a = qs + q * DIM + k0 + kk;
-                    const float d0 = a[0] - c0, d1 = a[1] - c1, d2 = a[2] - c2, d3 = a[3] - c3;
-                    s[q] += ((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3;
-                }
-            }
-#pragma unroll
-            for (int kk = KC / 4 * 4; kk < KC; ++kk) {
-                const float ck = c[kk];
-#pragma unroll
-                for (int q = 0; q < kDetectGroup; ++q) {
-                    const float d = qs[q * DIM + k0 + kk] - ck;
-                    s[q] += d * d;
-                }
-            }
-        }
-    }
+    const int *lim = nn_tile_sums<DIM>(db, list, n, qkey, limit, nq, s);
+    const int t = threadIdx.x, base = blockIdx.x * kManyTile, i = base + t;
 #pragma unroll
     for (int q = 0; q < kDetectGroup; ++q) {
-        if (base >= lim[q]) continue;                                  // the same for every lane (lim[q] <= n; absent queries: 0)
+        if (base >= lim[q]) continue;                              // the same for every lane (lim[q] <= n; absent queries: 0)
         const bool valid = i < lim[q] && s[q] == s[q];
         unsigned long long key = valid ? ((unsigned long long)__float_as_uint(s[q]) << 32) | (unsigned int)i : ~0ull;
         key = wave_sort_ascending(key, t);
@@ -500,8 +472,8 @@ __global__ __launch_bounds__(kManyTile) void nn_l2_topk_kernel(const float *db, 
     }
 }
 
-// one listed candidate of a query: its position in the query's list and its global key (-1, -1: the slot is unused) and sqrtf of
-// the squared distance over the first report_dims floats (+inf for an unused slot)
+// one listed candidate of a query: its position in the query's list and its global key (-1, -1: the slot is unused) and the
+// reported distance (+inf for an unused slot)
 struct NnTopkEntry {
     int pos, key;
     float dist;
@@ -510,7 +482,7 @@ struct NnTopkEntry {
 // the merge and the finishing step, one workgroup per query of the whole call: the query's (tiles below its limit) * k partial keys,
 // which start at part[part_row[q] * k], go through LDS in rounds of up to kTopkMergeCap - k keys beside the k best so far, each
 // round one bitonic sort of the next power of two; then one thread per listed entry does what nn_finish_many_kernel does for the
-// winner (list_off[q]: where the query's list starts in `list`, -1 for keys 0 .. n - 1) and writes res[q * k + j]
+// winner and writes res[q * k + j]
 constexpr int kTopkMergeCap = 2048;
 
 template <int DIM>
@@ -548,41 +520,24 @@ __global__ __launch_bounds__(kNnThreads) void nn_topk_merge_kernel(const float *
     const unsigned long long b = buf[t];
     if (b != ~0ull) {
         r.pos = (int)(b & 0xffffffffu);
-        r.key = list_off[q] < 0 ? r.pos : list[list_off[q] + r.pos];
-        const float *c = db + (size_t)r.key * DIM;
-        float s = 0.0f;
-        int d = 0;
-        for (; d + 4 <= report_dims; d += 4) {
-            const float d0 = a[d] - c[d], d1 = a[d + 1] - c[d + 1], d2 = a[d + 2] - c[d + 2], d3 = a[d + 3] - c[d + 3];
-            s += ((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3;
-        }
-        for (; d < report_dims; ++d) {
-            const float dd = a[d] - c[d];
-            s += dd * dd;
-        }
-        r.dist = sqrtf(s);
+        r.dist = nn_reported<DIM>(db, list, list_off[q], r.pos, a, report_dims, &r.key);
     }
     res[(size_t)q * (size_t)k + t] = r;
 }
 
-// the candidate lists' work buffers of a handle (`scl::NnTopkWork topk`; the lists share d_list): they grow like d_list
-struct NnTopkWork {
-    int *d_q = nullptr;                          // qkey | limit | list_off | part_row, `count` elements each
-    unsigned long long *d_part = nullptr;        // [query][tile][k], group after group
-    NnTopkEntry *d_res = nullptr;                // [query][k]
-    size_t q_cap = 0, part_cap = 0, res_cap = 0;
+// the work buffers of a batched search on a handle (`many` with R = NnManyResult for the 1-NN form, `topk` with R = NnTopkEntry for
+// the candidate lists; the lists share d_list): they grow like d_list
+template <class R> struct NnWork {
+    int *d_q = nullptr;                          // the plan's table: qkey | limit | list_off [| part_row], `count` elements each
+    unsigned long long *d_keys = nullptr;        // 1-NN: best[query]; k-NN: the partial lists [query][tile][k], group after group
+    R *d_res = nullptr;                          // 1-NN: [query]; k-NN: [query][k]
+    size_t q_cap = 0, keys_cap = 0, res_cap = 0;
     void release()
     {
-        for (void *p : {(void *)d_q, (void *)d_part, (void *)d_res})
+        for (void *p : {(void *)d_q, (void *)d_keys, (void *)d_res})
             if (p) (void)hipFree(p);
-        d_q = nullptr; d_part = nullptr; d_res = nullptr; q_cap = part_cap = res_cap = 0;
+        d_q = nullptr; d_keys = nullptr; d_res = nullptr; q_cap = keys_cap = res_cap = 0;
     }
-};
-
-// a candidate list of a batched search: n global keys, keys == nullptr for keys 0 .. n - 1
-struct NnList {
-    const int *keys;
-    int n;
 };
 
 // ---- what every vector plugin's handle holds: scl_m2dp, scl_fpfh and scl_grsd derive from it and add `cfg` (device, dist_thres,
@@ -605,8 +560,8 @@ template <int DIM> struct VectorPlugin {
     FloatRows<DIM> db;
     unsigned long long *d_best = nullptr;
     int *d_list = nullptr; size_t list_cap = 0;
-    NnManyWork many;                                         // the batched detections' work buffers
-    NnTopkWork topk;                                         // the candidate lists' work buffers
+    NnWork<NnManyResult> many;                               // the batched detections' work buffers
+    NnWork<NnTopkEntry> topk;                                // the candidate lists' work buffers
     double kernel_us = 0.0;
     // the reference's inter detection state: the call counter and the snapshot [0, snap_n) taken at the last rebuild
     int tree_counter = 0, snap_n = 0;
@@ -618,71 +573,143 @@ template <int DIM> struct VectorPlugin {
     const char *bad_cloud(int) const { return "non-finite coordinate"; }
 };
 
-// `count` queries in one call: query i is row qkey[i] against the prefix [0, limit[i]) of lists[which[i]] (limit[i] <= its n).
-// The queries are grouped by list and run in groups of 16 back to back on the stream, then the finishing kernel; ONE device-to-host
-// copy and ONE synchronisation for the whole call.  out[i]: as NnManyResult says, in the caller's order.
+// ---- the driver of a batched search.  `count` queries in one call: query i is row qkey[i] against the prefix [0, limit[i]) of
+// lists[which[i]] (limit[i] <= its n).  k == 0 with R = NnManyResult: the nearest, out[i]; k >= 1 with R = NnTopkEntry: the k nearest,
+// out[i * k + j] the j-th by (squared distance bits, position), an unused slot (fewer than k candidates with a non-NaN distance) as
+// NnTopkEntry says; both in the caller's order.  The queries are grouped by list (nn_plan.hpp) and run in groups of 16 back to back
+// on the stream -- nn_l2_many_kernel into best[], or nn_l2_topk_kernel into the partial lists -- then the finishing or the merge
+// kernel over all queries; ONE device-to-host copy and ONE synchronisation for the whole call
+template <class H, class R>
+int nearest_batch_locked(H *h, NnWork<R> &w, const int *qkey, const int *limit, const int *which, const NnList lists[2], int count, int k,
+                         int report_dims, R *out)
+{
+    constexpr int DIM = decltype(h->db)::kDim;
+    constexpr bool kOne = std::is_same<R, NnManyResult>::value;        // k == 0
+    if (count <= 0) return SCL_OK;
+    NnPlan p;
+    if (!nn_plan<kDetectGroup, kManyTile>(qkey, limit, which, lists, count, k, &p))
+        return fail(h, SCL_ERR_NOMEM, "candidate lists: the partial lists pass 2^31 rows");
+    const size_t per = kOne ? 1 : (size_t)k, n_keys = kOne ? (size_t)count : p.rows * per, n_res = (size_t)count * per;
+    int rc;
+    if ((rc = dev_reserve(h, &h->d_list, &h->list_cap, p.keys)) || (rc = dev_reserve(h, &w.d_q, &w.q_cap, (size_t)count, (size_t)p.cols)) ||
+        (rc = dev_reserve(h, &w.d_keys, &w.keys_cap, n_keys)) || (rc = dev_reserve(h, &w.d_res, &w.res_cap, n_res)))
+        return rc;
+    for (int l = 0; l < 2; ++l)
+        if (p.off[l] >= 0)
+            SCL_HIP(h, hipMemcpyAsync(h->d_list + p.off[l], lists[l].keys, sizeof(int) * (size_t)p.used[l], hipMemcpyHostToDevice, h->stream));
+    SCL_HIP(h, hipMemcpyAsync(w.d_q, p.table.data(), sizeof(int) * p.table.size(), hipMemcpyHostToDevice, h->stream));
+    if (kOne) SCL_HIP(h, hipMemsetAsync(w.d_keys, 0xff, sizeof(unsigned long long) * (size_t)count, h->stream));
+    const int *d_qkey = w.d_q, *d_limit = w.d_q + count, *d_off = w.d_q + 2 * (size_t)count, *d_row = w.d_q + 3 * (size_t)count;
+    for (const NnGroup &g : p.groups) {
+        if (g.n <= 0) continue;                                        // every prefix empty: best stays unset, the merge reads no tile
+        const int *d_keys_of_list = p.off[g.list] >= 0 ? h->d_list + p.off[g.list] : nullptr;
+        if constexpr (kOne)
+            hipLaunchKernelGGL(nn_l2_many_kernel<DIM>, dim3((unsigned)g.tiles), dim3(kManyTile), 0, h->stream, h->db.d_db, d_keys_of_list, g.n,
+                               d_qkey + g.first, d_limit + g.first, g.G, w.d_keys + g.first);
+        else
+            hipLaunchKernelGGL(nn_l2_topk_kernel<DIM>, dim3((unsigned)g.tiles), dim3(kManyTile), 0, h->stream, h->db.d_db, d_keys_of_list, g.n,
+                               d_qkey + g.first, d_limit + g.first, g.G, k, w.d_keys + (size_t)p.table[3 * (size_t)count + g.first] * per);
+    }
+    if constexpr (kOne)
+        hipLaunchKernelGGL(nn_finish_many_kernel<DIM>, dim3((unsigned)((count + kNnThreads - 1) / kNnThreads)), dim3(kNnThreads), 0, h->stream,
+                           h->db.d_db, h->d_list, d_qkey, d_off, w.d_keys, count, report_dims, w.d_res);
+    else
+        hipLaunchKernelGGL(nn_topk_merge_kernel<DIM>, dim3((unsigned)count), dim3(kNnThreads), 0, h->stream, h->db.d_db, h->d_list, d_qkey, d_off,
+                           d_limit, d_row, w.d_keys, k, report_dims, w.d_res);
+    SCL_HIP(h, hipGetLastError());
+    std::vector<R> res(n_res);
+    SCL_HIP(h, hipMemcpyAsync(res.data(), w.d_res, sizeof(R) * n_res, hipMemcpyDeviceToHost, h->stream));
+    SCL_HIP(h, hipStreamSynchronize(h->stream));
+    for (int j = 0; j < count; ++j) std::copy_n(res.begin() + (size_t)j * per, per, out + (size_t)p.order[(size_t)j] * per);
+    return SCL_OK;
+}
+
 template <class H>
 int nearest_many_locked(H *h, const int *qkey, const int *limit, const int *which, const NnList lists[2], int count, int report_dims,
                         NnManyResult *out)
 {
-    constexpr int DIM = decltype(h->db)::kDim;
-    if (count <= 0) return SCL_OK;
-    std::vector<int> order((size_t)count);
-    int seg[3] = {0, 0, count}, used[2] = {0, 0};
+    return nearest_batch_locked(h, h->many, qkey, limit, which, lists, count, 0, report_dims, out);
+}
+
+template <class H>
+int nearest_topk_many_locked(H *h, const int *qkey, const int *limit, const int *which, const NnList lists[2], int count, int k,
+                             int report_dims, NnTopkEntry *out)
+{
+    return nearest_batch_locked(h, h->topk, qkey, limit, which, lists, count, k, report_dims, out);
+}
+
+// ---- the search sets of the detections, each rule written once: the single calls, the batched calls and the candidate lists all
+// take theirs from search_sets_locked.  Query i is row qkey[i] against the prefix [0, limit[i]) of lists[which[i]]
+struct NnSearch {
+    std::vector<int> qkey, limit, which, others;
+    NnList lists[2] = {{nullptr, 0}, {nullptr, 0}};
+    bool too_few = false;                        // the snapshot rule before num_exclude_recent + 1 keyframes: nothing is searched
+    int tree_counter = 0, snap_n = 0;            // the handle's snapshot state after these queries: commit_search_locked
+};
+
+// detect_intra: the keyframes of this robot before cur - num_exclude_recent
+template <class H> int intra_sets_locked(const H *h, const std::string &call, const int *curs, int count, NnSearch *s)
+{
+    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
+    for (int i = 0; i < count; ++i)
+        if (curs[i] < 0 || curs[i] >= (int)mine.size()) return fail(h, SCL_ERR_OUT_OF_RANGE, (call + ": no such keyframe of this robot").c_str());
     for (int i = 0; i < count; ++i) {
-        seg[1] += which[i] == 0;
-        used[which[i]] = std::max(used[which[i]], limit[i]);
+        s->qkey[(size_t)i] = mine[(size_t)curs[i]];
+        s->limit[(size_t)i] = std::max(0, curs[i] - h->cfg.num_exclude_recent);
     }
-    for (int i = 0, a = 0, b = seg[1]; i < count; ++i) order[(size_t)(which[i] == 0 ? a++ : b++)] = i;
-    // the prefixes of the lists the queries reach, one after the other in d_list
-    int off[2] = {-1, -1};
-    size_t keys = 0;
-    for (int l = 0; l < 2; ++l)
-        if (lists[l].keys && used[l] > 0) { off[l] = (int)keys; keys += (size_t)used[l]; }
-    if (keys > h->list_cap) {
-        h->list_cap = 0;
-        const size_t c = keys + keys / 2 + 256;
-        int rc = dev_regrow(h, &h->d_list, c);
-        if (rc) return rc;
-        h->list_cap = c;
-    }
-    NnManyWork &w = h->many;
-    if ((size_t)count > w.cap) {
-        w.cap = 0;
-        const size_t c = (size_t)count + (size_t)count / 2 + 256;
-        int rc;
-        if ((rc = dev_regrow(h, &w.d_q, 3 * c)) || (rc = dev_regrow(h, &w.d_best, c)) || (rc = dev_regrow(h, &w.d_res, c))) return rc;
-        w.cap = c;
-    }
-    std::vector<int> hq(3 * (size_t)count);
-    for (int j = 0; j < count; ++j) {
-        const int i = order[(size_t)j];
-        hq[(size_t)j] = qkey[i]; hq[(size_t)count + j] = limit[i]; hq[2 * (size_t)count + j] = off[which[i]];
-    }
-    for (int l = 0; l < 2; ++l)
-        if (off[l] >= 0)
-            SCL_HIP(h, hipMemcpyAsync(h->d_list + off[l], lists[l].keys, sizeof(int) * (size_t)used[l], hipMemcpyHostToDevice, h->stream));
-    SCL_HIP(h, hipMemcpyAsync(w.d_q, hq.data(), sizeof(int) * hq.size(), hipMemcpyHostToDevice, h->stream));
-    SCL_HIP(h, hipMemsetAsync(w.d_best, 0xff, sizeof(unsigned long long) * (size_t)count, h->stream));
-    const int *d_qkey = w.d_q, *d_limit = w.d_q + count, *d_off = w.d_q + 2 * (size_t)count;
-    for (int l = 0; l < 2; ++l)
-        for (int s = seg[l]; s < seg[l + 1]; s += kDetectGroup) {
-            const int G = std::min(kDetectGroup, seg[l + 1] - s);
-            int n = 0;
-            for (int j = s; j < s + G; ++j) n = std::max(n, hq[(size_t)count + j]);
-            if (n <= 0) continue;                                      // every prefix of the group empty: best stays unset
-            hipLaunchKernelGGL(nn_l2_many_kernel<DIM>, dim3((unsigned)((n + kManyTile - 1) / kManyTile)), dim3(kManyTile), 0, h->stream,
-                               h->db.d_db, off[l] >= 0 ? h->d_list + off[l] : nullptr, n, d_qkey + s, d_limit + s, G, w.d_best + s);
-        }
-    hipLaunchKernelGGL(nn_finish_many_kernel<DIM>, dim3((unsigned)((count + kNnThreads - 1) / kNnThreads)), dim3(kNnThreads), 0, h->stream,
-                       h->db.d_db, h->d_list, d_qkey, d_off, w.d_best, count, report_dims, w.d_res);
-    SCL_HIP(h, hipGetLastError());
-    std::vector<NnManyResult> res((size_t)count);
-    SCL_HIP(h, hipMemcpyAsync(res.data(), w.d_res, sizeof(NnManyResult) * (size_t)count, hipMemcpyDeviceToHost, h->stream));
-    SCL_HIP(h, hipStreamSynchronize(h->stream));
-    for (int j = 0; j < count; ++j) out[order[(size_t)j]] = res[(size_t)j];
+    s->lists[0] = {mine.data(), (int)mine.size()};                     // ascending keys: position = local index
     return SCL_OK;
 }
+
+// detect_inter by M2DP's rule (inter_mode 1 of FPFH and GRSD): a keyframe of this robot searches the sorted keys of every other
+// robot, a received keyframe searches this robot's
+template <class H> void inter_lists_sets_locked(const H *h, const int *curs, int count, NnSearch *s)
+{
+    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
+    for (int r = 0; r < h->reg.robot_num; ++r)
+        if (r != h->cfg.this_id) s->others.insert(s->others.end(), h->reg.keys_of(r).begin(), h->reg.keys_of(r).end());
+    std::sort(s->others.begin(), s->others.end());                     // ties go to the lowest key
+    s->lists[0] = {s->others.data(), (int)s->others.size()};
+    s->lists[1] = {mine.data(), (int)mine.size()};
+    for (int i = 0; i < count; ++i) {
+        s->which[(size_t)i] = h->reg.robots[(size_t)curs[i]] == h->cfg.this_id ? 0 : 1;
+        s->limit[(size_t)i] = s->lists[s->which[(size_t)i]].n;
+    }
+}
+
+// detect_inter of the reference (inter_mode 0 of FPFH and GRSD; FPFH: D.h:381-428, GRSD: D.h:116-167), the handle's tree_counter
+// and snap_n walked as `count` single calls in order would: before num_exclude_recent + 1 keyframes nothing is searched and the
+// counter stays; else the snapshot [0, snap_n) is retaken when tree_counter % tree_making_period == 0 and the counter advances
+template <class H> void inter_snapshot_sets_locked(const H *h, int count, NnSearch *s)
+{
+    if ((s->too_few = h->reg.n < h->cfg.num_exclude_recent + 1)) return;
+    for (int i = 0; i < count; ++i) {
+        if (s->tree_counter % h->snapshot_period() == 0) s->snap_n = h->reg.n - h->cfg.num_exclude_recent;
+        s->tree_counter += 1;
+        s->limit[(size_t)i] = s->snap_n;
+    }
+    s->lists[0] = {nullptr, h->reg.n};
+}
+
+// the search sets of `call` (detect_intra / detect_inter, or their _topk forms: the messages' prefix) for curs[0 .. count): every
+// cur is validated before anything runs
+template <class H> int search_sets_locked(const H *h, bool intra, const std::string &call, const int *curs, int count, NnSearch *s)
+{
+    s->qkey = std::vector<int>((size_t)count);
+    std::copy_n(curs, count, s->qkey.begin());                         // inter: a cur is a global key
+    s->limit.assign((size_t)count, 0);
+    s->which.assign((size_t)count, 0);
+    s->tree_counter = h->tree_counter; s->snap_n = h->snap_n;
+    if (intra) return intra_sets_locked(h, call, curs, count, s);
+    for (int i = 0; i < count; ++i)
+        if (curs[i] < 0 || curs[i] >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, (call + ": key out of range").c_str());
+    if (h->inter_snapshot()) inter_snapshot_sets_locked(h, count, s);
+    else inter_lists_sets_locked(h, curs, count, s);
+    return SCL_OK;
+}
+
+// the snapshot rule's state after the queries of `s`; the other rules leave it as it was
+template <class H> void commit_search_locked(H *h, const NnSearch &s) { h->tree_counter = s.tree_counter; h->snap_n = s.snap_n; }
 
 // the detections' answers from the search results, as the single calls give them: nothing searched -> (-1, +inf); every distance
 // NaN -> (-1, that NaN); else the reported distance, and the loop (the position for intra, the key for inter) when it is below
@@ -705,164 +732,21 @@ template <class H> void report_many(const H *h, const NnManyResult *res, int cou
     }
 }
 
-// detect_intra for curs[0 .. count): every cur validated first, then one batched search over this robot's keys
-template <class H> int detect_intra_many_locked(H *h, const int *curs, int count, int *loop_ids, float *dists)
+// detect_intra / detect_inter for curs[0 .. count) in one batched search.  The snapshot rule's state is committed on success only;
+// where it searches nothing it answers (-1, 0)
+template <class H> int detect_many_locked(H *h, bool intra, const int *curs, int count, int *loop_ids, float *dists)
 {
-    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
-    for (int i = 0; i < count; ++i)
-        if (curs[i] < 0 || curs[i] >= (int)mine.size()) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_intra: no such keyframe of this robot");
-    std::vector<int> qkey((size_t)count), limit((size_t)count), which((size_t)count, 0);
-    for (int i = 0; i < count; ++i) {
-        qkey[(size_t)i] = mine[(size_t)curs[i]];
-        limit[(size_t)i] = std::max(0, curs[i] - h->cfg.num_exclude_recent);
-    }
-    const NnList lists[2] = {{mine.data(), (int)mine.size()}, {nullptr, 0}};       // ascending keys: position = local index
-    std::vector<NnManyResult> res((size_t)count);
-    int rc = nearest_many_locked(h, qkey.data(), limit.data(), which.data(), lists, count, h->report_dims(), res.data());
+    NnSearch s;
+    int rc = search_sets_locked(h, intra, intra ? "detect_intra" : "detect_inter", curs, count, &s);
     if (rc) return rc;
-    report_many(h, res.data(), count, true, loop_ids, dists);
-    return SCL_OK;
-}
-
-// detect_inter by M2DP's rule (inter_mode 1 of FPFH and GRSD) for curs[0 .. count): a keyframe of this robot searches the sorted
-// keys of every other robot, a received keyframe searches this robot's
-template <class H> int detect_inter_lists_many_locked(H *h, const int *curs, int count, int *loop_ids, float *dists)
-{
-    for (int i = 0; i < count; ++i)
-        if (curs[i] < 0 || curs[i] >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter: key out of range");
-    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
-    std::vector<int> others;
-    for (int r = 0; r < h->reg.robot_num; ++r)
-        if (r != h->cfg.this_id) others.insert(others.end(), h->reg.keys_of(r).begin(), h->reg.keys_of(r).end());
-    std::sort(others.begin(), others.end());                                      // ties go to the lowest key
-    const NnList lists[2] = {{others.data(), (int)others.size()}, {mine.data(), (int)mine.size()}};
-    std::vector<int> limit((size_t)count), which((size_t)count);
-    for (int i = 0; i < count; ++i) {
-        which[(size_t)i] = h->reg.robots[(size_t)curs[i]] == h->cfg.this_id ? 0 : 1;
-        limit[(size_t)i] = lists[which[(size_t)i]].n;
-    }
-    std::vector<NnManyResult> res((size_t)count);
-    int rc = nearest_many_locked(h, curs, limit.data(), which.data(), lists, count, h->report_dims(), res.data());
-    if (rc) return rc;
-    report_many(h, res.data(), count, false, loop_ids, dists);
-    return SCL_OK;
-}
-
-// detect_inter of the reference (inter_mode 0 of FPFH and GRSD) for curs[0 .. count), the handle's tree_counter and snap_n walked
-// as `count` single calls in order would: before num_exclude_recent + 1 keyframes (-1, 0) and the counter stays; else the snapshot
-// [0, snap_n) is retaken when tree_counter % tree_making_period == 0 and the counter advances.  Both are committed on success only
-template <class H> int detect_inter_snapshot_many_locked(H *h, const int *curs, int count, int *loop_ids, float *dists)
-{
-    for (int i = 0; i < count; ++i)
-        if (curs[i] < 0 || curs[i] >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter: key out of range");
-    if (h->reg.n < h->cfg.num_exclude_recent + 1) {
+    if (s.too_few) {
         for (int i = 0; i < count; ++i) { loop_ids[i] = -1; if (dists) dists[i] = 0.0f; }
         return SCL_OK;
     }
-    int counter = h->tree_counter, snap_n = h->snap_n;
-    std::vector<int> limit((size_t)count), which((size_t)count, 0);
-    for (int i = 0; i < count; ++i) {
-        if (counter % h->snapshot_period() == 0) snap_n = h->reg.n - h->cfg.num_exclude_recent;
-        counter += 1;
-        limit[(size_t)i] = snap_n;
-    }
-    const NnList lists[2] = {{nullptr, h->reg.n}, {nullptr, 0}};
     std::vector<NnManyResult> res((size_t)count);
-    int rc = nearest_many_locked(h, curs, limit.data(), which.data(), lists, count, h->report_dims(), res.data());
-    if (rc) return rc;
-    h->tree_counter = counter; h->snap_n = snap_n;
-    report_many(h, res.data(), count, false, loop_ids, dists);
-    return SCL_OK;
-}
-
-// ---- the candidate lists: the k nearest instead of the nearest.  `count` queries as nearest_many_locked takes them; out[i * k + j]
-// is the j-th nearest of query i by (squared distance bits, position), an unused slot (fewer than k candidates with a non-NaN
-// distance) as NnTopkEntry says.  Grouped by list, groups of 16 back to back on the stream (nn_l2_topk_kernel into the partials),
-// then the merge over all queries; ONE device-to-host copy and ONE synchronisation for the whole call
-template <class H>
-int nearest_topk_many_locked(H *h, const int *qkey, const int *limit, const int *which, const NnList lists[2], int count, int k,
-                             int report_dims, NnTopkEntry *out)
-{
-    constexpr int DIM = decltype(h->db)::kDim;
-    if (count <= 0) return SCL_OK;
-    std::vector<int> order((size_t)count);
-    int seg[3] = {0, 0, count}, used[2] = {0, 0};
-    for (int i = 0; i < count; ++i) {
-        seg[1] += which[i] == 0;
-        used[which[i]] = std::max(used[which[i]], limit[i]);
-    }
-    for (int i = 0, a = 0, b = seg[1]; i < count; ++i) order[(size_t)(which[i] == 0 ? a++ : b++)] = i;
-    int off[2] = {-1, -1};
-    size_t keys = 0;
-    for (int l = 0; l < 2; ++l)
-        if (lists[l].keys && used[l] > 0) { off[l] = (int)keys; keys += (size_t)used[l]; }
-    // qkey | limit | list_off | part_row in the grouped order; a group's partials: [query][tile][k] over the tiles of its longest prefix
-    std::vector<int> hq(4 * (size_t)count);
-    for (int j = 0; j < count; ++j) {
-        const int i = order[(size_t)j];
-        hq[(size_t)j] = qkey[i]; hq[(size_t)count + j] = limit[i]; hq[2 * (size_t)count + j] = off[which[i]];
-    }
-    size_t rows = 0;
-    for (int l = 0; l < 2; ++l)
-        for (int s = seg[l]; s < seg[l + 1]; s += kDetectGroup) {
-            const int G = std::min(kDetectGroup, seg[l + 1] - s);
-            int n = 0;
-            for (int j = s; j < s + G; ++j) n = std::max(n, hq[(size_t)count + j]);
-            const size_t tiles = ((size_t)n + kManyTile - 1) / kManyTile;
-            if (rows + (size_t)G * tiles > (size_t)INT32_MAX) return fail(h, SCL_ERR_NOMEM, "candidate lists: the partial lists pass 2^31 rows");
-            for (int j = s; j < s + G; ++j) hq[3 * (size_t)count + j] = (int)(rows + (size_t)(j - s) * tiles);
-            rows += (size_t)G * tiles;
-        }
-    if (keys > h->list_cap) {
-        h->list_cap = 0;
-        const size_t c = keys + keys / 2 + 256;
-        int rc = dev_regrow(h, &h->d_list, c);
-        if (rc) return rc;
-        h->list_cap = c;
-    }
-    NnTopkWork &w = h->topk;
-    const size_t n_part = rows * (size_t)k, n_res = (size_t)count * (size_t)k;
-    int rc;
-    if ((size_t)count > w.q_cap) {
-        w.q_cap = 0;
-        const size_t c = (size_t)count + (size_t)count / 2 + 256;
-        if ((rc = dev_regrow(h, &w.d_q, 4 * c))) return rc;
-        w.q_cap = c;
-    }
-    if (n_part > w.part_cap) {
-        w.part_cap = 0;
-        const size_t c = n_part + n_part / 2 + 256;
-        if ((rc = dev_regrow(h, &w.d_part, c))) return rc;
-        w.part_cap = c;
-    }
-    if (n_res > w.res_cap) {
-        w.res_cap = 0;
-        const size_t c = n_res + n_res / 2 + 256;
-        if ((rc = dev_regrow(h, &w.d_res, c))) return rc;
-        w.res_cap = c;
-    }
-    for (int l = 0; l < 2; ++l)
-        if (off[l] >= 0)
-            SCL_HIP(h, hipMemcpyAsync(h->d_list + off[l], lists[l].keys, sizeof(int) * (size_t)used[l], hipMemcpyHostToDevice, h->stream));
-    SCL_HIP(h, hipMemcpyAsync(w.d_q, hq.data(), sizeof(int) * hq.size(), hipMemcpyHostToDevice, h->stream));
-    const int *d_qkey = w.d_q, *d_limit = w.d_q + count, *d_off = w.d_q + 2 * (size_t)count, *d_row = w.d_q + 3 * (size_t)count;
-    for (int l = 0; l < 2; ++l)
-        for (int s = seg[l]; s < seg[l + 1]; s += kDetectGroup) {
-            const int G = std::min(kDetectGroup, seg[l + 1] - s);
-            int n = 0;
-            for (int j = s; j < s + G; ++j) n = std::max(n, hq[(size_t)count + j]);
-            if (n <= 0) continue;                                      // every prefix of the group empty: the merge reads no tile
-            hipLaunchKernelGGL(nn_l2_topk_kernel<DIM>, dim3((unsigned)((n + kManyTile - 1) / kManyTile)), dim3(kManyTile), 0, h->stream,
-                               h->db.d_db, off[l] >= 0 ? h->d_list + off[l] : nullptr, n, d_qkey + s, d_limit + s, G, k,
-                               w.d_part + (size_t)hq[3 * (size_t)count + s] * (size_t)k);
-        }
-    hipLaunchKernelGGL(nn_topk_merge_kernel<DIM>, dim3((unsigned)count), dim3(kNnThreads), 0, h->stream, h->db.d_db, h->d_list, d_qkey, d_off,
-                       d_limit, d_row, w.d_part, k, report_dims, w.d_res);
-    SCL_HIP(h, hipGetLastError());
-    std::vector<NnTopkEntry> res(n_res);
-    SCL_HIP(h, hipMemcpyAsync(res.data(), w.d_res, sizeof(NnTopkEntry) * n_res, hipMemcpyDeviceToHost, h->stream));
-    SCL_HIP(h, hipStreamSynchronize(h->stream));
-    for (int j = 0; j < count; ++j) std::copy_n(res.begin() + (size_t)j * k, k, out + (size_t)order[(size_t)j] * k);
+    if ((rc = nearest_many_locked(h, s.qkey.data(), s.limit.data(), s.which.data(), s.lists, count, h->report_dims(), res.data()))) return rc;
+    commit_search_locked(h, s);
+    report_many(h, res.data(), count, intra, loop_ids, dists);
     return SCL_OK;
 }
 
@@ -882,81 +766,23 @@ inline void report_topk(const NnTopkEntry *res, int count, int k, bool local_ids
     }
 }
 
-inline bool topk_ok(int k) { return k >= 1 && k <= kTopkMax; }
-
-// the candidate list of detect_intra for curs[0 .. count): the search sets of detect_intra_many_locked
+// the candidate lists of detect_intra / detect_inter for curs[0 .. count): the search sets of detect_many_locked, a bad k refused
+// before curs is looked at.  The snapshot rule's state is committed on success only; where it searches nothing every list is empty
 template <class H>
-int detect_intra_topk_locked(H *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
+int detect_topk_locked(H *h, bool intra, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
 {
-    if (!topk_ok(k)) return fail(h, SCL_ERR_INVALID_ARG, "detect_intra_topk: k outside [1, SCL_PLUGIN_TOPK_MAX]");
-    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
-    for (int i = 0; i < count; ++i)
-        if (curs[i] < 0 || curs[i] >= (int)mine.size()) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_intra_topk: no such keyframe of this robot");
-    std::vector<int> qkey((size_t)count), limit((size_t)count), which((size_t)count, 0);
-    for (int i = 0; i < count; ++i) {
-        qkey[(size_t)i] = mine[(size_t)curs[i]];
-        limit[(size_t)i] = std::max(0, curs[i] - h->cfg.num_exclude_recent);
-    }
-    const NnList lists[2] = {{mine.data(), (int)mine.size()}, {nullptr, 0}};       // ascending keys: position = local index
-    std::vector<NnTopkEntry> res((size_t)count * k);
-    int rc = nearest_topk_many_locked(h, qkey.data(), limit.data(), which.data(), lists, count, k, h->report_dims(), res.data());
+    const std::string call = intra ? "detect_intra_topk" : "detect_inter_topk";
+    if (k < 1 || k > kTopkMax) return fail(h, SCL_ERR_INVALID_ARG, (call + ": k outside [1, SCL_PLUGIN_TOPK_MAX]").c_str());
+    NnSearch s;
+    int rc = search_sets_locked(h, intra, call, curs, count, &s);
     if (rc) return rc;
-    report_topk(res.data(), count, k, true, cand_ids, cand_dists, n_found);
-    return SCL_OK;
-}
-
-// the candidate list of detect_inter by M2DP's rule (inter_mode 1 of FPFH and GRSD): the search sets of detect_inter_lists_many_locked
-template <class H>
-int detect_inter_lists_topk_locked(H *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
-{
-    if (!topk_ok(k)) return fail(h, SCL_ERR_INVALID_ARG, "detect_inter_topk: k outside [1, SCL_PLUGIN_TOPK_MAX]");
-    for (int i = 0; i < count; ++i)
-        if (curs[i] < 0 || curs[i] >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter_topk: key out of range");
-    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
-    std::vector<int> others;
-    for (int r = 0; r < h->reg.robot_num; ++r)
-        if (r != h->cfg.this_id) others.insert(others.end(), h->reg.keys_of(r).begin(), h->reg.keys_of(r).end());
-    std::sort(others.begin(), others.end());                                      // ties go to the lowest key
-    const NnList lists[2] = {{others.data(), (int)others.size()}, {mine.data(), (int)mine.size()}};
-    std::vector<int> limit((size_t)count), which((size_t)count);
-    for (int i = 0; i < count; ++i) {
-        which[(size_t)i] = h->reg.robots[(size_t)curs[i]] == h->cfg.this_id ? 0 : 1;
-        limit[(size_t)i] = lists[which[(size_t)i]].n;
-    }
     std::vector<NnTopkEntry> res((size_t)count * k);
-    int rc = nearest_topk_many_locked(h, curs, limit.data(), which.data(), lists, count, k, h->report_dims(), res.data());
-    if (rc) return rc;
-    report_topk(res.data(), count, k, false, cand_ids, cand_dists, n_found);
-    return SCL_OK;
-}
-
-// the candidate list of detect_inter of the reference (inter_mode 0 of FPFH and GRSD): tree_counter and snap_n walk as in
-// detect_inter_snapshot_many_locked and are committed on success only; before num_exclude_recent + 1 keyframes every list is empty
-// and the counter stays
-template <class H>
-int detect_inter_snapshot_topk_locked(H *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
-{
-    if (!topk_ok(k)) return fail(h, SCL_ERR_INVALID_ARG, "detect_inter_topk: k outside [1, SCL_PLUGIN_TOPK_MAX]");
-    for (int i = 0; i < count; ++i)
-        if (curs[i] < 0 || curs[i] >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter_topk: key out of range");
-    if (h->reg.n < h->cfg.num_exclude_recent + 1) {
-        for (size_t e = 0; e < (size_t)count * k; ++e) { cand_ids[e] = -1; if (cand_dists) cand_dists[e] = INFINITY; }
-        for (int i = 0; n_found && i < count; ++i) n_found[i] = 0;
-        return SCL_OK;
+    if (s.too_few) std::fill(res.begin(), res.end(), NnTopkEntry{-1, -1, INFINITY});
+    else {
+        if ((rc = nearest_topk_many_locked(h, s.qkey.data(), s.limit.data(), s.which.data(), s.lists, count, k, h->report_dims(), res.data()))) return rc;
+        commit_search_locked(h, s);
     }
-    int counter = h->tree_counter, snap_n = h->snap_n;
-    std::vector<int> limit((size_t)count), which((size_t)count, 0);
-    for (int i = 0; i < count; ++i) {
-        if (counter % h->snapshot_period() == 0) snap_n = h->reg.n - h->cfg.num_exclude_recent;
-        counter += 1;
-        limit[(size_t)i] = snap_n;
-    }
-    const NnList lists[2] = {{nullptr, h->reg.n}, {nullptr, 0}};
-    std::vector<NnTopkEntry> res((size_t)count * k);
-    int rc = nearest_topk_many_locked(h, curs, limit.data(), which.data(), lists, count, k, h->report_dims(), res.data());
-    if (rc) return rc;
-    h->tree_counter = counter; h->snap_n = snap_n;
-    report_topk(res.data(), count, k, false, cand_ids, cand_dists, n_found);
+    report_topk(res.data(), count, k, intra, cand_ids, cand_dists, n_found);
     return SCL_OK;
 }
 
@@ -989,7 +815,7 @@ int make_save_and_detect_locked(H *h, const void *const *clouds, const int *n_po
         if (robots[i] == h->cfg.this_id) { curs.push_back(first + (int)curs.size()); at.push_back(i); }
     std::vector<int> loops(curs.size());
     std::vector<float> ds(curs.size());
-    if ((rc = detect_intra_many_locked(h, curs.data(), (int)curs.size(), loops.data(), ds.data()))) return rc;
+    if ((rc = detect_many_locked(h, true, curs.data(), (int)curs.size(), loops.data(), ds.data()))) return rc;
     for (int i = 0; i < count; ++i) { loop_ids[i] = -1; if (dists) dists[i] = INFINITY; }
     for (size_t j = 0; j < at.size(); ++j) { loop_ids[at[j]] = loops[j]; if (dists) dists[at[j]] = ds[j]; }
     return SCL_OK;
@@ -1106,71 +932,39 @@ template <class H> int report_one_locked(H *h, int q, int key, int loop, float d
     return SCL_OK;
 }
 
-template <class H> int detect_intra(H *h, int cur, int *loop_id, float *dist)
+// detect_intra / detect_inter of one keyframe: the search set of search_sets_locked for it, searched by nn_l2_kernel.  The snapshot
+// rule's counter advances before the search, as the reference's does
+template <class H> int detect_one(H *h, bool intra, int cur, int *loop_id, float *dist)
 {
     if (!h || !loop_id) return SCL_ERR_INVALID_ARG;
     Entered<H> in(h);
     *loop_id = -1;
     if (dist) *dist = INFINITY;
-    const std::vector<int> &mine = h->reg.keys_of(h->cfg.this_id);
-    if (cur < 0 || cur >= (int)mine.size()) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_intra: no such keyframe of this robot");
-    int pos; float d2;                                            // ascending keys: position = local index
-    int rc = nearest_locked(h, mine[(size_t)cur], mine.data(), cur - h->cfg.num_exclude_recent, &pos, &d2);
-    if (rc || pos < 0) return rc;
-    return report_one_locked(h, mine[(size_t)cur], mine[(size_t)pos], pos, d2, loop_id, dist);
-}
-
-template <class H> int detect_inter(H *h, int cur, int *loop_id, float *dist)
-{
-    if (!h || !loop_id) return SCL_ERR_INVALID_ARG;
-    Entered<H> in(h);
-    *loop_id = -1;
-    if (dist) *dist = INFINITY;
-    if (cur < 0 || cur >= h->reg.n) return fail(h, SCL_ERR_OUT_OF_RANGE, "detect_inter: key out of range");
-    int pos = -1, rc;
+    NnSearch s;
+    int rc = search_sets_locked(h, intra, intra ? "detect_intra" : "detect_inter", &cur, 1, &s);
+    if (rc) return rc;
+    if (s.too_few) { if (dist) *dist = 0.0f; return SCL_OK; }
+    commit_search_locked(h, s);
+    const NnList &list = s.lists[s.which[0]];
+    int pos;
     float d2;
-    if (h->inter_snapshot()) {                                    // the reference's detection (FPFH: D.h:381-428, GRSD: D.h:116-167)
-        if (h->reg.n < h->cfg.num_exclude_recent + 1) { if (dist) *dist = 0.0f; return SCL_OK; }
-        if (h->tree_counter % h->snapshot_period() == 0) h->snap_n = h->reg.n - h->cfg.num_exclude_recent;
-        h->tree_counter += 1;
-        if ((rc = nearest_locked(h, cur, nullptr, h->snap_n, &pos, &d2)) || pos < 0) return rc;
-    } else {
-        std::vector<int> list = h->reg.inter_candidates(cur, h->cfg.this_id);
-        std::sort(list.begin(), list.end());                      // ties go to the lowest key
-        if ((rc = nearest_locked(h, cur, list.data(), (int)list.size(), &pos, &d2)) || pos < 0) return rc;
-        pos = list[(size_t)pos];
-    }
-    return report_one_locked(h, cur, pos, pos, d2, loop_id, dist);
+    if ((rc = nearest_locked(h, s.qkey[0], list.keys, s.limit[0], &pos, &d2)) || pos < 0) return rc;
+    const int key = list.keys ? list.keys[pos] : pos;
+    return report_one_locked(h, s.qkey[0], key, intra ? pos : key, d2, loop_id, dist);
 }
 
-template <class H> int detect_intra_many(H *h, const int *curs, int count, int *loop_ids, float *dists)
+template <class H> int detect_many(H *h, bool intra, const int *curs, int count, int *loop_ids, float *dists)
 {
     if (!h || count < 0 || (count > 0 && (!curs || !loop_ids))) return SCL_ERR_INVALID_ARG;
     Entered<H> in(h);
-    return detect_intra_many_locked(h, curs, count, loop_ids, dists);
+    return detect_many_locked(h, intra, curs, count, loop_ids, dists);
 }
 
-template <class H> int detect_inter_many(H *h, const int *curs, int count, int *loop_ids, float *dists)
-{
-    if (!h || count < 0 || (count > 0 && (!curs || !loop_ids))) return SCL_ERR_INVALID_ARG;
-    Entered<H> in(h);
-    if (h->inter_snapshot()) return detect_inter_snapshot_many_locked(h, curs, count, loop_ids, dists);
-    return detect_inter_lists_many_locked(h, curs, count, loop_ids, dists);
-}
-
-template <class H> int detect_intra_topk(H *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
+template <class H> int detect_topk(H *h, bool intra, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
 {
     if (!h || count < 0 || (count > 0 && (!curs || !cand_ids))) return SCL_ERR_INVALID_ARG;
     Entered<H> in(h);
-    return detect_intra_topk_locked(h, curs, count, k, cand_ids, cand_dists, n_found);
-}
-
-template <class H> int detect_inter_topk(H *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)
-{
-    if (!h || count < 0 || (count > 0 && (!curs || !cand_ids))) return SCL_ERR_INVALID_ARG;
-    Entered<H> in(h);
-    if (h->inter_snapshot()) return detect_inter_snapshot_topk_locked(h, curs, count, k, cand_ids, cand_dists, n_found);
-    return detect_inter_lists_topk_locked(h, curs, count, k, cand_ids, cand_dists, n_found);
+    return detect_topk_locked(h, intra, curs, count, k, cand_ids, cand_dists, n_found);
 }
 
 template <class H>
@@ -1207,16 +1001,16 @@ int make_save_and_detect(H *h, const void *const *clouds, const int *n_points, i
     int P##_get_index(const P *h, int key, int8_t *robot, int *index) { return scl::get_index(h, key, robot, index); }                 \
     int P##_local_to_global(const P *h, int robot, int local, int *key) { return scl::local_to_global(h, robot, local, key); }         \
     int P##_get_signature(P *h, int key, float *values) { return scl::get_signature(h, key, values); }                                 \
-    int P##_detect_intra(P *h, int cur, int *loop_id, float *dist) { return scl::detect_intra(h, cur, loop_id, dist); }                \
-    int P##_detect_inter(P *h, int cur, int *loop_id, float *dist) { return scl::detect_inter(h, cur, loop_id, dist); }                \
+    int P##_detect_intra(P *h, int cur, int *loop_id, float *dist) { return scl::detect_one(h, true, cur, loop_id, dist); }                 \
+    int P##_detect_inter(P *h, int cur, int *loop_id, float *dist) { return scl::detect_one(h, false, cur, loop_id, dist); }                \
     int P##_detect_intra_many(P *h, const int *curs, int count, int *loop_ids, float *dists)                                           \
-    { return scl::detect_intra_many(h, curs, count, loop_ids, dists); }                                                                \
+    { return scl::detect_many(h, true, curs, count, loop_ids, dists); }                                                                 \
     int P##_detect_inter_many(P *h, const int *curs, int count, int *loop_ids, float *dists)                                           \
-    { return scl::detect_inter_many(h, curs, count, loop_ids, dists); }                                                                \
+    { return scl::detect_many(h, false, curs, count, loop_ids, dists); }                                                                \
     int P##_detect_intra_topk(P *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)                 \
-    { return scl::detect_intra_topk(h, curs, count, k, cand_ids, cand_dists, n_found); }                                               \
+    { return scl::detect_topk(h, true, curs, count, k, cand_ids, cand_dists, n_found); }                                                \
     int P##_detect_inter_topk(P *h, const int *curs, int count, int k, int *cand_ids, float *cand_dists, int *n_found)                 \
-    { return scl::detect_inter_topk(h, curs, count, k, cand_ids, cand_dists, n_found); }                                               \
+    { return scl::detect_topk(h, false, curs, count, k, cand_ids, cand_dists, n_found); }                                               \
     int P##_make_save_and_detect(P *h, const void *const *clouds, const int *n_points, int stride_bytes, const int8_t *robots,         \
                                  const int *indexs, int count, int *loop_ids, float *dists, float *out_values)                         \
     { return scl::make_save_and_detect(h, clouds, n_points, stride_bytes, robots, indexs, count, loop_ids, dists, out_values); }       \
