@@ -537,6 +537,57 @@ int  scl_geometric_verification_batch_from_store_guess(scl_engine *e, const void
                                                        float *T, float *T_fit, int *success, int *n_src_filtered, int *n_tgts,
                                                        int *n_correspondences, int *n_inliers);
 
+/*
+ * THE BATCHED ICP WITH INITIAL GUESSES.  pcl::IterativeClosestPoint::align takes a `guess`; the reference aligns every loop candidate
+ * from the identity (DM.h:1107-1121) and drops the yaw Scan Context reported, so a loop entered from the opposite direction starts
+ * 180 degrees off; and its inter-robot verification ends at RANSAC + SVD with a constant noise on the factor, where its own comment
+ * asks for the fitness score (DM.h:1361).  These three calls are the batched ICP with one initial guess per candidate.
+ *   * Arguments.  Those of the unguessed call, and guesses: n x 16 floats, candidate c's G_c = guesses + 16 * c, a row-major 4x4 whose
+ *     first three rows are read (the last is taken as 0, 0, 0, 1): the layout of the guessed verification.  Candidate c's source is
+ *     the source cloud moved by G_c with the arithmetic of scl_transform_cloud (DM.h:247-249); fields other than x, y, z play no part.
+ *     scl_icp_align_batch_guess: scl_icp_align_batch with guesses (clouds on the host).  scl_loop_icp_batch_from_store_guess, the
+ *     intra-robot side: the source is submap(key_cur, 0), moved per candidate (scl_loop_guess_from_shift with both poses of the same
+ *     robot gives G_c).  scl_icp_align_batch_from_store_guess, the inter-robot side: a RECEIVED cloud, voxel-filtered once with
+ *     src_leaf and then moved per candidate, against submaps from the store, with the layout and gates of
+ *     scl_geometric_verification_batch_from_store_guess -- whose T is the intended guess: the call answers the refined motion and
+ *     the fitness for the factor's noise.
+ *   * Outputs.  T_icp (n x 16, may be NULL), fitness, converged, iterations (n entries each, may be NULL): entry c is, bit for bit,
+ *     what scl_icp_align answers for (scl_transform_cloud(src, G_c), tgt_c) with the same parameters, for both estimators -- in the
+ *     store forms for the store's source (submap(key_cur, 0), or scl_voxel_grid(src, src_leaf)) and
+ *     scl_submap_from_store(keys_pre[c], ...).  An alignment that fails (fewer than three pairs in a search) has T_icp = identity and
+ *     converged 0, as there.  T (n x 16, required): the whole motion source -> candidate, T_icp[c] * G_c, every entry formed on the
+ *     host in double as ((a0 b0 + a1 b1) + a2 b2) + a3 b3 and rounded to float once; where T_icp[c] is the identity, T[c] is G_c with
+ *     the last row 0, 0, 0, 1.  The size gate of the store forms looks at the unmoved sizes; a gated candidate keeps T = T_icp =
+ *     identity, converged 0, fitness 0, its n_tgts reported.  Identity guesses on a cloud of finite points give the unguessed call's
+ *     bits.
+ *   * Errors.  Whatever the unguessed call refuses, with the same status -- its parameter checks (estimator, normal_radius,
+ *     max_iterations) are made here whenever n > 0 --; the received form refuses what scl_geometric_verification_batch_from_store
+ *     refuses in its cloud arguments; then guesses == NULL with n > 0, or a non-finite entry in the first three rows of any guess:
+ *     SCL_ERR_INVALID_ARG.  All before anything runs, no output written; that includes a key whose window holds a keyframe that was
+ *     never stored.  n == 0 is SCL_OK (guesses may then be NULL); the store forms still report the source's filtered size.
+ *   * How it runs.  Rounds of 32 candidates, as the unguessed calls.  A round has, in front of the unguessed chain and on the
+ *     engine's stream, one launch over all candidates for each of: the moved sources (float4 clouds in source order), their boxes,
+ *     their Hilbert keys, and one stable segmented sort (three passes) -- every sum of an alignment runs in the working order of its
+ *     source, so each candidate gets the order the single call derives from its own moved cloud; the working clouds and the fitness
+ *     pass then read candidate c's cloud through candidate c's order.  The iterations are the unguessed call's launches.  Memory, in
+ *     the grow-only control workspace: (16 + 4) bytes x n_src per candidate of a round for the sources and orders, 12 bytes x n_src
+ *     per candidate and the histograms for the sort; a later call without guesses reads none of it.  On a scl_create_sharded engine
+ *     scl_icp_align_batch_guess sends candidate c, with its guess, to shard c mod G; the store forms run on the shard that owns the
+ *     keyframe store.
+ */
+int  scl_icp_align_batch_guess(scl_engine *e, const void *src, int n_src, const void *const *tgts, const int *n_tgts,
+                               int n_targets, int stride_bytes, const float *guesses, const scl_icp_params *p,
+                               float *T, float *T_icp, float *fitness, int *converged, int *iterations);
+int  scl_loop_icp_batch_from_store_guess(scl_engine *e, int robot, int key_cur, const float *pose_cur,
+                                         int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                                         const float *guesses, const scl_icp_params *p, int min_src_points, int min_tgt_points,
+                                         float *T, float *T_icp, float *fitness, int *converged, int *iterations, int *n_src, int *n_tgts);
+int  scl_icp_align_batch_from_store_guess(scl_engine *e, const void *src, int n_src, int stride_bytes, float src_leaf,
+                                          int robot, int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                                          const float *guesses, const scl_icp_params *p, int min_src_points, int min_tgt_points,
+                                          float *T, float *T_icp, float *fitness, int *converged, int *iterations,
+                                          int *n_src_filtered, int *n_tgts);
+
 /* ---- measurement ----------------------------------------------------------- */
 int  scl_profile_enable(scl_engine *e, int on);   /* 0 off, 1 every kernel family, 2 SC distance only,
                                                      3 SC distance only, sampled: one launch in thirteen -- in the stream form one

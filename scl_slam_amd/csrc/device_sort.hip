@@ -380,6 +380,12 @@ hipError_t sort_pairs_u64(void *scratch, unsigned long long *keys_in, unsigned l
     return sort_run<unsigned long long>(scratch, keys_in, keys_out, vals_in, vals_out, seg, bits, stream);
 }
 
+hipError_t sort_pairs_u32_segmented(void *scratch, unsigned int *keys_in, unsigned int *keys_out, unsigned int *vals_in, unsigned int *vals_out,
+                                    const SortSegments &seg, int bits, hipStream_t stream)
+{
+    return sort_run<unsigned int>(scratch, keys_in, keys_out, vals_in, vals_out, seg, bits, stream);
+}
+
 hipError_t sort_pairs_u64_segmented(void *scratch, unsigned long long *keys_in, unsigned long long *keys_out, unsigned int *vals_in,
                                     unsigned int *vals_out, const SortSegments &seg, int bits, hipStream_t stream, const unsigned int *seg_hi)
 {

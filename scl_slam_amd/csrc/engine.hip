@@ -504,7 +504,7 @@ const char *scl_status_string(int status)
 
 const char *scl_last_error(const scl_engine *e) { return e ? e->last_error.c_str() : "null engine"; }
 
-int scl_abi_version(void) { return 8; }
+int scl_abi_version(void) { return 9; }
 
 int scl_default_config(scl_config *c)
 {
@@ -2938,12 +2938,29 @@ int scl_icp_align(scl_engine *e, const void *src, int n_src, const void *tgt, in
     return rc;
 }
 
+namespace {
+int icp_align_batch_host(scl_engine *e, const void *src, int n_src, const void *const *tgts, const int *n_tgts,
+                         int n_targets, int stride_bytes, const float *guesses, const scl_icp_params *p,
+                         float *T, float *fitness, int *converged, int *iterations);
+}  // namespace
+
 int scl_icp_align_batch(scl_engine *e, const void *src, int n_src, const void *const *tgts, const int *n_tgts,
                         int n_targets, int stride_bytes, const scl_icp_params *p,
                         float *T, float *fitness, int *converged, int *iterations)
 {
     if (!e || !src || !p || !T || n_targets < 0 || (n_targets > 0 && (!tgts || !n_tgts))) return SCL_ERR_INVALID_ARG;
-    if (e->front) return front_icp_align_batch(e, src, n_src, tgts, n_tgts, n_targets, stride_bytes, p, T, fitness, converged, iterations);
+    if (e->front) return front_icp_align_batch(e, src, n_src, tgts, n_tgts, n_targets, stride_bytes, nullptr, p, T, nullptr, fitness, converged, iterations);
+    return icp_align_batch_host(e, src, n_src, tgts, n_tgts, n_targets, stride_bytes, nullptr, p, T, fitness, converged, iterations);
+}
+
+namespace {
+
+// scl_icp_align_batch (guesses == nullptr) and, on one engine, scl_icp_align_batch_guess (guesses = the call's n x 16, checked by the
+// caller; T then receives every alignment's own transform, from the moved source)
+int icp_align_batch_host(scl_engine *e, const void *src, int n_src, const void *const *tgts, const int *n_tgts,
+                         int n_targets, int stride_bytes, const float *guesses, const scl_icp_params *p,
+                         float *T, float *fitness, int *converged, int *iterations)
+{
     std::lock_guard<std::mutex> lk(e->mu);
     (void)hipSetDevice(e->device);
     const int lanes = n_targets < scl_engine::kIcpLanes ? n_targets : scl_engine::kIcpLanes;
@@ -2991,13 +3008,17 @@ int scl_icp_align_batch(scl_engine *e, const void *src, int n_src, const void *c
         IcpWorkspace *wss[scl_engine::kIcpBatch];
         for (int c = 0; c < m; ++c) wss[c] = &e->icp_batch_ws[c];
         std::string err;
-        rc = icp_batch_run(wss, m, &e->icp_batch_ctl, e->stream, e->d_points, n_src, stride_bytes, *p, T + 16 * (size_t)first,
+        float g12[12 * scl_engine::kIcpBatch];                          // rows 0 .. 2 of the round's guesses
+        if (guesses) for (int c = 0; c < m; ++c) std::memcpy(g12 + 12 * (size_t)c, guesses + 16 * (size_t)(first + c), 12 * sizeof(float));
+        rc = icp_batch_run(wss, m, &e->icp_batch_ctl, e->stream, e->d_points, n_src, stride_bytes, *p, guesses ? g12 : nullptr, T + 16 * (size_t)first,
                            fitness ? fitness + first : nullptr, converged ? converged + first : nullptr,
                            iterations ? iterations + first : nullptr, &err);
         if (rc) { e->last_error = err; return rc; }
     }
     return SCL_OK;
 }
+
+}  // namespace
 
 int scl_nn_correspondences(scl_engine *e, const void *src, int n_src, const void *tgt, int n_tgt,
                            int stride_bytes, int *nn_index, float *nn_dist2)
@@ -3379,7 +3400,7 @@ int scl_loop_icp_batch_from_store(scl_engine *e, int robot, int key_cur, const f
         rc = icp_batch_prepare_all(wss, live, &e->icp_batch_ctl, e->stream, ns, tg, tn, stride, *p, &err);
         if (rc) { e->last_error = err; return rc; }
         std::vector<float> Tl(16 * (size_t)live), fl((size_t)live); std::vector<int> cl((size_t)live), il((size_t)live);
-        rc = icp_batch_run(wss, live, &e->icp_batch_ctl, e->stream, d_src, ns, stride, *p, Tl.data(), fl.data(), cl.data(), il.data(), &err);
+        rc = icp_batch_run(wss, live, &e->icp_batch_ctl, e->stream, d_src, ns, stride, *p, nullptr, Tl.data(), fl.data(), cl.data(), il.data(), &err);
         if (rc) { e->last_error = err; return rc; }
         for (int j = 0; j < live; ++j) {
             std::memcpy(T + 16 * (size_t)which[j], Tl.data() + 16 * (size_t)j, 16 * sizeof(float));
@@ -3711,6 +3732,169 @@ int verification_batch_store(scl_engine *e, const void *src, int n_src, int stri
 }
 
 }  // namespace
+
+/* ---- the batched ICP with one initial guess per candidate ------------------------ */
+
+namespace {
+
+// what icp_batch_prepare refuses in the parameters, before anything runs
+const char *icp_params_bad(const scl_icp_params &p)
+{
+    if (p.estimator != 0 && p.estimator != 1) return "unknown estimator";
+    if (p.estimator == 1 && !(p.normal_radius > 0.0)) return "normal_radius must be > 0";
+    if (p.max_iterations < 1) return "max_iterations < 1";
+    return nullptr;
+}
+
+// scl_loop_icp_batch_from_store_guess (received == false: the source is submap(key_cur, 0), assembled with every round's candidates
+// as the unguessed call does) and scl_icp_align_batch_from_store_guess (received == true: src filtered once with src_leaf and placed
+// in icp_batch_ctl, as the guessed verification places it).  A round: the submaps (one batched filter), the search grids of the
+// candidates behind the size gate, then icp_batch_run with the live candidates' guesses.
+int icp_batch_store_guess(scl_engine *e, bool received, const void *src, int n_src, int stride_bytes, float src_leaf,
+                          int robot, int key_cur, const float *pose_cur,
+                          int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                          const float *guesses, const scl_icp_params *p, int min_src_points, int min_tgt_points,
+                          float *T, float *T_icp, float *fitness, int *converged, int *iterations, int *n_src_out, int *n_tgts)
+{
+    const char *const name = received ? "icp_align_batch_from_store_guess: " : "loop_icp_batch_from_store_guess: ";
+    if (!e || !p || !T || n_candidates < 0 || (n_candidates > 0 && (!keys_pre || !poses_pre))) return SCL_ERR_INVALID_ARG;
+    if (received ? (!src && n_src > 0) : !pose_cur) return SCL_ERR_INVALID_ARG;
+    if (e->front) e = front_primary(e);
+    std::lock_guard<std::mutex> lk(e->mu);
+    const int stride = e->kf_stride ? e->kf_stride : (received ? stride_bytes : 16);
+    if (received) {
+        if (stride != stride_bytes) return fail(e, SCL_ERR_INVALID_ARG, (std::string(name) + "stride differs from the store's").c_str());
+        if (n_src < 0 || stride < 12 || (stride & 3) || !(src_leaf > 0.f)) return fail(e, SCL_ERR_INVALID_ARG, (std::string(name) + "bad arguments").c_str());
+    }
+    if (!(leaf > 0.f)) return fail(e, SCL_ERR_INVALID_ARG, (std::string(name) + "bad arguments").c_str());
+    // every window before anything runs: an unstored keyframe inside one fails the call with no output written
+    const int win = 2 * search_num + 1;
+    std::vector<const void *> clouds, cl_src, cl_all; std::vector<int> counts, cn_src, cn_all, first_of; std::vector<float> Tw, tw_src, tw_all;
+    int rc;
+    if (!received && (rc = kf_window(e, robot, key_cur, 0, pose_cur, &cl_src, &cn_src, &tw_src))) return rc;   // loopFindNearKeyframes(cur, 0), DM.h:1105
+    first_of.push_back(0);
+    for (int c = 0; c < n_candidates; ++c) {
+        if ((rc = kf_window(e, robot, keys_pre[c], search_num, poses_pre + (size_t)c * win * 16, &clouds, &counts, &Tw))) return rc;
+        cl_all.insert(cl_all.end(), clouds.begin(), clouds.end()); cn_all.insert(cn_all.end(), counts.begin(), counts.end()); tw_all.insert(tw_all.end(), Tw.begin(), Tw.end());
+        first_of.push_back((int)cl_all.size());
+    }
+    if (n_candidates > 0) if (const char *bad = icp_params_bad(*p)) return fail(e, SCL_ERR_INVALID_ARG, (std::string(name) + bad).c_str());
+    if (const char *bad = verification_guesses_bad(guesses, n_candidates)) return fail(e, SCL_ERR_INVALID_ARG, (std::string(name) + bad).c_str());
+    (void)hipSetDevice(e->device);
+    std::string err;
+    int ns = 0;
+    const void *d_src = nullptr;
+    if (received) {                                                        // downSizeFilterICP (DM.h:1199-1201), once per call; a guess moves the filtered cloud
+        const void *d_res = nullptr;
+        rc = voxel_grid_to_device(&e->vox_ws, e->stream, src, n_src, stride, src_leaf, &d_res, &ns, &err);
+        if (!rc) rc = icp_stage_cloud(&e->icp_batch_ctl, e->stream, false, d_res, ns, stride, &err);
+        if (rc) { e->last_error = err; return rc; }
+        d_src = icp_staged_cloud(&e->icp_batch_ctl, false);
+        if (n_src_out) *n_src_out = ns;
+    }
+    std::vector<float> own;                                                // the alignments' own transforms, where the caller does not ask for them
+    float *Ti = T_icp;
+    if (!Ti) { own.resize(16 * (size_t)n_candidates + 16); Ti = own.data(); }
+    std::vector<char> gated_all((size_t)n_candidates + 1, 0);
+    bool cleared = false;
+    for (int first = 0; first < n_candidates || (first == 0 && !received); first += scl_engine::kIcpBatch) {
+        const int m = n_candidates - first < scl_engine::kIcpBatch ? n_candidates - first : scl_engine::kIcpBatch;
+        // the round's submaps, every step of the voxel filter one launch over all of them (voxel.hip, assemble_submaps_batch); the
+        // loop form's source in front, redone per round as in scl_loop_icp_batch_from_store
+        std::vector<const void *> cl_r(cl_src); std::vector<int> cn_r(cn_src), first_r; std::vector<float> tw_r(tw_src);
+        const int lead = received ? 0 : 1;
+        first_r.push_back(0);
+        if (lead) first_r.push_back((int)cl_r.size());
+        const int p0 = first_of[(size_t)first], p1 = first_of[(size_t)(first + m)];
+        cl_r.insert(cl_r.end(), cl_all.begin() + p0, cl_all.begin() + p1); cn_r.insert(cn_r.end(), cn_all.begin() + p0, cn_all.begin() + p1);
+        tw_r.insert(tw_r.end(), tw_all.begin() + 16 * (size_t)p0, tw_all.begin() + 16 * (size_t)p1);
+        for (int c = 1; c <= m; ++c) first_r.push_back(first_r[(size_t)lead] + first_of[(size_t)(first + c)] - p0);
+        std::vector<const void *> d_sub((size_t)(m + lead) + 1); std::vector<int> n_sub((size_t)(m + lead) + 1);
+        rc = assemble_submaps_batch(&e->vox_ws, e->stream, cl_r.data(), cn_r.data(), tw_r.data(), first_r.data(), m + lead, stride, leaf,
+                                    d_sub.data(), n_sub.data(), &err);
+        if (rc) { e->last_error = err; return rc; }
+        if (lead) { ns = n_sub[0]; d_src = d_sub[0]; if (n_src_out) *n_src_out = ns; }   // (stays in the filter's workspace until the round is over)
+        if (!cleared) {
+            for (int c = 0; c < n_candidates; ++c) {
+                for (int i = 0; i < 16; ++i) T[16 * (size_t)c + i] = Ti[16 * (size_t)c + i] = (i % 5 == 0) ? 1.0f : 0.0f;
+                if (fitness) fitness[c] = 0.0f;
+                if (converged) converged[c] = 0;
+                if (iterations) iterations[c] = 0;
+                if (n_tgts) n_tgts[c] = 0;
+            }
+            cleared = true;
+        }
+        if (m <= 0) break;
+        IcpWorkspace *wss[scl_engine::kIcpBatch]; int which[scl_engine::kIcpBatch]; int live = 0;
+        const void *tg[scl_engine::kIcpBatch]; int tn[scl_engine::kIcpBatch];
+        float g12[12 * scl_engine::kIcpBatch];                             // rows 0 .. 2 of the live candidates' guesses
+        for (int c = 0; c < m; ++c) {
+            const int nt = n_sub[(size_t)(c + lead)];
+            if (n_tgts) n_tgts[first + c] = nt;
+            if ((gated_all[(size_t)(first + c)] = ns < min_src_points || nt < min_tgt_points)) continue;   // DM.h:1108: the unmoved sizes
+            std::memcpy(g12 + 12 * (size_t)live, guesses + 16 * (size_t)(first + c), 12 * sizeof(float));
+            wss[live] = &e->icp_batch_ws[c]; which[live] = first + c; tg[live] = d_sub[(size_t)(c + lead)]; tn[live] = nt; ++live;
+        }
+        if (live == 0) continue;
+        rc = icp_batch_prepare_all(wss, live, &e->icp_batch_ctl, e->stream, ns, tg, tn, stride, *p, &err);
+        if (rc) { e->last_error = err; return rc; }
+        float Tl[16 * scl_engine::kIcpBatch], fl[scl_engine::kIcpBatch]; int cl[scl_engine::kIcpBatch], il[scl_engine::kIcpBatch];
+        rc = icp_batch_run(wss, live, &e->icp_batch_ctl, e->stream, d_src, ns, stride, *p, g12, Tl, fl, cl, il, &err);
+        if (rc) { e->last_error = err; return rc; }
+        for (int j = 0; j < live; ++j) {
+            std::memcpy(Ti + 16 * (size_t)which[j], Tl + 16 * (size_t)j, 16 * sizeof(float));
+            if (fitness) fitness[which[j]] = fl[j];
+            if (converged) converged[which[j]] = cl[j];
+            if (iterations) iterations[which[j]] = il[j];
+        }
+    }
+    if (n_candidates > 0) verification_compose(n_candidates, Ti, guesses, gated_all.data(), T);   // T = T_icp * G; a gated candidate keeps the identity
+    return SCL_OK;
+}
+
+}  // namespace
+
+int scl_icp_align_batch_guess(scl_engine *e, const void *src, int n_src, const void *const *tgts, const int *n_tgts,
+                              int n_targets, int stride_bytes, const float *guesses, const scl_icp_params *p,
+                              float *T, float *T_icp, float *fitness, int *converged, int *iterations)
+{
+    if (!e || !src || !p || !T || n_targets < 0 || (n_targets > 0 && (!tgts || !n_tgts))) return SCL_ERR_INVALID_ARG;
+    {   // everything the unguessed call refuses, then the guesses: before anything runs (on a sharded engine: before any shard does)
+        std::lock_guard<std::mutex> lk(e->mu);
+        if (n_src < 0 || stride_bytes < 12 || (stride_bytes & 3)) return fail(e, SCL_ERR_INVALID_ARG, "icp_align_batch_guess: bad cloud layout");
+        for (int c = 0; c < n_targets; ++c)
+            if ((!tgts[c] && n_tgts[c] > 0) || n_tgts[c] < 0) return fail(e, SCL_ERR_INVALID_ARG, "icp_align_batch_guess: bad target");
+        if (n_targets > 0) if (const char *bad = icp_params_bad(*p)) return fail(e, SCL_ERR_INVALID_ARG, (std::string("icp_align_batch_guess: ") + bad).c_str());
+        if (const char *bad = verification_guesses_bad(guesses, n_targets)) return fail(e, SCL_ERR_INVALID_ARG, (std::string("icp_align_batch_guess: ") + bad).c_str());
+    }
+    if (n_targets == 0) return SCL_OK;
+    std::vector<float> own;
+    float *Ti = T_icp;
+    if (!Ti) { own.resize(16 * (size_t)n_targets); Ti = own.data(); }
+    const int rc = e->front ? front_icp_align_batch(e, src, n_src, tgts, n_tgts, n_targets, stride_bytes, guesses, p, T, Ti, fitness, converged, iterations)
+                            : icp_align_batch_host(e, src, n_src, tgts, n_tgts, n_targets, stride_bytes, guesses, p, Ti, fitness, converged, iterations);
+    if (rc) return rc;
+    if (!e->front) verification_compose(n_targets, Ti, guesses, nullptr, T);   // (the shards composed their own entries)
+    return SCL_OK;
+}
+
+int scl_loop_icp_batch_from_store_guess(scl_engine *e, int robot, int key_cur, const float *pose_cur,
+                                        int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                                        const float *guesses, const scl_icp_params *p, int min_src_points, int min_tgt_points,
+                                        float *T, float *T_icp, float *fitness, int *converged, int *iterations, int *n_src, int *n_tgts)
+{
+    return icp_batch_store_guess(e, false, nullptr, 0, 0, 0.f, robot, key_cur, pose_cur, n_candidates, keys_pre, search_num, poses_pre, leaf,
+                                 guesses, p, min_src_points, min_tgt_points, T, T_icp, fitness, converged, iterations, n_src, n_tgts);
+}
+
+int scl_icp_align_batch_from_store_guess(scl_engine *e, const void *src, int n_src, int stride_bytes, float src_leaf,
+                                         int robot, int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                                         const float *guesses, const scl_icp_params *p, int min_src_points, int min_tgt_points,
+                                         float *T, float *T_icp, float *fitness, int *converged, int *iterations, int *n_src_filtered, int *n_tgts)
+{
+    return icp_batch_store_guess(e, true, src, n_src, stride_bytes, src_leaf, robot, 0, nullptr, n_candidates, keys_pre, search_num, poses_pre, leaf,
+                                 guesses, p, min_src_points, min_tgt_points, T, T_icp, fitness, converged, iterations, n_src_filtered, n_tgts);
+}
 
 /* ---- measurement ------------------------------------------------------------- */
 

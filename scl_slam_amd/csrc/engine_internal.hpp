@@ -239,9 +239,10 @@ int front_collect(scl_engine *e, int ticket, int *nn_idx, int *shift, double *di
 int front_detect_full_stream(scl_engine *e, const int *queries, const int *lo, const int *hi, int n_queries,
                              int scans_per_launch, int launches_in_flight, int *nn_idx, int *shift, double *dist);
 int front_get_last_topk(scl_engine *e, int k, int *idx, float *d2);
+// guesses == nullptr: scl_icp_align_batch (T_icp is not looked at); otherwise scl_icp_align_batch_guess, arguments checked by the caller
 int front_icp_align_batch(scl_engine *e, const void *src, int n_src, const void *const *tgts, const int *n_tgts,
-                          int n_targets, int stride_bytes, const scl_icp_params *p,
-                          float *T, float *fitness, int *converged, int *iterations);
+                          int n_targets, int stride_bytes, const float *guesses, const scl_icp_params *p,
+                          float *T, float *T_icp, float *fitness, int *converged, int *iterations);
 int front_profile_enable(scl_engine *e, int on);
 int front_profile_reset(scl_engine *e);
 int front_profile_get(scl_engine *e, scl_profile *out);

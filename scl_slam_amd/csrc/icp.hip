@@ -62,8 +62,8 @@ struct IcpState {
 };
 
 enum Buf { B_SRC = 0, B_TGT, B_WORK, B_TSORT, B_CSTART, B_CFILL, B_NNI, B_NND, B_PART, B_STATE, B_BBOX, B_SI, B_TI, B_OUT, B_MASK, B_HYP, B_PROB,
-           B_NNQ, B_PERM, B_SORT, B_FLAG, B_PAIR };
-static_assert(B_PAIR < (int)(sizeof(IcpWorkspace::buf) / sizeof(void *)), "IcpWorkspace::buf is too short");
+           B_NNQ, B_PERM, B_SORT, B_FLAG, B_PAIR, B_GSRC, B_GORD };
+static_assert(B_GORD < (int)(sizeof(IcpWorkspace::buf) / sizeof(void *)), "IcpWorkspace::buf is too short");
 constexpr int B_NORM = B_OUT;             // target normals share the slot of the raw-transform output (never live together)
 
 int ensure(IcpWorkspace *ws, int k, size_t bytes, std::string *err)
@@ -1875,8 +1875,8 @@ __device__ __forceinline__ unsigned int spread10(unsigned int v)
     return v;
 }
 
-__global__ __launch_bounds__(256) void source_key_kernel(const unsigned char *src, int n, int stride, const float *part, int nparts,
-                                                         unsigned int *keys, int *vals)
+__device__ __forceinline__ void source_key_body(const unsigned char *src, int n, int stride, const float *part, int nparts,
+                                                unsigned int *keys, int *vals)
 {
     __shared__ float s_box[6];
     if (threadIdx.x < 64) {                                      // the cloud's box from bbox_partial_kernel's records
@@ -1921,6 +1921,11 @@ __global__ __launch_bounds__(256) void source_key_kernel(const unsigned char *sr
     X[0] ^= tt; X[1] ^= tt; X[2] ^= tt;
     keys[i] = (spread10(X[0]) << 2) | (spread10(X[1]) << 1) | spread10(X[2]);
     vals[i] = i;
+}
+__global__ __launch_bounds__(256) void source_key_kernel(const unsigned char *src, int n, int stride, const float *part, int nparts,
+                                                         unsigned int *keys, int *vals)
+{
+    source_key_body(src, n, stride, part, nparts, keys, vals);
 }
 
 __global__ void work_init_batch_kernel(const IcpProblem *pr, const unsigned char *src, const int *perm, int n, int stride)
@@ -2084,10 +2089,9 @@ __global__ __launch_bounds__(64) void verify_solve_batch_kernel(const VerifyJob 
 // candidate, rows 0 .. 2 of G_c), written as a float4 working cloud in SOURCE order.  The cold search reads it as p.work, the
 // RANSAC and covariance bodies as records of 16 bytes through load_xyz.  A streaming kernel: one point per thread, one 16-byte
 // store; the guess is uniform over the workgroup and sits in scalar registers.
-__global__ __launch_bounds__(256) void guess_move_batch_kernel(const IcpProblem *__restrict__ pr, const unsigned char *__restrict__ src,
-                                                               int n, int stride, const float *__restrict__ guesses)
+__device__ __forceinline__ void guess_move_body(float4 *__restrict__ work, const unsigned char *__restrict__ src, int n, int stride,
+                                                const float *__restrict__ guesses)
 {
-    float4 *__restrict__ work = pr[blockIdx.y].work;
     float g[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) g[k] = guesses[12 * blockIdx.y + k];
@@ -2096,6 +2100,60 @@ __global__ __launch_bounds__(256) void guess_move_batch_kernel(const IcpProblem 
     const float3 p = load_xyz(src, i, stride);
     const float3 q = transform_xyz(g, p.x, p.y, p.z);
     work[i] = make_float4(q.x, q.y, q.z, 0.f);
+}
+__global__ __launch_bounds__(256) void guess_move_batch_kernel(const IcpProblem *__restrict__ pr, const unsigned char *__restrict__ src,
+                                                               int n, int stride, const float *__restrict__ guesses)
+{
+    guess_move_body(pr[blockIdx.y].work, src, n, stride, guesses);
+}
+
+// ---- the guessed ICP batch: every alignment has a source of its own, and a working order of its own (icp_batch_run) ---------------
+// Candidate blockIdx.y's cloud lives at moved + blockIdx.y * n (float4, SOURCE order, written once and read again by the fitness
+// pass), its order at order + blockIdx.y * n.  Each kernel is the single path's body on the candidate's slice: the boxes of
+// bbox_partial_kernel, the keys of source_key_kernel, work_init / work_final's gathers -- so that candidate c's working cloud is,
+// entry for entry, the one icp_batch_run makes for the single call on the moved cloud.  All of them stream: one point per thread.
+__global__ __launch_bounds__(256) void guess_source_batch_kernel(float4 *__restrict__ moved, const unsigned char *__restrict__ src,
+                                                                 int n, int stride, const float *__restrict__ guesses)
+{
+    guess_move_body(moved + (size_t)blockIdx.y * (size_t)n, src, n, stride, guesses);
+}
+
+__global__ void guess_bbox_batch_kernel(const float4 *moved, int n, float *boxes)
+{
+    bbox_partial_body(reinterpret_cast<const unsigned char *>(moved + (size_t)blockIdx.y * (size_t)n), n, (int)sizeof(float4),
+                      boxes + (size_t)blockIdx.y * 6 * gridDim.x);
+}
+
+__global__ __launch_bounds__(256) void guess_key_batch_kernel(const float4 *moved, int n, const float *boxes, int nparts, unsigned int *keys, int *vals)
+{
+    const size_t first = (size_t)blockIdx.y * (size_t)n;
+    source_key_body(reinterpret_cast<const unsigned char *>(moved + first), n, (int)sizeof(float4), boxes + (size_t)blockIdx.y * 6 * nparts, nparts,
+                    keys + first, vals + first);
+}
+
+__global__ void work_init_guess_batch_kernel(const IcpProblem *pr, const float4 *moved, const int *order, int n)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const size_t first = (size_t)blockIdx.y * (size_t)n;
+    const float4 s = moved[first + order[first + k]];
+    pr[blockIdx.y].work[k] = make_float4(s.x, s.y, s.z, 0.f);
+}
+
+// work_final_batch_kernel on the candidate's own cloud and order
+__global__ void work_final_guess_batch_kernel(const IcpProblem *pr, const float4 *moved, const int *order, int n)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const IcpProblem p = pr[blockIdx.y];
+    const float *T = p.st->final_T;
+    const size_t first = (size_t)blockIdx.y * (size_t)n;
+    const float4 s = moved[first + order[first + k]];
+    // distributedMapping.h:247-249 (fp32, left-to-right, no FMA)
+    const float ox = T[0] * s.x + T[1] * s.y + T[2] * s.z + T[3];
+    const float oy = T[4] * s.x + T[5] * s.y + T[6] * s.z + T[7];
+    const float oz = T[8] * s.x + T[9] * s.y + T[10] * s.z + T[11];
+    p.work[k] = make_float4(ox, oy, oz, 0.f);
 }
 
 
@@ -2260,7 +2318,8 @@ int icp_stage_cloud(IcpWorkspace *ws, hipStream_t stream, bool target, const voi
 int icp_batch_prepare(IcpWorkspace *ws, hipStream_t stream, const void *d_src, int n_src, int n_tgt, int stride,
                       const scl_icp_params &p, std::string *err);
 int icp_batch_run(IcpWorkspace *const *wss, int nprob, IcpWorkspace *ctl, hipStream_t stream, const void *d_src, int n_src,
-                  int stride, const scl_icp_params &p, float *T, float *fitness, int *converged, int *iterations, std::string *err);
+                  int stride, const scl_icp_params &p, const float *guesses, float *T, float *fitness, int *converged, int *iterations,
+                  std::string *err);
 
 // One alignment = a batch of one: the same launches, the same order of every sum (tests compare the two bit for bit).
 int icp_align_staged(IcpWorkspace *ws, hipStream_t stream, int n_src, int n_tgt, int stride, const scl_icp_params &p,
@@ -2270,7 +2329,7 @@ int icp_align_staged(IcpWorkspace *ws, hipStream_t stream, int n_src, int n_tgt,
     if (rc) return rc;
     IcpWorkspace *one[1] = {ws};
     float fit = 0.f; int conv = 0, iters = 0;
-    rc = icp_batch_run(one, 1, ws, stream, ws->buf[B_SRC], n_src, stride, p, T, &fit, &conv, &iters, err);
+    rc = icp_batch_run(one, 1, ws, stream, ws->buf[B_SRC], n_src, stride, p, nullptr, T, &fit, &conv, &iters, err);
     if (rc) return rc;
     if (fitness) *fitness = fit;
     if (converged) *converged = conv;
@@ -2298,6 +2357,44 @@ static int source_order(IcpWorkspace *ctl, hipStream_t stream, const void *d_src
     hipLaunchKernelGGL(source_key_kernel, dim3((n_src + 255) / 256), dim3(256), 0, stream, (const unsigned char *)d_src, n_src, stride,
                        (const float *)ctl->buf[B_BBOX], nb, keys_in, vals_in);
     ICP_HIP(sort_pairs_u32(tmp, keys_in, keys_out, (unsigned int *)vals_in, (unsigned int *)ctl->buf[B_PERM], n_src, 30, stream));
+    ICP_HIP(hipGetLastError());
+    return SCL_OK;
+}
+
+// The guessed batch's sources (B_GSRC of ctl: nprob float4 clouds of n_src points back to back, candidate c's = the source moved by
+// d_guess + 12 * c) and the order each is worked in (B_GORD, n_src entries per candidate: positions within the candidate's cloud).
+// An alignment's sums run in its working order, so candidate c's order has to be the one source_order gives the single call on
+// candidate c's moved cloud: the same boxes, the same 30-bit keys, and ONE stable sort over the round with a segment per candidate
+// (a stable sort's result is a function of the keys: which passes produced it does not matter).  Four steps, each one launch chain
+// over all candidates, on the caller's stream.
+static int guess_sources(IcpWorkspace *ctl, hipStream_t stream, const void *d_src, int n_src, int stride, int nprob, const float *d_guess,
+                         std::string *err)
+{
+    int rc;
+    const size_t n = n_src > 0 ? (size_t)n_src : 1, total = n * (size_t)nprob;
+    if (nprob > kSortMaxSegments || total > (size_t)INT_MAX) { if (err) *err = "icp: a guessed round is too large"; return SCL_ERR_INVALID_ARG; }
+    if ((rc = ensure(ctl, B_GSRC, sizeof(float4) * (total + 1), err))) return rc;
+    if ((rc = ensure(ctl, B_GORD, sizeof(int) * (total + 1), err))) return rc;
+    if (n_src <= 0) return SCL_OK;
+    int nb = (n_src + 255) / 256; nb = nb > 256 ? 256 : nb;     // (source_order's partition of the box)
+    if ((rc = ensure(ctl, B_BBOX, sizeof(float) * 6 * (size_t)nb * (size_t)nprob, err))) return rc;
+    const size_t tmp_bytes = sort_scratch_bytes(total, nprob);
+    const size_t arr = (sizeof(int) * total + 255) & ~(size_t)255;
+    if ((rc = ensure(ctl, B_SORT, 3 * arr + tmp_bytes + 256, err))) return rc;
+    unsigned char *base = static_cast<unsigned char *>(ctl->buf[B_SORT]);
+    unsigned int *keys_in = reinterpret_cast<unsigned int *>(base), *keys_out = reinterpret_cast<unsigned int *>(base + arr);
+    int *vals_in = reinterpret_cast<int *>(base + 2 * arr);
+    void *tmp = base + 3 * arr;
+    float4 *moved = static_cast<float4 *>(ctl->buf[B_GSRC]);
+    float *boxes = static_cast<float *>(ctl->buf[B_BBOX]);
+    const int pb = (n_src + 255) / 256;
+    hipLaunchKernelGGL(guess_source_batch_kernel, dim3(pb, nprob), dim3(256), 0, stream, moved, (const unsigned char *)d_src, n_src, stride, d_guess);
+    hipLaunchKernelGGL(guess_bbox_batch_kernel, dim3(nb, nprob), dim3(256), 0, stream, (const float4 *)moved, n_src, boxes);
+    hipLaunchKernelGGL(guess_key_batch_kernel, dim3(pb, nprob), dim3(256), 0, stream, (const float4 *)moved, n_src, (const float *)boxes, nb, keys_in, vals_in);
+    SortSegments seg{};
+    seg.nseg = nprob;
+    for (int c = 0; c <= nprob; ++c) seg.off[c] = c * n_src;
+    ICP_HIP(sort_pairs_u32_segmented(tmp, keys_in, keys_out, (unsigned int *)vals_in, (unsigned int *)ctl->buf[B_GORD], seg, 30, stream));
     ICP_HIP(hipGetLastError());
     return SCL_OK;
 }
@@ -2420,15 +2517,20 @@ static void fill_problem(IcpProblem *hp, IcpWorkspace *ws, bool normals)
 // them.  ctl keeps the sources' working order, the problem table (device) and the pinned read-back area (it may be the one
 // alignment's own workspace).  An iteration (DM.h:1107-1121's loop body) is two launches: icp_tile_search_kernel (the previous
 // increment applied, neighbours, this workgroup's sums) and the solve; point to plane keeps its reduction as a launch of its own.
+// guesses (host; nullptr: none) = 12 floats per alignment, rows 0 .. 2 of its initial guess: alignment c then runs on d_src moved by
+// guesses + 12 * c (scl_transform_cloud's values), worked in an order of its own (guess_sources), and T[c] is the alignment's own
+// transform, from the MOVED cloud to the target -- what the single call answers for that cloud, bit for bit.  Without guesses
+// nothing of that is launched, allocated or read.
 int icp_batch_run(IcpWorkspace *const *wss, int nprob, IcpWorkspace *ctl, hipStream_t stream, const void *d_src, int n_src,
-                  int stride, const scl_icp_params &p, float *T, float *fitness, int *converged, int *iterations, std::string *err)
+                  int stride, const scl_icp_params &p, const float *guesses, float *T, float *fitness, int *converged, int *iterations,
+                  std::string *err)
 {
     if (nprob <= 0) return SCL_OK;
     int rc;
     constexpr int kAhead = SCL_ICP_AHEAD;                        // iterations the host may be ahead of what a part has finished
     constexpr int kMaxParts = IcpWorkspace::kMaxParts;
     constexpr size_t kWordPitch = 64;                            // a part's progress word has a cache line of pinned memory to itself
-    if ((rc = ensure(ctl, B_MASK, sizeof(IcpProblem) * (size_t)nprob, err))) return rc;
+    if ((rc = ensure(ctl, B_MASK, (sizeof(IcpProblem) + (guesses ? 12 * sizeof(float) : 0)) * (size_t)nprob, err))) return rc;
     if ((rc = ensure(ctl, B_HYP, sizeof(IcpState) * (size_t)nprob + 2 * sizeof(int) * kMaxParts, err))) return rc;
     if ((rc = pinned(ctl, (sizeof(IcpProblem) + sizeof(IcpState)) * (size_t)nprob + 64 + kWordPitch * kMaxParts, err))) return rc;
     IcpProblem *hp = static_cast<IcpProblem *>(ctl->pinned);
@@ -2438,17 +2540,25 @@ int icp_batch_run(IcpWorkspace *const *wss, int nprob, IcpWorkspace *ctl, hipStr
     int *d_counters = reinterpret_cast<int *>(d_states + nprob);
     for (int k = 0; k < kMaxParts; ++k) *reinterpret_cast<volatile unsigned long long *>(h_words + kWordPitch * (size_t)k) = 0ull;
     ICP_HIP(hipMemsetAsync(d_counters, 0, 2 * sizeof(int) * kMaxParts, stream));
-    if ((rc = source_order(ctl, stream, d_src, n_src, stride, err))) return rc;
+    if (guesses) {                                               // (the table behind the problems': both are read by this call's launches only)
+        float *dg = reinterpret_cast<float *>(static_cast<IcpProblem *>(ctl->buf[B_MASK]) + nprob);
+        ICP_HIP(hipMemcpyAsync(dg, guesses, sizeof(float) * 12 * (size_t)nprob, hipMemcpyHostToDevice, stream));   // (pageable: staged before the call returns)
+        if ((rc = guess_sources(ctl, stream, d_src, n_src, stride, nprob, dg, err))) return rc;
+    } else if ((rc = source_order(ctl, stream, d_src, n_src, stride, err))) return rc;
     for (int c = 0; c < nprob; ++c) fill_problem(&hp[c], wss[c], p.estimator == 1);
     const IcpProblem *dp_all = static_cast<const IcpProblem *>(ctl->buf[B_MASK]);
     ICP_HIP(hipMemcpyAsync(ctl->buf[B_MASK], hp, sizeof(IcpProblem) * (size_t)nprob, hipMemcpyHostToDevice, stream));
     const unsigned char *src = static_cast<const unsigned char *>(d_src);
     const int *perm = static_cast<const int *>(ctl->buf[B_PERM]);
+    const float4 *moved = guesses ? static_cast<const float4 *>(ctl->buf[B_GSRC]) : nullptr;   // candidate c's cloud and order: + c * n_src
+    const int *order = guesses ? static_cast<const int *>(ctl->buf[B_GORD]) : nullptr;
+    const size_t gpitch = n_src > 0 ? (size_t)n_src : 0;
     const long long q = n_src > 0 ? n_src : 1;
     const int pb = (int)((q + 255) / 256), tb = (int)((q + kTileQ - 1) / kTileQ);
     const int rb = pb < kRedBlocks ? pb : kRedBlocks;
     const float maxd2 = (float)(p.max_correspondence_dist * p.max_correspondence_dist);
-    hipLaunchKernelGGL(work_init_batch_kernel, dim3(pb, nprob), dim3(256), 0, stream, dp_all, src, perm, n_src, stride);
+    if (guesses) hipLaunchKernelGGL(work_init_guess_batch_kernel, dim3(pb, nprob), dim3(256), 0, stream, dp_all, moved, order, n_src);
+    else hipLaunchKernelGGL(work_init_batch_kernel, dim3(pb, nprob), dim3(256), 0, stream, dp_all, src, perm, n_src, stride);
     const bool tiles = (long long)nprob * q >= kTileMinQueries;   // (no bit of the result depends on it: see chunk_reduce_batch_kernel)
     // The alignments are independent, and an iteration is a chain -- search, finish, solve -- whose last two links are short launches
     // that leave the chip almost idle (38-48 of an iteration's 280 us; the search's own last workgroups likewise).  So a batch that is
@@ -2592,7 +2702,9 @@ int icp_batch_run(IcpWorkspace *const *wss, int nprob, IcpWorkspace *ctl, hipStr
     // neighbour bounds the search)
     for (int k = 0; k < parts; ++k) {
         const Part &P = part[k];
-        hipLaunchKernelGGL(work_final_batch_kernel, dim3(pb, P.n), dim3(256), 0, P.s, dp_all + P.first, src, perm, n_src, stride);
+        if (guesses) hipLaunchKernelGGL(work_final_guess_batch_kernel, dim3(pb, P.n), dim3(256), 0, P.s, dp_all + P.first, moved + gpitch * (size_t)P.first,
+                                        order + gpitch * (size_t)P.first, n_src);
+        else hipLaunchKernelGGL(work_final_batch_kernel, dim3(pb, P.n), dim3(256), 0, P.s, dp_all + P.first, src, perm, n_src, stride);
         search_and_sums(P, false, 0, 0, FLT_MAX, true);
         hipLaunchKernelGGL(icp_solve_batch_kernel, dim3(P.n), dim3(256), 0, P.s, dp_all + P.first, tb, 2, 0, 0.0, 0.0, PartSync{nullptr, nullptr, 0u});
         if (k > 0) {

@@ -48,8 +48,11 @@ int icp_batch_prepare(IcpWorkspace *ws, hipStream_t stream, const void *d_src, i
 // the same for n alignments whose targets are already on the device (read in place), every step one launch over all of them
 int icp_batch_prepare_all(IcpWorkspace *const *wss, int n, IcpWorkspace *ctl, hipStream_t stream, int n_src, const void *const *d_tgts,
                           const int *n_tgts, int stride, const scl_icp_params &p, std::string *err);
+// guesses (host; may be nullptr) = 12 floats per alignment, rows 0 .. 2 of its initial guess: alignment c is then answered for d_src
+// moved by it (icp_transform_cloud's values), as icp_align_staged answers for that cloud
 int icp_batch_run(IcpWorkspace *const *wss, int nprob, IcpWorkspace *ctl, hipStream_t stream, const void *d_src, int n_src,
-                  int stride, const scl_icp_params &p, float *T, float *fitness, int *converged, int *iterations, std::string *err);
+                  int stride, const scl_icp_params &p, const float *guesses, float *T, float *fitness, int *converged, int *iterations,
+                  std::string *err);
 int icp_nn_correspondences(IcpWorkspace *ws, hipStream_t stream, int num_cu, const void *src, int n_src,
                            const void *tgt, int n_tgt, int stride_bytes, const float *T_move, int *nn_index, float *nn_dist2,
                            std::string *err);

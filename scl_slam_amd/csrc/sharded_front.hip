@@ -1017,9 +1017,10 @@ int front_get_last_topk(scl_engine *e, int k, int *idx, float *d2)
 
 // ---- geometric verification: the loop candidates of one scan are independent -> candidate c runs on shard c % G ----
 
+// (with guesses: candidate c travels with its guess, and the shard answers T = T_icp * G_c for it as one engine would)
 int front_icp_align_batch(scl_engine *e, const void *src, int n_src, const void *const *tgts, const int *n_tgts,
-                          int n_targets, int stride_bytes, const scl_icp_params *p,
-                          float *T, float *fitness, int *converged, int *iterations)
+                          int n_targets, int stride_bytes, const float *guesses, const scl_icp_params *p,
+                          float *T, float *T_icp, float *fitness, int *converged, int *iterations)
 {
     std::lock_guard<std::mutex> lk(e->mu);
     ShardedFront *f = e->front;
@@ -1031,11 +1032,18 @@ int front_icp_align_batch(scl_engine *e, const void *src, int n_src, const void 
         for (int i = c; i < n_targets; i += G) { tp.push_back(tgts[i]); tn.push_back(n_tgts[i]); which.push_back(i); }
         if (which.empty()) return;
         const size_t m = which.size();
-        std::vector<float> Tl(16 * m), fl(m); std::vector<int> cl(m), il(m);
-        const int rc = scl_icp_align_batch(f->sh[c], src, n_src, tp.data(), tn.data(), (int)m, stride_bytes, p, Tl.data(), fl.data(), cl.data(), il.data());
+        std::vector<float> Tl(16 * m), fl(m), gl, Til; std::vector<int> cl(m), il(m);
+        if (guesses) {
+            gl.resize(16 * m); Til.resize(16 * m);
+            for (size_t j = 0; j < m; ++j) std::memcpy(gl.data() + 16 * j, guesses + 16 * (size_t)which[j], 16 * sizeof(float));
+        }
+        const int rc = guesses ? scl_icp_align_batch_guess(f->sh[c], src, n_src, tp.data(), tn.data(), (int)m, stride_bytes, gl.data(), p, Tl.data(), Til.data(),
+                                                           fl.data(), cl.data(), il.data())
+                               : scl_icp_align_batch(f->sh[c], src, n_src, tp.data(), tn.data(), (int)m, stride_bytes, p, Tl.data(), fl.data(), cl.data(), il.data());
         if (rc) { int ok = SCL_OK; if (first_rc.compare_exchange_strong(ok, rc)) e->last_error = std::string("icp_align_batch on shard: ") + scl_last_error(f->sh[c]); return; }
         for (size_t j = 0; j < m; ++j) {
             std::memcpy(T + 16 * (size_t)which[j], Tl.data() + 16 * j, 16 * sizeof(float));
+            if (guesses && T_icp) std::memcpy(T_icp + 16 * (size_t)which[j], Til.data() + 16 * j, 16 * sizeof(float));
             if (fitness) fitness[which[j]] = fl[j];
             if (converged) converged[which[j]] = cl[j];
             if (iterations) iterations[which[j]] = il[j];

@@ -139,6 +139,11 @@ def _bind(lib):
         "scl_geometric_verification_batch_from_store_guess": (c_int, [P, P, c_int, c_int, c_float, c_int, c_int, ip, c_int, fp, c_float, fp, c_int, c_int,
                                                                       c_int, c_double, c_double, c_uint64, fp, fp, ip, ip, ip, ip, ip]),
         "scl_loop_guess_from_shift": (c_int, [c_int, c_int, fp, fp, fp]),
+        "scl_icp_align_batch_guess": (c_int, [P, P, c_int, POINTER(c_void_p), ip, c_int, c_int, fp, POINTER(IcpParams), fp, fp, fp, ip, ip]),
+        "scl_loop_icp_batch_from_store_guess": (c_int, [P, c_int, c_int, fp, c_int, ip, c_int, fp, c_float, fp, POINTER(IcpParams), c_int, c_int,
+                                                        fp, fp, fp, ip, ip, ip, ip]),
+        "scl_icp_align_batch_from_store_guess": (c_int, [P, P, c_int, c_int, c_float, c_int, c_int, ip, c_int, fp, c_float, fp, POINTER(IcpParams),
+                                                         c_int, c_int, fp, fp, fp, ip, ip, ip, ip]),
         "scl_profile_enable": (c_int, [P, c_int]),
         "scl_profile_reset": (c_int, [P]),
         "scl_profile_get": (c_int, [P, POINTER(SclProfile)]),
@@ -889,6 +894,61 @@ class ScanContextEngine:
             _ptr(T, c_float), _ptr(Tf, c_float), _ptr(ok, c_int), byref(ns), _ptr(nt, c_int), _ptr(nc, c_int), _ptr(ni, c_int)),
             "scl_geometric_verification_batch_from_store_guess")
         return T[:m].reshape(m, 4, 4), ok[:m].astype(bool), ns.value, nt[:m], nc[:m], ni[:m], Tf[:m].reshape(m, 4, 4)
+
+    def icp_align_batch_guess(self, src, tgts, guesses, params=None):
+        """icp_align_batch with an initial guess per target (guesses[m,4,4]): entry c is icp_align(transform_cloud(src, guesses[c]),
+        tgts[c]); returns (T[m,4,4] = T_icp @ guess, T_icp[m,4,4], fitness[m], converged[m], iterations[m])"""
+        s_, ns, stride = _cloud(src)
+        arrs, ptrs, counts, m, stride_t = self._cloud_list(tgts)
+        if m and stride != stride_t:
+            raise ValueError("source and targets must share a record layout")
+        p = params if params is not None else self.icp_default_params()
+        G = _f32(np.asarray(guesses)).reshape(m, 16)
+        k = max(m, 1)
+        T = np.empty((k, 16), np.float32); Ti = np.empty((k, 16), np.float32); fit = np.zeros(k, np.float32)
+        conv = np.zeros(k, np.int32); it = np.zeros(k, np.int32)
+        self._check(self._lib.scl_icp_align_batch_guess(self._h, s_.ctypes.data_as(c_void_p), ns, ptrs, _ptr(counts, c_int), m, stride,
+                                                        _ptr(G, c_float), byref(p), _ptr(T, c_float), _ptr(Ti, c_float), _ptr(fit, c_float),
+                                                        _ptr(conv, c_int), _ptr(it, c_int)), "scl_icp_align_batch_guess")
+        return T[:m].reshape(m, 4, 4), Ti[:m].reshape(m, 4, 4), fit[:m], conv[:m].astype(bool), it[:m]
+
+    def loop_icp_batch_from_store_guess(self, robot, key_cur, pose_cur, keys_pre, search_num, poses_pre, leaf, guesses, params=None,
+                                        min_src_points=300, min_tgt_points=1000):
+        """loop_icp_batch_from_store with an initial guess per candidate (guesses[m,4,4]; loop_guess_from_shift with both poses of the
+        same robot), applied to submap(key_cur, 0): returns (T[m,4,4] = T_icp @ guess, T_icp[m,4,4], fitness[m], converged[m],
+        iterations[m], n_src, n_tgts[m])"""
+        p = params if params is not None else self.icp_default_params()
+        keys = np.ascontiguousarray(keys_pre, dtype=np.int32); m = keys.size
+        Tc = _f32(np.asarray(pose_cur)).reshape(16)
+        Tp = _f32(np.asarray(poses_pre)).reshape(m, 2 * search_num + 1, 16)
+        G = _f32(np.asarray(guesses)).reshape(m, 16)
+        k = max(m, 1)
+        T = np.empty((k, 16), np.float32); Ti = np.empty((k, 16), np.float32); fit = np.zeros(k, np.float32)
+        conv = np.zeros(k, np.int32); it = np.zeros(k, np.int32); ns = c_int(); nt = np.zeros(k, np.int32)
+        self._check(self._lib.scl_loop_icp_batch_from_store_guess(
+            self._h, robot, key_cur, _ptr(Tc, c_float), m, _ptr(keys, c_int), search_num, _ptr(Tp, c_float), leaf, _ptr(G, c_float), byref(p),
+            min_src_points, min_tgt_points, _ptr(T, c_float), _ptr(Ti, c_float), _ptr(fit, c_float), _ptr(conv, c_int), _ptr(it, c_int),
+            byref(ns), _ptr(nt, c_int)), "scl_loop_icp_batch_from_store_guess")
+        return T[:m].reshape(m, 4, 4), Ti[:m].reshape(m, 4, 4), fit[:m], conv[:m].astype(bool), it[:m], ns.value, nt[:m]
+
+    def icp_align_batch_from_store_guess(self, src, src_leaf, robot, keys_pre, search_num, poses_pre, leaf, guesses, params=None,
+                                         min_src_points=300, min_tgt_points=1000):
+        """ICP of one RECEIVED scan (voxel-filtered once with src_leaf) against the submaps of keys_pre, from one initial guess per
+        candidate (guesses[m,4,4]: the T of geometric_verification_batch_from_store_guess): returns (T[m,4,4] = T_icp @ guess,
+        T_icp[m,4,4], fitness[m], converged[m], iterations[m], n_src_filtered, n_tgts[m])"""
+        a, n, stride = _cloud(src)
+        p = params if params is not None else self.icp_default_params()
+        keys = np.ascontiguousarray(keys_pre, dtype=np.int32); m = keys.size
+        Tp = _f32(np.asarray(poses_pre)).reshape(m, 2 * search_num + 1, 16)
+        G = _f32(np.asarray(guesses)).reshape(m, 16)
+        k = max(m, 1)
+        T = np.empty((k, 16), np.float32); Ti = np.empty((k, 16), np.float32); fit = np.zeros(k, np.float32)
+        conv = np.zeros(k, np.int32); it = np.zeros(k, np.int32); ns = c_int(); nt = np.zeros(k, np.int32)
+        self._check(self._lib.scl_icp_align_batch_from_store_guess(
+            self._h, a.ctypes.data_as(c_void_p), n, stride, src_leaf, robot, m, _ptr(keys, c_int), search_num, _ptr(Tp, c_float), leaf,
+            _ptr(G, c_float), byref(p), min_src_points, min_tgt_points, _ptr(T, c_float), _ptr(Ti, c_float), _ptr(fit, c_float),
+            _ptr(conv, c_int), _ptr(it, c_int), byref(ns), _ptr(nt, c_int)), "scl_icp_align_batch_from_store_guess")
+        return T[:m].reshape(m, 4, 4), Ti[:m].reshape(m, 4, 4), fit[:m], conv[:m].astype(bool), it[:m], ns.value, nt[:m]
 
     @staticmethod
     def loop_guess_from_shift(shift, num_sector, pose_cur, pose_pre):
