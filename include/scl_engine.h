@@ -588,6 +588,63 @@ int  scl_icp_align_batch_from_store_guess(scl_engine *e, const void *src, int n_
                                           float *T, float *T_icp, float *fitness, int *converged, int *iterations,
                                           int *n_src_filtered, int *n_tgts);
 
+/*
+ * BATCHED REGISTRATION SCORING: OVERLAP, RMSE AND INFORMATION MATRIX.  The chain above ends with up to 32 motions per query and one
+ * scalar per motion (ICP's fitness; the RANSAC side reports no distance at all).  The reference fills the loop factor's noise with
+ * that one number on all six axes, or with a constant 0.2 and the comment "change to max fitness score" (DM.h:1361-1364).  These
+ * calls answer, for every candidate at its motion T_c, what a consumer chooses among candidates by and weights the factor with:
+ * how much of the source takes part, how well, and the sums the 6 x 6 information matrix of the pairs is made of.
+ *   * Arguments.  Those of the guessed calls they sit beside (scl_geometric_verification_batch_guess, its store form, and
+ *     scl_loop_icp_batch_from_store_guess), with transforms in the place of guesses: n x 16 floats, candidate c's T_c = transforms +
+ *     16 * c, a row-major 4x4 whose first three rows are read.  Candidate c's source is the source cloud moved by T_c with the
+ *     arithmetic of scl_transform_cloud (DM.h:247-249); in the store forms the filter runs first, once.  The intended T_c is the T
+ *     the guessed verification or the guessed ICP returned (the T of the unguessed calls serves the same way).  max_dist: the
+ *     rejection distance, metres.
+ *   * Outputs, n entries each; each may be NULL, but with n > 0 at least one must be given.  n_valid[c]: the moved source points
+ *     whose search found a neighbour (a point with a non-finite coordinate after the move finds none: scl_geometric_verification's
+ *     rule).  n_inliers[c]: those of them with nn_dist2 <= maxd2, where maxd2 = (float)(max_dist * max_dist) and nn_dist2 is the float
+ *     scl_nn_correspondences reports for (scl_transform_cloud(src, T_c), tgt_c) -- ICP's rule, equality kept.  moments[10 c .. 10 c +
+ *     9]: fp64 sums over the inliers of x, y, z, xx, yy, zz, xy, xz, yz and d2 -- x, y, z the coordinates of the matched TARGET point
+ *     converted to double, the products formed in double (where they are exact), d2 = (double)nn_dist2.  The sums are taken in an
+ *     order that depends on n_src alone (a fixed partition into workgroups, a fixed tree inside one, the workgroups' records in
+ *     order, no floating-point atomics): the same inputs give the same bits on every run, and the store forms give the bits of the
+ *     host form on scl_voxel_grid's / scl_submap_from_store's clouds.  Each sum is within m * 2^-53 * sum |term| of the exact one
+ *     (m = n_inliers).  The store forms' size gate looks at the unmoved sizes; a gated candidate keeps zeros, its n_tgts reported.
+ *     The overlap n_inliers / n_src and the RMSE sqrt(moments[9] / n_inliers) are left to the caller.
+ *   * Errors.  Whatever the corresponding guessed call refuses in the arguments they share, with the same status; then max_dist
+ *     non-finite or < 0, no output given with n > 0, transforms == NULL with n > 0, or a non-finite entry in the first three rows of
+ *     a transform: SCL_ERR_INVALID_ARG.  All before anything runs, no output written.  n == 0 is SCL_OK; the store forms still report
+ *     the source's filtered size.
+ *   * How it runs.  Rounds of 32 candidates on the engine's stream, one wait per round.  A round: the submaps (store forms), then one
+ *     launch over all candidates for each of the moved sources (the guessed verification's kernel), the steps of the search grids,
+ *     the cold neighbour search, the reduction (blocks x candidates) and a finishing launch of one wave per candidate.  Memory: the
+ *     guessed verification's, in the same grow-only workspaces; a later call of any other batch reads nothing these calls leave.
+ *     On a scl_create_sharded engine the calls run on the shard that owns the keyframe store, as the guessed verification does.
+ */
+int  scl_registration_eval_batch(scl_engine *e, const void *src, int n_src, const void *const *tgts, const int *n_tgts,
+                                 int n_targets, int stride_bytes, const float *transforms, double max_dist,
+                                 int *n_valid, int *n_inliers, double *moments);
+/* inter-robot: a RECEIVED cloud, voxel-filtered once with src_leaf */
+int  scl_registration_eval_batch_from_store(scl_engine *e, const void *src, int n_src, int stride_bytes, float src_leaf,
+                                            int robot, int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                                            const float *transforms, int min_src_points, int min_tgt_points, double max_dist,
+                                            int *n_valid, int *n_inliers, double *moments, int *n_src_filtered, int *n_tgts);
+/* intra-robot: the source is submap(key_cur, 0) */
+int  scl_loop_eval_batch_from_store(scl_engine *e, int robot, int key_cur, const float *pose_cur,
+                                    int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                                    const float *transforms, int min_src_points, int min_tgt_points, double max_dist,
+                                    int *n_valid, int *n_inliers, double *moments, int *n_src, int *n_tgts);
+/* The 6 x 6 information matrix of the pairs (host only, no engine): with m = n_inliers and S the sums of one candidate, info is the
+ * row-major sum of G^T G for G = [-[q]x | I3] over the matched target points q, rotation first -- the convention pose-graph tools use:
+ *     Syy+Szz  -Sxy     -Sxz      0    -Sz    Sy
+ *     -Sxy     Sxx+Szz  -Syz      Sz    0    -Sx
+ *     -Sxz     -Syz     Sxx+Syy  -Sy    Sx    0
+ *      0        Sz      -Sy       m     0     0
+ *     -Sz       0        Sx       0     m     0
+ *      Sy      -Sx       0        0     0     m
+ * Every entry is at most one fp64 addition.  A NULL pointer or n_inliers < 0: SCL_ERR_INVALID_ARG, nothing written. */
+int  scl_registration_information(int n_inliers, const double moments[10], double info[36]);
+
 /* ---- measurement ----------------------------------------------------------- */
 int  scl_profile_enable(scl_engine *e, int on);   /* 0 off, 1 every kernel family, 2 SC distance only,
                                                      3 SC distance only, sampled: one launch in thirteen -- in the stream form one

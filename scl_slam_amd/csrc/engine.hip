@@ -504,7 +504,7 @@ const char *scl_status_string(int status)
 
 const char *scl_last_error(const scl_engine *e) { return e ? e->last_error.c_str() : "null engine"; }
 
-int scl_abi_version(void) { return 9; }
+int scl_abi_version(void) { return 10; }
 
 int scl_default_config(scl_config *c)
 {
@@ -3894,6 +3894,205 @@ int scl_icp_align_batch_from_store_guess(scl_engine *e, const void *src, int n_s
 {
     return icp_batch_store_guess(e, true, src, n_src, stride_bytes, src_leaf, robot, 0, nullptr, n_candidates, keys_pre, search_num, poses_pre, leaf,
                                  guesses, p, min_src_points, min_tgt_points, T, T_icp, fitness, converged, iterations, n_src_filtered, n_tgts);
+}
+
+/* ---- batched registration scoring: overlap, RMSE and information matrix ----------- */
+
+namespace {
+
+// what the three scoring calls refuse last, behind their own cloud and window checks -> nullptr or the message
+const char *eval_args_bad(const float *transforms, int n, double max_dist, const int *n_valid, const int *n_inliers, const double *moments)
+{
+    if (!std::isfinite(max_dist) || max_dist < 0.0) return "max_dist must be finite and >= 0";
+    if (n > 0 && !n_valid && !n_inliers && !moments) return "no output asked for";
+    if (n > 0 && !transforms) return "transforms is NULL";
+    for (size_t k = 0; k < 16 * (size_t)n; ++k)
+        if ((k & 15) < 12 && !std::isfinite(transforms[k])) return "a transform has a non-finite entry in its first three rows";
+    return nullptr;
+}
+
+void eval_clear(int n, int *n_valid, int *n_inliers, double *moments, int *n_tgts)
+{
+    for (int c = 0; c < n; ++c) {
+        if (n_valid) n_valid[c] = 0;
+        if (n_inliers) n_inliers[c] = 0;
+        if (n_tgts) n_tgts[c] = 0;
+    }
+    if (moments) for (size_t k = 0; k < 10 * (size_t)n; ++k) moments[k] = 0.0;
+}
+
+// one round (at most kIcpBatch candidates, entries first .. first + m - 1 of the outputs): the source on the device at d_src, target c
+// at d_tgts[c]; a candidate that is gated or has no pair to find keeps the zeros the caller wrote
+int eval_round(scl_engine *e, int first, int m, const void *d_src, int ns, const void *const *d_tgts, const int *n_tgts, const bool *gated,
+               int stride, const float *transforms, double max_dist, int *n_valid, int *n_inliers, double *moments)
+{
+    IcpWorkspace *wss[scl_engine::kIcpBatch]; int which[scl_engine::kIcpBatch]; int live = 0;
+    const void *tg[scl_engine::kIcpBatch]; int tn[scl_engine::kIcpBatch];
+    float t12[12 * scl_engine::kIcpBatch];                               // rows 0 .. 2 of the live candidates' transforms
+    for (int c = 0; c < m; ++c) {
+        if (gated[c] || ns < 1 || n_tgts[c] < 1) continue;
+        std::memcpy(t12 + 12 * (size_t)live, transforms + 16 * (size_t)(first + c), 12 * sizeof(float));
+        wss[live] = &e->icp_batch_ws[c]; which[live] = first + c; tg[live] = d_tgts[c]; tn[live] = n_tgts[c]; ++live;
+    }
+    if (live == 0) return SCL_OK;
+    int nv[scl_engine::kIcpBatch], ni[scl_engine::kIcpBatch]; double mo[10 * scl_engine::kIcpBatch];
+    std::string err;
+    const float maxd2 = (float)(max_dist * max_dist);                    // ICP's rejection rule (icp.hip, icp_batch_run)
+    int rc = icp_registration_eval_batch(wss, live, &e->icp_batch_ctl, e->stream, d_src, ns, tg, tn, stride, t12, maxd2, nv, ni, mo, &err);
+    if (rc) { e->last_error = err; return rc; }
+    for (int j = 0; j < live; ++j) {
+        if (n_valid) n_valid[which[j]] = nv[j];
+        if (n_inliers) n_inliers[which[j]] = ni[j];
+        if (moments) std::memcpy(moments + 10 * (size_t)which[j], mo + 10 * (size_t)j, 10 * sizeof(double));
+    }
+    return SCL_OK;
+}
+
+// scl_loop_eval_batch_from_store (received == false: the source is submap(key_cur, 0), assembled with every round's candidates as
+// the guessed loop ICP does) and scl_registration_eval_batch_from_store (received == true: src filtered once with src_leaf and
+// placed in icp_batch_ctl, as the guessed verification places it)
+int eval_batch_store(scl_engine *e, bool received, const void *src, int n_src, int stride_bytes, float src_leaf,
+                     int robot, int key_cur, const float *pose_cur,
+                     int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                     const float *transforms, int min_src_points, int min_tgt_points, double max_dist,
+                     int *n_valid, int *n_inliers, double *moments, int *n_src_out, int *n_tgts)
+{
+    const char *const name = received ? "registration_eval_batch_from_store: " : "loop_eval_batch_from_store: ";
+    if (!e || n_candidates < 0 || (n_candidates > 0 && (!keys_pre || !poses_pre))) return SCL_ERR_INVALID_ARG;
+    if (received ? (!src && n_src > 0) : !pose_cur) return SCL_ERR_INVALID_ARG;
+    if (e->front) e = front_primary(e);
+    std::lock_guard<std::mutex> lk(e->mu);
+    const int stride = e->kf_stride ? e->kf_stride : (received ? stride_bytes : 16);
+    if (received) {
+        if (stride != stride_bytes) return fail(e, SCL_ERR_INVALID_ARG, (std::string(name) + "stride differs from the store's").c_str());
+        if (n_src < 0 || stride < 12 || (stride & 3) || !(src_leaf > 0.f)) return fail(e, SCL_ERR_INVALID_ARG, (std::string(name) + "bad arguments").c_str());
+    }
+    if (!(leaf > 0.f)) return fail(e, SCL_ERR_INVALID_ARG, (std::string(name) + "bad arguments").c_str());
+    // every window before anything runs: an unstored keyframe inside one fails the call with no output written
+    const int win = 2 * search_num + 1;
+    std::vector<const void *> clouds, cl_src, cl_all; std::vector<int> counts, cn_src, cn_all, first_of; std::vector<float> Tw, tw_src, tw_all;
+    int rc;
+    if (!received && (rc = kf_window(e, robot, key_cur, 0, pose_cur, &cl_src, &cn_src, &tw_src))) return rc;   // loopFindNearKeyframes(cur, 0), DM.h:1105
+    first_of.push_back(0);
+    for (int c = 0; c < n_candidates; ++c) {
+        if ((rc = kf_window(e, robot, keys_pre[c], search_num, poses_pre + (size_t)c * win * 16, &clouds, &counts, &Tw))) return rc;
+        cl_all.insert(cl_all.end(), clouds.begin(), clouds.end()); cn_all.insert(cn_all.end(), counts.begin(), counts.end()); tw_all.insert(tw_all.end(), Tw.begin(), Tw.end());
+        first_of.push_back((int)cl_all.size());
+    }
+    if (const char *bad = eval_args_bad(transforms, n_candidates, max_dist, n_valid, n_inliers, moments)) return fail(e, SCL_ERR_INVALID_ARG, (std::string(name) + bad).c_str());
+    (void)hipSetDevice(e->device);
+    std::string err;
+    int ns = 0;
+    const void *d_src = nullptr;
+    if (received) {                                                        // downSizeFilterICP (DM.h:1199-1201), once per call; a transform moves the filtered cloud
+        const void *d_res = nullptr;
+        rc = voxel_grid_to_device(&e->vox_ws, e->stream, src, n_src, stride, src_leaf, &d_res, &ns, &err);
+        if (!rc) rc = icp_stage_cloud(&e->icp_batch_ctl, e->stream, false, d_res, ns, stride, &err);
+        if (rc) { e->last_error = err; return rc; }
+        d_src = icp_staged_cloud(&e->icp_batch_ctl, false);
+        if (n_src_out) *n_src_out = ns;
+    }
+    bool cleared = false;
+    for (int first = 0; first < n_candidates || (first == 0 && !received); first += scl_engine::kIcpBatch) {
+        const int m = n_candidates - first < scl_engine::kIcpBatch ? n_candidates - first : scl_engine::kIcpBatch;
+        // the round's submaps, every step of the voxel filter one launch over all of them (voxel.hip, assemble_submaps_batch); the
+        // loop form's source in front, redone per round as in scl_loop_icp_batch_from_store_guess
+        std::vector<const void *> cl_r(cl_src); std::vector<int> cn_r(cn_src), first_r; std::vector<float> tw_r(tw_src);
+        const int lead = received ? 0 : 1;
+        first_r.push_back(0);
+        if (lead) first_r.push_back((int)cl_r.size());
+        const int p0 = first_of[(size_t)first], p1 = first_of[(size_t)(first + m)];
+        cl_r.insert(cl_r.end(), cl_all.begin() + p0, cl_all.begin() + p1); cn_r.insert(cn_r.end(), cn_all.begin() + p0, cn_all.begin() + p1);
+        tw_r.insert(tw_r.end(), tw_all.begin() + 16 * (size_t)p0, tw_all.begin() + 16 * (size_t)p1);
+        for (int c = 1; c <= m; ++c) first_r.push_back(first_r[(size_t)lead] + first_of[(size_t)(first + c)] - p0);
+        std::vector<const void *> d_sub((size_t)(m + lead) + 1); std::vector<int> n_sub((size_t)(m + lead) + 1);
+        rc = assemble_submaps_batch(&e->vox_ws, e->stream, cl_r.data(), cn_r.data(), tw_r.data(), first_r.data(), m + lead, stride, leaf,
+                                    d_sub.data(), n_sub.data(), &err);
+        if (rc) { e->last_error = err; return rc; }
+        if (lead) { ns = n_sub[0]; d_src = d_sub[0]; if (n_src_out) *n_src_out = ns; }   // (stays in the filter's workspace until the round is over)
+        if (!cleared) { eval_clear(n_candidates, n_valid, n_inliers, moments, n_tgts); cleared = true; }
+        if (m <= 0) break;
+        bool gated[scl_engine::kIcpBatch];
+        for (int c = 0; c < m; ++c) {
+            const int nt = n_sub[(size_t)(c + lead)];
+            if (n_tgts) n_tgts[first + c] = nt;
+            gated[c] = ns < min_src_points || nt < min_tgt_points;         // DM.h:1108 / 1204: the unmoved sizes
+        }
+        rc = eval_round(e, first, m, d_src, ns, d_sub.data() + lead, n_sub.data() + lead, gated, stride, transforms, max_dist, n_valid, n_inliers, moments);
+        if (rc) return rc;
+    }
+    return SCL_OK;
+}
+
+}  // namespace
+
+int scl_registration_eval_batch(scl_engine *e, const void *src, int n_src, const void *const *tgts, const int *n_tgts,
+                                int n_targets, int stride_bytes, const float *transforms, double max_dist,
+                                int *n_valid, int *n_inliers, double *moments)
+{
+    if (!e || n_targets < 0 || (!src && n_src > 0) || (n_targets > 0 && (!tgts || !n_tgts))) return SCL_ERR_INVALID_ARG;
+    if (e->front) e = front_primary(e);
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (n_src < 0 || stride_bytes < 12 || (stride_bytes & 3)) return fail(e, SCL_ERR_INVALID_ARG, "registration_eval_batch: bad cloud layout");
+    for (int c = 0; c < n_targets; ++c)
+        if (n_tgts[c] < 0 || (!tgts[c] && n_tgts[c] > 0)) return fail(e, SCL_ERR_INVALID_ARG, "registration_eval_batch: bad target");
+    if (const char *bad = eval_args_bad(transforms, n_targets, max_dist, n_valid, n_inliers, moments)) return fail(e, SCL_ERR_INVALID_ARG, (std::string("registration_eval_batch: ") + bad).c_str());
+    if (n_targets == 0) return SCL_OK;
+    (void)hipSetDevice(e->device);
+    eval_clear(n_targets, n_valid, n_inliers, moments, nullptr);
+    std::string err;
+    int rc = SCL_OK;
+    if (n_src >= 1) rc = icp_stage_cloud_host(&e->icp_batch_ctl, e->stream, false, src, n_src, stride_bytes, &err);   // once per call (none: no pair at all)
+    if (rc) { e->last_error = err; return rc; }
+    for (int first = 0; n_src >= 1 && first < n_targets; first += scl_engine::kIcpBatch) {
+        const int m = n_targets - first < scl_engine::kIcpBatch ? n_targets - first : scl_engine::kIcpBatch;
+        const void *d_tgts[scl_engine::kIcpBatch]; bool gated[scl_engine::kIcpBatch];
+        for (int c = 0; c < m; ++c) {
+            gated[c] = false; d_tgts[c] = nullptr;
+            if (n_tgts[first + c] < 1) continue;
+            rc = icp_stage_cloud_host(&e->icp_batch_ws[c], e->stream, true, tgts[first + c], n_tgts[first + c], stride_bytes, &err);
+            if (rc) { e->last_error = err; return rc; }
+            d_tgts[c] = icp_staged_cloud(&e->icp_batch_ws[c], true);
+        }
+        rc = eval_round(e, first, m, icp_staged_cloud(&e->icp_batch_ctl, false), n_src, d_tgts, n_tgts + first, gated, stride_bytes, transforms, max_dist,
+                        n_valid, n_inliers, moments);
+        if (rc) return rc;
+    }
+    return SCL_OK;
+}
+
+int scl_registration_eval_batch_from_store(scl_engine *e, const void *src, int n_src, int stride_bytes, float src_leaf,
+                                           int robot, int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                                           const float *transforms, int min_src_points, int min_tgt_points, double max_dist,
+                                           int *n_valid, int *n_inliers, double *moments, int *n_src_filtered, int *n_tgts)
+{
+    return eval_batch_store(e, true, src, n_src, stride_bytes, src_leaf, robot, 0, nullptr, n_candidates, keys_pre, search_num, poses_pre, leaf,
+                            transforms, min_src_points, min_tgt_points, max_dist, n_valid, n_inliers, moments, n_src_filtered, n_tgts);
+}
+
+int scl_loop_eval_batch_from_store(scl_engine *e, int robot, int key_cur, const float *pose_cur,
+                                   int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                                   const float *transforms, int min_src_points, int min_tgt_points, double max_dist,
+                                   int *n_valid, int *n_inliers, double *moments, int *n_src, int *n_tgts)
+{
+    return eval_batch_store(e, false, nullptr, 0, 0, 0.f, robot, key_cur, pose_cur, n_candidates, keys_pre, search_num, poses_pre, leaf,
+                            transforms, min_src_points, min_tgt_points, max_dist, n_valid, n_inliers, moments, n_src, n_tgts);
+}
+
+int scl_registration_information(int n_inliers, const double moments[10], double info[36])
+{
+    if (!moments || !info || n_inliers < 0) return SCL_ERR_INVALID_ARG;
+    const double m = (double)n_inliers;
+    const double Sx = moments[0], Sy = moments[1], Sz = moments[2], Sxx = moments[3], Syy = moments[4], Szz = moments[5];
+    const double Sxy = moments[6], Sxz = moments[7], Syz = moments[8];
+    const double out[36] = {Syy + Szz, -Sxy, -Sxz, 0.0, -Sz, Sy,
+                            -Sxy, Sxx + Szz, -Syz, Sz, 0.0, -Sx,
+                            -Sxz, -Syz, Sxx + Syy, -Sy, Sx, 0.0,
+                            0.0, Sz, -Sy, m, 0.0, 0.0,
+                            -Sz, 0.0, Sx, 0.0, m, 0.0,
+                            Sy, -Sx, 0.0, 0.0, 0.0, m};
+    std::memcpy(info, out, sizeof out);
+    return SCL_OK;
 }
 
 /* ---- measurement ------------------------------------------------------------- */

@@ -2107,6 +2107,106 @@ __global__ __launch_bounds__(256) void guess_move_batch_kernel(const IcpProblem 
     guess_move_body(pr[blockIdx.y].work, src, n, stride, guesses);
 }
 
+// ---- registration scoring: what the pairs of a finished registration say, for all candidates of a round (blockIdx.y = candidate) ----
+// Behind the moved sources, the grids and the cold search: per candidate the sources that found a neighbour, those of them within
+// the rejection distance (ICP's rule, d2 <= maxd2 in float) and, over the latter, the fp64 sums of the matched TARGET point's x, y, z,
+// xx, yy, zz, xy, xz, yz and of d2 -- the ten numbers the 6 x 6 information matrix and the RMSE are made of.  A gather: nni / nnd
+// stream (8 bytes per source), the target point behind nni is 12 bytes of a record somewhere in the candidate's cloud; nothing is
+// reused, so nothing is staged in LDS, and the loads of a trip are independent of the sums.  The order of every sum depends on
+// n_src alone: workgroup b of eb = eval_blocks(n_src) takes sources b * 256 + t + k * eb * 256 in ascending k, the 64 lanes of a
+// wave join in one xor butterfly, the four waves in wave order, eval_finish_batch_kernel the eb records in block order.  No atomics.
+// Every term is exact in double (a float, or the product of two), so fp contraction could not change a bit either.
+constexpr int kEvalBlocks = 64;
+constexpr int kNEval = 10;
+struct EvalJob { const unsigned char *tgt; const int *nni; const float *nnd; double *part; };   // part: kEvalBlocks records of kNEval + 1 doubles
+struct EvalOut { double s[kNEval]; int n_valid, n_inl; };
+
+static int eval_blocks(int n_src)
+{
+    const int b = (n_src + 255) / 256;
+    return b < 1 ? 1 : (b > kEvalBlocks ? kEvalBlocks : b);
+}
+
+__global__ __launch_bounds__(256) void eval_reduce_batch_kernel(const EvalJob *jobs, int stride, int n_src, float maxd2)
+{
+    const EvalJob j = jobs[blockIdx.y];
+    double acc[kNEval];
+#pragma unroll
+    for (int k = 0; k < kNEval; ++k) acc[k] = 0.0;
+    int nv = 0, ni = 0;
+    // four trips at a time, their loads issued together (one trip at a time left every wave waiting out two dependent round trips per
+    // source: 42 us for 25 x 99 000 where the bytes take 10); the additions stay in ascending k
+    const int step = (int)(gridDim.x * blockDim.x);
+    for (long long i = (long long)(blockIdx.x * blockDim.x + threadIdx.x); i < n_src; i += 4 * step) {
+        int t[4]; float d2[4]; float3 q[4]; bool in[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const long long iu = i + (long long)u * step;
+            t[u] = iu < n_src ? j.nni[iu] : -1;
+            d2[u] = iu < n_src ? j.nnd[iu] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            in[u] = t[u] >= 0 && d2[u] <= maxd2;                 // no neighbour: a non-finite point, or one out of the target's reach; equality is kept
+            q[u] = in[u] ? load_xyz(j.tgt, t[u], stride) : make_float3(0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            nv += t[u] >= 0;
+            if (!in[u]) continue;
+            ++ni;
+            const double x = (double)q[u].x, y = (double)q[u].y, z = (double)q[u].z;
+            acc[0] += x; acc[1] += y; acc[2] += z;
+            acc[3] += x * x; acc[4] += y * y; acc[5] += z * z;
+            acc[6] += x * y; acc[7] += x * z; acc[8] += y * z;
+            acc[9] += (double)d2[u];
+        }
+    }
+    __shared__ double s[4][kNEval];
+    __shared__ int sc[4][2];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < kNEval; ++k) acc[k] += __shfl_xor(acc[k], off, kWave);
+        nv += __shfl_xor(nv, off, kWave); ni += __shfl_xor(ni, off, kWave);
+    }
+    const int wv = threadIdx.x / kWave;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < kNEval; ++k) s[wv][k] = acc[k];
+        sc[wv][0] = nv; sc[wv][1] = ni;
+    }
+    __syncthreads();
+    double *rec = j.part + (size_t)blockIdx.x * (kNEval + 1);
+    if (threadIdx.x < kNEval) rec[threadIdx.x] = ((s[0][threadIdx.x] + s[1][threadIdx.x]) + s[2][threadIdx.x]) + s[3][threadIdx.x];
+    if (threadIdx.x == kNEval) {
+        int *cnt = reinterpret_cast<int *>(rec + kNEval);
+        cnt[0] = (sc[0][0] + sc[1][0]) + (sc[2][0] + sc[3][0]);
+        cnt[1] = (sc[0][1] + sc[1][1]) + (sc[2][1] + sc[3][1]);
+    }
+}
+
+// a candidate's eb records joined in block order: the 64 lanes fetch them into LDS side by side (one lane adding straight from memory
+// waited out a round trip per record, 15 us for 64), then lane k < 10 adds sum k, lanes 10 and 11 the counts
+__global__ __launch_bounds__(64) void eval_finish_batch_kernel(const EvalJob *jobs, int eb, EvalOut *out)
+{
+    const EvalJob j = jobs[blockIdx.x];
+    __shared__ double rec[kEvalBlocks * (kNEval + 1)];
+    const int k = threadIdx.x;
+    eb = eb < 1 ? 1 : (eb > kEvalBlocks ? kEvalBlocks : eb);
+    for (int w = k; w < eb * (kNEval + 1); w += 64) rec[w] = j.part[w];
+    __syncthreads();
+    if (k < kNEval) {
+        double sum = rec[k];
+        for (int b = 1; b < eb; ++b) sum += rec[b * (kNEval + 1) + k];
+        out[blockIdx.x].s[k] = sum;
+    } else if (k < kNEval + 2) {
+        int sum = 0;
+        for (int b = 0; b < eb; ++b) sum += reinterpret_cast<const int *>(rec + b * (kNEval + 1) + kNEval)[k - kNEval];
+        if (k == kNEval) out[blockIdx.x].n_valid = sum; else out[blockIdx.x].n_inl = sum;
+    }
+}
+
 // ---- the guessed ICP batch: every alignment has a source of its own, and a working order of its own (icp_batch_run) ---------------
 // Candidate blockIdx.y's cloud lives at moved + blockIdx.y * n (float4, SOURCE order, written once and read again by the fitness
 // pass), its order at order + blockIdx.y * n.  Each kernel is the single path's body on the candidate's slice: the boxes of
@@ -3073,6 +3173,72 @@ int icp_geometric_verification_batch(IcpWorkspace *const *wss, int m, IcpWorkspa
         n_inliers_out[c] = n_inl;
         if (n_inl >= 3) std::memcpy(T + 16 * (size_t)c, h[c].T, sizeof(float) * 16);
         success[c] = !((double)n_inl < inlier_ratio * (double)n_corr);                             // DM.h:1238
+    }
+    return SCL_OK;
+}
+
+// The scoring of m registrations of ONE source (d_src on the device, n_src >= 1 points, read in place) against the candidates'
+// targets (on the device, n_tgts[c] >= 1 points, read in place): transforms = 12 floats per candidate, rows 0 .. 2 of T_c.  One
+// chain on the stream -- moved sources, grids, cold search, eval_reduce_batch_kernel, eval_finish_batch_kernel -- and one wait.
+// n_valid and n_inliers have m entries, moments 10 * m; none may be nullptr.  The moved clouds, nni / nnd and the records live in
+// the candidates' grow-only workspaces (B_WORK, B_NNI, B_NND, B_PART), the tables in ctl as in icp_geometric_verification_batch.
+int icp_registration_eval_batch(IcpWorkspace *const *wss, int m, IcpWorkspace *ctl, hipStream_t stream, const void *d_src, int n_src,
+                                const void *const *d_tgts, const int *n_tgts, int stride, const float *transforms, float maxd2,
+                                int *n_valid, int *n_inliers, double *moments, std::string *err)
+{
+    if (m <= 0) return SCL_OK;
+    int rc;
+    if (n_src < 1 || !d_src) { if (err) *err = "registration eval batch: no source"; return SCL_ERR_INVALID_ARG; }
+    for (int c = 0; c < m; ++c) {
+        if ((rc = check_cloud_args(n_src, n_tgts[c], stride, err))) return rc;
+        if (n_tgts[c] < 1 || !d_tgts[c]) { if (err) *err = "registration eval batch: empty target"; return SCL_ERR_INVALID_ARG; }
+    }
+    const GridJob *dj = nullptr;
+    int max_n = 0;
+    const int eb = eval_blocks(n_src);
+    if ((rc = ensure(ctl, B_MASK, sizeof(IcpProblem) * (size_t)m, err))) return rc;
+    if ((rc = ensure(ctl, B_PAIR, (sizeof(EvalJob) + sizeof(EvalOut) + sizeof(float) * 12) * (size_t)m, err))) return rc;
+    if ((rc = pinned(ctl, sizeof(EvalOut) * (size_t)m, err))) return rc;
+    for (int c = 0; c < m; ++c) {
+        IcpWorkspace *ws = wss[c];
+        if ((rc = ensure(ws, B_WORK, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
+        if ((rc = ensure(ws, B_NNI, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
+        if ((rc = ensure(ws, B_NND, sizeof(float) * (size_t)(n_src + 1), err))) return rc;
+        if ((rc = ensure(ws, B_PART, sizeof(double) * (kNEval + 1) * kEvalBlocks, err))) return rc;
+    }
+    if ((rc = grid_build_batch(wss, m, ctl, stream, d_tgts, n_tgts, stride, false, &dj, &max_n, err))) return rc;
+    std::vector<IcpProblem> hp((size_t)m);
+    std::vector<EvalJob> hj((size_t)m);
+    for (int c = 0; c < m; ++c) {
+        IcpWorkspace *ws = wss[c];
+        IcpProblem &p = hp[(size_t)c];
+        std::memset(&p, 0, sizeof(p));
+        p.work = static_cast<float4 *>(ws->buf[B_WORK]); p.st = (IcpState *)ws->buf[B_STATE]; p.cell_start = (const int *)ws->buf[B_CSTART];
+        p.sorted = (const float4 *)ws->buf[B_TSORT]; p.nni = (int *)ws->buf[B_NNI]; p.nnd = (float *)ws->buf[B_NND];
+        p.tgt = static_cast<const unsigned char *>(d_tgts[c]); p.n_tgt = n_tgts[c];
+        EvalJob &j = hj[(size_t)c];
+        j.tgt = p.tgt; j.nni = p.nni; j.nnd = p.nnd; j.part = (double *)ws->buf[B_PART];
+    }
+    EvalJob *djobs = static_cast<EvalJob *>(ctl->buf[B_PAIR]);
+    EvalOut *dout = reinterpret_cast<EvalOut *>(djobs + m);
+    float *dt = reinterpret_cast<float *>(dout + m);
+    const IcpProblem *dp = static_cast<const IcpProblem *>(ctl->buf[B_MASK]);
+    ICP_HIP(hipMemcpyAsync(ctl->buf[B_MASK], hp.data(), sizeof(IcpProblem) * (size_t)m, hipMemcpyHostToDevice, stream));   // (pageable: staged before the call returns)
+    ICP_HIP(hipMemcpyAsync(djobs, hj.data(), sizeof(EvalJob) * (size_t)m, hipMemcpyHostToDevice, stream));
+    ICP_HIP(hipMemcpyAsync(dt, transforms, sizeof(float) * 12 * (size_t)m, hipMemcpyHostToDevice, stream));
+    const int pb = (n_src + 255) / 256;
+    hipLaunchKernelGGL(guess_move_batch_kernel, dim3(pb, m), dim3(256), 0, stream, dp, static_cast<const unsigned char *>(d_src), n_src, stride, (const float *)dt);
+    hipLaunchKernelGGL(nn_search_batch_kernel<kNnGroup>, dim3((unsigned)(((long long)n_src * kNnGroup + 255) / 256), m), dim3(256), 0, stream,
+                       dp, n_src, 0, -1, stride, 0);                                               // cold
+    hipLaunchKernelGGL(eval_reduce_batch_kernel, dim3(eb, m), dim3(256), 0, stream, (const EvalJob *)djobs, stride, n_src, maxd2);
+    hipLaunchKernelGGL(eval_finish_batch_kernel, dim3(m), dim3(64), 0, stream, (const EvalJob *)djobs, eb, dout);
+    ICP_HIP(hipGetLastError());
+    EvalOut *h = static_cast<EvalOut *>(ctl->pinned);
+    ICP_HIP(hipMemcpyAsync(h, dout, sizeof(EvalOut) * (size_t)m, hipMemcpyDeviceToHost, stream));
+    ICP_HIP(hipStreamSynchronize(stream));
+    for (int c = 0; c < m; ++c) {
+        n_valid[c] = h[c].n_valid; n_inliers[c] = h[c].n_inl;
+        std::memcpy(moments + (size_t)kNEval * c, h[c].s, sizeof(double) * kNEval);
     }
     return SCL_OK;
 }

@@ -85,6 +85,14 @@ int icp_geometric_verification_batch(IcpWorkspace *const *wss, int m, IcpWorkspa
                                      const void *const *d_tgts, const int *n_tgts, int stride, const float *guesses, int ransac_iterations,
                                      double inlier_threshold, double inlier_ratio, unsigned long long seed, float *T, int *success,
                                      int *n_corr_out, int *n_inliers_out, std::string *err);
+// the scoring of m registrations of ONE source (d_src: on the device, read in place, n_src >= 1) against the candidates' targets
+// (d_tgts[c], n_tgts[c] >= 1, read in place): candidate c's source is d_src moved by transforms + 12 * c (rows 0 .. 2 of T_c,
+// icp_transform_cloud's values); n_valid[c] = moved sources with a neighbour, n_inliers[c] = those with nn_dist2 <= maxd2,
+// moments + 10 * c = fp64 sums over them of the matched target point's x, y, z, xx, yy, zz, xy, xz, yz and of nn_dist2, in an order
+// that depends on n_src alone.  One chain of launches over all candidates, one wait; no output may be nullptr.
+int icp_registration_eval_batch(IcpWorkspace *const *wss, int m, IcpWorkspace *ctl, hipStream_t stream, const void *d_src, int n_src,
+                                const void *const *d_tgts, const int *n_tgts, int stride, const float *transforms, float maxd2,
+                                int *n_valid, int *n_inliers, double *moments, std::string *err);
 // where icp_stage_cloud / icp_stage_cloud_host left a cloud
 const void *icp_staged_cloud(const IcpWorkspace *ws, bool target);
 

@@ -144,6 +144,12 @@ def _bind(lib):
                                                         fp, fp, fp, ip, ip, ip, ip]),
         "scl_icp_align_batch_from_store_guess": (c_int, [P, P, c_int, c_int, c_float, c_int, c_int, ip, c_int, fp, c_float, fp, POINTER(IcpParams),
                                                          c_int, c_int, fp, fp, fp, ip, ip, ip, ip]),
+        "scl_registration_eval_batch": (c_int, [P, P, c_int, POINTER(c_void_p), ip, c_int, c_int, fp, c_double, ip, ip, dp]),
+        "scl_registration_eval_batch_from_store": (c_int, [P, P, c_int, c_int, c_float, c_int, c_int, ip, c_int, fp, c_float, fp, c_int, c_int,
+                                                           c_double, ip, ip, dp, ip, ip]),
+        "scl_loop_eval_batch_from_store": (c_int, [P, c_int, c_int, fp, c_int, ip, c_int, fp, c_float, fp, c_int, c_int, c_double,
+                                                   ip, ip, dp, ip, ip]),
+        "scl_registration_information": (c_int, [c_int, dp, dp]),
         "scl_profile_enable": (c_int, [P, c_int]),
         "scl_profile_reset": (c_int, [P]),
         "scl_profile_get": (c_int, [P, POINTER(SclProfile)]),
@@ -185,6 +191,33 @@ def _cloud(points):
     if a.ndim != 2 or a.shape[1] < 3:
         raise ValueError("point cloud must be (n, >=3) float32")
     return a, a.shape[0], a.shape[1] * 4
+
+
+class RegistrationEval:
+    """What registration_eval_batch and its store forms answer for m candidates: n_src (the source's size, after the filter in the
+    store forms), n_valid[m], n_inliers[m], moments[m,10] (fp64 sums over the inliers of the matched target point's x, y, z, xx, yy,
+    zz, xy, xz, yz and of the squared distance) and, from the store forms, n_tgts[m]."""
+
+    def __init__(self, n_src, n_valid, n_inliers, moments, n_tgts=None):
+        self.n_src, self.n_valid, self.n_inliers, self.moments, self.n_tgts = n_src, n_valid, n_inliers, moments, n_tgts
+
+    def __len__(self):
+        return len(self.n_inliers)
+
+    @property
+    def overlap(self):
+        """n_inliers / n_src per candidate (0 for an empty source)"""
+        return self.n_inliers / float(self.n_src) if self.n_src > 0 else np.zeros(len(self), np.float64)
+
+    @property
+    def rmse(self):
+        """sqrt(sum d2 / n_inliers) per candidate, NaN where there is no inlier"""
+        m = self.n_inliers.astype(np.float64)
+        return np.sqrt(np.divide(self.moments[:, 9], m, out=np.full(len(self), np.nan), where=m > 0))
+
+    def information(self, c):
+        """the 6 x 6 information matrix of candidate c's pairs, rotation first (scl_registration_information)"""
+        return ScanContextEngine.registration_information(int(self.n_inliers[c]), self.moments[c])
 
 
 class ScanContextEngine:
@@ -949,6 +982,65 @@ class ScanContextEngine:
             _ptr(G, c_float), byref(p), min_src_points, min_tgt_points, _ptr(T, c_float), _ptr(Ti, c_float), _ptr(fit, c_float),
             _ptr(conv, c_int), _ptr(it, c_int), byref(ns), _ptr(nt, c_int)), "scl_icp_align_batch_from_store_guess")
         return T[:m].reshape(m, 4, 4), Ti[:m].reshape(m, 4, 4), fit[:m], conv[:m].astype(bool), it[:m], ns.value, nt[:m]
+
+    def registration_eval_batch(self, src, tgts, transforms, max_dist):
+        """the pairs of m finished registrations scored in one chain: candidate c's source is src moved by transforms[c] (m,4,4: the T
+        of the guessed verification or of the guessed ICP); returns a RegistrationEval (overlap, rmse, information(c))"""
+        s, ns, stride = _cloud(src)
+        arrs, ptrs, counts, m, stride_t = self._cloud_list(tgts)
+        if m and stride != stride_t:
+            raise ValueError("source and targets must share a record layout")
+        Tm = _f32(np.asarray(transforms)).reshape(m, 16)
+        k = max(m, 1)
+        nv = np.zeros(k, np.int32); ni = np.zeros(k, np.int32); mo = np.zeros((k, 10), np.float64)
+        self._check(self._lib.scl_registration_eval_batch(self._h, s.ctypes.data_as(c_void_p), ns, ptrs, _ptr(counts, c_int), m, stride,
+                                                          _ptr(Tm, c_float), max_dist, _ptr(nv, c_int), _ptr(ni, c_int), _ptr(mo, c_double)),
+                    "scl_registration_eval_batch")
+        return RegistrationEval(ns, nv[:m], ni[:m], mo[:m])
+
+    def registration_eval_batch_from_store(self, src, src_leaf, robot, keys_pre, search_num, poses_pre, leaf, transforms, max_dist,
+                                           min_src_points=300, min_tgt_points=1000):
+        """registration_eval_batch for one RECEIVED scan (voxel-filtered once with src_leaf) against the submaps of keys_pre, with the
+        layout and gates of geometric_verification_batch_from_store_guess; n_src is the filtered size"""
+        a, n, stride = _cloud(src)
+        keys = np.ascontiguousarray(keys_pre, dtype=np.int32); m = keys.size
+        Tp = _f32(np.asarray(poses_pre)).reshape(m, 2 * search_num + 1, 16)
+        Tm = _f32(np.asarray(transforms)).reshape(m, 16)
+        k = max(m, 1)
+        nv = np.zeros(k, np.int32); ni = np.zeros(k, np.int32); mo = np.zeros((k, 10), np.float64); ns = c_int(); nt = np.zeros(k, np.int32)
+        self._check(self._lib.scl_registration_eval_batch_from_store(
+            self._h, a.ctypes.data_as(c_void_p), n, stride, src_leaf, robot, m, _ptr(keys, c_int), search_num, _ptr(Tp, c_float), leaf,
+            _ptr(Tm, c_float), min_src_points, min_tgt_points, max_dist, _ptr(nv, c_int), _ptr(ni, c_int), _ptr(mo, c_double),
+            byref(ns), _ptr(nt, c_int)), "scl_registration_eval_batch_from_store")
+        return RegistrationEval(ns.value, nv[:m], ni[:m], mo[:m], nt[:m])
+
+    def loop_eval_batch_from_store(self, robot, key_cur, pose_cur, keys_pre, search_num, poses_pre, leaf, transforms, max_dist,
+                                   min_src_points=300, min_tgt_points=1000):
+        """registration_eval_batch on the intra-robot side: the source is submap(key_cur, 0), with the layout and gates of
+        loop_icp_batch_from_store_guess, whose T is the intended transforms"""
+        keys = np.ascontiguousarray(keys_pre, dtype=np.int32); m = keys.size
+        Tc = _f32(np.asarray(pose_cur)).reshape(16)
+        Tp = _f32(np.asarray(poses_pre)).reshape(m, 2 * search_num + 1, 16)
+        Tm = _f32(np.asarray(transforms)).reshape(m, 16)
+        k = max(m, 1)
+        nv = np.zeros(k, np.int32); ni = np.zeros(k, np.int32); mo = np.zeros((k, 10), np.float64); ns = c_int(); nt = np.zeros(k, np.int32)
+        self._check(self._lib.scl_loop_eval_batch_from_store(
+            self._h, robot, key_cur, _ptr(Tc, c_float), m, _ptr(keys, c_int), search_num, _ptr(Tp, c_float), leaf, _ptr(Tm, c_float),
+            min_src_points, min_tgt_points, max_dist, _ptr(nv, c_int), _ptr(ni, c_int), _ptr(mo, c_double), byref(ns), _ptr(nt, c_int)),
+            "scl_loop_eval_batch_from_store")
+        return RegistrationEval(ns.value, nv[:m], ni[:m], mo[:m], nt[:m])
+
+    @staticmethod
+    def registration_information(n_inliers, moments):
+        """the 6 x 6 information matrix (rotation first) of a candidate's pairs from its inlier count and ten sums
+        (scl_registration_information); needs no engine"""
+        lib = load_library(); _bind(lib)
+        mo = np.ascontiguousarray(moments, dtype=np.float64).reshape(10)
+        info = np.empty(36, np.float64)
+        rc = lib.scl_registration_information(int(n_inliers), _ptr(mo, c_double), _ptr(info, c_double))
+        if rc != 0:
+            raise SclError(rc, "scl_registration_information")
+        return info.reshape(6, 6)
 
     @staticmethod
     def loop_guess_from_shift(shift, num_sector, pose_cur, pose_pre):
