@@ -645,6 +645,68 @@ int  scl_loop_eval_batch_from_store(scl_engine *e, int robot, int key_cur, const
  * Every entry is at most one fp64 addition.  A NULL pointer or n_inliers < 0: SCL_ERR_INVALID_ARG, nothing written. */
 int  scl_registration_information(int n_inliers, const double moments[10], double info[36]);
 
+/*
+ * POINT-TO-PLANE REGISTRATION SCORING: PLANE HESSIAN, RESIDUALS, NORMALS.  The matrix above is the point-to-point one: its translation
+ * block is n_inliers * I3 whatever the scene looks like.  It says how many pairs there are, never which directions they constrain --
+ * in a corridor, a tunnel or on open ground the answer a consumer of a loop factor needs most.  These calls score the same pairs
+ * against the planes of the target: the 6 x 6 normal equations sum J^T J with J = [p x n | n], whose small eigenvalues and their
+ * eigenvectors name the motions the geometry leaves free.
+ *   * scl_target_normals.  The normals the point-to-plane estimator (scl_icp_params.estimator = 1) uses for this cloud and radius, n_tgt
+ *     x 3 floats: over all points of the cloud with d^2 <= radius^2 in double (the point itself included), fewer than three give
+ *     (0, 0, 0), otherwise the eigenvector of the smallest eigenvalue of their covariance, formed in double and rounded to float (its
+ *     sign is whatever the solver leaves; the sums below do not depend on it).  The call builds its own search grid and runs the kernel
+ *     body the batch paths run, as the calls below do: the same bits from both, on every run.  (These calls put the points of every
+ *     grid cell in index order first, so that every sum of a covariance is taken in one order; the batched ICP, which hands no
+ *     normal out, leaves a cell in the order its scatter filled it, and forms the same normals from the same neighbours up to the
+ *     rare float that another order of a sum of doubles rounds differently.)  n_tgt == 0: SCL_OK.  radius: refused as scl_icp_params.normal_radius is (not > 0, or NaN: SCL_ERR_INVALID_ARG).  A stride < 12 or no multiple
+ *     of 4, or a NULL pointer with n_tgt > 0: SCL_ERR_INVALID_ARG.  Nothing is written on error.
+ *   * The three scoring calls take the arguments of the three calls above, and normal_radius behind max_dist.  Per candidate c at T_c,
+ *     with p the source point moved by T_c in float (scl_transform_cloud's arithmetic), q its nearest target point and d2 the float
+ *     nn_dist2 (scl_nn_correspondences'), n the normal of q (scl_target_normals(tgt_c, normal_radius)):
+ *       n_valid, n_inliers   exactly the numbers of the calls above (d2 <= (float)(max_dist * max_dist), equality kept)
+ *       n_planar             the inliers whose n is not (0, 0, 0); the other inliers add nothing to sums 0 .. 27
+ *       sums[0 .. 20]        the upper triangle, row by row, of sum J^T J for
+ *                            J = (p_y n_z - p_z n_y, p_z n_x - p_x n_z, p_x n_y - p_y n_x, n_x, n_y, n_z)
+ *                            -- rotation first, the axis order of scl_registration_information
+ *       sums[21 .. 26]       sum J r with r = (q - p) . n
+ *       sums[27]             sum r r
+ *       sums[28]             sum (double)d2 over ALL inliers: moments[9] of the calls above, bit for bit
+ *     Every input is converted to double and every product and difference is formed in double.  The sums are taken in the order of
+ *     the calls above (a function of n_src alone, no floating-point atomics): the same bits on every run, and the store forms give
+ *     the bits of the host form on scl_voxel_grid's / scl_submap_from_store's clouds.
+ *   * Bound.  Each of the sums 0 .. 27 lies within (m + 10) * 2^-53 * M of the exact sum over the float inputs, where m = n_planar and M
+ *     is the same sum with every term replaced by its majorant: R = (|p_y n_z| + |p_z n_y|, |p_z n_x| + |p_x n_z|, |p_x n_y| + |p_y n_x|,
+ *     |n_x|, |n_y|, |n_z|) for J and rbar = sum_k (|q_k| + |p_k|) |n_k| for r.  Derivation: the product of two floats is exact in
+ *     double, so an entry of p x n is ONE rounding of an exact difference of exact products; every addend of r passes through at
+ *     most four roundings (its difference, its product, two additions), each relative to a quantity below rbar; a term J_a J_b,
+ *     J_a r or r r carries the roundings of its two factors and one of its own -- at most nine (r r: 4 + 4 + 1) --, each relative to
+ *     a quantity below the term's majorant; the accumulation adds m - 1, each relative to a partial sum below M.  To first order
+ *     that is (m + 8) * 2^-53 * M; the remaining 2 * 2^-53 * M cover the second-order terms for every m below 2^50.  Contraction
+ *     into fma only removes roundings.
+ *   * Gates, errors, rounds, n == 0, outputs: those of the calls above (with n > 0 at least one of n_valid, n_inliers, n_planar, sums
+ *     must be given), and normal_radius refused as in scl_target_normals.  Nothing is written on error; a gated candidate keeps zeros
+ *     and reports its n_tgts.
+ *   * How it runs.  The chain of the calls above with the targets' normals in front of the cold search (one launch over all
+ *     candidates), a reduction that also reads the moved point and 16 bytes of normal behind every pair, and a finishing launch of
+ *     one wave per candidate.  The normals live in the slot of scl_transform_cloud's output of the candidates' workspaces, which
+ *     nothing in the chain writes.  Sharded engines: served as the calls above.
+ */
+int  scl_target_normals(scl_engine *e, const void *tgt, int n_tgt, int stride_bytes, double radius, float *normals);
+int  scl_registration_eval_plane_batch(scl_engine *e, const void *src, int n_src, const void *const *tgts, const int *n_tgts,
+                                       int n_targets, int stride_bytes, const float *transforms, double max_dist, double normal_radius,
+                                       int *n_valid, int *n_inliers, int *n_planar, double *sums);
+int  scl_registration_eval_plane_batch_from_store(scl_engine *e, const void *src, int n_src, int stride_bytes, float src_leaf,
+                                                  int robot, int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                                                  const float *transforms, int min_src_points, int min_tgt_points, double max_dist, double normal_radius,
+                                                  int *n_valid, int *n_inliers, int *n_planar, double *sums, int *n_src_filtered, int *n_tgts);
+int  scl_loop_eval_plane_batch_from_store(scl_engine *e, int robot, int key_cur, const float *pose_cur,
+                                          int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                                          const float *transforms, int min_src_points, int min_tgt_points, double max_dist, double normal_radius,
+                                          int *n_valid, int *n_inliers, int *n_planar, double *sums, int *n_src, int *n_tgts);
+/* Host only, no engine: info = the row-major symmetric 6 x 6 whose upper triangle is sums[0 .. 20] (rotation first), grad (may be NULL)
+ * = sums[21 .. 26], the sum of J r.  sums == NULL or info == NULL: SCL_ERR_INVALID_ARG, nothing written. */
+int  scl_registration_information_plane(const double sums[29], double info[36], double grad[6]);
+
 /* ---- measurement ----------------------------------------------------------- */
 int  scl_profile_enable(scl_engine *e, int on);   /* 0 off, 1 every kernel family, 2 SC distance only,
                                                      3 SC distance only, sampled: one launch in thirteen -- in the stream form one

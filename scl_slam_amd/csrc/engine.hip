@@ -504,7 +504,7 @@ const char *scl_status_string(int status)
 
 const char *scl_last_error(const scl_engine *e) { return e ? e->last_error.c_str() : "null engine"; }
 
-int scl_abi_version(void) { return 10; }
+int scl_abi_version(void) { return 11; }
 
 int scl_default_config(scl_config *c)
 {
@@ -3900,31 +3900,39 @@ int scl_icp_align_batch_from_store_guess(scl_engine *e, const void *src, int n_s
 
 namespace {
 
-// what the three scoring calls refuse last, behind their own cloud and window checks -> nullptr or the message
-const char *eval_args_bad(const float *transforms, int n, double max_dist, const int *n_valid, const int *n_inliers, const double *moments)
+// the plane forms' own arguments (nullptr: the point-to-point forms): the normals' radius, and n_planar and sums (29 per candidate)
+// where the point forms have moments
+struct EvalPlane { double normal_radius; int *n_planar; double *sums; };
+
+// what the scoring calls refuse last, behind their own cloud and window checks -> nullptr or the message
+const char *eval_args_bad(const float *transforms, int n, double max_dist, const int *n_valid, const int *n_inliers, const double *moments,
+                          const EvalPlane *pl = nullptr)
 {
     if (!std::isfinite(max_dist) || max_dist < 0.0) return "max_dist must be finite and >= 0";
-    if (n > 0 && !n_valid && !n_inliers && !moments) return "no output asked for";
+    if (pl && !(pl->normal_radius > 0.0)) return "normal_radius must be > 0";                      // the ICP's parameter check (icp_params_bad)
+    if (n > 0 && !n_valid && !n_inliers && !moments && !(pl && (pl->n_planar || pl->sums))) return "no output asked for";
     if (n > 0 && !transforms) return "transforms is NULL";
     for (size_t k = 0; k < 16 * (size_t)n; ++k)
         if ((k & 15) < 12 && !std::isfinite(transforms[k])) return "a transform has a non-finite entry in its first three rows";
     return nullptr;
 }
 
-void eval_clear(int n, int *n_valid, int *n_inliers, double *moments, int *n_tgts)
+void eval_clear(int n, int *n_valid, int *n_inliers, double *moments, int *n_tgts, const EvalPlane *pl = nullptr)
 {
     for (int c = 0; c < n; ++c) {
         if (n_valid) n_valid[c] = 0;
         if (n_inliers) n_inliers[c] = 0;
         if (n_tgts) n_tgts[c] = 0;
+        if (pl && pl->n_planar) pl->n_planar[c] = 0;
     }
     if (moments) for (size_t k = 0; k < 10 * (size_t)n; ++k) moments[k] = 0.0;
+    if (pl && pl->sums) for (size_t k = 0; k < 29 * (size_t)n; ++k) pl->sums[k] = 0.0;
 }
 
 // one round (at most kIcpBatch candidates, entries first .. first + m - 1 of the outputs): the source on the device at d_src, target c
 // at d_tgts[c]; a candidate that is gated or has no pair to find keeps the zeros the caller wrote
 int eval_round(scl_engine *e, int first, int m, const void *d_src, int ns, const void *const *d_tgts, const int *n_tgts, const bool *gated,
-               int stride, const float *transforms, double max_dist, int *n_valid, int *n_inliers, double *moments)
+               int stride, const float *transforms, double max_dist, int *n_valid, int *n_inliers, double *moments, const EvalPlane *pl = nullptr)
 {
     IcpWorkspace *wss[scl_engine::kIcpBatch]; int which[scl_engine::kIcpBatch]; int live = 0;
     const void *tg[scl_engine::kIcpBatch]; int tn[scl_engine::kIcpBatch];
@@ -3935,15 +3943,19 @@ int eval_round(scl_engine *e, int first, int m, const void *d_src, int ns, const
         wss[live] = &e->icp_batch_ws[c]; which[live] = first + c; tg[live] = d_tgts[c]; tn[live] = n_tgts[c]; ++live;
     }
     if (live == 0) return SCL_OK;
-    int nv[scl_engine::kIcpBatch], ni[scl_engine::kIcpBatch]; double mo[10 * scl_engine::kIcpBatch];
+    int nv[scl_engine::kIcpBatch], ni[scl_engine::kIcpBatch], np[scl_engine::kIcpBatch]; double mo[29 * scl_engine::kIcpBatch];
     std::string err;
     const float maxd2 = (float)(max_dist * max_dist);                    // ICP's rejection rule (icp.hip, icp_batch_run)
-    int rc = icp_registration_eval_batch(wss, live, &e->icp_batch_ctl, e->stream, d_src, ns, tg, tn, stride, t12, maxd2, nv, ni, mo, &err);
+    int rc = pl ? icp_registration_eval_plane_batch(wss, live, &e->icp_batch_ctl, e->stream, d_src, ns, tg, tn, stride, t12, maxd2, pl->normal_radius,
+                                                    nv, ni, np, mo, &err)
+                : icp_registration_eval_batch(wss, live, &e->icp_batch_ctl, e->stream, d_src, ns, tg, tn, stride, t12, maxd2, nv, ni, mo, &err);
     if (rc) { e->last_error = err; return rc; }
     for (int j = 0; j < live; ++j) {
         if (n_valid) n_valid[which[j]] = nv[j];
         if (n_inliers) n_inliers[which[j]] = ni[j];
         if (moments) std::memcpy(moments + 10 * (size_t)which[j], mo + 10 * (size_t)j, 10 * sizeof(double));
+        if (pl && pl->n_planar) pl->n_planar[which[j]] = np[j];
+        if (pl && pl->sums) std::memcpy(pl->sums + 29 * (size_t)which[j], mo + 29 * (size_t)j, 29 * sizeof(double));
     }
     return SCL_OK;
 }
@@ -3955,9 +3967,10 @@ int eval_batch_store(scl_engine *e, bool received, const void *src, int n_src, i
                      int robot, int key_cur, const float *pose_cur,
                      int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
                      const float *transforms, int min_src_points, int min_tgt_points, double max_dist,
-                     int *n_valid, int *n_inliers, double *moments, int *n_src_out, int *n_tgts)
+                     int *n_valid, int *n_inliers, double *moments, int *n_src_out, int *n_tgts, const EvalPlane *pl = nullptr)
 {
-    const char *const name = received ? "registration_eval_batch_from_store: " : "loop_eval_batch_from_store: ";
+    const char *const name = pl ? (received ? "registration_eval_plane_batch_from_store: " : "loop_eval_plane_batch_from_store: ")
+                                : (received ? "registration_eval_batch_from_store: " : "loop_eval_batch_from_store: ");
     if (!e || n_candidates < 0 || (n_candidates > 0 && (!keys_pre || !poses_pre))) return SCL_ERR_INVALID_ARG;
     if (received ? (!src && n_src > 0) : !pose_cur) return SCL_ERR_INVALID_ARG;
     if (e->front) e = front_primary(e);
@@ -3979,7 +3992,7 @@ int eval_batch_store(scl_engine *e, bool received, const void *src, int n_src, i
         cl_all.insert(cl_all.end(), clouds.begin(), clouds.end()); cn_all.insert(cn_all.end(), counts.begin(), counts.end()); tw_all.insert(tw_all.end(), Tw.begin(), Tw.end());
         first_of.push_back((int)cl_all.size());
     }
-    if (const char *bad = eval_args_bad(transforms, n_candidates, max_dist, n_valid, n_inliers, moments)) return fail(e, SCL_ERR_INVALID_ARG, (std::string(name) + bad).c_str());
+    if (const char *bad = eval_args_bad(transforms, n_candidates, max_dist, n_valid, n_inliers, moments, pl)) return fail(e, SCL_ERR_INVALID_ARG, (std::string(name) + bad).c_str());
     (void)hipSetDevice(e->device);
     std::string err;
     int ns = 0;
@@ -4010,7 +4023,7 @@ int eval_batch_store(scl_engine *e, bool received, const void *src, int n_src, i
                                     d_sub.data(), n_sub.data(), &err);
         if (rc) { e->last_error = err; return rc; }
         if (lead) { ns = n_sub[0]; d_src = d_sub[0]; if (n_src_out) *n_src_out = ns; }   // (stays in the filter's workspace until the round is over)
-        if (!cleared) { eval_clear(n_candidates, n_valid, n_inliers, moments, n_tgts); cleared = true; }
+        if (!cleared) { eval_clear(n_candidates, n_valid, n_inliers, moments, n_tgts, pl); cleared = true; }
         if (m <= 0) break;
         bool gated[scl_engine::kIcpBatch];
         for (int c = 0; c < m; ++c) {
@@ -4018,28 +4031,28 @@ int eval_batch_store(scl_engine *e, bool received, const void *src, int n_src, i
             if (n_tgts) n_tgts[first + c] = nt;
             gated[c] = ns < min_src_points || nt < min_tgt_points;         // DM.h:1108 / 1204: the unmoved sizes
         }
-        rc = eval_round(e, first, m, d_src, ns, d_sub.data() + lead, n_sub.data() + lead, gated, stride, transforms, max_dist, n_valid, n_inliers, moments);
+        rc = eval_round(e, first, m, d_src, ns, d_sub.data() + lead, n_sub.data() + lead, gated, stride, transforms, max_dist, n_valid, n_inliers, moments, pl);
         if (rc) return rc;
     }
     return SCL_OK;
 }
 
-}  // namespace
-
-int scl_registration_eval_batch(scl_engine *e, const void *src, int n_src, const void *const *tgts, const int *n_tgts,
-                                int n_targets, int stride_bytes, const float *transforms, double max_dist,
-                                int *n_valid, int *n_inliers, double *moments)
+// scl_registration_eval_batch (pl == nullptr) and scl_registration_eval_plane_batch: host clouds
+int eval_batch_host(scl_engine *e, const void *src, int n_src, const void *const *tgts, const int *n_tgts,
+                    int n_targets, int stride_bytes, const float *transforms, double max_dist,
+                    int *n_valid, int *n_inliers, double *moments, const EvalPlane *pl)
 {
+    const std::string name = pl ? "registration_eval_plane_batch: " : "registration_eval_batch: ";
     if (!e || n_targets < 0 || (!src && n_src > 0) || (n_targets > 0 && (!tgts || !n_tgts))) return SCL_ERR_INVALID_ARG;
     if (e->front) e = front_primary(e);
     std::lock_guard<std::mutex> lk(e->mu);
-    if (n_src < 0 || stride_bytes < 12 || (stride_bytes & 3)) return fail(e, SCL_ERR_INVALID_ARG, "registration_eval_batch: bad cloud layout");
+    if (n_src < 0 || stride_bytes < 12 || (stride_bytes & 3)) return fail(e, SCL_ERR_INVALID_ARG, (name + "bad cloud layout").c_str());
     for (int c = 0; c < n_targets; ++c)
-        if (n_tgts[c] < 0 || (!tgts[c] && n_tgts[c] > 0)) return fail(e, SCL_ERR_INVALID_ARG, "registration_eval_batch: bad target");
-    if (const char *bad = eval_args_bad(transforms, n_targets, max_dist, n_valid, n_inliers, moments)) return fail(e, SCL_ERR_INVALID_ARG, (std::string("registration_eval_batch: ") + bad).c_str());
+        if (n_tgts[c] < 0 || (!tgts[c] && n_tgts[c] > 0)) return fail(e, SCL_ERR_INVALID_ARG, (name + "bad target").c_str());
+    if (const char *bad = eval_args_bad(transforms, n_targets, max_dist, n_valid, n_inliers, moments, pl)) return fail(e, SCL_ERR_INVALID_ARG, (name + bad).c_str());
     if (n_targets == 0) return SCL_OK;
     (void)hipSetDevice(e->device);
-    eval_clear(n_targets, n_valid, n_inliers, moments, nullptr);
+    eval_clear(n_targets, n_valid, n_inliers, moments, nullptr, pl);
     std::string err;
     int rc = SCL_OK;
     if (n_src >= 1) rc = icp_stage_cloud_host(&e->icp_batch_ctl, e->stream, false, src, n_src, stride_bytes, &err);   // once per call (none: no pair at all)
@@ -4055,10 +4068,19 @@ int scl_registration_eval_batch(scl_engine *e, const void *src, int n_src, const
             d_tgts[c] = icp_staged_cloud(&e->icp_batch_ws[c], true);
         }
         rc = eval_round(e, first, m, icp_staged_cloud(&e->icp_batch_ctl, false), n_src, d_tgts, n_tgts + first, gated, stride_bytes, transforms, max_dist,
-                        n_valid, n_inliers, moments);
+                        n_valid, n_inliers, moments, pl);
         if (rc) return rc;
     }
     return SCL_OK;
+}
+
+}  // namespace
+
+int scl_registration_eval_batch(scl_engine *e, const void *src, int n_src, const void *const *tgts, const int *n_tgts,
+                                int n_targets, int stride_bytes, const float *transforms, double max_dist,
+                                int *n_valid, int *n_inliers, double *moments)
+{
+    return eval_batch_host(e, src, n_src, tgts, n_tgts, n_targets, stride_bytes, transforms, max_dist, n_valid, n_inliers, moments, nullptr);
 }
 
 int scl_registration_eval_batch_from_store(scl_engine *e, const void *src, int n_src, int stride_bytes, float src_leaf,
@@ -4092,6 +4114,58 @@ int scl_registration_information(int n_inliers, const double moments[10], double
                             -Sz, 0.0, Sx, 0.0, m, 0.0,
                             Sy, -Sx, 0.0, 0.0, 0.0, m};
     std::memcpy(info, out, sizeof out);
+    return SCL_OK;
+}
+
+/* ---- point-to-plane registration scoring: normals, plane Hessian, residuals ------ */
+
+int scl_target_normals(scl_engine *e, const void *tgt, int n_tgt, int stride_bytes, double radius, float *normals)
+{
+    if (!e || n_tgt < 0 || (n_tgt > 0 && (!tgt || !normals))) return SCL_ERR_INVALID_ARG;
+    if (e->front) e = front_primary(e);
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    std::string err;
+    int rc = icp_target_normals(&e->icp_ws, e->stream, tgt, n_tgt, stride_bytes, radius, normals, &err);
+    if (rc) e->last_error = err;
+    return rc;
+}
+
+int scl_registration_eval_plane_batch(scl_engine *e, const void *src, int n_src, const void *const *tgts, const int *n_tgts,
+                                      int n_targets, int stride_bytes, const float *transforms, double max_dist, double normal_radius,
+                                      int *n_valid, int *n_inliers, int *n_planar, double *sums)
+{
+    const EvalPlane pl = {normal_radius, n_planar, sums};
+    return eval_batch_host(e, src, n_src, tgts, n_tgts, n_targets, stride_bytes, transforms, max_dist, n_valid, n_inliers, nullptr, &pl);
+}
+
+int scl_registration_eval_plane_batch_from_store(scl_engine *e, const void *src, int n_src, int stride_bytes, float src_leaf,
+                                                 int robot, int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                                                 const float *transforms, int min_src_points, int min_tgt_points, double max_dist, double normal_radius,
+                                                 int *n_valid, int *n_inliers, int *n_planar, double *sums, int *n_src_filtered, int *n_tgts)
+{
+    const EvalPlane pl = {normal_radius, n_planar, sums};
+    return eval_batch_store(e, true, src, n_src, stride_bytes, src_leaf, robot, 0, nullptr, n_candidates, keys_pre, search_num, poses_pre, leaf,
+                            transforms, min_src_points, min_tgt_points, max_dist, n_valid, n_inliers, nullptr, n_src_filtered, n_tgts, &pl);
+}
+
+int scl_loop_eval_plane_batch_from_store(scl_engine *e, int robot, int key_cur, const float *pose_cur,
+                                         int n_candidates, const int *keys_pre, int search_num, const float *poses_pre, float leaf,
+                                         const float *transforms, int min_src_points, int min_tgt_points, double max_dist, double normal_radius,
+                                         int *n_valid, int *n_inliers, int *n_planar, double *sums, int *n_src, int *n_tgts)
+{
+    const EvalPlane pl = {normal_radius, n_planar, sums};
+    return eval_batch_store(e, false, nullptr, 0, 0, 0.f, robot, key_cur, pose_cur, n_candidates, keys_pre, search_num, poses_pre, leaf,
+                            transforms, min_src_points, min_tgt_points, max_dist, n_valid, n_inliers, nullptr, n_src, n_tgts, &pl);
+}
+
+int scl_registration_information_plane(const double sums[29], double info[36], double grad[6])
+{
+    if (!sums || !info) return SCL_ERR_INVALID_ARG;
+    int t = 0;
+    for (int a = 0; a < 6; ++a)
+        for (int b = a; b < 6; ++b) { info[6 * a + b] = sums[t]; info[6 * b + a] = sums[t]; ++t; }
+    if (grad) for (int a = 0; a < 6; ++a) grad[a] = sums[21 + a];
     return SCL_OK;
 }
 

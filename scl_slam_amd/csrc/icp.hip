@@ -62,8 +62,8 @@ struct IcpState {
 };
 
 enum Buf { B_SRC = 0, B_TGT, B_WORK, B_TSORT, B_CSTART, B_CFILL, B_NNI, B_NND, B_PART, B_STATE, B_BBOX, B_SI, B_TI, B_OUT, B_MASK, B_HYP, B_PROB,
-           B_NNQ, B_PERM, B_SORT, B_FLAG, B_PAIR, B_GSRC, B_GORD };
-static_assert(B_GORD < (int)(sizeof(IcpWorkspace::buf) / sizeof(void *)), "IcpWorkspace::buf is too short");
+           B_NNQ, B_PERM, B_SORT, B_FLAG, B_PAIR, B_GSRC, B_GORD, B_TORD };
+static_assert(B_TORD < (int)(sizeof(IcpWorkspace::buf) / sizeof(void *)), "IcpWorkspace::buf is too short");
 constexpr int B_NORM = B_OUT;             // target normals share the slot of the raw-transform output (never live together)
 
 int ensure(IcpWorkspace *ws, int k, size_t bytes, std::string *err)
@@ -1118,6 +1118,34 @@ __global__ __launch_bounds__(1024) void grid_scan_batch_kernel(const GridJob *jo
 }
 __global__ void grid_scatter_batch_kernel(const GridJob *jobs, int stride) { const GridJob j = jobs[blockIdx.y]; grid_scatter_body(j.tgt, j.n, stride, j.st, j.cfill, j.tsort); }
 __global__ void state_init_batch_kernel(const GridJob *jobs) { state_init_body(jobs[blockIdx.x].st); }
+
+// The scatter places the points of a cell in the order its atomics happen to be served: the neighbour search does not care (ties go
+// to the lowest index), the alignments' normals see it only where a sum of doubles, taken in another order, rounds to another float.
+// The calls that hand normals or sums over them OUT promise the same bits on every run, so behind their scatter they read the grid
+// through a copy in which every cell is in ascending order of the points' indices: one thread per entry of `sorted` finds its cell
+// (cell_index on the coordinates the scatter binned), counts the entries of that cell with a smaller index -- a handful, in the cache
+// lines it has just read -- and writes itself to that rank.  Every index occurs once, so the ranks of a cell are a permutation.  (One
+// thread per CELL sorting in place waited out a chain of dependent loads per cell: 570 us for 25 x 100 k points against 110 for the
+// scatter itself.  A cloud whose points share one cell costs n^2 here, as it does the neighbour search.)
+struct OrderJob { const IcpState *st; const int *cell_start; const float4 *sorted; float4 *out; int n; };
+__device__ __forceinline__ void grid_cell_order_body(const OrderJob &j)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= j.n) return;
+    const float4 me = j.sorted[k];
+    int c[3];
+    const int cell = cell_index(j.st, make_float3(me.x, me.y, me.z), c);
+    const int b = j.cell_start[cell], e = j.cell_start[cell + 1];
+    int at = k;                                                  // (an entry outside its cell's range cannot happen; it would stay where it is)
+    if (k >= b && k < e && b >= 0 && e <= j.n) {
+        const int mine = __float_as_int(me.w);
+        at = b;
+        for (int i = b; i < e; ++i) at += __float_as_int(j.sorted[i].w) < mine;
+    }
+    j.out[at] = me;
+}
+__global__ __launch_bounds__(256) void grid_cell_order_kernel(OrderJob j) { grid_cell_order_body(j); }
+__global__ __launch_bounds__(256) void grid_cell_order_batch_kernel(const OrderJob *jobs) { grid_cell_order_body(jobs[blockIdx.y]); }
 
 // ---- RANSAC correspondence rejection (CorrespondenceRejectorSampleConsensus, DM.h:1218-1225) ----------
 // Deterministic restatement (see oracle/icp_oracle.h): hypothesis h = 3 distinct correspondences drawn
@@ -2207,6 +2235,106 @@ __global__ __launch_bounds__(64) void eval_finish_batch_kernel(const EvalJob *jo
     }
 }
 
+// ---- point-to-plane scoring: the 6 x 6 normal equations of the pairs of a finished registration (blockIdx.y = candidate) -----------
+// eval_reduce_batch_kernel's walk -- the same partition, trips, butterfly and record order, so n_valid, n_inl and the sum of d2 are
+// its bits -- with, per inlier whose matched target point q has a normal n (not (0, 0, 0)), plane_reduce_kernel_body's row
+// J = (p x n, n) and r = (q - p) . n for the moved source p: the upper triangle of J^T J (21), J r (6) and r r, every input converted
+// to double first.  A product of two converted floats is exact; an entry of p x n is one rounding, r four, a term of a sum at most
+// nine more (whether or not the compiler contracts into fma, which only removes roundings).  Still a gather: nni / nnd / the moved
+// point stream (24 bytes per source), 12 bytes of target and 16 of normal sit behind nni.  The loads of four trips are issued
+// together as there; 29 fp64 sums and four trips of operands are the register bill (profiles/registration_plane/resources.txt).
+constexpr int kNEvalPlane = 29;           // 21 + 6 + r r + sum d2
+constexpr int kPlaneRec = kNEvalPlane + 2;   // a workgroup's record: the sums, then n_valid, n_inl, n_planar (ints) in two doubles' room
+struct EvalPlaneJob { const unsigned char *tgt; const int *nni; const float *nnd; const float4 *work; const float4 *normals; double *part; };
+struct EvalPlaneOut { double s[kNEvalPlane]; int n_valid, n_inl, n_planar, pad_; };
+
+__global__ __launch_bounds__(256) void eval_plane_reduce_batch_kernel(const EvalPlaneJob *jobs, int stride, int n_src, float maxd2)
+{
+    const EvalPlaneJob j = jobs[blockIdx.y];
+    double acc[kNEvalPlane];
+#pragma unroll
+    for (int k = 0; k < kNEvalPlane; ++k) acc[k] = 0.0;
+    int nv = 0, ni = 0, np = 0;
+    const int step = (int)(gridDim.x * blockDim.x);
+    for (long long i = (long long)(blockIdx.x * blockDim.x + threadIdx.x); i < n_src; i += 4 * step) {
+        int t[4]; float d2[4]; float3 q[4]; float4 p[4], nn[4]; bool in[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const long long iu = i + (long long)u * step;
+            t[u] = iu < n_src ? j.nni[iu] : -1;
+            d2[u] = iu < n_src ? j.nnd[iu] : 0.f;
+            p[u] = iu < n_src ? j.work[iu] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            in[u] = t[u] >= 0 && d2[u] <= maxd2;                 // eval_reduce_batch_kernel's rule
+            q[u] = in[u] ? load_xyz(j.tgt, t[u], stride) : make_float3(0.f, 0.f, 0.f);
+            nn[u] = in[u] ? j.normals[t[u]] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            nv += t[u] >= 0;
+            if (!in[u]) continue;
+            ++ni;
+            acc[28] += (double)d2[u];
+            if (nn[u].x == 0.f && nn[u].y == 0.f && nn[u].z == 0.f) continue;   // fewer than three neighbours in the ball: no plane
+            ++np;
+            const double px = p[u].x, py = p[u].y, pz = p[u].z, nx = nn[u].x, ny = nn[u].y, nz = nn[u].z;
+            const double row[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
+            const double r = ((double)q[u].x - px) * nx + ((double)q[u].y - py) * ny + ((double)q[u].z - pz) * nz;
+            int s = 0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int b = a; b < 6; ++b) acc[s++] += row[a] * row[b];
+#pragma unroll
+            for (int a = 0; a < 6; ++a) acc[21 + a] += row[a] * r;
+            acc[27] += r * r;
+        }
+    }
+    __shared__ double s[4][kNEvalPlane];
+    __shared__ int sc[4][3];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < kNEvalPlane; ++k) acc[k] += __shfl_xor(acc[k], off, kWave);
+        nv += __shfl_xor(nv, off, kWave); ni += __shfl_xor(ni, off, kWave); np += __shfl_xor(np, off, kWave);
+    }
+    const int wv = threadIdx.x / kWave;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < kNEvalPlane; ++k) s[wv][k] = acc[k];
+        sc[wv][0] = nv; sc[wv][1] = ni; sc[wv][2] = np;
+    }
+    __syncthreads();
+    double *rec = j.part + (size_t)blockIdx.x * kPlaneRec;
+    if (threadIdx.x < kNEvalPlane) rec[threadIdx.x] = ((s[0][threadIdx.x] + s[1][threadIdx.x]) + s[2][threadIdx.x]) + s[3][threadIdx.x];
+    if (threadIdx.x >= 32 && threadIdx.x < 35) {
+        const int w = threadIdx.x - 32;
+        reinterpret_cast<int *>(rec + kNEvalPlane)[w] = (sc[0][w] + sc[1][w]) + (sc[2][w] + sc[3][w]);
+    }
+}
+
+// a candidate's eb records joined in block order, as eval_finish_batch_kernel joins its: lane k < 29 adds sum k, lanes 29 .. 31 the counts
+__global__ __launch_bounds__(64) void eval_plane_finish_batch_kernel(const EvalPlaneJob *jobs, int eb, EvalPlaneOut *out)
+{
+    const EvalPlaneJob j = jobs[blockIdx.x];
+    __shared__ double rec[kEvalBlocks * kPlaneRec];
+    const int k = threadIdx.x;
+    eb = eb < 1 ? 1 : (eb > kEvalBlocks ? kEvalBlocks : eb);
+    for (int w = k; w < eb * kPlaneRec; w += 64) rec[w] = j.part[w];
+    __syncthreads();
+    if (k < kNEvalPlane) {
+        double sum = rec[k];
+        for (int b = 1; b < eb; ++b) sum += rec[b * kPlaneRec + k];
+        out[blockIdx.x].s[k] = sum;
+    } else if (k < kNEvalPlane + 3) {
+        int sum = 0;
+        for (int b = 0; b < eb; ++b) sum += reinterpret_cast<const int *>(rec + b * kPlaneRec + kNEvalPlane)[k - kNEvalPlane];
+        if (k == kNEvalPlane) out[blockIdx.x].n_valid = sum; else if (k == kNEvalPlane + 1) out[blockIdx.x].n_inl = sum; else out[blockIdx.x].n_planar = sum;
+    }
+}
+
 // ---- the guessed ICP batch: every alignment has a source of its own, and a working order of its own (icp_batch_run) ---------------
 // Candidate blockIdx.y's cloud lives at moved + blockIdx.y * n (float4, SOURCE order, written once and read again by the fitness
 // pass), its order at order + blockIdx.y * n.  Each kernel is the single path's body on the candidate's slice: the boxes of
@@ -3240,6 +3368,109 @@ int icp_registration_eval_batch(IcpWorkspace *const *wss, int m, IcpWorkspace *c
         n_valid[c] = h[c].n_valid; n_inliers[c] = h[c].n_inl;
         std::memcpy(moments + (size_t)kNEval * c, h[c].s, sizeof(double) * kNEval);
     }
+    return SCL_OK;
+}
+
+// icp_registration_eval_batch against planes: the same chain with the targets' normals (normals_problems_kernel at normal_radius,
+// behind the grids, in B_NORM -- B_OUT's slot, which nothing of this chain writes) in front of the cold search, then
+// eval_plane_reduce_batch_kernel and eval_plane_finish_batch_kernel; grid_cell_order_batch_kernel behind the scatter.  n_valid,
+// n_inliers and n_planar have m entries, sums 29 * m; none may be nullptr.  B_PART holds kEvalBlocks records of kPlaneRec doubles (grow-only: never less than another batch left).
+int icp_registration_eval_plane_batch(IcpWorkspace *const *wss, int m, IcpWorkspace *ctl, hipStream_t stream, const void *d_src, int n_src,
+                                      const void *const *d_tgts, const int *n_tgts, int stride, const float *transforms, float maxd2,
+                                      double normal_radius, int *n_valid, int *n_inliers, int *n_planar, double *sums, std::string *err)
+{
+    if (m <= 0) return SCL_OK;
+    int rc;
+    if (!(normal_radius > 0.0)) { if (err) *err = "normal_radius must be > 0"; return SCL_ERR_INVALID_ARG; }
+    if (n_src < 1 || !d_src) { if (err) *err = "registration eval plane batch: no source"; return SCL_ERR_INVALID_ARG; }
+    for (int c = 0; c < m; ++c) {
+        if ((rc = check_cloud_args(n_src, n_tgts[c], stride, err))) return rc;
+        if (n_tgts[c] < 1 || !d_tgts[c]) { if (err) *err = "registration eval plane batch: empty target"; return SCL_ERR_INVALID_ARG; }
+    }
+    const GridJob *dj = nullptr;
+    int max_n = 0;
+    const int eb = eval_blocks(n_src);
+    if ((rc = ensure(ctl, B_MASK, sizeof(IcpProblem) * (size_t)m, err))) return rc;
+    if ((rc = ensure(ctl, B_PAIR, (sizeof(EvalPlaneJob) + sizeof(EvalPlaneOut) + sizeof(OrderJob) + sizeof(float) * 12) * (size_t)m, err))) return rc;
+    if ((rc = pinned(ctl, sizeof(EvalPlaneOut) * (size_t)m, err))) return rc;
+    for (int c = 0; c < m; ++c) {
+        IcpWorkspace *ws = wss[c];
+        if ((rc = ensure(ws, B_WORK, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
+        if ((rc = ensure(ws, B_NNI, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
+        if ((rc = ensure(ws, B_NND, sizeof(float) * (size_t)(n_src + 1), err))) return rc;
+        if ((rc = ensure(ws, B_PART, sizeof(double) * kPlaneRec * kEvalBlocks, err))) return rc;
+        if ((rc = ensure(ws, B_TORD, sizeof(float4) * (size_t)(n_tgts[c] + 1), err))) return rc;
+    }
+    if ((rc = grid_build_batch(wss, m, ctl, stream, d_tgts, n_tgts, stride, true, &dj, &max_n, err))) return rc;
+    std::vector<IcpProblem> hp((size_t)m);
+    std::vector<EvalPlaneJob> hj((size_t)m);
+    std::vector<OrderJob> ho((size_t)m);
+    for (int c = 0; c < m; ++c) {
+        IcpWorkspace *ws = wss[c];
+        IcpProblem &p = hp[(size_t)c];
+        std::memset(&p, 0, sizeof(p));
+        p.work = static_cast<float4 *>(ws->buf[B_WORK]); p.st = (IcpState *)ws->buf[B_STATE]; p.cell_start = (const int *)ws->buf[B_CSTART];
+        p.sorted = (const float4 *)ws->buf[B_TORD]; p.nni = (int *)ws->buf[B_NNI]; p.nnd = (float *)ws->buf[B_NND];    // the grid's points, every cell in index order
+        p.tgt = static_cast<const unsigned char *>(d_tgts[c]); p.n_tgt = n_tgts[c]; p.normals = (const float4 *)ws->buf[B_NORM];
+        ho[(size_t)c] = OrderJob{p.st, p.cell_start, (const float4 *)ws->buf[B_TSORT], (float4 *)ws->buf[B_TORD], n_tgts[c]};
+        EvalPlaneJob &j = hj[(size_t)c];
+        j.tgt = p.tgt; j.nni = p.nni; j.nnd = p.nnd; j.work = p.work; j.normals = p.normals; j.part = (double *)ws->buf[B_PART];
+    }
+    EvalPlaneJob *djobs = static_cast<EvalPlaneJob *>(ctl->buf[B_PAIR]);
+    EvalPlaneOut *dout = reinterpret_cast<EvalPlaneOut *>(djobs + m);
+    OrderJob *dord = reinterpret_cast<OrderJob *>(dout + m);
+    float *dt = reinterpret_cast<float *>(dord + m);
+    const IcpProblem *dp = static_cast<const IcpProblem *>(ctl->buf[B_MASK]);
+    ICP_HIP(hipMemcpyAsync(ctl->buf[B_MASK], hp.data(), sizeof(IcpProblem) * (size_t)m, hipMemcpyHostToDevice, stream));   // (pageable: staged before the call returns)
+    ICP_HIP(hipMemcpyAsync(djobs, hj.data(), sizeof(EvalPlaneJob) * (size_t)m, hipMemcpyHostToDevice, stream));
+    ICP_HIP(hipMemcpyAsync(dord, ho.data(), sizeof(OrderJob) * (size_t)m, hipMemcpyHostToDevice, stream));
+    ICP_HIP(hipMemcpyAsync(dt, transforms, sizeof(float) * 12 * (size_t)m, hipMemcpyHostToDevice, stream));
+    const int pb = (n_src + 255) / 256;
+    hipLaunchKernelGGL(guess_move_batch_kernel, dim3(pb, m), dim3(256), 0, stream, dp, static_cast<const unsigned char *>(d_src), n_src, stride, (const float *)dt);
+    hipLaunchKernelGGL(grid_cell_order_batch_kernel, dim3((unsigned)((max_n + 255) / 256), m), dim3(256), 0, stream, (const OrderJob *)dord);
+    hipLaunchKernelGGL(normals_problems_kernel, dim3((unsigned)(((size_t)max_n * kNormGroup + kNormBlock - 1) / kNormBlock), m), dim3(kNormBlock), 0, stream,
+                       dp, normal_radius);
+    hipLaunchKernelGGL(nn_search_batch_kernel<kNnGroup>, dim3((unsigned)(((long long)n_src * kNnGroup + 255) / 256), m), dim3(256), 0, stream,
+                       dp, n_src, 0, -1, stride, 0);                                               // cold
+    hipLaunchKernelGGL(eval_plane_reduce_batch_kernel, dim3(eb, m), dim3(256), 0, stream, (const EvalPlaneJob *)djobs, stride, n_src, maxd2);
+    hipLaunchKernelGGL(eval_plane_finish_batch_kernel, dim3(m), dim3(64), 0, stream, (const EvalPlaneJob *)djobs, eb, dout);
+    ICP_HIP(hipGetLastError());
+    EvalPlaneOut *h = static_cast<EvalPlaneOut *>(ctl->pinned);
+    ICP_HIP(hipMemcpyAsync(h, dout, sizeof(EvalPlaneOut) * (size_t)m, hipMemcpyDeviceToHost, stream));
+    ICP_HIP(hipStreamSynchronize(stream));
+    for (int c = 0; c < m; ++c) {
+        n_valid[c] = h[c].n_valid; n_inliers[c] = h[c].n_inl; n_planar[c] = h[c].n_planar;
+        std::memcpy(sums + (size_t)kNEvalPlane * c, h[c].s, sizeof(double) * kNEvalPlane);
+    }
+    return SCL_OK;
+}
+
+// The normals the point-to-plane estimator uses for one cloud (host, n_tgt >= 1 points) and radius: the cloud staged in B_TGT, the
+// single path's grid (build_grid), its cells put in order (grid_cell_order_kernel) and normals_kernel -- normals_body, as
+// normals_problems_kernel runs it -- then the x, y, z of every float4 to normals (n_tgt x 3, host), which is written only after everything has succeeded.
+int icp_target_normals(IcpWorkspace *ws, hipStream_t stream, const void *tgt, int n_tgt, int stride, double radius, float *normals, std::string *err)
+{
+    int rc = check_cloud_args(0, n_tgt, stride, err);
+    if (rc) return rc;
+    if (!(radius > 0.0)) { if (err) *err = "normal_radius must be > 0"; return SCL_ERR_INVALID_ARG; }
+    if (n_tgt == 0) return SCL_OK;
+    ws->ext_tgt = nullptr;
+    if ((rc = upload(ws, B_TGT, tgt, (size_t)n_tgt * stride, stream, err))) return rc;
+    ws->n_tgt = n_tgt;
+    if ((rc = build_grid(ws, stream, n_tgt, stride, err))) return rc;
+    if ((rc = ensure(ws, B_NORM, sizeof(float4) * (size_t)(n_tgt + 1), err))) return rc;
+    if ((rc = ensure(ws, B_TORD, sizeof(float4) * (size_t)(n_tgt + 1), err))) return rc;
+    hipLaunchKernelGGL(grid_cell_order_kernel, dim3((unsigned)((n_tgt + 255) / 256)), dim3(256), 0, stream,
+                       OrderJob{(const IcpState *)ws->buf[B_STATE], (const int *)ws->buf[B_CSTART], (const float4 *)ws->buf[B_TSORT],
+                                (float4 *)ws->buf[B_TORD], n_tgt});
+    hipLaunchKernelGGL(normals_kernel, dim3((unsigned)(((size_t)n_tgt * kNormGroup + kNormBlock - 1) / kNormBlock)), dim3(kNormBlock), 0, stream,
+                       (const unsigned char *)ws->buf[B_TGT], n_tgt, stride, (const IcpState *)ws->buf[B_STATE],
+                       (const int *)ws->buf[B_CSTART], (const float4 *)ws->buf[B_TORD], radius, (float4 *)ws->buf[B_NORM]);
+    ICP_HIP(hipGetLastError());
+    std::vector<float4> h((size_t)n_tgt);
+    ICP_HIP(hipMemcpyAsync(h.data(), ws->buf[B_NORM], sizeof(float4) * (size_t)n_tgt, hipMemcpyDeviceToHost, stream));
+    ICP_HIP(hipStreamSynchronize(stream));
+    for (int i = 0; i < n_tgt; ++i) { normals[3 * (size_t)i] = h[(size_t)i].x; normals[3 * (size_t)i + 1] = h[(size_t)i].y; normals[3 * (size_t)i + 2] = h[(size_t)i].z; }
     return SCL_OK;
 }
 

@@ -10,8 +10,8 @@
 namespace scl {
 
 struct IcpWorkspace {
-    void *buf[24] = {nullptr};
-    size_t cap[24] = {0};
+    void *buf[26] = {nullptr};
+    size_t cap[26] = {0};
     void *pinned = nullptr;
     size_t pinned_cap = 0;
     const void *ext_tgt = nullptr;             // the alignment's target when it is read in place (icp_batch_prepare_all) instead of staged in the workspace
@@ -93,6 +93,16 @@ int icp_geometric_verification_batch(IcpWorkspace *const *wss, int m, IcpWorkspa
 int icp_registration_eval_batch(IcpWorkspace *const *wss, int m, IcpWorkspace *ctl, hipStream_t stream, const void *d_src, int n_src,
                                 const void *const *d_tgts, const int *n_tgts, int stride, const float *transforms, float maxd2,
                                 int *n_valid, int *n_inliers, double *moments, std::string *err);
+// the same against planes: n_planar[c] = the inliers whose matched target point has a normal (normals_problems_kernel at
+// normal_radius), sums + 29 * c = the upper triangle of sum J^T J for J = (p x n, n) (21), sum J r for r = (q - p) . n (6), sum r r and
+// the sum of nn_dist2 over all inliers (icp_registration_eval_batch's moments[9], bit for bit); no output may be nullptr
+int icp_registration_eval_plane_batch(IcpWorkspace *const *wss, int m, IcpWorkspace *ctl, hipStream_t stream, const void *d_src, int n_src,
+                                      const void *const *d_tgts, const int *n_tgts, int stride, const float *transforms, float maxd2,
+                                      double normal_radius, int *n_valid, int *n_inliers, int *n_planar, double *sums, std::string *err);
+// the normals of one host cloud as the point-to-plane estimator forms them at this radius (n_tgt x 3 floats; (0, 0, 0): fewer than
+// three neighbours); normals is written only on success
+int icp_target_normals(IcpWorkspace *ws, hipStream_t stream, const void *tgt, int n_tgt, int stride_bytes, double radius, float *normals,
+                       std::string *err);
 // where icp_stage_cloud / icp_stage_cloud_host left a cloud
 const void *icp_staged_cloud(const IcpWorkspace *ws, bool target);
 

@@ -150,6 +150,13 @@ def _bind(lib):
         "scl_loop_eval_batch_from_store": (c_int, [P, c_int, c_int, fp, c_int, ip, c_int, fp, c_float, fp, c_int, c_int, c_double,
                                                    ip, ip, dp, ip, ip]),
         "scl_registration_information": (c_int, [c_int, dp, dp]),
+        "scl_target_normals": (c_int, [P, P, c_int, c_int, c_double, fp]),
+        "scl_registration_eval_plane_batch": (c_int, [P, P, c_int, POINTER(c_void_p), ip, c_int, c_int, fp, c_double, c_double, ip, ip, ip, dp]),
+        "scl_registration_eval_plane_batch_from_store": (c_int, [P, P, c_int, c_int, c_float, c_int, c_int, ip, c_int, fp, c_float, fp, c_int, c_int,
+                                                                 c_double, c_double, ip, ip, ip, dp, ip, ip]),
+        "scl_loop_eval_plane_batch_from_store": (c_int, [P, c_int, c_int, fp, c_int, ip, c_int, fp, c_float, fp, c_int, c_int, c_double, c_double,
+                                                         ip, ip, ip, dp, ip, ip]),
+        "scl_registration_information_plane": (c_int, [dp, dp, dp]),
         "scl_profile_enable": (c_int, [P, c_int]),
         "scl_profile_reset": (c_int, [P]),
         "scl_profile_get": (c_int, [P, POINTER(SclProfile)]),
@@ -218,6 +225,32 @@ class RegistrationEval:
     def information(self, c):
         """the 6 x 6 information matrix of candidate c's pairs, rotation first (scl_registration_information)"""
         return ScanContextEngine.registration_information(int(self.n_inliers[c]), self.moments[c])
+
+
+class RegistrationPlaneEval:
+    """What registration_eval_plane_batch and its store forms answer for m candidates: n_src (after the filter in the store forms),
+    n_valid[m], n_inliers[m], n_planar[m] (the inliers whose matched target point has a normal), sums[m,29] (the upper triangle of
+    sum J^T J for J = [p x n | n], rotation first; sum J r for r = (q - p) . n; sum r r; the sum of the squared distances of ALL
+    inliers) and, from the store forms, n_tgts[m]."""
+
+    def __init__(self, n_src, n_valid, n_inliers, n_planar, sums, n_tgts=None):
+        self.n_src, self.n_valid, self.n_inliers, self.n_planar, self.sums, self.n_tgts = n_src, n_valid, n_inliers, n_planar, sums, n_tgts
+
+    def __len__(self):
+        return len(self.n_inliers)
+
+    def information(self, c):
+        """the 6 x 6 point-to-plane information matrix sum J^T J of candidate c's pairs, rotation first"""
+        return ScanContextEngine.registration_information_plane(self.sums[c])[0]
+
+    def gradient(self, c):
+        """sum J r of candidate c's pairs: the right-hand side of the point-to-plane normal equations at T_c"""
+        return ScanContextEngine.registration_information_plane(self.sums[c])[1]
+
+    def rmse_plane(self, c):
+        """sqrt(sum r r / n_planar): the root mean square point-to-plane distance of candidate c, NaN without a planar inlier"""
+        m = int(self.n_planar[c])
+        return float(np.sqrt(self.sums[c, 27] / m)) if m > 0 else float("nan")
 
 
 class ScanContextEngine:
@@ -1041,6 +1074,74 @@ class ScanContextEngine:
         if rc != 0:
             raise SclError(rc, "scl_registration_information")
         return info.reshape(6, 6)
+
+    def target_normals(self, tgt, radius):
+        """the normals the point-to-plane estimator uses for this cloud and radius, (n,3) float32 ((0, 0, 0): fewer than three
+        neighbours within the radius)"""
+        a, n, stride = _cloud(tgt)
+        out = np.zeros((max(n, 1), 3), np.float32)
+        self._check(self._lib.scl_target_normals(self._h, a.ctypes.data_as(c_void_p), n, stride, radius, _ptr(out, c_float)), "scl_target_normals")
+        return out[:n]
+
+    def registration_eval_plane_batch(self, src, tgts, transforms, max_dist, normal_radius):
+        """registration_eval_batch against the planes of the targets (normals at normal_radius); returns a RegistrationPlaneEval
+        (information(c), gradient(c), rmse_plane(c))"""
+        s, ns, stride = _cloud(src)
+        arrs, ptrs, counts, m, stride_t = self._cloud_list(tgts)
+        if m and stride != stride_t:
+            raise ValueError("source and targets must share a record layout")
+        Tm = _f32(np.asarray(transforms)).reshape(m, 16)
+        k = max(m, 1)
+        nv = np.zeros(k, np.int32); ni = np.zeros(k, np.int32); npl = np.zeros(k, np.int32); su = np.zeros((k, 29), np.float64)
+        self._check(self._lib.scl_registration_eval_plane_batch(self._h, s.ctypes.data_as(c_void_p), ns, ptrs, _ptr(counts, c_int), m, stride,
+                                                                _ptr(Tm, c_float), max_dist, normal_radius, _ptr(nv, c_int), _ptr(ni, c_int),
+                                                                _ptr(npl, c_int), _ptr(su, c_double)),
+                    "scl_registration_eval_plane_batch")
+        return RegistrationPlaneEval(ns, nv[:m], ni[:m], npl[:m], su[:m])
+
+    def registration_eval_plane_batch_from_store(self, src, src_leaf, robot, keys_pre, search_num, poses_pre, leaf, transforms, max_dist,
+                                                 normal_radius, min_src_points=300, min_tgt_points=1000):
+        """registration_eval_plane_batch with the layout and gates of registration_eval_batch_from_store"""
+        a, n, stride = _cloud(src)
+        keys = np.ascontiguousarray(keys_pre, dtype=np.int32); m = keys.size
+        Tp = _f32(np.asarray(poses_pre)).reshape(m, 2 * search_num + 1, 16)
+        Tm = _f32(np.asarray(transforms)).reshape(m, 16)
+        k = max(m, 1)
+        nv = np.zeros(k, np.int32); ni = np.zeros(k, np.int32); npl = np.zeros(k, np.int32); su = np.zeros((k, 29), np.float64)
+        ns = c_int(); nt = np.zeros(k, np.int32)
+        self._check(self._lib.scl_registration_eval_plane_batch_from_store(
+            self._h, a.ctypes.data_as(c_void_p), n, stride, src_leaf, robot, m, _ptr(keys, c_int), search_num, _ptr(Tp, c_float), leaf,
+            _ptr(Tm, c_float), min_src_points, min_tgt_points, max_dist, normal_radius, _ptr(nv, c_int), _ptr(ni, c_int), _ptr(npl, c_int),
+            _ptr(su, c_double), byref(ns), _ptr(nt, c_int)), "scl_registration_eval_plane_batch_from_store")
+        return RegistrationPlaneEval(ns.value, nv[:m], ni[:m], npl[:m], su[:m], nt[:m])
+
+    def loop_eval_plane_batch_from_store(self, robot, key_cur, pose_cur, keys_pre, search_num, poses_pre, leaf, transforms, max_dist,
+                                         normal_radius, min_src_points=300, min_tgt_points=1000):
+        """registration_eval_plane_batch with the layout and gates of loop_eval_batch_from_store"""
+        keys = np.ascontiguousarray(keys_pre, dtype=np.int32); m = keys.size
+        Tc = _f32(np.asarray(pose_cur)).reshape(16)
+        Tp = _f32(np.asarray(poses_pre)).reshape(m, 2 * search_num + 1, 16)
+        Tm = _f32(np.asarray(transforms)).reshape(m, 16)
+        k = max(m, 1)
+        nv = np.zeros(k, np.int32); ni = np.zeros(k, np.int32); npl = np.zeros(k, np.int32); su = np.zeros((k, 29), np.float64)
+        ns = c_int(); nt = np.zeros(k, np.int32)
+        self._check(self._lib.scl_loop_eval_plane_batch_from_store(
+            self._h, robot, key_cur, _ptr(Tc, c_float), m, _ptr(keys, c_int), search_num, _ptr(Tp, c_float), leaf, _ptr(Tm, c_float),
+            min_src_points, min_tgt_points, max_dist, normal_radius, _ptr(nv, c_int), _ptr(ni, c_int), _ptr(npl, c_int), _ptr(su, c_double),
+            byref(ns), _ptr(nt, c_int)), "scl_loop_eval_plane_batch_from_store")
+        return RegistrationPlaneEval(ns.value, nv[:m], ni[:m], npl[:m], su[:m], nt[:m])
+
+    @staticmethod
+    def registration_information_plane(sums):
+        """(info[6,6], grad[6]) of a candidate's 29 plane sums: the symmetric sum J^T J, rotation first, and sum J r
+        (scl_registration_information_plane); needs no engine"""
+        lib = load_library(); _bind(lib)
+        su = np.ascontiguousarray(sums, dtype=np.float64).reshape(29)
+        info = np.empty(36, np.float64); grad = np.empty(6, np.float64)
+        rc = lib.scl_registration_information_plane(_ptr(su, c_double), _ptr(info, c_double), _ptr(grad, c_double))
+        if rc != 0:
+            raise SclError(rc, "scl_registration_information_plane")
+        return info.reshape(6, 6), grad
 
     @staticmethod
     def loop_guess_from_shift(shift, num_sector, pose_cur, pose_pre):
