@@ -309,7 +309,11 @@ int  scl_detect_full_submit(scl_engine *e, int query, int lo, int hi, int *ticke
 int  scl_detect_full_submit_many(scl_engine *e, const int *queries, const int *lo, const int *hi, int n_queries, int *tickets);
 /* A backlog of n_queries scans in one call: the submit / collect pipeline of the two calls above run natively
  * (scans_per_launch queries per kernel launch, launches_in_flight launches enqueued ahead), results in
- * submission order.  Blocks until the last scan is done; no other pass may be in flight. */
+ * submission order.  Blocks until the last scan is done; no other pass may be in flight.
+ * scans_per_launch is the size of a launch GROUP (the unit of alignment, finishing and buffer sets), not a promise of
+ * one pass over the database per group: on the 64x120 grid two consecutive full groups (16 scans each) of a chunk may
+ * share one pass -- one products launch with two scan sets -- with results bit-identical to separate launches
+ * (SCL_SCREEN_PAIR=0 keeps every group's pass to itself). */
 int  scl_detect_full_stream(scl_engine *e, const int *queries, const int *lo, const int *hi, int n_queries,
                             int scans_per_launch, int launches_in_flight, int *nn_idx, int *shift, double *dist);
 int  scl_detect_full_collect(scl_engine *e, int ticket, int *nn_idx, int *shift, double *dist);

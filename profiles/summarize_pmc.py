@@ -1,6 +1,8 @@
 """Condense rocprofv3 --pmc counter_collection CSVs into a small per-kernel summary.
 
 usage: python profiles/summarize_pmc.py <dir with pN/runc/*_counter_collection.csv ...> <out.json> [kernel substring[,kernel substring...]]
+A filter that holds a ';' is split there instead of at ',': template arguments tell instances apart -- the products' two-set
+instance is "sc_screen2_kernel<16, 120, 13, 2>", the one-set instance "sc_screen2_kernel<16, 120, 13, 1>" (blanks are ignored).
 HBM traffic follows MI355X_MICROARCH.md §HBM: FETCH_SIZE (KB) counts 64 B per 128-B request of a wide
 coalesced stream on gfx950 -> doubled; WRITE_SIZE (KB) is exact for 16-B-per-lane stores.  Separate
 passes per counter group, no tracing domains combined with --pmc.
@@ -16,7 +18,7 @@ def summarize(root, needle):
     agg = collections.defaultdict(list)
     for f in glob.glob(f"{root}/**/*_counter_collection.csv", recursive=True):
         for row in csv.DictReader(open(f)):
-            if needle in row["Kernel_Name"]:
+            if needle.replace(" ", "") in row["Kernel_Name"].replace(" ", ""):
                 agg[row["Counter_Name"]].append(float(row["Counter_Value"]))
     summary = {k: {"launches": len(v), "mean_per_launch": sum(v) / len(v)} for k, v in sorted(agg.items())}
     res = {"kernel_filter": needle, "counters": summary}
@@ -31,7 +33,8 @@ def summarize(root, needle):
 
 def main():
     root, out = sys.argv[1], sys.argv[2]
-    needles = (sys.argv[3] if len(sys.argv) > 3 else "sc_distance").split(",")
+    needles = sys.argv[3] if len(sys.argv) > 3 else "sc_distance"
+    needles = [n for n in needles.split(";" if ";" in needles else ",") if n]
     if len(needles) == 1:
         res = summarize(root, needles[0])
     else:       # a launch group of several kernels (one launch of each per group): per kernel, and the HBM bytes summed

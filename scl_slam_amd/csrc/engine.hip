@@ -525,13 +525,13 @@ static void log_env_overrides_once()
 {
     static std::atomic<bool> done{false};
     if (done.exchange(true)) return;
-    static const char *const names[] = {"SCL_SCREEN", "SCL_SCREEN_FORM", "SCL_SCREEN_V2_MIN", "SCL_RCCL_LIB",
+    static const char *const names[] = {"SCL_SCREEN", "SCL_SCREEN_FORM", "SCL_SCREEN_V2_MIN", "SCL_SCREEN_PAIR", "SCL_RCCL_LIB",
                                         // experiments: read by a diagnostics build only (kernels.hpp: scl_lab_int)
                                         "SCL_SCREEN_VARIANT", "SCL_SCREEN_PROBE", "SCL_SCREEN_TAIL", "SCL_ALIGN_WGS",
                                         "SCL_ALIGN2_WGS", "SCL_ALIGN_FILTER", "SCL_SC_KERNEL", "SCL_SC_WAVES", "SCL_STAMP", "SCL_ABLATE",
                                         "SCL_ICP_REDUCE", "SCL_MATRIX_PLAIN", "SCL_MATRIX_KERNEL", "SCL_MATRIX_KR", "SCL_WIDE_EXACT", "SCL_STREAM_EXACT", "SCL_SMALL_EXACT_OFF",
                                         "SCL_SELF_ALIGN_OFF", "SCL_CAND_EXACT_OFF"};
-    constexpr int kProduct = 4;
+    constexpr int kProduct = 5;
     int i = 0;
     for (const char *n : names) {
         const char *v = getenv(n);
@@ -1392,27 +1392,29 @@ int submit_full_many_locked(scl_engine *e, const int *queries, const int *los, c
 struct ScreenGroup { const int *qslot, *lo, *n; int nq, set0; int part_half = 0; bool masks = false; bool keys_later = false; };   // part_half: which half of d_part holds the batch's partial sums;
                                                                                                              // masks: the batch's exact pass evaluates the open shifts only (the shift masks are formed and written)
                                                                                                              // keys_later: ScreenBatch::no_ring_metric
+void fill_screen_batch(scl_engine *e, ScreenBatch &sb, const ScreenGroup &g)
+{
+    sb.nq = g.nq;
+    for (int j = 0; j < g.nq; ++j) { sb.slot[j] = g.qslot[j]; sb.base[j] = g.lo[j]; sb.n[j] = g.n[j]; sb.buf[j] = g.set0 + j; }
+    sb.pair_stride = e->set_stride;
+    sb.approx = e->d_approx; sb.starts = e->d_starts; sb.align_fallbacks = e->d_align_fallbacks; sb.ring_d2 = e->d_ring_d2;
+    sb.survivors = nullptr; sb.n_surv = nullptr; sb.t_min = e->d_tmin;
+    sb.smask = (g.masks || sc_screen_is_wide(db_view(e), e->SR)) ? e->d_smask : nullptr;   // (the 64 x 120 stream's exact pass scores all 13 shifts of its few survivors: no masks)
+    sb.part = e->d_part + (g.part_half ? e->part_cap / 2 : 0);
+    sb.no_ring_metric = g.keys_later;
+    sb.k = e->cfg.num_candidates; sb.exclude_eps = e->cfg.knn_exclude_eps; sb.topk_idx = e->d_topk_idx; sb.topk_d2 = e->d_topk_d2;
+}
+
 // next (optional, nq > 0): the launch that will follow; its alignment rides in this one (the next call then passes
 // kScreenProducts only).
 int launch_screen_group(scl_engine *e, const ScreenGroup &cur, int phases = kScreenAlign | kScreenProducts,
                         const ScreenGroup *next = nullptr, hipStream_t stream = nullptr)
 {
     if (!stream) stream = e->stream;
-    auto fill = [&](ScreenBatch &sb, const ScreenGroup &g) {
-        sb.nq = g.nq;
-        for (int j = 0; j < g.nq; ++j) { sb.slot[j] = g.qslot[j]; sb.base[j] = g.lo[j]; sb.n[j] = g.n[j]; sb.buf[j] = g.set0 + j; }
-        sb.pair_stride = e->set_stride;
-        sb.approx = e->d_approx; sb.starts = e->d_starts; sb.align_fallbacks = e->d_align_fallbacks; sb.ring_d2 = e->d_ring_d2;
-        sb.survivors = nullptr; sb.n_surv = nullptr; sb.t_min = e->d_tmin;
-        sb.smask = (g.masks || sc_screen_is_wide(db_view(e), e->SR)) ? e->d_smask : nullptr;   // (the 64 x 120 stream's exact pass scores all 13 shifts of its few survivors: no masks)
-        sb.part = e->d_part + (g.part_half ? e->part_cap / 2 : 0);
-        sb.no_ring_metric = g.keys_later;
-        sb.k = e->cfg.num_candidates; sb.exclude_eps = e->cfg.knn_exclude_eps; sb.topk_idx = e->d_topk_idx; sb.topk_d2 = e->d_topk_d2;
-    };
     ScreenBatch sb{}, nx{};
-    fill(sb, cur);
+    fill_screen_batch(e, sb, cur);
     const bool has_next = next && next->nq > 0;
-    if (has_next) fill(nx, *next);
+    if (has_next) fill_screen_batch(e, nx, *next);
     if (phases & kScreenAlign) for (int j = 0; j < cur.nq; ++j) e->align_pairs += (uint64_t)cur.n[j];
     if (has_next) for (int j = 0; j < next->nq; ++j) e->align_pairs += (uint64_t)next->n[j];
     if ((phases & kScreenAlign) && (phases & kScreenProducts) && has_next) {   // a sequence's first launch: its own alignment outside the
@@ -1422,6 +1424,31 @@ int launch_screen_group(scl_engine *e, const ScreenGroup &cur, int phases = kScr
     ProfScope ps(e, P_SC, stream);
     SCL_HIP(e, launch_sc_screen_batch(db_view(e), sb, e->SR, sc_align_filter_enabled(), e->num_cu, stream, phases, has_next ? &nx : nullptr));
     if (ps.active()) { for (int j = 0; j < cur.nq; ++j) e->prof.sc_distance_pairs += (uint64_t)cur.n[j]; }
+    return SCL_OK;
+}
+
+// Two consecutive full launch groups of the stream form as ONE products launch (sc_screen.hip: two scan sets share the pass over the
+// database), each with its own tail.  g0 / g1 use the two halves of d_part.  align0 / align1: the group aligns for itself (no tail did it);
+// next0 / next1 (optional, nq > 0): the groups whose alignment rides in the tails of g0 / g1.  One entry of the profile.
+int launch_screen_pair_group(scl_engine *e, ScreenGroup g0, ScreenGroup g1, bool align0, bool align1, const ScreenGroup *next0, const ScreenGroup *next1)
+{
+    hipStream_t stream = e->stream;
+    g0.part_half = 0; g1.part_half = 1;
+    ScreenBatch sb0{}, sb1{}, nx0{}, nx1{};
+    fill_screen_batch(e, sb0, g0);
+    fill_screen_batch(e, sb1, g1);
+    const bool has0 = next0 && next0->nq > 0, has1 = next1 && next1->nq > 0;
+    if (has0) fill_screen_batch(e, nx0, *next0);
+    if (has1) fill_screen_batch(e, nx1, *next1);
+    const ScreenGroup *counted[4] = {align0 ? &g0 : nullptr, align1 ? &g1 : nullptr, has0 ? next0 : nullptr, has1 ? next1 : nullptr};
+    for (const ScreenGroup *g : counted)
+        if (g) for (int j = 0; j < g->nq; ++j) e->align_pairs += (uint64_t)g->n[j];
+    // (a sequence's first pair, or a pair behind a single group: the alignment of its own outside the event pair)
+    if (align0) SCL_HIP(e, launch_sc_screen_batch(db_view(e), sb0, e->SR, sc_align_filter_enabled(), e->num_cu, stream, kScreenAlign, nullptr));
+    if (align1) SCL_HIP(e, launch_sc_screen_batch(db_view(e), sb1, e->SR, sc_align_filter_enabled(), e->num_cu, stream, kScreenAlign, nullptr));
+    ProfScope ps(e, P_SC, stream);
+    SCL_HIP(e, launch_sc_screen_pair(db_view(e), sb0, sb1, e->SR, sc_align_filter_enabled(), e->num_cu, stream, has0 ? &nx0 : nullptr, has1 ? &nx1 : nullptr));
+    if (ps.active()) { for (int j = 0; j < g0.nq; ++j) e->prof.sc_distance_pairs += (uint64_t)g0.n[j] + (uint64_t)g1.n[j]; }
     return SCL_OK;
 }
 
@@ -1868,13 +1895,14 @@ int stream_screened_locked(scl_engine *e, std::unique_lock<std::mutex> &db, cons
     const int chmax = wide && CH > SCL_WIDE_CHUNK ? SCL_WIDE_CHUNK : CH;
     const int chn = spl >= 1 && spl <= chmax ? (chmax / spl) * spl : chmax;
     struct List { int qslot[CH], qlo[CH], qn[CH], pos[CH], m = 0; };     // the scans of a chunk that have something to score
-    struct Chunk { int first = 0, count = 0; bool busy = false, aligned = false, small = false; std::vector<int> lo, empty; };
+    struct Chunk { int first = 0, count = 0; int aligned = 0; bool busy = false, small = false; std::vector<int> lo, empty; };   // aligned: leading scans of its list that the chunk before aligned
     Chunk ch[2];
     bool sub0_valid[2] = {false, false};                    // ev_sub0[c] was recorded by the exact pass that ev_chunk[c] ends
     // 64 x 120: the chunk's exact pass by one workgroup per scan (SCL_STREAM_EXACT=survivors keeps round 3's kernel, which also forms the
     // ring-key metric of its ranges -- keys_later)
     const bool small_exact = sc_small_exact_supported(db_view(e), e->SR) && (!wide || e->d_smask) && !scl_lab_is("SCL_STREAM_EXACT", "s");
     const bool keys_later = !wide && !small_exact;
+    const bool pairs = !wide && sc_screen_pairs(db_view(e), e->SR);   // two consecutive full launch groups share one products launch (SCL_SCREEN_PAIR=0: never)
     int nmax = 1;
     for (int i = 0; i < n_queries; ++i) {
         const int l = lo[i] < 0 ? 0 : lo[i], h = hi[i] > n0 ? n0 : hi[i];
@@ -1915,7 +1943,9 @@ int stream_screened_locked(scl_engine *e, std::unique_lock<std::mutex> &db, cons
         const int set0 = c * CH, nset0 = (c ^ 1) * CH;
         // Every launch carries the alignment of the launch behind it -- the chunk's last one that of the next chunk's first
         // launch, whose buffer sets the exact pass of the chunk before this one may still be reading: the main stream waits
-        // for it there (it finished long ago).  Only the very first launch aligns for itself.
+        // for it there (it finished long ago).  Only the very first launch aligns for itself.  (Pairs of full groups, below: a pair
+        // carries the alignment of the TWO groups behind it, the chunk's last pair that of the next chunk's first pair; the wait is for
+        // the event behind that chunk's whole exact pass, so it covers the buffer sets of both groups.)
         // the exact pass's argument sets go to the device now, ahead of the products it has to wait for
         // one workgroup per scan scores its survivors at every shift: right for the handful a scan leaves as a rule; dozens per scan (what
         // the chunks collected last reported) go to the survivors' kernel
@@ -1946,29 +1976,51 @@ int stream_screened_locked(scl_engine *e, std::unique_lock<std::mutex> &db, cons
             for (int j = 0; j < cur.m; ++j) e->prof.sc_distance_pairs += (uint64_t)cur.qn[j];
             span_start = nullptr;
         };
-        bool next_aligned = false;
-        for (int g = 0; g < cur.m; g += spl) {
-            const int w = cur.m - g < spl ? cur.m - g : spl;
-            ScreenGroup grp{cur.qslot + g, cur.qlo + g, cur.qn + g, w, set0 + g};
-            grp.keys_later = keys_later;
-            ScreenGroup nx{nullptr, nullptr, nullptr, 0, 0};
-            if (g + w < cur.m) {
-                const int wn = cur.m - g - w < spl ? cur.m - g - w : spl;
-                nx = ScreenGroup{cur.qslot + g + w, cur.qlo + g + w, cur.qn + g + w, wn, set0 + g + w};
-                nx.keys_later = keys_later;
-            } else if (ncount > 0 && nxt.m > 0) {
-                const int wn = nxt.m < spl ? nxt.m : spl;
-                nx = ScreenGroup{nxt.qslot, nxt.qlo, nxt.qn, wn, nset0};
-                nx.keys_later = keys_later;
+        // The launch group at scan offset `off` of this chunk's list -- or, past its end, of the next chunk's (nq = 0: there is none)
+        auto group_at = [&](int off) {
+            ScreenGroup g{nullptr, nullptr, nullptr, 0, 0};
+            if (off < cur.m) {
+                g = ScreenGroup{cur.qslot + off, cur.qlo + off, cur.qn + off, cur.m - off < spl ? cur.m - off : spl, set0 + off};
+            } else if (ncount > 0 && off - cur.m < nxt.m) {
+                const int o = off - cur.m;
+                g = ScreenGroup{nxt.qslot + o, nxt.qlo + o, nxt.qn + o, nxt.m - o < spl ? nxt.m - o : spl, nset0 + o};
+            }
+            g.keys_later = keys_later;
+            return g;
+        };
+        // Two consecutive FULL groups go as a pair: one products launch for both (sc_screen.hip: the database crosses the fabric once for
+        // 32 scans), a tail each.  A pair's tails carry the alignment of the pair behind it -- two groups ahead instead of one --, the
+        // last pair of a chunk that of the next chunk's first two groups; whatever follows a pair and is no pair (a ragged or odd last
+        // group) is aligned by the first tail, as a single group aligns the group behind it.
+        auto pair_at = [&](int off) { return pairs && group_at(off).nq == kMaxScreenBatch && group_at(off + kMaxScreenBatch).nq == kMaxScreenBatch &&
+                                             (off + 2 * kMaxScreenBatch <= cur.m || off >= cur.m); };   // (both in ONE chunk)
+        int aligned_to = k.aligned;                          // scans [0, aligned_to) of this chunk's list have their first shifts (or will have, in stream order)
+        for (int g = 0; g < cur.m;) {
+            const bool pair = pair_at(g);
+            const ScreenGroup g0 = group_at(g), g1 = pair ? group_at(g + g0.nq) : ScreenGroup{nullptr, nullptr, nullptr, 0, 0};
+            const int end = g + g0.nq + g1.nq;
+            // what the tails align: the group(s) behind this unit, unless a tail before did
+            ScreenGroup n0{nullptr, nullptr, nullptr, 0, 0}, n1 = n0;
+            if (end >= aligned_to) {
+                n0 = group_at(end);
+                if (pair && pair_at(end)) n1 = group_at(end + n0.nq);
+            }
+            const int reach = end + n0.nq + n1.nq;
+            if (reach > cur.m && n0.nq > 0) {
+                // the next chunk's first buffer sets, which the exact pass of the chunk before this one may still be reading
                 // (80 x 180: the exact pass of a chunk is several launch groups, one per kWideExactBatch buffer sets, and nearly as
                 //  long as the next chunk's screening: this launch's alignment writes the first group's sets only and waits for those)
-                if (ch[c ^ 1].busy) SCL_HIP(e, hipStreamWaitEvent(e->stream, (wide && sub0_valid[c ^ 1] && wn <= kWideExactBatch) ? e->ev_sub0[c ^ 1] : e->ev_chunk[c ^ 1], 0));
-                next_aligned = true;
+                if (ch[c ^ 1].busy) SCL_HIP(e, hipStreamWaitEvent(e->stream, (wide && sub0_valid[c ^ 1] && reach - cur.m <= kWideExactBatch) ? e->ev_sub0[c ^ 1] : e->ev_chunk[c ^ 1], 0));
             }
-            const int phases = (g == 0 && !k.aligned) ? (kScreenAlign | kScreenProducts) : kScreenProducts;
-            if ((rc = launch_screen_group(e, grp, phases, nx.nq > 0 ? &nx : nullptr))) return rc;
+            const bool align0 = g >= aligned_to, align1 = pair && g + g0.nq >= aligned_to;
+            if (pair) rc = launch_screen_pair_group(e, g0, g1, align0, align1, n0.nq > 0 ? &n0 : nullptr, n1.nq > 0 ? &n1 : nullptr);
+            else rc = launch_screen_group(e, g0, align0 ? (kScreenAlign | kScreenProducts) : kScreenProducts, n0.nq > 0 ? &n0 : nullptr);
+            if (rc) return rc;
+            if (reach > aligned_to) aligned_to = reach;
             ++span_groups;
+            g = end;
         }
+        const int next_aligned = aligned_to > cur.m ? aligned_to - cur.m : 0;
         span_end();
         // The exact pass of a chunk runs beside the next chunk's products, on the side stream -- except the call's last one,
         // which nothing follows: it stays on the main stream (no hop between streams in front of it; its argument sets are
@@ -1989,8 +2041,8 @@ int stream_screened_locked(scl_engine *e, std::unique_lock<std::mutex> &db, cons
                                     : launch_survivor_pass(e, cur.qslot, cur.qlo, cur.qn, cur.m, set0, out3, xs, kSurvivorKernel, region, keys_later))) return rc;
         SCL_HIP(e, hipEventRecord(e->ev_chunk[c], xs));
         k.busy = true;
-        k.aligned = false;
-        ch[c ^ 1].aligned = next_aligned;                    // the next chunk's first launch needs no alignment of its own
+        k.aligned = 0;
+        ch[c ^ 1].aligned = next_aligned;                    // the next chunk's first launch (pair) needs no alignment of its own
         e->last_pass_empty = cur.m == 0;
         return SCL_OK;
     };

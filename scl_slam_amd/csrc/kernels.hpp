@@ -9,9 +9,10 @@
 namespace scl {
 
 // ---- switches of experiments ---------------------------------------------------------------------------------------------------
-// A product build (plain `make`) reads three environment variables, all of which select shipped, tested paths: SCL_SCREEN (0: the
+// A product build (plain `make`) reads four environment variables, all of which select shipped, tested paths: SCL_SCREEN (0: the
 // exact kernel on every pair), SCL_SCREEN_FORM (1: the products' first form on every batch), SCL_SCREEN_V2_MIN (smallest batch the
-// second form scores) -- plus SCL_RCCL_LIB (which collective library the sharded front loads).  Every other SCL_* switch selects a
+// second form scores), SCL_SCREEN_PAIR (0: no two-set products launches in the stream form) -- plus SCL_RCCL_LIB (which collective
+// library the sharded front loads).  Every other SCL_* switch selects a
 // measured alternative or an ablation and exists only in a diagnostics build (make EXTRA=-DSCL_DIAGNOSTICS): here it is its default,
 // a constant, and the code it would select is not compiled in.
 #ifdef SCL_DIAGNOSTICS
@@ -244,6 +245,14 @@ size_t sc_screen_scratch_floats(const struct DbView &db, int SR);   // partial-s
 constexpr int kScreenAlign = 1, kScreenProducts = 2;
 hipError_t launch_sc_screen_batch(const struct DbView &db, const ScreenBatch &sb, int SR, int align_filter, int num_cu, hipStream_t stream,
                                   int phases = kScreenAlign | kScreenProducts, const ScreenBatch *next = nullptr);
+// Two consecutive FULL batches of the stream form on the 64 x 120 grid, second form: ONE products launch scores both (two scan sets
+// side by side on every XCD: the database crosses the fabric once for 32 scans), then the first batch's tail (its finishing beside the
+// alignment of next0) and the second's (beside next1).  sb0.part and sb1.part: different scratch.  Both batches are aligned already (a tail
+// before, or a kScreenAlign call each).  sc_screen_pairs: whether this grid and build take pairs (SCL_SCREEN_PAIR=0 and
+// SCL_SCREEN_FORM=1 turn them off) -- anything else is an invalid value here.
+bool sc_screen_pairs(const struct DbView &db, int SR);
+hipError_t launch_sc_screen_pair(const struct DbView &db, const ScreenBatch &sb0, const ScreenBatch &sb1, int SR, int align_filter, int num_cu,
+                                 hipStream_t stream, const ScreenBatch *next0, const ScreenBatch *next1);
 hipError_t launch_sc_select_batch(const ScreenBatch &sb, hipStream_t stream);
 // Exact pass over the survivors of nq screened queries (any number: the argument sets travel through device memory).
 // Query i: keyframe slot[i] against the range [base[i], base[i] + n[i]); its screening results live in buffer set

@@ -31,11 +31,14 @@
 //                                           fetched per pair (rotated by the pair's first shift) -- bound by what the L2s deliver;
 //                                           the next batch's alignment rides in the same grid (SCL_SCREEN_FORM=1; probes)
 //   sc_screen2_kernel                       K1s, SECOND form (default on 64 x 120 and 80 x 180): one KEYFRAME against the launch's
-//                                           scans per tile, the scans rotated out of LDS, ring parts in separate workgroups
+//                                           scans per tile, the scans rotated out of LDS, ring parts in separate workgroups;
+//                                           <.., 2>: two scan sets (two launch groups of the 64 x 120 stream) share the pass over
+//                                           the database (launch_sc_screen_pair; SCL_SCREEN_PAIR=0: never)
 //   sc_screen2_finish_body / _tail_kernel   the ring parts of a pair meet: bound d~, flags, ring-key metric -- in one launch with the
 //                                           next batch's alignment
 //   sc_select_kernel                        survivors + ring-key top-k (80 x 180's exact pass; scl_screen_distances)
 //   launch_sc_screen_batch                  the launch group of a batch
+//   launch_sc_screen_pair                   two full batches: one products launch, a tail each
 #include <atomic>
 #include <type_traits>
 
@@ -1238,11 +1241,25 @@ struct Screen2Args {
     int u_lo, u_n;                                 // union of the scans' ranges (database slots)
     int nwg;                                       // workgroups of the products (a multiple of 8 x ring parts)
 };
+// Two scan sets in ONE products launch (NS = 2, 64 x 120, the stream form: two consecutive full launch groups): the workgroups of set 0
+// and of set 1 walk the same keyframes in the same order side by side on one XCD, so the database crosses the fabric once for 32 scans --
+// the second set finds the lines in that XCD's L2 -- and the launch's prologue (ramp, staging, first fragments) is paid once.  Every
+// workgroup stages, reads and writes its OWN set only, by the one-set instance's instruction sequence per (wave, keyframe): the partial sums are bit for
+// bit those of two single launches.  Nothing synchronises the workgroups: where they run decides the traffic, never the result.
+struct Screen2PairArgs {
+    ScreenBatchArgs prod[2];
+    float *part[2];                                // the sets' partial sums (the two halves of the engine's scratch)
+    int u_lo, u_n;                                 // union of BOTH sets' ranges: a scan whose range leaves a keyframe out skips the store
+    int nwg;                                       // a multiple of 8 x ring parts x 2
+};
+template <int NS> struct S2KernelArgs { using type = Screen2Args; };
+template <> struct S2KernelArgs<2> { using type = Screen2PairArgs; };
 
-template <int RG, int S, int W>
-__global__ __launch_bounds__((S2Cfg<RG, S, W>::WV * kWave), 1) void sc_screen2_kernel(Screen2Args fa)
+template <int RG, int S, int W, int NS = 1>
+__global__ __launch_bounds__((S2Cfg<RG, S, W>::WV * kWave), 1) void sc_screen2_kernel(typename S2KernelArgs<NS>::type fa)
 {
     using C = S2Cfg<RG, S, W>;
+    static_assert(NS == 1 || NS == 2, "scan sets of a products launch");
     constexpr int WVP = C::WV;                         // waves of the workgroup: each takes every (workgroups x WVP)-th keyframe of its ring part
     constexpr int NP = C::NP, NPASS = C::NPASS, STEPS = C::STEPS, NQ = C::NQ, SPK = C::SPK, PS = C::PS;
     constexpr bool AOFF = PS != kS2PassRows;           // the passes share the scans' fragments (see S2Cfg)
@@ -1260,15 +1277,20 @@ __global__ __launch_bounds__((S2Cfg<RG, S, W>::WV * kWave), 1) void sc_screen2_k
                   && NQ % SPR == 0 && NQ <= kMaxScreenBatch && (SPK == 1 || SPK == 2), "second form");
     static_assert(SPK == 2 ? QUAD % 256 == 0 : (QUAD / 16) % 4 == 2, "bank slots of the image's blocks");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem2[];
-    const ScreenBatchArgs &ab = fa.prod;
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    // workgroup -> (XCD, ring part, index): the parts of index i sit next to each other on one XCD
+    // workgroup -> (XCD, ring part, set, index): the parts -- and sets -- of index i sit next to each other on one XCD
+    // (two sets: workgroups b, b + 8, b + 16, b + 24 = (half 0, set 0), (half 1, set 0), (half 0, set 1), (half 1, set 1))
     const int b = (int)blockIdx.x, xcd = b & 7, jx = b >> 3;
     const int part = jx % NP;
-    const int gi = (jx / NP) * 8 + xcd;                // 0 .. nwg / NP - 1
-    const int waves_part = (fa.nwg / NP) * WVP;
+    const int set = (jx / NP) % NS;                    // (uniform over the workgroup: scalar)
+    const int gi = (jx / (NP * NS)) * 8 + xcd;         // 0 .. nwg / (NP NS) - 1
+    const int waves_part = (fa.nwg / (NP * NS)) * WVP;
     const int gw = gi * WVP + wave;
+    const ScreenBatchArgs *abp; float *part_out;
+    if constexpr (NS == 2) { abp = set ? &fa.prod[1] : &fa.prod[0]; part_out = set ? fa.part[1] : fa.part[0]; }
+    else { abp = &fa.prod; part_out = fa.part; }
+    const ScreenBatchArgs &ab = *abp;
 
 #ifdef S2_STAMP
 #define S2_STAMP_AT(slot) do { if ((wave == 0 || wave == 5) && (b == 0 || b == 37) && lane == 0) g_s2_stamps[((b ? 2 : 0) + (wave ? 1 : 0)) * 64 + (slot)] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -1555,7 +1577,7 @@ __global__ __launch_bounds__((S2Cfg<RG, S, W>::WV * kWave), 1) void sc_screen2_k
                     for (int i = 0; i < 4; ++i) sum[i] += (i + sh <= 3) ? acc[p][u][(i + sh) & 3] : nx[(i + sh - 4) & 3];
                 }
                 if (ok && j4 < s2_pass_f4<RG, S, W>(p))
-                    *reinterpret_cast<f4v *>(fa.part + (((size_t)c16 * (size_t)ab.pair_stride + (size_t)ci) * NP + part) * (s2_part_f4<RG, S, W>() * 4) + (s2_pass_off<RG, S, W>(p) + j4) * 4) = sum;
+                    *reinterpret_cast<f4v *>(part_out + (((size_t)c16 * (size_t)ab.pair_stride + (size_t)ci) * NP + part) * (s2_part_f4<RG, S, W>() * 4) + (s2_pass_off<RG, S, W>(p) + j4) * 4) = sum;
             }
         }
         base_cur = base_nxt; base_nxt = kf_base(k + 2);
@@ -1848,6 +1870,11 @@ static bool screen_second_form()
     static const int form = [] { const char *e = getenv("SCL_SCREEN_FORM"); return e ? atoi(e) : 2; }();
     return form != 1;
 }
+static bool screen_pair_enabled()
+{   // SCL_SCREEN_PAIR=0: every launch group of the stream form streams the database for itself (no two-set products launches)
+    static const int on = [] { const char *e = getenv("SCL_SCREEN_PAIR"); return e ? atoi(e) : 1; }();
+    return on != 0;
+}
 static int screen_v2_min_env()
 {   // SCL_SCREEN_V2_MIN: the smallest batch the second form scores (0 / unset: the grid's own; tests: 1 = always the second form)
     static const int v = [] { const char *e = getenv("SCL_SCREEN_V2_MIN"); return e ? atoi(e) : 0; }();
@@ -1880,15 +1907,22 @@ static int fill_screen_args(const DbView &db, const ScreenBatch &sb, int align_f
     return nmax;
 }
 
+// the second set of a paired products launch: its batch and the batch its tail aligns (nullptr: none)
+struct ScreenPairMate { const ScreenBatch *sb; const ScreenBatch *next; };
+
 // one grid: RG ring groups, S sectors, W shifts; OCC0 / OCC1 = waves per SIMD of the default kernel / of variant 1
 template <int RG, int S, int W, int OCC0, int OCC1>
 static hipError_t launch_screen_grid(const DbView &db, const ScreenBatch &sb, int align_filter, int num_cu, hipStream_t stream, int phases,
-                                     const ScreenBatch *next)
+                                     const ScreenBatch *next, const ScreenPairMate *mate = nullptr)
 {
     constexpr int RGH = hdesc_rgh(RG);
     ScreenBatchArgs ab{};
     const int nmax = fill_screen_args(db, sb, align_filter, &ab);
     if (nmax < 0) return hipErrorInvalidValue;
+    // the second set of a paired products launch (launch_sc_screen_pair): its own argument block, partial sums and tail
+    ScreenBatchArgs ab_m{};
+    const int nmax_m = mate ? fill_screen_args(db, *mate->sb, align_filter, &ab_m) : 0;
+    if (nmax_m < 0) return hipErrorInvalidValue;
     const int ngroups = (nmax + kGroup - 1) / kGroup;
     // (the alignment's second form reads the keyframes' alignment images: both screened grids have them, allocated with the database)
     static_assert(halign_bytes(S) > 0, "alignment image");
@@ -1946,6 +1980,12 @@ static hipError_t launch_screen_grid(const DbView &db, const ScreenBatch &sb, in
     const bool use_v2 = second_form_for(sb);
     const bool next_v2 = next && second_form_for(*next);
     ab.skip_d2 = use_v2 ? 1 : 0;
+    ab_m.skip_d2 = 1;
+    // a pair: two FULL batches of the second form on the grid whose products have the two-set instance, and a products launch to share
+    constexpr bool kPairGrid = S == 120 && S2Cfg<RG, S, W>::NP == 2;
+    if (mate && !(kPairGrid && screen_pair_enabled() && phases == kScreenProducts && use_v2 && second_form_for(*mate->sb) &&
+                  sb.nq == S2Cfg<RG, S, W>::NQ && mate->sb->nq == S2Cfg<RG, S, W>::NQ && mate->sb->part != sb.part))
+        return hipErrorInvalidValue;
     constexpr size_t lds_a2 = (size_t)kScreenWaves * Align2Cfg<S>::LDS_WAVE;
     auto union_of = [](const ScreenBatch &b, int *lo_out, int *n_out) {
         int lo = b.base[0], hi = b.base[0] + b.n[0];
@@ -1986,63 +2026,89 @@ static hipError_t launch_screen_grid(const DbView &db, const ScreenBatch &sb, in
             if (e != hipSuccess) return e;
             attr2.store(true, std::memory_order_release);
         }
-        Screen2Args f2{};
+        Screen2Args f2{}, f2_m{};
         f2.prod = ab; f2.part = sb.part;
         union_of(sb, &f2.u_lo, &f2.u_n);
-        constexpr int WGU = 8 * S2Cfg<RG, S, W>::NP;                           // the ring parts of an index on one XCD
+        const int WGU = 8 * S2Cfg<RG, S, W>::NP * (mate ? 2 : 1);             // the ring parts (and sets) of an index on one XCD
         int nwg = (num_cu / WGU) * WGU;
         if (nwg < WGU) nwg = WGU;
         f2.nwg = nwg;
         hipError_t e = hipSuccess;
-        hipLaunchKernelGGL((sc_screen2_kernel<RG, S, W>), dim3(nwg), dim3(S2Cfg<RG, S, W>::WV * kWave), (s2_lds<RG, S, W>()), stream, f2);
+        if constexpr (kPairGrid) {
+            if (mate) {
+                // ---- two sets, one pass over the database: the union of both sets' ranges ----
+                static std::atomic<bool> attrp_dev[64];
+                std::atomic<bool> &attrp = attrp_dev[dev_ & 63];
+                if (!attrp.load(std::memory_order_acquire)) {
+                    e = hipFuncSetAttribute((const void *)sc_screen2_kernel<RG, S, W, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(s2_lds<RG, S, W>()));
+                    if (e != hipSuccess) return e;
+                    attrp.store(true, std::memory_order_release);
+                }
+                f2_m.prod = ab_m; f2_m.part = mate->sb->part; f2_m.nwg = nwg;
+                union_of(*mate->sb, &f2_m.u_lo, &f2_m.u_n);
+                Screen2PairArgs fp{};
+                fp.prod[0] = ab; fp.prod[1] = ab_m; fp.part[0] = sb.part; fp.part[1] = mate->sb->part; fp.nwg = nwg;
+                const int hi0 = f2.u_lo + f2.u_n, hi1 = f2_m.u_lo + f2_m.u_n;
+                fp.u_lo = f2.u_lo < f2_m.u_lo ? f2.u_lo : f2_m.u_lo;
+                fp.u_n = (hi0 > hi1 ? hi0 : hi1) - fp.u_lo;
+                hipLaunchKernelGGL((sc_screen2_kernel<RG, S, W, 2>), dim3(nwg), dim3(S2Cfg<RG, S, W>::WV * kWave), (s2_lds<RG, S, W>()), stream, fp);
+            }
+        }
+        if (!mate) hipLaunchKernelGGL((sc_screen2_kernel<RG, S, W>), dim3(nwg), dim3(S2Cfg<RG, S, W>::WV * kWave), (s2_lds<RG, S, W>()), stream, f2);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         // The next batch's alignment runs in line on this stream.  (On a low-priority side stream, forked at the start or at the end of
         // the products, it measured 0.67 / 0.51 G pairs/s against 1.45 G in line: the two event hops between the queues per launch cost
         // more than the alignment itself.  As extra waves of the products' workgroups: one launch of 81-87 us against 47.8 + 26.9.
         // Both removed)
-        const int chunks = (nmax + 255) / 256;                                 // finishing workgroups per scan
-        const dim3 fgrid(finish_blocks(chunks, sb.nq)), ablock(kScreenWaves * kWave);
-        if (!next) {
+        // (a pair: one tail per set, the first set's in front -- each finishes its set beside the alignment of the batch TWO behind it)
+        auto launch_tail = [&](const ScreenBatch &sb, const Screen2Args &f2, const int nmax, const ScreenBatch *next) -> hipError_t {
+            const bool next_v2 = next && second_form_for(*next);
+            const int chunks = (nmax + 255) / 256;                                 // finishing workgroups per scan
+            const dim3 fgrid(finish_blocks(chunks, sb.nq)), ablock(kScreenWaves * kWave);
+            if (!next) {
+                hipLaunchKernelGGL((sc_screen2_finish_kernel<RG, S, W>), fgrid, dim3(256), 0, stream, f2, chunks);
+                return hipGetLastError();
+            }
+            // the next batch's argument block and the grid of its alignment
+            if (next->nq < 1 || next->nq > kMaxScreenBatch) return hipErrorInvalidValue;
+            ScreenBatchArgs nb{};
+            const int nmax2 = fill_screen_args(db, *next, align_filter, &nb);
+            if (nmax2 < 0) return hipErrorInvalidValue;
+            nb.skip_d2 = next_v2 ? 1 : 0;
+            int ulo = 0, un = 0, ablocks;
+            if (next_v2) {
+                union_of(*next, &ulo, &un);
+                ablocks = align2_blocks(un);
+            } else {
+                // first form: persistent workgroups, three per CU (167 registers: three waves per SIMD; 128 spill and double the time) over the
+                // whole batch, every wave walks several groups with the next group's keys in flight
+                const int ng2 = (nmax2 + kGroup - 1) / kGroup;
+                int per_q = 3 * num_cu / next->nq;                                   // (two to nine per CU measure the same 29 us)
+                per_q = per_q < 1 ? 1 : per_q;
+                nb.nb = (ng2 + kScreenWaves - 1) / kScreenWaves;
+                nb.nb = nb.nb > per_q ? per_q : nb.nb;
+                ablocks = nb.nb * next->nq;
+            }
+            static const int tail_env = scl_lab_int("SCL_SCREEN_TAIL", 1);   // 0: finish and alignment as two launches
+            if (tail_env) {
+                // one launch: the alignment's workgroups in front, this batch's finishing behind them
+                const dim3 tgrid(ablocks + finish_blocks(chunks, sb.nq));
+                const bool d2 = !sb.no_ring_metric;                       // (left to the exact pass of the range: kernels.hpp)
+                if (!next_v2) hipLaunchKernelGGL((sc_screen2_tail_kernel<RG, S, W>), tgrid, ablock, lds0, stream, f2, nb, ablocks, chunks);
+                else if (sb.smask && d2) hipLaunchKernelGGL((sc_screen2_tail2_kernel<RG, S, W, true, true>), tgrid, ablock, lds_a2, stream, f2, nb, db.halign, ulo, un, ablocks, chunks);
+                else if (sb.smask) hipLaunchKernelGGL((sc_screen2_tail2_kernel<RG, S, W, true, false>), tgrid, ablock, lds_a2, stream, f2, nb, db.halign, ulo, un, ablocks, chunks);
+                else if (d2) hipLaunchKernelGGL((sc_screen2_tail2_kernel<RG, S, W, false, true>), tgrid, ablock, lds_a2, stream, f2, nb, db.halign, ulo, un, ablocks, chunks);
+                else hipLaunchKernelGGL((sc_screen2_tail2_kernel<RG, S, W, false, false>), tgrid, ablock, lds_a2, stream, f2, nb, db.halign, ulo, un, ablocks, chunks);
+                return hipGetLastError();
+            }
             hipLaunchKernelGGL((sc_screen2_finish_kernel<RG, S, W>), fgrid, dim3(256), 0, stream, f2, chunks);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+            if (next_v2) hipLaunchKernelGGL((sc_align2_kernel<RG, S, W>), dim3(ablocks), ablock, lds_a2, stream, nb, db.halign, ulo, un);
+            else hipLaunchKernelGGL((sc_align_kernel<RG, S, W>), dim3(ablocks), ablock, lds0, stream, nb);
             return hipGetLastError();
-        }
-        // the next batch's argument block and the grid of its alignment
-        if (next->nq < 1 || next->nq > kMaxScreenBatch) return hipErrorInvalidValue;
-        ScreenBatchArgs nb{};
-        const int nmax2 = fill_screen_args(db, *next, align_filter, &nb);
-        if (nmax2 < 0) return hipErrorInvalidValue;
-        nb.skip_d2 = next_v2 ? 1 : 0;
-        int ulo = 0, un = 0, ablocks;
-        if (next_v2) {
-            union_of(*next, &ulo, &un);
-            ablocks = align2_blocks(un);
-        } else {
-            // first form: persistent workgroups, three per CU (167 registers: three waves per SIMD; 128 spill and double the time) over the
-            // whole batch, every wave walks several groups with the next group's keys in flight
-            const int ng2 = (nmax2 + kGroup - 1) / kGroup;
-            int per_q = 3 * num_cu / next->nq;                                   // (two to nine per CU measure the same 29 us)
-            per_q = per_q < 1 ? 1 : per_q;
-            nb.nb = (ng2 + kScreenWaves - 1) / kScreenWaves;
-            nb.nb = nb.nb > per_q ? per_q : nb.nb;
-            ablocks = nb.nb * next->nq;
-        }
-        static const int tail_env = scl_lab_int("SCL_SCREEN_TAIL", 1);   // 0: finish and alignment as two launches
-        if (tail_env) {
-            // one launch: the alignment's workgroups in front, this batch's finishing behind them
-            const dim3 tgrid(ablocks + finish_blocks(chunks, sb.nq));
-            const bool d2 = !sb.no_ring_metric;                       // (left to the exact pass of the range: kernels.hpp)
-            if (!next_v2) hipLaunchKernelGGL((sc_screen2_tail_kernel<RG, S, W>), tgrid, ablock, lds0, stream, f2, nb, ablocks, chunks);
-            else if (sb.smask && d2) hipLaunchKernelGGL((sc_screen2_tail2_kernel<RG, S, W, true, true>), tgrid, ablock, lds_a2, stream, f2, nb, db.halign, ulo, un, ablocks, chunks);
-            else if (sb.smask) hipLaunchKernelGGL((sc_screen2_tail2_kernel<RG, S, W, true, false>), tgrid, ablock, lds_a2, stream, f2, nb, db.halign, ulo, un, ablocks, chunks);
-            else if (d2) hipLaunchKernelGGL((sc_screen2_tail2_kernel<RG, S, W, false, true>), tgrid, ablock, lds_a2, stream, f2, nb, db.halign, ulo, un, ablocks, chunks);
-            else hipLaunchKernelGGL((sc_screen2_tail2_kernel<RG, S, W, false, false>), tgrid, ablock, lds_a2, stream, f2, nb, db.halign, ulo, un, ablocks, chunks);
-            return hipGetLastError();
-        }
-        hipLaunchKernelGGL((sc_screen2_finish_kernel<RG, S, W>), fgrid, dim3(256), 0, stream, f2, chunks);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (next_v2) hipLaunchKernelGGL((sc_align2_kernel<RG, S, W>), dim3(ablocks), ablock, lds_a2, stream, nb, db.halign, ulo, un);
-        else hipLaunchKernelGGL((sc_align_kernel<RG, S, W>), dim3(ablocks), ablock, lds0, stream, nb);
-        return hipGetLastError();
+        };
+        if ((e = launch_tail(sb, f2, nmax, next)) != hipSuccess || !mate) return e;
+        return launch_tail(*mate->sb, f2_m, nmax_m, mate->next);
     }
     // ---- first form ----
     // the products of this batch + the alignment of the next one
@@ -2082,6 +2148,20 @@ hipError_t launch_sc_screen_batch(const DbView &db, const ScreenBatch &sb, int S
     // (64 x 120: the first form scores batches of one to three scans -- blocking calls -- and the kernel built for two waves per SIMD takes
     //  4 us less of a one-scan call than the one for three, which was the better one when the first form still scored batches of four)
     return launch_screen_grid<16, 120, 13, 2, 3>(db, sb, align_filter, num_cu, stream, phases, next);                                   // 64 x 120
+}
+
+bool sc_screen_pairs(const DbView &db, int SR)
+{
+    return sc_screen_supported(db, SR) && !sc_screen_is_wide(db, SR) && screen_second_form() && screen_pair_enabled() && screen_v2_min_env() <= kMaxScreenBatch &&
+           scl_lab_int("SCL_SCREEN_VARIANT", 0) == 0 && scl_lab_int("SCL_SCREEN_PROBE", 0) == 0;
+}
+
+hipError_t launch_sc_screen_pair(const DbView &db, const ScreenBatch &sb0, const ScreenBatch &sb1, int SR, int align_filter, int num_cu, hipStream_t stream,
+                                 const ScreenBatch *next0, const ScreenBatch *next1)
+{
+    if (!sc_screen_pairs(db, SR) || sb0.nq != kMaxScreenBatch || sb1.nq != kMaxScreenBatch) return hipErrorInvalidValue;
+    const ScreenPairMate mate{&sb1, next1};
+    return launch_screen_grid<16, 120, 13, 2, 3>(db, sb0, align_filter, num_cu, stream, kScreenProducts, next0, &mate);
 }
 
 }  // namespace scl
