@@ -3274,6 +3274,23 @@ int kf_window(scl_engine *e, int robot, int key, int search_num, const float *po
     return SCL_OK;
 }
 
+// The candidates of one round (at most kIcpBatch) that go on to a batch function of icp.hip, as that function takes them: live
+// candidate j is candidate c of the round (its workspace: icp_batch_ws[c]) and entry which[j] of the call's outputs.  Who is live is
+// the call site's rule; the results come back through which[].
+struct LiveCandidates {
+    scl_engine *e;
+    IcpWorkspace *wss[scl_engine::kIcpBatch]; int which[scl_engine::kIcpBatch];
+    const void *tg[scl_engine::kIcpBatch]; int tn[scl_engine::kIcpBatch];
+    float rows[12 * scl_engine::kIcpBatch];                             // rows 0 .. 2 of the live candidates' guesses or transforms
+    int live = 0;
+    explicit LiveCandidates(scl_engine *engine) : e(engine) {}
+    void add(int c, int global_index, const void *d_tgt, int n_tgt, const float *T16 /* nullptr: none */)
+    {
+        if (T16) std::memcpy(rows + 12 * (size_t)live, T16, 12 * sizeof(float));
+        wss[live] = &e->icp_batch_ws[c]; which[live] = global_index; tg[live] = d_tgt; tn[live] = n_tgt; ++live;
+    }
+};
+
 }  // namespace
 
 int scl_keyframe_put(scl_engine *e, int robot, int index, const void *points, int n_points, int stride_bytes)
@@ -3440,25 +3457,25 @@ int scl_loop_icp_batch_from_store(scl_engine *e, int robot, int key_cur, const f
         if (m <= 0) break;
         // search grids (+ normals) of the candidates that are large enough (DM.h:1108), their submaps read where the filter left them:
         // one launch per step over all of them (icp.hip, icp_batch_prepare_all), on the engine's stream
-        IcpWorkspace *wss[scl_engine::kIcpBatch]; int which[scl_engine::kIcpBatch]; int live = 0;
-        const void *tg[scl_engine::kIcpBatch]; int tn[scl_engine::kIcpBatch];
+        LiveCandidates lc(e);
         for (int c = 0; c < m; ++c) {
             const int nt = n_sub[(size_t)c + 1];
             if (n_tgts) n_tgts[first + c] = nt;
             if (ns < min_src_points || nt < min_tgt_points) continue;
-            wss[live] = &e->icp_batch_ws[c]; which[live] = first + c; tg[live] = d_sub[(size_t)c + 1]; tn[live] = nt; ++live;
+            lc.add(c, first + c, d_sub[(size_t)c + 1], nt, nullptr);
         }
+        const int live = lc.live;
         if (live == 0) continue;
-        rc = icp_batch_prepare_all(wss, live, &e->icp_batch_ctl, e->stream, ns, tg, tn, stride, *p, &err);
+        rc = icp_batch_prepare_all(lc.wss, live, &e->icp_batch_ctl, e->stream, ns, lc.tg, lc.tn, stride, *p, &err);
         if (rc) { e->last_error = err; return rc; }
         std::vector<float> Tl(16 * (size_t)live), fl((size_t)live); std::vector<int> cl((size_t)live), il((size_t)live);
-        rc = icp_batch_run(wss, live, &e->icp_batch_ctl, e->stream, d_src, ns, stride, *p, nullptr, Tl.data(), fl.data(), cl.data(), il.data(), &err);
+        rc = icp_batch_run(lc.wss, live, &e->icp_batch_ctl, e->stream, d_src, ns, stride, *p, nullptr, Tl.data(), fl.data(), cl.data(), il.data(), &err);
         if (rc) { e->last_error = err; return rc; }
         for (int j = 0; j < live; ++j) {
-            std::memcpy(T + 16 * (size_t)which[j], Tl.data() + 16 * (size_t)j, 16 * sizeof(float));
-            if (fitness) fitness[which[j]] = fl[(size_t)j];
-            if (converged) converged[which[j]] = cl[(size_t)j];
-            if (iterations) iterations[which[j]] = il[(size_t)j];
+            std::memcpy(T + 16 * (size_t)lc.which[j], Tl.data() + 16 * (size_t)j, 16 * sizeof(float));
+            if (fitness) fitness[lc.which[j]] = fl[(size_t)j];
+            if (converged) converged[lc.which[j]] = cl[(size_t)j];
+            if (iterations) iterations[lc.which[j]] = il[(size_t)j];
         }
     }
     return SCL_OK;
@@ -3555,25 +3572,23 @@ int verification_round(scl_engine *e, int first, int m, int ns, const void *cons
                        const float *guesses /* nullptr, or the call's n x 16 */, int ransac_iterations, double inlier_threshold, double inlier_ratio, uint64_t seed,
                        float *T, int *success, int *n_correspondences, int *n_inliers)
 {
-    IcpWorkspace *wss[scl_engine::kIcpBatch]; int which[scl_engine::kIcpBatch]; int live = 0;
-    const void *tg[scl_engine::kIcpBatch]; int tn[scl_engine::kIcpBatch];
+    LiveCandidates lc(e);
     for (int c = 0; c < m; ++c) {
         if (gated[c] || ns < 1 || n_tgts[c] < 1) continue;                  // (no pair at all: scl_geometric_verification's early answer)
-        wss[live] = &e->icp_batch_ws[c]; which[live] = first + c; tg[live] = d_tgts[c]; tn[live] = n_tgts[c]; ++live;
+        lc.add(c, first + c, d_tgts[c], n_tgts[c], guesses ? guesses + 16 * (size_t)(first + c) : nullptr);
     }
+    const int live = lc.live;
     if (live == 0) return SCL_OK;
     float Tl[16 * scl_engine::kIcpBatch]; int ok[scl_engine::kIcpBatch], nc[scl_engine::kIcpBatch], ni[scl_engine::kIcpBatch];
-    float g12[12 * scl_engine::kIcpBatch];                               // rows 0 .. 2 of the live candidates' guesses
-    if (guesses) for (int j = 0; j < live; ++j) std::memcpy(g12 + 12 * (size_t)j, guesses + 16 * (size_t)which[j], 12 * sizeof(float));
     std::string err;
-    int rc = icp_geometric_verification_batch(wss, live, &e->icp_batch_ctl, e->stream, ns, tg, tn, stride, guesses ? g12 : nullptr, ransac_iterations,
+    int rc = icp_geometric_verification_batch(lc.wss, live, &e->icp_batch_ctl, e->stream, ns, lc.tg, lc.tn, stride, guesses ? lc.rows : nullptr, ransac_iterations,
                                               inlier_threshold, inlier_ratio, (unsigned long long)seed, Tl, ok, nc, ni, &err);
     if (rc) { e->last_error = err; return rc; }
     for (int j = 0; j < live; ++j) {
-        std::memcpy(T + 16 * (size_t)which[j], Tl + 16 * (size_t)j, 16 * sizeof(float));
-        if (success) success[which[j]] = ok[j];
-        if (n_correspondences) n_correspondences[which[j]] = nc[j];
-        if (n_inliers) n_inliers[which[j]] = ni[j];
+        std::memcpy(T + 16 * (size_t)lc.which[j], Tl + 16 * (size_t)j, 16 * sizeof(float));
+        if (success) success[lc.which[j]] = ok[j];
+        if (n_correspondences) n_correspondences[lc.which[j]] = nc[j];
+        if (n_inliers) n_inliers[lc.which[j]] = ni[j];
     }
     return SCL_OK;
 }
@@ -3789,15 +3804,6 @@ int verification_batch_store(scl_engine *e, const void *src, int n_src, int stri
 
 namespace {
 
-// what icp_batch_prepare refuses in the parameters, before anything runs
-const char *icp_params_bad(const scl_icp_params &p)
-{
-    if (p.estimator != 0 && p.estimator != 1) return "unknown estimator";
-    if (p.estimator == 1 && !(p.normal_radius > 0.0)) return "normal_radius must be > 0";
-    if (p.max_iterations < 1) return "max_iterations < 1";
-    return nullptr;
-}
-
 // scl_loop_icp_batch_from_store_guess (received == false: the source is submap(key_cur, 0), assembled with every round's candidates
 // as the unguessed call does) and scl_icp_align_batch_from_store_guess (received == true: src filtered once with src_leaf and placed
 // in icp_batch_ctl, as the guessed verification places it).  A round: the submaps (one batched filter), the search grids of the
@@ -3877,27 +3883,25 @@ int icp_batch_store_guess(scl_engine *e, bool received, const void *src, int n_s
             cleared = true;
         }
         if (m <= 0) break;
-        IcpWorkspace *wss[scl_engine::kIcpBatch]; int which[scl_engine::kIcpBatch]; int live = 0;
-        const void *tg[scl_engine::kIcpBatch]; int tn[scl_engine::kIcpBatch];
-        float g12[12 * scl_engine::kIcpBatch];                             // rows 0 .. 2 of the live candidates' guesses
+        LiveCandidates lc(e);
         for (int c = 0; c < m; ++c) {
             const int nt = n_sub[(size_t)(c + lead)];
             if (n_tgts) n_tgts[first + c] = nt;
             if ((gated_all[(size_t)(first + c)] = ns < min_src_points || nt < min_tgt_points)) continue;   // DM.h:1108: the unmoved sizes
-            std::memcpy(g12 + 12 * (size_t)live, guesses + 16 * (size_t)(first + c), 12 * sizeof(float));
-            wss[live] = &e->icp_batch_ws[c]; which[live] = first + c; tg[live] = d_sub[(size_t)(c + lead)]; tn[live] = nt; ++live;
+            lc.add(c, first + c, d_sub[(size_t)(c + lead)], nt, guesses + 16 * (size_t)(first + c));
         }
+        const int live = lc.live;
         if (live == 0) continue;
-        rc = icp_batch_prepare_all(wss, live, &e->icp_batch_ctl, e->stream, ns, tg, tn, stride, *p, &err);
+        rc = icp_batch_prepare_all(lc.wss, live, &e->icp_batch_ctl, e->stream, ns, lc.tg, lc.tn, stride, *p, &err);
         if (rc) { e->last_error = err; return rc; }
         float Tl[16 * scl_engine::kIcpBatch], fl[scl_engine::kIcpBatch]; int cl[scl_engine::kIcpBatch], il[scl_engine::kIcpBatch];
-        rc = icp_batch_run(wss, live, &e->icp_batch_ctl, e->stream, d_src, ns, stride, *p, g12, Tl, fl, cl, il, &err);
+        rc = icp_batch_run(lc.wss, live, &e->icp_batch_ctl, e->stream, d_src, ns, stride, *p, lc.rows, Tl, fl, cl, il, &err);
         if (rc) { e->last_error = err; return rc; }
         for (int j = 0; j < live; ++j) {
-            std::memcpy(Ti + 16 * (size_t)which[j], Tl + 16 * (size_t)j, 16 * sizeof(float));
-            if (fitness) fitness[which[j]] = fl[j];
-            if (converged) converged[which[j]] = cl[j];
-            if (iterations) iterations[which[j]] = il[j];
+            std::memcpy(Ti + 16 * (size_t)lc.which[j], Tl + 16 * (size_t)j, 16 * sizeof(float));
+            if (fitness) fitness[lc.which[j]] = fl[j];
+            if (converged) converged[lc.which[j]] = cl[j];
+            if (iterations) iterations[lc.which[j]] = il[j];
         }
     }
     if (n_candidates > 0) verification_compose(n_candidates, Ti, guesses, gated_all.data(), T);   // T = T_icp * G; a gated candidate keeps the identity
@@ -3986,28 +3990,26 @@ void eval_clear(int n, int *n_valid, int *n_inliers, double *moments, int *n_tgt
 int eval_round(scl_engine *e, int first, int m, const void *d_src, int ns, const void *const *d_tgts, const int *n_tgts, const bool *gated,
                int stride, const float *transforms, double max_dist, int *n_valid, int *n_inliers, double *moments, const EvalPlane *pl = nullptr)
 {
-    IcpWorkspace *wss[scl_engine::kIcpBatch]; int which[scl_engine::kIcpBatch]; int live = 0;
-    const void *tg[scl_engine::kIcpBatch]; int tn[scl_engine::kIcpBatch];
-    float t12[12 * scl_engine::kIcpBatch];                               // rows 0 .. 2 of the live candidates' transforms
+    LiveCandidates lc(e);
     for (int c = 0; c < m; ++c) {
         if (gated[c] || ns < 1 || n_tgts[c] < 1) continue;
-        std::memcpy(t12 + 12 * (size_t)live, transforms + 16 * (size_t)(first + c), 12 * sizeof(float));
-        wss[live] = &e->icp_batch_ws[c]; which[live] = first + c; tg[live] = d_tgts[c]; tn[live] = n_tgts[c]; ++live;
+        lc.add(c, first + c, d_tgts[c], n_tgts[c], transforms + 16 * (size_t)(first + c));
     }
+    const int live = lc.live;
     if (live == 0) return SCL_OK;
     int nv[scl_engine::kIcpBatch], ni[scl_engine::kIcpBatch], np[scl_engine::kIcpBatch]; double mo[29 * scl_engine::kIcpBatch];
     std::string err;
     const float maxd2 = (float)(max_dist * max_dist);                    // ICP's rejection rule (icp.hip, icp_batch_run)
-    int rc = pl ? icp_registration_eval_plane_batch(wss, live, &e->icp_batch_ctl, e->stream, d_src, ns, tg, tn, stride, t12, maxd2, pl->normal_radius,
+    int rc = pl ? icp_registration_eval_plane_batch(lc.wss, live, &e->icp_batch_ctl, e->stream, d_src, ns, lc.tg, lc.tn, stride, lc.rows, maxd2, pl->normal_radius,
                                                     nv, ni, np, mo, &err)
-                : icp_registration_eval_batch(wss, live, &e->icp_batch_ctl, e->stream, d_src, ns, tg, tn, stride, t12, maxd2, nv, ni, mo, &err);
+                : icp_registration_eval_batch(lc.wss, live, &e->icp_batch_ctl, e->stream, d_src, ns, lc.tg, lc.tn, stride, lc.rows, maxd2, nv, ni, mo, &err);
     if (rc) { e->last_error = err; return rc; }
     for (int j = 0; j < live; ++j) {
-        if (n_valid) n_valid[which[j]] = nv[j];
-        if (n_inliers) n_inliers[which[j]] = ni[j];
-        if (moments) std::memcpy(moments + 10 * (size_t)which[j], mo + 10 * (size_t)j, 10 * sizeof(double));
-        if (pl && pl->n_planar) pl->n_planar[which[j]] = np[j];
-        if (pl && pl->sums) std::memcpy(pl->sums + 29 * (size_t)which[j], mo + 29 * (size_t)j, 29 * sizeof(double));
+        if (n_valid) n_valid[lc.which[j]] = nv[j];
+        if (n_inliers) n_inliers[lc.which[j]] = ni[j];
+        if (moments) std::memcpy(moments + 10 * (size_t)lc.which[j], mo + 10 * (size_t)j, 10 * sizeof(double));
+        if (pl && pl->n_planar) pl->n_planar[lc.which[j]] = np[j];
+        if (pl && pl->sums) std::memcpy(pl->sums + 29 * (size_t)lc.which[j], mo + 29 * (size_t)j, 29 * sizeof(double));
     }
     return SCL_OK;
 }

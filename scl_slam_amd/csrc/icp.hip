@@ -25,6 +25,8 @@
 //                    criteria, final = T*final
 //   K6  transform    working source cloud <- T_inc * cloud (fp32, no FMA), folded into the next search
 //   normals          point to plane: PCA of the neighbours within a radius through the same grid (normals_body)
+//   rounds           batched verification (pairs, RANSAC, masked fit) and registration scoring: one chain of launches over a round
+//                    of candidates and one wait; the host side they share is CandidateRound
 // The whole ICP loop is enqueued without host round trips: every kernel looks at a device-side `done` flag; the flags travel to the
 // host every four iterations and are looked at one period later.
 #include "icp.hpp"
@@ -61,6 +63,19 @@ struct IcpState {
     unsigned int pad_[2];
 };
 
+// The slots of a workspace.  A batched call has the candidates' workspaces (wss[c]) and one that keeps what all share (ctl); a single
+// alignment is a batch of one whose ctl IS its workspace (icp_align_staged), so icp_batch_run's two columns may never claim one
+// slot; a round likewise keeps its tables out of every slot a candidate's workspace uses:
+//                      a candidate's workspace                                    ctl
+//   every batched call B_TSORT B_CSTART B_CFILL B_BBOX B_STATE (grid_build_batch) B_PROB (GridJobs), pinned
+//   a round (verify,   B_NNI B_NND B_PART; plane: B_NORM B_TORD;                  B_PAIR (round_tables), B_SRC (the verification's
+//    scorings)         verify: B_SI B_TI B_MASK B_HYP, B_TGT when read in place;   staged source), B_WORK (its cloud for all, unguessed:
+//                      B_WORK (a moved source of its own: scorings, guessed)       no candidate then has one of its own)
+//   icp_batch_run      B_WORK B_NNQ B_FLAG B_NNI B_NND B_PART B_NORM, B_TGT       B_MASK (problems, guesses), B_HYP (states, counters),
+//                      unless the target is read in place (ext_tgt)               B_PERM B_SORT B_GSRC B_GORD, B_BBOX (source_order: behind the grids)
+// The remaining single calls (icp_geometric_verification*, icp_ransac, icp_rigid_svd, icp_nn_correspondences, icp_transform_cloud,
+// icp_target_normals) have one workspace and use its slots one call at a time.  Every slot is grow-only and ensure may move it: a pointer is taken behind the
+// slot's last ensure of the call.
 enum Buf { B_SRC = 0, B_TGT, B_WORK, B_TSORT, B_CSTART, B_CFILL, B_NNI, B_NND, B_PART, B_STATE, B_BBOX, B_SI, B_TI, B_OUT, B_MASK, B_HYP, B_PROB,
            B_NNQ, B_PERM, B_SORT, B_FLAG, B_PAIR, B_GSRC, B_GORD, B_TORD };
 static_assert(B_TORD < (int)(sizeof(IcpWorkspace::buf) / sizeof(void *)), "IcpWorkspace::buf is too short");
@@ -2003,7 +2018,8 @@ __global__ void gather_states_kernel(const IcpProblem *pr, int nprob, IcpState *
 // at 1 000 hypotheses.  The candidates of a ranked list are independent, so here every step is one launch over all of them, a
 // candidate's pair count stays on the device (every kernel reads it, clamped to n_src, and leaves below 3) and the host waits once.
 // Every value comes from the single path's bodies over the single path's partition of the pairs: candidate c's answer is the
-// single call's, bit for bit.
+// single call's, bit for bit.  (The single call keeps its own chain: a round of ONE candidate of 100 k points is slower than it,
+// 26.1 - 26.5 ms against 23.5 - 23.8 for 25 calls -- the one-workgroup scans of this chain are made for many candidates.)
 struct VerifyJob {
     const unsigned char *src; int sstride;                   // the candidate's source: the staged cloud (its stride), or with a guess its own moved float4 cloud (16)
     const unsigned char *tgt; IcpState *st; const int *nni;
@@ -2628,6 +2644,27 @@ static int guess_sources(IcpWorkspace *ctl, hipStream_t stream, const void *d_sr
 }
 
 // ---- the alignments of one scan's loop candidates, every loop step one launch for all of them (BASELINE configs[2]) ------------
+// what the prepare functions (and the engine, before anything runs) refuse in the parameters -> nullptr or the message
+const char *icp_params_bad(const scl_icp_params &p)
+{
+    if (p.estimator != 0 && p.estimator != 1) return "unknown estimator";
+    if (p.estimator == 1 && !(p.normal_radius > 0.0)) return "normal_radius must be > 0";
+    if (p.max_iterations < 1) return "max_iterations < 1";
+    return nullptr;
+}
+
+// the buffers of one alignment that depend on the clouds' sizes alone
+static int ensure_alignment(IcpWorkspace *ws, int n_src, int n_tgt, std::string *err)
+{
+    int rc;
+    if ((rc = ensure(ws, B_WORK, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
+    if ((rc = ensure(ws, B_NNQ, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
+    if ((rc = ensure(ws, B_FLAG, sizeof(int) * ((size_t)(n_src > n_tgt ? n_src : n_tgt) / kTileQ + 2), err))) return rc;
+    if ((rc = ensure(ws, B_NNI, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
+    if ((rc = ensure(ws, B_NND, sizeof(float) * (size_t)(n_src + 1), err))) return rc;
+    return ensure(ws, B_PART, part_bytes(n_src), err);
+}
+
 // icp_batch_prepare: everything an alignment needs before its first iteration that depends on its target (staged in ws, B_TGT):
 // buffers, NN grid, normals (point-to-plane), state.  (The working clouds are set up by icp_batch_run, in the sources' working order.)
 int icp_batch_prepare(IcpWorkspace *ws, hipStream_t stream, const void *d_src, int n_src, int n_tgt, int stride,
@@ -2637,15 +2674,8 @@ int icp_batch_prepare(IcpWorkspace *ws, hipStream_t stream, const void *d_src, i
     ws->ext_tgt = nullptr;                                       // the target is the one staged in B_TGT
     int rc = check_cloud_args(n_src, n_tgt, stride, err);
     if (rc) return rc;
-    if (p.estimator != 0 && p.estimator != 1) { if (err) *err = "unknown estimator"; return SCL_ERR_INVALID_ARG; }
-    if (p.estimator == 1 && !(p.normal_radius > 0.0)) { if (err) *err = "normal_radius must be > 0"; return SCL_ERR_INVALID_ARG; }
-    if (p.max_iterations < 1) { if (err) *err = "max_iterations < 1"; return SCL_ERR_INVALID_ARG; }
-    if ((rc = ensure(ws, B_WORK, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
-    if ((rc = ensure(ws, B_NNQ, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
-    if ((rc = ensure(ws, B_FLAG, sizeof(int) * ((size_t)(n_src > n_tgt ? n_src : n_tgt) / kTileQ + 2), err))) return rc;
-    if ((rc = ensure(ws, B_NNI, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
-    if ((rc = ensure(ws, B_NND, sizeof(float) * (size_t)(n_src + 1), err))) return rc;
-    if ((rc = ensure(ws, B_PART, part_bytes(n_src), err))) return rc;
+    if (const char *bad = icp_params_bad(p)) { if (err) *err = bad; return SCL_ERR_INVALID_ARG; }
+    if ((rc = ensure_alignment(ws, n_src, n_tgt, err))) return rc;
     ws->n_tgt = n_tgt;
     if ((rc = build_grid(ws, stream, n_tgt, stride, err))) return rc;
     if (p.estimator == 1) {
@@ -2705,20 +2735,11 @@ int icp_batch_prepare_all(IcpWorkspace *const *wss, int n, IcpWorkspace *ctl, hi
                           const int *n_tgts, int stride, const scl_icp_params &p, std::string *err)
 {
     if (n <= 0) return SCL_OK;
-    if (p.estimator != 0 && p.estimator != 1) { if (err) *err = "unknown estimator"; return SCL_ERR_INVALID_ARG; }
-    if (p.estimator == 1 && !(p.normal_radius > 0.0)) { if (err) *err = "normal_radius must be > 0"; return SCL_ERR_INVALID_ARG; }
-    if (p.max_iterations < 1) { if (err) *err = "max_iterations < 1"; return SCL_ERR_INVALID_ARG; }
+    if (const char *bad = icp_params_bad(p)) { if (err) *err = bad; return SCL_ERR_INVALID_ARG; }
     int rc, max_n = 0;
     for (int c = 0; c < n; ++c) {
-        IcpWorkspace *ws = wss[c];
-        const int n_tgt = n_tgts[c];
-        if ((rc = check_cloud_args(n_src, n_tgt, stride, err))) return rc;
-        if ((rc = ensure(ws, B_WORK, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
-        if ((rc = ensure(ws, B_NNQ, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
-        if ((rc = ensure(ws, B_FLAG, sizeof(int) * ((size_t)(n_src > n_tgt ? n_src : n_tgt) / kTileQ + 2), err))) return rc;
-        if ((rc = ensure(ws, B_NNI, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
-        if ((rc = ensure(ws, B_NND, sizeof(float) * (size_t)(n_src + 1), err))) return rc;
-        if ((rc = ensure(ws, B_PART, part_bytes(n_src), err))) return rc;
+        if ((rc = check_cloud_args(n_src, n_tgts[c], stride, err))) return rc;
+        if ((rc = ensure_alignment(wss[c], n_src, n_tgts[c], err))) return rc;
     }
     const GridJob *dj = nullptr;
     if ((rc = grid_build_batch(wss, n, ctl, stream, d_tgts, n_tgts, stride, p.estimator == 1, &dj, &max_n, err))) return rc;
@@ -2731,10 +2752,12 @@ int icp_batch_prepare_all(IcpWorkspace *const *wss, int n, IcpWorkspace *ctl, hi
     return SCL_OK;
 }
 
-static void fill_problem(IcpProblem *hp, IcpWorkspace *ws, bool normals)
+// The device's view of one prepared alignment or candidate.  work: another working cloud than the workspace's own (the unguessed
+// verification's candidates share ctl's); sorted: another order of the grid's points than the scatter's (the plane scoring's B_TORD).
+static void fill_problem(IcpProblem *hp, IcpWorkspace *ws, bool normals, float4 *work = nullptr, const float4 *sorted = nullptr)
 {
-    hp->work = (float4 *)ws->buf[B_WORK]; hp->st = (IcpState *)ws->buf[B_STATE];
-    hp->cell_start = (const int *)ws->buf[B_CSTART]; hp->sorted = (const float4 *)ws->buf[B_TSORT];
+    hp->work = work ? work : (float4 *)ws->buf[B_WORK]; hp->st = (IcpState *)ws->buf[B_STATE];
+    hp->cell_start = (const int *)ws->buf[B_CSTART]; hp->sorted = sorted ? sorted : (const float4 *)ws->buf[B_TSORT];
     hp->nni = (int *)ws->buf[B_NNI]; hp->nnd = (float *)ws->buf[B_NND]; hp->part = (double *)ws->buf[B_PART];
     hp->tgt = (const unsigned char *)(ws->ext_tgt ? ws->ext_tgt : ws->buf[B_TGT]); hp->normals = normals ? (const float4 *)ws->buf[B_NORM] : nullptr;
     hp->nnq = (float4 *)ws->buf[B_NNQ]; hp->flag = (int *)ws->buf[B_FLAG];
@@ -3204,6 +3227,112 @@ int icp_geometric_verification_staged(IcpWorkspace *ws, hipStream_t stream, int 
 
 const void *icp_staged_cloud(const IcpWorkspace *ws, bool target) { return ws->buf[target ? B_TGT : B_SRC]; }
 
+// ---- one round of candidates: what the verification and the two scorings share -------------------------------------------------
+// m candidates of ONE source, their targets read in place, one chain of launches and one wait.  A caller: round_check, round_begin
+// (buffers, grids, problem table), its own job records from r.hp, round_start (job records, moved sources), its own kernels around
+// round_search (the cold search), round_finish (the wait: m out records in ctl->pinned).
+struct CandidateRound {
+    IcpWorkspace *const *wss; int m; IcpWorkspace *ctl; hipStream_t stream; int n_src, stride;
+    size_t job_bytes, out_bytes;                 // of one job and one out record
+    int max_tgt;                                 // points of the largest target
+    std::vector<IcpProblem> hp;                  // the problem table as uploaded: a job record is made of its pointers
+    // the round's device tables (round_tables), m entries each; order and rows are nullptr where the round has none
+    const IcpProblem *problems; void *jobs, *outs; const OrderJob *order; float *rows;
+};
+
+// every candidate as the batch functions require it; name = the caller's, for the message
+static int round_check(const char *name, int m, bool have_src, int n_src, const void *const *d_tgts, const int *n_tgts, int stride, std::string *err)
+{
+    int rc;
+    if (n_src < 1 || !have_src) { if (err) *err = std::string(name) + ": no source"; return SCL_ERR_INVALID_ARG; }
+    for (int c = 0; c < m; ++c) {
+        if ((rc = check_cloud_args(n_src, n_tgts[c], stride, err))) return rc;
+        if (n_tgts[c] < 1 || !d_tgts[c]) { if (err) *err = std::string(name) + ": empty target"; return SCL_ERR_INVALID_ARG; }
+    }
+    return SCL_OK;
+}
+
+// The round's tables in ONE buffer of ctl (B_PAIR, a slot no candidate's workspace uses in a round): the problems, the caller's
+// jobs and outs, the OrderJobs and 12 floats per candidate, each on a 16-byte boundary -> the bytes in all.
+static size_t round_tables(CandidateRound *r, bool order, bool rows)
+{
+    unsigned char *base = static_cast<unsigned char *>(r->ctl->buf[B_PAIR]);
+    size_t at = 0;
+    auto take = [&](size_t bytes) {                             // m records of `bytes` (0: no such table)
+        unsigned char *p = base && bytes ? base + at : nullptr;
+        at += (bytes * (size_t)r->m + 15) & ~(size_t)15;
+        return p;
+    };
+    r->problems = reinterpret_cast<const IcpProblem *>(take(sizeof(IcpProblem)));
+    r->jobs = take(r->job_bytes);
+    r->outs = take(r->out_bytes);
+    r->order = reinterpret_cast<const OrderJob *>(take(order ? sizeof(OrderJob) : 0));
+    r->rows = reinterpret_cast<float *>(take(rows ? sizeof(float) * 12 : 0));
+    return at;
+}
+
+// Buffers (every candidate: B_NNI, B_NND, B_PART of part_bytes, a working cloud of its own unless shared_work serves all; plane:
+// B_TORD), the grids (plane: with room for the normals), the problem table and, plane, the OrderJobs.  Every device pointer is
+// taken behind the last ensure of its slot.
+static int round_begin(CandidateRound *r, const void *const *d_tgts, const int *n_tgts, float4 *shared_work, bool plane, size_t part_bytes,
+                       bool rows, std::string *err)
+{
+    int rc;
+    IcpWorkspace *ctl = r->ctl;
+    const int m = r->m, n_src = r->n_src;
+    if ((rc = ensure(ctl, B_PAIR, round_tables(r, plane, rows), err))) return rc;
+    round_tables(r, plane, rows);                                // (again: the pointers into the buffer that stays)
+    if ((rc = pinned(ctl, r->out_bytes * (size_t)m, err))) return rc;
+    for (int c = 0; c < m; ++c) {
+        IcpWorkspace *ws = r->wss[c];
+        if (!shared_work && (rc = ensure(ws, B_WORK, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
+        if ((rc = ensure(ws, B_NNI, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
+        if ((rc = ensure(ws, B_NND, sizeof(float) * (size_t)(n_src + 1), err))) return rc;
+        if ((rc = ensure(ws, B_PART, part_bytes, err))) return rc;
+        if (plane && (rc = ensure(ws, B_TORD, sizeof(float4) * (size_t)(n_tgts[c] + 1), err))) return rc;
+    }
+    const GridJob *dj = nullptr;
+    if ((rc = grid_build_batch(r->wss, m, ctl, r->stream, d_tgts, n_tgts, r->stride, plane, &dj, &r->max_tgt, err))) return rc;
+    r->hp.assign((size_t)m, IcpProblem{});
+    std::vector<OrderJob> ho(plane ? (size_t)m : 0);
+    for (int c = 0; c < m; ++c) {
+        IcpWorkspace *ws = r->wss[c];
+        IcpProblem &p = r->hp[(size_t)c];
+        fill_problem(&p, ws, plane, shared_work, plane ? (const float4 *)ws->buf[B_TORD] : nullptr);   // (plane: the grid's points, every cell in index order)
+        if (plane) ho[(size_t)c] = OrderJob{p.st, p.cell_start, (const float4 *)ws->buf[B_TSORT], (float4 *)ws->buf[B_TORD], n_tgts[c]};
+    }
+    ICP_HIP(hipMemcpyAsync(const_cast<IcpProblem *>(r->problems), r->hp.data(), sizeof(IcpProblem) * (size_t)m, hipMemcpyHostToDevice, r->stream));   // (pageable: staged before the call returns)
+    if (plane) ICP_HIP(hipMemcpyAsync(const_cast<OrderJob *>(r->order), ho.data(), sizeof(OrderJob) * (size_t)m, hipMemcpyHostToDevice, r->stream));
+    return SCL_OK;
+}
+
+// the caller's job records and, with h_rows (12 floats per candidate, rows 0 .. 2 of its motion), every candidate's own moved source
+static int round_start(CandidateRound *r, const void *h_jobs, const float *h_rows, const void *d_src, std::string *err)
+{
+    ICP_HIP(hipMemcpyAsync(r->jobs, h_jobs, r->job_bytes * (size_t)r->m, hipMemcpyHostToDevice, r->stream));   // (pageable: staged before the call returns)
+    if (!h_rows) return SCL_OK;
+    ICP_HIP(hipMemcpyAsync(r->rows, h_rows, sizeof(float) * 12 * (size_t)r->m, hipMemcpyHostToDevice, r->stream));
+    hipLaunchKernelGGL(guess_move_batch_kernel, dim3((r->n_src + 255) / 256, r->m), dim3(256), 0, r->stream, r->problems,
+                       static_cast<const unsigned char *>(d_src), r->n_src, r->stride, (const float *)r->rows);
+    return SCL_OK;
+}
+
+// every source's nearest target point, cold (DM.h:1211-1215)
+static void round_search(const CandidateRound &r)
+{
+    hipLaunchKernelGGL(nn_search_batch_kernel<kNnGroup>, dim3((unsigned)(((long long)r.n_src * kNnGroup + 255) / 256), r.m), dim3(256), 0, r.stream,
+                       r.problems, r.n_src, 0, -1, r.stride, 0);
+}
+
+// the one wait: the m out records are in ctl->pinned behind it
+static int round_finish(const CandidateRound &r, std::string *err)
+{
+    ICP_HIP(hipGetLastError());
+    ICP_HIP(hipMemcpyAsync(r.ctl->pinned, r.outs, r.out_bytes * (size_t)r.m, hipMemcpyDeviceToHost, r.stream));
+    ICP_HIP(hipStreamSynchronize(r.stream));
+    return SCL_OK;
+}
+
 // geometricVerificationService's core for m candidates of one source: the source staged in ctl (icp_stage_cloud*), the targets on
 // the device and read in place, every candidate with at least one point (and n_src >= 1): the caller answers the others itself.
 // One chain of launches over all candidates, one wait.  Outputs have m entries, none may be nullptr.
@@ -3217,65 +3346,39 @@ int icp_geometric_verification_batch(IcpWorkspace *const *wss, int m, IcpWorkspa
 {
     if (m <= 0) return SCL_OK;
     int rc;
-    if (n_src < 1) { if (err) *err = "geometric verification batch: no source"; return SCL_ERR_INVALID_ARG; }
-    for (int c = 0; c < m; ++c) {
-        if ((rc = check_cloud_args(n_src, n_tgts[c], stride, err))) return rc;
-        if (n_tgts[c] < 1 || !d_tgts[c]) { if (err) *err = "geometric verification batch: empty target"; return SCL_ERR_INVALID_ARG; }
-    }
+    if ((rc = round_check("geometric verification batch", m, true, n_src, d_tgts, n_tgts, stride, err))) return rc;
     const bool sample = n_src >= 3;                              // (below three sources no candidate has three pairs: the pairs are only counted)
     if (sample && (ransac_iterations < 1 || ransac_iterations > (1 << 20))) { if (err) *err = "ransac iterations out of range"; return SCL_ERR_INVALID_ARG; }
     const int n_hyp = sample ? ransac_iterations : 0;
-    const GridJob *dj = nullptr;
-    int max_n = 0;
     if (!guesses && (rc = ensure(ctl, B_WORK, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
-    if ((rc = ensure(ctl, B_MASK, sizeof(IcpProblem) * (size_t)m, err))) return rc;
-    if ((rc = ensure(ctl, B_PAIR, (sizeof(VerifyJob) + sizeof(VerifyOut) + (guesses ? sizeof(float) * 12 : 0)) * (size_t)m, err))) return rc;
-    if ((rc = pinned(ctl, sizeof(VerifyOut) * (size_t)m, err))) return rc;
     for (int c = 0; c < m; ++c) {
         IcpWorkspace *ws = wss[c];
-        if ((rc = ensure(ws, B_NNI, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
-        if ((rc = ensure(ws, B_NND, sizeof(float) * (size_t)(n_src + 1), err))) return rc;
         if ((rc = ensure(ws, B_SI, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
         if ((rc = ensure(ws, B_TI, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
         if ((rc = ensure(ws, B_MASK, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
         if ((rc = ensure(ws, B_HYP, sizeof(int) * (size_t)(n_hyp + 8), err))) return rc;
-        if ((rc = ensure(ws, B_PART, sizeof(double) * kNSum * kRedBlocks, err))) return rc;
-        if (guesses && (rc = ensure(ws, B_WORK, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
     }
     const unsigned char *d_src = static_cast<const unsigned char *>(ctl->buf[B_SRC]);
     float4 *work = guesses ? nullptr : static_cast<float4 *>(ctl->buf[B_WORK]);
     const int pb = (n_src + 255) / 256;
     // the working cloud in SOURCE order (the pairs are defined in it), one for all candidates: the cold search only reads it
     if (!guesses) hipLaunchKernelGGL(work_init_kernel, dim3(pb), dim3(256), 0, stream, d_src, n_src, stride, work);
-    if ((rc = grid_build_batch(wss, m, ctl, stream, d_tgts, n_tgts, stride, false, &dj, &max_n, err))) return rc;
-    std::vector<IcpProblem> hp((size_t)m);
+    CandidateRound r{wss, m, ctl, stream, n_src, stride, sizeof(VerifyJob), sizeof(VerifyOut)};
+    if ((rc = round_begin(&r, d_tgts, n_tgts, work, false, sizeof(double) * kNSum * kRedBlocks, guesses != nullptr, err))) return rc;
     std::vector<VerifyJob> hj((size_t)m);
     for (int c = 0; c < m; ++c) {
         IcpWorkspace *ws = wss[c];
-        IcpProblem &p = hp[(size_t)c];
-        std::memset(&p, 0, sizeof(p));
-        p.work = guesses ? static_cast<float4 *>(ws->buf[B_WORK]) : work; p.st = (IcpState *)ws->buf[B_STATE]; p.cell_start = (const int *)ws->buf[B_CSTART];
-        p.sorted = (const float4 *)ws->buf[B_TSORT]; p.nni = (int *)ws->buf[B_NNI]; p.nnd = (float *)ws->buf[B_NND];
-        p.tgt = static_cast<const unsigned char *>(d_tgts[c]); p.n_tgt = n_tgts[c];
+        const IcpProblem &p = r.hp[(size_t)c];
         VerifyJob &j = hj[(size_t)c];
         j.src = guesses ? reinterpret_cast<const unsigned char *>(p.work) : d_src; j.sstride = guesses ? (int)sizeof(float4) : stride;
         j.tgt = p.tgt; j.st = p.st; j.nni = p.nni;
         j.si = (int *)ws->buf[B_SI]; j.ti = (int *)ws->buf[B_TI]; j.mask = (int *)ws->buf[B_MASK];
         j.counts = (int *)ws->buf[B_HYP]; j.best = j.counts + n_hyp + 2; j.n_corr = j.counts + n_hyp + 4;
-        j.part = (double *)ws->buf[B_PART];
+        j.part = p.part;
     }
-    VerifyJob *djobs = static_cast<VerifyJob *>(ctl->buf[B_PAIR]);
-    VerifyOut *dout = reinterpret_cast<VerifyOut *>(djobs + m);
-    const IcpProblem *dp = static_cast<const IcpProblem *>(ctl->buf[B_MASK]);
-    ICP_HIP(hipMemcpyAsync(ctl->buf[B_MASK], hp.data(), sizeof(IcpProblem) * (size_t)m, hipMemcpyHostToDevice, stream));   // (pageable: staged before the call returns)
-    ICP_HIP(hipMemcpyAsync(djobs, hj.data(), sizeof(VerifyJob) * (size_t)m, hipMemcpyHostToDevice, stream));
-    if (guesses) {                                                                                 // every candidate's own source, one launch
-        float *dg = reinterpret_cast<float *>(dout + m);
-        ICP_HIP(hipMemcpyAsync(dg, guesses, sizeof(float) * 12 * (size_t)m, hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(guess_move_batch_kernel, dim3(pb, m), dim3(256), 0, stream, dp, d_src, n_src, stride, (const float *)dg);
-    }
-    hipLaunchKernelGGL(nn_search_batch_kernel<kNnGroup>, dim3((unsigned)(((long long)n_src * kNnGroup + 255) / 256), m), dim3(256), 0, stream,
-                       dp, n_src, 0, -1, stride, 0);                                               // DM.h:1211-1215, cold
+    if ((rc = round_start(&r, hj.data(), guesses, d_src, err))) return rc;   // (guesses: every candidate's own source)
+    round_search(r);
+    const VerifyJob *djobs = static_cast<const VerifyJob *>(r.jobs);
     hipLaunchKernelGGL(verify_pairs_batch_kernel, dim3(m), dim3(1024), 0, stream, djobs, n_src);
     if (sample) {
         const double thr2 = inlier_threshold * inlier_threshold;
@@ -3288,11 +3391,9 @@ int icp_geometric_verification_batch(IcpWorkspace *const *wss, int m, IcpWorkspa
         if (use_mfma_reduce()) hipLaunchKernelGGL(verify_reduce_batch_kernel<true>, dim3(rb, m), dim3(256), 0, stream, djobs, stride, n_src);   // DM.h:1228-1230
         else hipLaunchKernelGGL(verify_reduce_batch_kernel<false>, dim3(rb, m), dim3(256), 0, stream, djobs, stride, n_src);
     }
-    hipLaunchKernelGGL(verify_solve_batch_kernel, dim3(m), dim3(64), 0, stream, djobs, n_src, dout);
-    ICP_HIP(hipGetLastError());
-    VerifyOut *h = static_cast<VerifyOut *>(ctl->pinned);
-    ICP_HIP(hipMemcpyAsync(h, dout, sizeof(VerifyOut) * (size_t)m, hipMemcpyDeviceToHost, stream));
-    ICP_HIP(hipStreamSynchronize(stream));
+    hipLaunchKernelGGL(verify_solve_batch_kernel, dim3(m), dim3(64), 0, stream, djobs, n_src, static_cast<VerifyOut *>(r.outs));
+    if ((rc = round_finish(r, err))) return rc;
+    const VerifyOut *h = static_cast<const VerifyOut *>(ctl->pinned);
     for (int c = 0; c < m; ++c) {
         const int n_corr = h[c].n_corr, n_inl = h[c].n_inl;
         for (int k = 0; k < 16; ++k) T[16 * (size_t)c + k] = (k % 5 == 0) ? 1.f : 0.f;
@@ -3307,63 +3408,31 @@ int icp_geometric_verification_batch(IcpWorkspace *const *wss, int m, IcpWorkspa
 
 // The scoring of m registrations of ONE source (d_src on the device, n_src >= 1 points, read in place) against the candidates'
 // targets (on the device, n_tgts[c] >= 1 points, read in place): transforms = 12 floats per candidate, rows 0 .. 2 of T_c.  One
-// chain on the stream -- moved sources, grids, cold search, eval_reduce_batch_kernel, eval_finish_batch_kernel -- and one wait.
+// round -- moved sources, grids, cold search, eval_reduce_batch_kernel, eval_finish_batch_kernel -- and one wait.
 // n_valid and n_inliers have m entries, moments 10 * m; none may be nullptr.  The moved clouds, nni / nnd and the records live in
-// the candidates' grow-only workspaces (B_WORK, B_NNI, B_NND, B_PART), the tables in ctl as in icp_geometric_verification_batch.
+// the candidates' grow-only workspaces (B_WORK, B_NNI, B_NND, B_PART), the tables in ctl.
 int icp_registration_eval_batch(IcpWorkspace *const *wss, int m, IcpWorkspace *ctl, hipStream_t stream, const void *d_src, int n_src,
                                 const void *const *d_tgts, const int *n_tgts, int stride, const float *transforms, float maxd2,
                                 int *n_valid, int *n_inliers, double *moments, std::string *err)
 {
     if (m <= 0) return SCL_OK;
     int rc;
-    if (n_src < 1 || !d_src) { if (err) *err = "registration eval batch: no source"; return SCL_ERR_INVALID_ARG; }
-    for (int c = 0; c < m; ++c) {
-        if ((rc = check_cloud_args(n_src, n_tgts[c], stride, err))) return rc;
-        if (n_tgts[c] < 1 || !d_tgts[c]) { if (err) *err = "registration eval batch: empty target"; return SCL_ERR_INVALID_ARG; }
-    }
-    const GridJob *dj = nullptr;
-    int max_n = 0;
+    if ((rc = round_check("registration eval batch", m, d_src != nullptr, n_src, d_tgts, n_tgts, stride, err))) return rc;
     const int eb = eval_blocks(n_src);
-    if ((rc = ensure(ctl, B_MASK, sizeof(IcpProblem) * (size_t)m, err))) return rc;
-    if ((rc = ensure(ctl, B_PAIR, (sizeof(EvalJob) + sizeof(EvalOut) + sizeof(float) * 12) * (size_t)m, err))) return rc;
-    if ((rc = pinned(ctl, sizeof(EvalOut) * (size_t)m, err))) return rc;
-    for (int c = 0; c < m; ++c) {
-        IcpWorkspace *ws = wss[c];
-        if ((rc = ensure(ws, B_WORK, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
-        if ((rc = ensure(ws, B_NNI, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
-        if ((rc = ensure(ws, B_NND, sizeof(float) * (size_t)(n_src + 1), err))) return rc;
-        if ((rc = ensure(ws, B_PART, sizeof(double) * (kNEval + 1) * kEvalBlocks, err))) return rc;
-    }
-    if ((rc = grid_build_batch(wss, m, ctl, stream, d_tgts, n_tgts, stride, false, &dj, &max_n, err))) return rc;
-    std::vector<IcpProblem> hp((size_t)m);
+    CandidateRound r{wss, m, ctl, stream, n_src, stride, sizeof(EvalJob), sizeof(EvalOut)};
+    if ((rc = round_begin(&r, d_tgts, n_tgts, nullptr, false, sizeof(double) * (kNEval + 1) * kEvalBlocks, true, err))) return rc;
     std::vector<EvalJob> hj((size_t)m);
     for (int c = 0; c < m; ++c) {
-        IcpWorkspace *ws = wss[c];
-        IcpProblem &p = hp[(size_t)c];
-        std::memset(&p, 0, sizeof(p));
-        p.work = static_cast<float4 *>(ws->buf[B_WORK]); p.st = (IcpState *)ws->buf[B_STATE]; p.cell_start = (const int *)ws->buf[B_CSTART];
-        p.sorted = (const float4 *)ws->buf[B_TSORT]; p.nni = (int *)ws->buf[B_NNI]; p.nnd = (float *)ws->buf[B_NND];
-        p.tgt = static_cast<const unsigned char *>(d_tgts[c]); p.n_tgt = n_tgts[c];
-        EvalJob &j = hj[(size_t)c];
-        j.tgt = p.tgt; j.nni = p.nni; j.nnd = p.nnd; j.part = (double *)ws->buf[B_PART];
+        const IcpProblem &p = r.hp[(size_t)c];
+        hj[(size_t)c] = EvalJob{p.tgt, p.nni, p.nnd, p.part};
     }
-    EvalJob *djobs = static_cast<EvalJob *>(ctl->buf[B_PAIR]);
-    EvalOut *dout = reinterpret_cast<EvalOut *>(djobs + m);
-    float *dt = reinterpret_cast<float *>(dout + m);
-    const IcpProblem *dp = static_cast<const IcpProblem *>(ctl->buf[B_MASK]);
-    ICP_HIP(hipMemcpyAsync(ctl->buf[B_MASK], hp.data(), sizeof(IcpProblem) * (size_t)m, hipMemcpyHostToDevice, stream));   // (pageable: staged before the call returns)
-    ICP_HIP(hipMemcpyAsync(djobs, hj.data(), sizeof(EvalJob) * (size_t)m, hipMemcpyHostToDevice, stream));
-    ICP_HIP(hipMemcpyAsync(dt, transforms, sizeof(float) * 12 * (size_t)m, hipMemcpyHostToDevice, stream));
-    const int pb = (n_src + 255) / 256;
-    hipLaunchKernelGGL(guess_move_batch_kernel, dim3(pb, m), dim3(256), 0, stream, dp, static_cast<const unsigned char *>(d_src), n_src, stride, (const float *)dt);
-    hipLaunchKernelGGL(nn_search_batch_kernel<kNnGroup>, dim3((unsigned)(((long long)n_src * kNnGroup + 255) / 256), m), dim3(256), 0, stream,
-                       dp, n_src, 0, -1, stride, 0);                                               // cold
-    hipLaunchKernelGGL(eval_reduce_batch_kernel, dim3(eb, m), dim3(256), 0, stream, (const EvalJob *)djobs, stride, n_src, maxd2);
-    hipLaunchKernelGGL(eval_finish_batch_kernel, dim3(m), dim3(64), 0, stream, (const EvalJob *)djobs, eb, dout);
-    ICP_HIP(hipGetLastError());
-    EvalOut *h = static_cast<EvalOut *>(ctl->pinned);
-    ICP_HIP(hipMemcpyAsync(h, dout, sizeof(EvalOut) * (size_t)m, hipMemcpyDeviceToHost, stream));
-    ICP_HIP(hipStreamSynchronize(stream));
+    if ((rc = round_start(&r, hj.data(), transforms, d_src, err))) return rc;
+    round_search(r);
+    const EvalJob *djobs = static_cast<const EvalJob *>(r.jobs);
+    hipLaunchKernelGGL(eval_reduce_batch_kernel, dim3(eb, m), dim3(256), 0, stream, djobs, stride, n_src, maxd2);
+    hipLaunchKernelGGL(eval_finish_batch_kernel, dim3(m), dim3(64), 0, stream, djobs, eb, static_cast<EvalOut *>(r.outs));
+    if ((rc = round_finish(r, err))) return rc;
+    const EvalOut *h = static_cast<const EvalOut *>(ctl->pinned);
     for (int c = 0; c < m; ++c) {
         n_valid[c] = h[c].n_valid; n_inliers[c] = h[c].n_inl;
         std::memcpy(moments + (size_t)kNEval * c, h[c].s, sizeof(double) * kNEval);
@@ -3371,7 +3440,7 @@ int icp_registration_eval_batch(IcpWorkspace *const *wss, int m, IcpWorkspace *c
     return SCL_OK;
 }
 
-// icp_registration_eval_batch against planes: the same chain with the targets' normals (normals_problems_kernel at normal_radius,
+// icp_registration_eval_batch against planes: the same round with the targets' normals (normals_problems_kernel at normal_radius,
 // behind the grids, in B_NORM -- B_OUT's slot, which nothing of this chain writes) in front of the cold search, then
 // eval_plane_reduce_batch_kernel and eval_plane_finish_batch_kernel; grid_cell_order_batch_kernel behind the scatter.  n_valid,
 // n_inliers and n_planar have m entries, sums 29 * m; none may be nullptr.  B_PART holds kEvalBlocks records of kPlaneRec doubles (grow-only: never less than another batch left).
@@ -3382,62 +3451,25 @@ int icp_registration_eval_plane_batch(IcpWorkspace *const *wss, int m, IcpWorksp
     if (m <= 0) return SCL_OK;
     int rc;
     if (!(normal_radius > 0.0)) { if (err) *err = "normal_radius must be > 0"; return SCL_ERR_INVALID_ARG; }
-    if (n_src < 1 || !d_src) { if (err) *err = "registration eval plane batch: no source"; return SCL_ERR_INVALID_ARG; }
-    for (int c = 0; c < m; ++c) {
-        if ((rc = check_cloud_args(n_src, n_tgts[c], stride, err))) return rc;
-        if (n_tgts[c] < 1 || !d_tgts[c]) { if (err) *err = "registration eval plane batch: empty target"; return SCL_ERR_INVALID_ARG; }
-    }
-    const GridJob *dj = nullptr;
-    int max_n = 0;
+    if ((rc = round_check("registration eval plane batch", m, d_src != nullptr, n_src, d_tgts, n_tgts, stride, err))) return rc;
     const int eb = eval_blocks(n_src);
-    if ((rc = ensure(ctl, B_MASK, sizeof(IcpProblem) * (size_t)m, err))) return rc;
-    if ((rc = ensure(ctl, B_PAIR, (sizeof(EvalPlaneJob) + sizeof(EvalPlaneOut) + sizeof(OrderJob) + sizeof(float) * 12) * (size_t)m, err))) return rc;
-    if ((rc = pinned(ctl, sizeof(EvalPlaneOut) * (size_t)m, err))) return rc;
-    for (int c = 0; c < m; ++c) {
-        IcpWorkspace *ws = wss[c];
-        if ((rc = ensure(ws, B_WORK, sizeof(float4) * (size_t)(n_src + 1), err))) return rc;
-        if ((rc = ensure(ws, B_NNI, sizeof(int) * (size_t)(n_src + 1), err))) return rc;
-        if ((rc = ensure(ws, B_NND, sizeof(float) * (size_t)(n_src + 1), err))) return rc;
-        if ((rc = ensure(ws, B_PART, sizeof(double) * kPlaneRec * kEvalBlocks, err))) return rc;
-        if ((rc = ensure(ws, B_TORD, sizeof(float4) * (size_t)(n_tgts[c] + 1), err))) return rc;
-    }
-    if ((rc = grid_build_batch(wss, m, ctl, stream, d_tgts, n_tgts, stride, true, &dj, &max_n, err))) return rc;
-    std::vector<IcpProblem> hp((size_t)m);
+    CandidateRound r{wss, m, ctl, stream, n_src, stride, sizeof(EvalPlaneJob), sizeof(EvalPlaneOut)};
+    if ((rc = round_begin(&r, d_tgts, n_tgts, nullptr, true, sizeof(double) * kPlaneRec * kEvalBlocks, true, err))) return rc;
     std::vector<EvalPlaneJob> hj((size_t)m);
-    std::vector<OrderJob> ho((size_t)m);
     for (int c = 0; c < m; ++c) {
-        IcpWorkspace *ws = wss[c];
-        IcpProblem &p = hp[(size_t)c];
-        std::memset(&p, 0, sizeof(p));
-        p.work = static_cast<float4 *>(ws->buf[B_WORK]); p.st = (IcpState *)ws->buf[B_STATE]; p.cell_start = (const int *)ws->buf[B_CSTART];
-        p.sorted = (const float4 *)ws->buf[B_TORD]; p.nni = (int *)ws->buf[B_NNI]; p.nnd = (float *)ws->buf[B_NND];    // the grid's points, every cell in index order
-        p.tgt = static_cast<const unsigned char *>(d_tgts[c]); p.n_tgt = n_tgts[c]; p.normals = (const float4 *)ws->buf[B_NORM];
-        ho[(size_t)c] = OrderJob{p.st, p.cell_start, (const float4 *)ws->buf[B_TSORT], (float4 *)ws->buf[B_TORD], n_tgts[c]};
-        EvalPlaneJob &j = hj[(size_t)c];
-        j.tgt = p.tgt; j.nni = p.nni; j.nnd = p.nnd; j.work = p.work; j.normals = p.normals; j.part = (double *)ws->buf[B_PART];
+        const IcpProblem &p = r.hp[(size_t)c];
+        hj[(size_t)c] = EvalPlaneJob{p.tgt, p.nni, p.nnd, p.work, p.normals, p.part};
     }
-    EvalPlaneJob *djobs = static_cast<EvalPlaneJob *>(ctl->buf[B_PAIR]);
-    EvalPlaneOut *dout = reinterpret_cast<EvalPlaneOut *>(djobs + m);
-    OrderJob *dord = reinterpret_cast<OrderJob *>(dout + m);
-    float *dt = reinterpret_cast<float *>(dord + m);
-    const IcpProblem *dp = static_cast<const IcpProblem *>(ctl->buf[B_MASK]);
-    ICP_HIP(hipMemcpyAsync(ctl->buf[B_MASK], hp.data(), sizeof(IcpProblem) * (size_t)m, hipMemcpyHostToDevice, stream));   // (pageable: staged before the call returns)
-    ICP_HIP(hipMemcpyAsync(djobs, hj.data(), sizeof(EvalPlaneJob) * (size_t)m, hipMemcpyHostToDevice, stream));
-    ICP_HIP(hipMemcpyAsync(dord, ho.data(), sizeof(OrderJob) * (size_t)m, hipMemcpyHostToDevice, stream));
-    ICP_HIP(hipMemcpyAsync(dt, transforms, sizeof(float) * 12 * (size_t)m, hipMemcpyHostToDevice, stream));
-    const int pb = (n_src + 255) / 256;
-    hipLaunchKernelGGL(guess_move_batch_kernel, dim3(pb, m), dim3(256), 0, stream, dp, static_cast<const unsigned char *>(d_src), n_src, stride, (const float *)dt);
-    hipLaunchKernelGGL(grid_cell_order_batch_kernel, dim3((unsigned)((max_n + 255) / 256), m), dim3(256), 0, stream, (const OrderJob *)dord);
-    hipLaunchKernelGGL(normals_problems_kernel, dim3((unsigned)(((size_t)max_n * kNormGroup + kNormBlock - 1) / kNormBlock), m), dim3(kNormBlock), 0, stream,
-                       dp, normal_radius);
-    hipLaunchKernelGGL(nn_search_batch_kernel<kNnGroup>, dim3((unsigned)(((long long)n_src * kNnGroup + 255) / 256), m), dim3(256), 0, stream,
-                       dp, n_src, 0, -1, stride, 0);                                               // cold
-    hipLaunchKernelGGL(eval_plane_reduce_batch_kernel, dim3(eb, m), dim3(256), 0, stream, (const EvalPlaneJob *)djobs, stride, n_src, maxd2);
-    hipLaunchKernelGGL(eval_plane_finish_batch_kernel, dim3(m), dim3(64), 0, stream, (const EvalPlaneJob *)djobs, eb, dout);
-    ICP_HIP(hipGetLastError());
-    EvalPlaneOut *h = static_cast<EvalPlaneOut *>(ctl->pinned);
-    ICP_HIP(hipMemcpyAsync(h, dout, sizeof(EvalPlaneOut) * (size_t)m, hipMemcpyDeviceToHost, stream));
-    ICP_HIP(hipStreamSynchronize(stream));
+    if ((rc = round_start(&r, hj.data(), transforms, d_src, err))) return rc;
+    hipLaunchKernelGGL(grid_cell_order_batch_kernel, dim3((unsigned)((r.max_tgt + 255) / 256), m), dim3(256), 0, stream, r.order);
+    hipLaunchKernelGGL(normals_problems_kernel, dim3((unsigned)(((size_t)r.max_tgt * kNormGroup + kNormBlock - 1) / kNormBlock), m), dim3(kNormBlock), 0, stream,
+                       r.problems, normal_radius);
+    round_search(r);
+    const EvalPlaneJob *djobs = static_cast<const EvalPlaneJob *>(r.jobs);
+    hipLaunchKernelGGL(eval_plane_reduce_batch_kernel, dim3(eb, m), dim3(256), 0, stream, djobs, stride, n_src, maxd2);
+    hipLaunchKernelGGL(eval_plane_finish_batch_kernel, dim3(m), dim3(64), 0, stream, djobs, eb, static_cast<EvalPlaneOut *>(r.outs));
+    if ((rc = round_finish(r, err))) return rc;
+    const EvalPlaneOut *h = static_cast<const EvalPlaneOut *>(ctl->pinned);
     for (int c = 0; c < m; ++c) {
         n_valid[c] = h[c].n_valid; n_inliers[c] = h[c].n_inl; n_planar[c] = h[c].n_planar;
         std::memcpy(sums + (size_t)kNEvalPlane * c, h[c].s, sizeof(double) * kNEvalPlane);

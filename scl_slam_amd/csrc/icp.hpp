@@ -42,6 +42,9 @@ int icp_stage_cloud_host(IcpWorkspace *ws, hipStream_t stream, bool target, cons
 int icp_align_staged(IcpWorkspace *ws, hipStream_t stream, int n_src, int n_tgt, int stride_bytes,
                      const scl_icp_params &p, float T[16], float *fitness, int *converged, int *iterations,
                      std::string *err);
+// what icp_batch_prepare and icp_batch_prepare_all refuse in the parameters: nullptr, or "unknown estimator", "normal_radius must
+// be > 0", "max_iterations < 1" (checked in that order)
+const char *icp_params_bad(const scl_icp_params &p);
 // the alignments of one scan's loop candidates, every loop step one launch for all of them (icp.hip)
 int icp_batch_prepare(IcpWorkspace *ws, hipStream_t stream, const void *d_src, int n_src, int n_tgt, int stride,
                       const scl_icp_params &p, std::string *err);
