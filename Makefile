@@ -10,7 +10,7 @@ CSRC    := scl_slam_amd/csrc
 LIBDIR  := scl_slam_amd/lib
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math \
             -fhip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-result -Iinclude -I$(CSRC) $(EXTRA)
-SRCS    := $(CSRC)/engine.hip $(CSRC)/sc_distance.hip $(CSRC)/ringkey_topk.hip $(CSRC)/make_sc.hip $(CSRC)/icp.hip $(CSRC)/voxel.hip $(CSRC)/sharded_front.hip $(CSRC)/sc_screen.hip $(CSRC)/sc_masked.hip $(CSRC)/sc_matrix.hip $(CSRC)/sc_rank.hip $(CSRC)/messages.hip $(CSRC)/iris.hip $(CSRC)/device_sort.hip $(CSRC)/m2dp.hip $(CSRC)/fpfh.hip $(CSRC)/grsd.hip
+SRCS    := $(CSRC)/engine.hip $(CSRC)/sc_distance.hip $(CSRC)/ringkey_topk.hip $(CSRC)/make_sc.hip $(CSRC)/icp.hip $(CSRC)/voxel.hip $(CSRC)/sharded_front.hip $(CSRC)/sc_screen.hip $(CSRC)/sc_masked.hip $(CSRC)/sc_matrix.hip $(CSRC)/sc_rank.hip $(CSRC)/messages.hip $(CSRC)/iris.hip $(CSRC)/device_sort.hip $(CSRC)/m2dp.hip $(CSRC)/fpfh.hip $(CSRC)/grsd.hip $(CSRC)/pcm.hip
 OBJS    := $(SRCS:.hip=.o)
 # the adapter template the M2DP, FPFH and GRSD adapters derive from, and the batch declarations their C headers share
 VP_ADAPTER := include/scl/vector_plugin_hip_descriptor.hpp include/scl_plugin_batch.h

@@ -711,6 +711,73 @@ int  scl_loop_eval_plane_batch_from_store(scl_engine *e, int robot, int key_cur,
  * = sums[21 .. 26], the sum of J r.  sums == NULL or info == NULL: SCL_ERR_INVALID_ARG, nothing written. */
 int  scl_registration_information_plane(const double sums[29], double info[36], double grad[6]);
 
+/*
+ * PAIRWISE CONSISTENCY OF LOOP CLOSURES: MATRIX, GRAPH, MAX CLIQUE.  The outlier rejection in front of a pose-graph solve (PCM, pairwise
+ * consistency maximisation; the reference hands usePCM / pcmThreshold / useHeuristics to its optimiser, DM.h:147, 296, 375-377, 533,
+ * 877-880): every pair of loops between two trajectories is tested for mutual consistency through the odometry of both robots, and the
+ * largest mutually consistent set is kept.  N loops are N (N - 1) / 2 independent SE(3) cycle tests in fp64 and a clique search on N-bit sets.
+ *   * Inputs, for one pair of trajectories A and B (A = B is allowed, and the pointers may alias).  poses_a: n_a x 7 doubles, poses_b:
+ *     n_b x 7 doubles; a pose is x, y, z and a quaternion x, y, z, w -- the layout scl_loop_pose_between writes --, X^A_k keyframe k of A in
+ *     A's world frame.  Loop i: idx_a[i] in [0, n_a), idx_b[i] in [0, n_b); z + 7 i = Z_i, the pose of B's keyframe in the frame of A's
+ *     keyframe (poseFrom.between(poseTo) with A the current robot, DM.h:1141); cov + 36 i, a row-major 6 x 6 covariance of the right
+ *     perturbation Z_i Exp(xi), rotation first (the axis order of scl_registration_information and of gtsam's Pose3), of which only the
+ *     upper triangle is read.  odom_var[6] (NULL: zeros): variance added per keyframe step -- a stated drift model; the reference has no
+ *     such term (its trajectories' covariances are not available at this boundary).  Quaternions are normalised in double before use.
+ *   * Statistic, for i < j.  With T_A = (X^A_ai)^-1 X^A_aj and T_B = (X^B_bj)^-1 X^B_bi the cycle is E = T_A Z_j T_B Z_i^-1, the identity
+ *     for two perfect loops.  Residual r = (Log_SO3(R_E), t_E): the rotation vector from the quaternion of E with w made >= 0, 2 atan2(|v|,
+ *     w) v / |v|, and 2 v where |v| = 0; the translation as it is (gtsam's default Pose3 chart).
+ *         Sigma = Ad(Z_i) Sigma_i Ad(Z_i)^T + Ad(M) Sigma_j Ad(M)^T + diag(odom_var) (|a_i - a_j| + |b_i - b_j|),
+ *         M = Z_i T_B^-1,   Ad(R, t) = [[R, 0], [[t]x R, R]],
+ *     the first-order covariance of E's right perturbation:
+ *         Z_j Exp(xi_j) moves E to T_A Z_j Exp(xi_j) (T_B Z_i^-1) = E M Exp(xi_j) M^-1   = E Exp( Ad(M)   xi_j),
+ *         Z_i Exp(xi_i) moves E to T_A Z_j T_B Exp(-xi_i) Z_i^-1  = E Z_i Exp(-xi_i) Z_i^-1 = E Exp(-Ad(Z_i) xi_i).
+ *     d2(i, j) = r^T Sigma^-1 r by a Cholesky factorisation in double; a pivot that is not > 0 (NaN included) gives d2 = +inf.  d2(j, i) =
+ *     d2(i, j) and d2(i, i) = 0 by construction: only i < j is ever computed (the statistic taken the other way round differs for large
+ *     residuals).  Everything is fp64; each pair is one fixed sequence of operations with no atomics: the same inputs give the same bits
+ *     on every run.  The covariance is first order: see DESIGN.md section 4, PCM, for where that stops being enough.
+ *   * Graph.  i and j are adjacent iff d2(i, j) <= threshold, equality kept; +inf and NaN are never adjacent.  adj: N rows of W = (N + 63)
+ *     / 64 uint64 words, bit j of row i = word j / 64, bit j % 64; the diagonal and every bit at or beyond N are zero.  degree[i]: the
+ *     popcount of row i.  threshold is a chi-square quantile with 6 degrees of freedom; for the reference's pcmThreshold (a probability):
+ *     0.75 -> 7.84080, 0.90 -> 10.6446, 0.95 -> 12.5916, 0.99 -> 16.8119.
+ *   * Clique.  The reference's useHeuristics = true path is a greedy maximum clique; this one is fully deterministic.  For every seed s:
+ *     C = {s}, P = adj[s]; while P is not empty take the u in P with the largest |adj[u] & P|, ties to the lowest u; C += u, P &= adj[u].
+ *     The answer is the largest C over all seeds, ties to the lowest seed; members in ascending order, and the winning seed.  (A seed whose
+ *     degree + 1 is strictly smaller than a clique already found may be skipped: it could not even have tied, so the answer does not
+ *     depend on timing.)  Exact maximum clique is out of scope.
+ *   * scl_pcm_consistency: d2 (n x n), adj (n x W), degree (n); each may be NULL, one must be given with n > 0.  scl_pcm_max_clique: the
+ *     clique of any graph from the host; members holds up to n entries.  scl_pcm_select: both on the device -- only the inputs and the
+ *     member list cross the bus --, equal to scl_pcm_max_clique on scl_pcm_consistency's adj; degree may be NULL.
+ *   * Errors, all SCL_ERR_INVALID_ARG, checked before anything runs, nothing written: a NULL engine; a negative count; n_loops or n > 4096;
+ *     a required pointer NULL with a positive count; no output given with n > 0; an index out of range; a non-finite pose, z, entry of
+ *     the upper triangle of a cov, odom_var or threshold; a negative odom_var or threshold; a quaternion with squared norm outside
+ *     [0.25, 4]; for scl_pcm_max_clique an adj that is not symmetric, has a diagonal bit set, or a bit at or beyond n.  n == 0: SCL_OK,
+ *     *n_members = 0, *seed = -1.
+ *   * How it runs.  A pre-pass per loop and per keyframe (normalised quaternions, Z_i^-1, Ad(Z_i) Sigma_i Ad(Z_i)^T), one thread per pair
+ *     of the upper triangle whose wave's ballot is a word of the graph, one wave per row for the lower triangle and the degrees, one wave
+ *     per seed for the clique, a finishing launch.  Memory: a grow-only workspace (the n x n matrix only when d2 is asked for); a later,
+ *     smaller call reads nothing an earlier one left.  On a scl_create_sharded engine the calls run on the primary shard, as
+ *     scl_target_normals does.
+ */
+int  scl_pcm_consistency(scl_engine *e, const double *poses_a, int n_a, const double *poses_b, int n_b,
+                         const int *idx_a, const int *idx_b, const double *z, const double *cov, int n_loops,
+                         const double *odom_var, double threshold, double *d2, uint64_t *adj, int *degree);
+int  scl_pcm_max_clique(scl_engine *e, const uint64_t *adj, int n, int *members, int *n_members, int *seed);
+int  scl_pcm_select(scl_engine *e, const double *poses_a, int n_a, const double *poses_b, int n_b,
+                    const int *idx_a, const int *idx_b, const double *z, const double *cov, int n_loops,
+                    const double *odom_var, double threshold, int *members, int *n_members, int *seed, int *degree);
+/* Device time of the last of the three calls above made while scl_profile_enable(e, 1) was in force, HIP events on the engine's stream:
+ * pairs_ms = pre-pass + pair kernel + lower triangle and degrees, clique_ms = clique kernel + finishing launch; 0 for a stage that call
+ * did not run.  Either pointer may be NULL. */
+int  scl_pcm_last_timing(scl_engine *e, double *pairs_ms, double *clique_ms);
+/* Host only, no engine: cov = s2 * info^-1 by a Cholesky factorisation in double -- the covariance a loop's factor gets from the
+ * information matrix of its pairs (scl_registration_information, scl_registration_information_plane) and a variance of a pair's
+ * residual.  A NULL pointer, a non-finite input, s2 <= 0, or an info whose factorisation fails -- a pivot that is not above 2^-43 of its
+ * diagonal entry, which rounding can leave of a column that depends on the ones before it --: SCL_ERR_INVALID_ARG, nothing written.
+ * That test also refuses a positive definite info whose condition number is beyond about 1e13 (a Schur complement below 2^-43 of its
+ * diagonal entry); the tests cover condition numbers up to 1e8.  A corridor's singular point-to-plane matrix is such an input: the caller regularises it first
+ * (adds a prior to its diagonal).  Only the upper triangle of info is read; cov is written symmetric. */
+int  scl_loop_covariance(const double info[36], double s2, double cov[36]);
+
 /* ---- measurement ----------------------------------------------------------- */
 int  scl_profile_enable(scl_engine *e, int on);   /* 0 off, 1 every kernel family, 2 SC distance only,
                                                      3 SC distance only, sampled: one launch in thirteen -- in the stream form one

@@ -504,7 +504,7 @@ const char *scl_status_string(int status)
 
 const char *scl_last_error(const scl_engine *e) { return e ? e->last_error.c_str() : "null engine"; }
 
-int scl_abi_version(void) { return 11; }
+int scl_abi_version(void) { return 12; }
 
 int scl_default_config(scl_config *c)
 {
@@ -658,6 +658,7 @@ int scl_destroy(scl_engine *e)
     for (int i = 0; i < scl_engine::kIcpBatch; ++i) icp_workspace_free(&e->icp_batch_ws[i]);
     for (int i = 0; i < scl_engine::kIcpLanes; ++i) icp_workspace_free(&e->vox_lane_ws[i]);
     icp_workspace_free(&e->icp_batch_ctl);
+    pcm_workspace_free(&e->pcm_ws);
     for (int i = 0; i < scl_engine::kIcpLanes; ++i) {
         if (e->ev_lane[i]) (void)hipEventDestroy(e->ev_lane[i]);
         icp_workspace_free(&e->icp_lane_ws[i]);
@@ -4220,6 +4221,120 @@ int scl_registration_information_plane(const double sums[29], double info[36], d
     for (int a = 0; a < 6; ++a)
         for (int b = a; b < 6; ++b) { info[6 * a + b] = sums[t]; info[6 * b + a] = sums[t]; ++t; }
     if (grad) for (int a = 0; a < 6; ++a) grad[a] = sums[21 + a];
+    return SCL_OK;
+}
+
+/* ---- pairwise consistency of loop closures: matrix, graph, max clique (pcm.hip) ------ */
+
+namespace {
+
+// scl_pcm_consistency (members == nullptr) and scl_pcm_select
+int pcm_call(scl_engine *e, const PcmInputs &in, double *d2, uint64_t *adj, int *degree, int *members, int *n_members, int *seed, bool select)
+{
+    if (!e) return SCL_ERR_INVALID_ARG;
+    if (e->front) {                                        // the primary shard does the work; its message goes to the handle the caller holds
+        scl_engine *front = e;
+        const int rc = pcm_call(front_primary(e), in, d2, adj, degree, members, n_members, seed, select);
+        if (rc) front->last_error = scl_last_error(front_primary(front));
+        return rc;
+    }
+    std::lock_guard<std::mutex> lk(e->mu);
+    const std::string name = select ? "pcm_select: " : "pcm_consistency: ";
+    if (const char *bad = pcm_inputs_bad(in)) return fail(e, SCL_ERR_INVALID_ARG, (name + bad).c_str());
+    if (select && (!n_members || !seed || (in.n_loops > 0 && !members))) return fail(e, SCL_ERR_INVALID_ARG, (name + "members, n_members or seed is NULL").c_str());
+    if (!select && in.n_loops > 0 && !d2 && !adj && !degree) return fail(e, SCL_ERR_INVALID_ARG, (name + "no output given").c_str());
+    if (in.n_loops == 0) {
+        if (select) { *n_members = 0; *seed = -1; }
+        return SCL_OK;
+    }
+    (void)hipSetDevice(e->device);
+    std::string err;
+    const int rc = pcm_consistency(&e->pcm_ws, e->stream, in, d2, adj, degree, select ? members : nullptr, n_members, seed, e->prof_on == 1, &err);
+    if (rc) e->last_error = err;
+    return rc;
+}
+
+}  // namespace
+
+int scl_pcm_consistency(scl_engine *e, const double *poses_a, int n_a, const double *poses_b, int n_b,
+                        const int *idx_a, const int *idx_b, const double *z, const double *cov, int n_loops,
+                        const double *odom_var, double threshold, double *d2, uint64_t *adj, int *degree)
+{
+    const PcmInputs in = {poses_a, n_a, poses_b, n_b, idx_a, idx_b, z, cov, n_loops, odom_var, threshold};
+    return pcm_call(e, in, d2, adj, degree, nullptr, nullptr, nullptr, false);
+}
+
+int scl_pcm_select(scl_engine *e, const double *poses_a, int n_a, const double *poses_b, int n_b,
+                   const int *idx_a, const int *idx_b, const double *z, const double *cov, int n_loops,
+                   const double *odom_var, double threshold, int *members, int *n_members, int *seed, int *degree)
+{
+    const PcmInputs in = {poses_a, n_a, poses_b, n_b, idx_a, idx_b, z, cov, n_loops, odom_var, threshold};
+    return pcm_call(e, in, nullptr, nullptr, degree, members, n_members, seed, true);
+}
+
+int scl_pcm_max_clique(scl_engine *e, const uint64_t *adj, int n, int *members, int *n_members, int *seed)
+{
+    if (!e) return SCL_ERR_INVALID_ARG;
+    if (e->front) {
+        const int rc = scl_pcm_max_clique(front_primary(e), adj, n, members, n_members, seed);
+        if (rc) e->last_error = scl_last_error(front_primary(e));
+        return rc;
+    }
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!n_members || !seed || (n > 0 && !members)) return fail(e, SCL_ERR_INVALID_ARG, "pcm_max_clique: members, n_members or seed is NULL");
+    if (const char *bad = pcm_graph_bad(adj, n)) return fail(e, SCL_ERR_INVALID_ARG, (std::string("pcm_max_clique: ") + bad).c_str());
+    if (n == 0) { *n_members = 0; *seed = -1; return SCL_OK; }
+    (void)hipSetDevice(e->device);
+    std::string err;
+    const int rc = pcm_max_clique(&e->pcm_ws, e->stream, adj, n, members, n_members, seed, e->prof_on == 1, &err);
+    if (rc) e->last_error = err;
+    return rc;
+}
+
+int scl_pcm_last_timing(scl_engine *e, double *pairs_ms, double *clique_ms)
+{
+    if (!e) return SCL_ERR_INVALID_ARG;
+    if (e->front) e = front_primary(e);
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (pairs_ms) *pairs_ms = e->pcm_ws.pairs_ms;
+    if (clique_ms) *clique_ms = e->pcm_ws.clique_ms;
+    return SCL_OK;
+}
+
+int scl_loop_covariance(const double info[36], double s2, double cov[36])
+{
+    if (!info || !cov || !(s2 > 0.0) || !std::isfinite(s2)) return SCL_ERR_INVALID_ARG;
+    for (int k = 0; k < 36; ++k) if (!std::isfinite(info[k])) return SCL_ERR_INVALID_ARG;
+    // info = L L^T from the upper triangle; a column that depends on the ones before it leaves a pivot of rounding's size
+    double L[6][6] = {{0.0}};
+    for (int c = 0; c < 6; ++c) {
+        double s = info[6 * c + c];
+        for (int k = 0; k < c; ++k) s -= L[c][k] * L[c][k];
+        if (!(s > std::ldexp(info[6 * c + c], -43))) return SCL_ERR_INVALID_ARG;
+        L[c][c] = std::sqrt(s);
+        for (int r = c + 1; r < 6; ++r) {
+            double v = info[6 * c + r];
+            for (int k = 0; k < c; ++k) v -= L[r][k] * L[c][k];
+            L[r][c] = v / L[c][c];
+        }
+    }
+    // Y = L^-1 (lower triangular, column by column), info^-1 = Y^T Y
+    double Y[6][6] = {{0.0}};
+    for (int c = 0; c < 6; ++c)
+        for (int r = c; r < 6; ++r) {
+            double v = r == c ? 1.0 : 0.0;
+            for (int k = c; k < r; ++k) v -= L[r][k] * Y[k][c];
+            Y[r][c] = v / L[r][r];
+        }
+    double out[36];
+    for (int a = 0; a < 6; ++a)
+        for (int b = a; b < 6; ++b) {
+            double v = 0.0;
+            for (int k = b; k < 6; ++k) v += Y[k][a] * Y[k][b];
+            out[6 * a + b] = out[6 * b + a] = s2 * v;
+        }
+    for (int k = 0; k < 36; ++k) if (!std::isfinite(out[k])) return SCL_ERR_INVALID_ARG;
+    std::memcpy(cov, out, sizeof out);
     return SCL_OK;
 }
 

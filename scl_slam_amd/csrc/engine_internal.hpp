@@ -13,6 +13,7 @@
 
 #include "icp.hpp"
 #include "kernels.hpp"
+#include "pcm.hpp"
 
 namespace scl {
 
@@ -167,6 +168,7 @@ struct scl_engine {
     scl::IcpWorkspace icp_batch_ctl;
     hipEvent_t ev_lane[kIcpLanes] = {nullptr};
     hipStream_t icp_lane_stream[kIcpLanes] = {nullptr};
+    scl::PcmWorkspace pcm_ws;                              // pairwise consistency of loop closures (pcm.hip)
 
     // on-device keyframe store (robots[id].keyFrameArray, DM.h:86): clouds live in slabs of HBM, bump allocated
     struct StoredCloud { unsigned char *d = nullptr; int n = -1; size_t cap_bytes = 0; };

@@ -157,6 +157,11 @@ def _bind(lib):
         "scl_loop_eval_plane_batch_from_store": (c_int, [P, c_int, c_int, fp, c_int, ip, c_int, fp, c_float, fp, c_int, c_int, c_double, c_double,
                                                          ip, ip, ip, dp, ip, ip]),
         "scl_registration_information_plane": (c_int, [dp, dp, dp]),
+        "scl_pcm_consistency": (c_int, [P, dp, c_int, dp, c_int, ip, ip, dp, dp, c_int, dp, c_double, dp, POINTER(c_uint64), ip]),
+        "scl_pcm_max_clique": (c_int, [P, POINTER(c_uint64), c_int, ip, ip, ip]),
+        "scl_pcm_select": (c_int, [P, dp, c_int, dp, c_int, ip, ip, dp, dp, c_int, dp, c_double, ip, ip, ip, ip]),
+        "scl_pcm_last_timing": (c_int, [P, dp, dp]),
+        "scl_loop_covariance": (c_int, [dp, c_double, dp]),
         "scl_profile_enable": (c_int, [P, c_int]),
         "scl_profile_reset": (c_int, [P]),
         "scl_profile_get": (c_int, [P, POINTER(SclProfile)]),
@@ -251,6 +256,36 @@ class RegistrationPlaneEval:
         """sqrt(sum r r / n_planar): the root mean square point-to-plane distance of candidate c, NaN without a planar inlier"""
         m = int(self.n_planar[c])
         return float(np.sqrt(self.sums[c, 27] / m)) if m > 0 else float("nan")
+
+
+class PcmConsistency:
+    """What pcm_consistency answers for n loops: d2[n,n] (the squared Mahalanobis distance of every pair's cycle, symmetric, zero
+    diagonal, +inf where the covariance could not be factored), adj[n,n] (bool: d2 <= threshold), words[n,W] (the same graph as
+    scl_pcm_consistency writes it: bit j of row i = word j // 64, bit j % 64) and degree[n]."""
+
+    def __init__(self, d2, adj, words, degree):
+        self.d2, self.adj, self.words, self.degree = d2, adj, words, degree
+
+    def __len__(self):
+        return len(self.degree)
+
+
+def pcm_words_to_bool(words, n):
+    """the n x n bool matrix of n rows of (n + 63) // 64 uint64 adjacency words"""
+    w = np.ascontiguousarray(words, dtype="<u8").reshape(n, (n + 63) // 64 if n else 0)
+    return np.unpackbits(w.view(np.uint8), axis=1, bitorder="little")[:, :n].astype(bool) if n else np.zeros((0, 0), bool)
+
+
+def pcm_bool_to_words(adj):
+    """n rows of (n + 63) // 64 uint64 adjacency words of an n x n bool matrix"""
+    a = np.asarray(adj, dtype=bool)
+    n = a.shape[0]
+    W = (n + 63) // 64
+    if n == 0:
+        return np.zeros((0, 0), np.uint64)
+    padded = np.zeros((n, W * 64), np.uint8)
+    padded[:, :n] = a
+    return np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little")).view("<u8").reshape(n, W)
 
 
 class ScanContextEngine:
@@ -1154,6 +1189,71 @@ class ScanContextEngine:
         if rc != 0:
             raise SclError(rc, "scl_loop_guess_from_shift")
         return G.reshape(4, 4)
+
+    # -- pairwise consistency of loop closures (scl_engine.h: PAIRWISE CONSISTENCY OF LOOP CLOSURES) ------------------
+    @staticmethod
+    def _pcm_inputs(poses_a, poses_b, idx_a, idx_b, z, cov, odom_var):
+        pa = np.ascontiguousarray(poses_a, dtype=np.float64).reshape(-1, 7)
+        pb = pa if poses_b is poses_a else np.ascontiguousarray(poses_b, dtype=np.float64).reshape(-1, 7)
+        ia = np.ascontiguousarray(idx_a, dtype=np.int32).reshape(-1); ib = np.ascontiguousarray(idx_b, dtype=np.int32).reshape(-1)
+        n = ia.size
+        zz = np.ascontiguousarray(z, dtype=np.float64).reshape(n, 7); cc = np.ascontiguousarray(cov, dtype=np.float64).reshape(n, 36)
+        if ib.size != n:
+            raise ValueError("idx_a and idx_b must have one entry per loop")
+        ov = None if odom_var is None else np.ascontiguousarray(odom_var, dtype=np.float64).reshape(6)
+        keep = (pa, pb, ia, ib, zz, cc, ov)
+        args = (_ptr(pa, c_double), pa.shape[0], _ptr(pb, c_double), pb.shape[0], _ptr(ia, c_int), _ptr(ib, c_int), _ptr(zz, c_double),
+                _ptr(cc, c_double), n, None if ov is None else _ptr(ov, c_double))
+        return keep, args, n
+
+    def pcm_consistency(self, poses_a, poses_b, idx_a, idx_b, z, cov, threshold, odom_var=None, want_d2=True):
+        """the consistency of every pair of the n loops (idx_a[i], idx_b[i], z[i], cov[i]) between trajectories poses_a and poses_b
+        ((n,7): x, y, z, qx, qy, qz, qw; pass the same array twice for intra-robot loops): a PcmConsistency (d2 None with
+        want_d2=False -- the n x n matrix then never leaves the device)"""
+        keep, args, n = self._pcm_inputs(poses_a, poses_b, idx_a, idx_b, z, cov, odom_var)
+        W = (n + 63) // 64
+        d2 = np.zeros((max(n, 1), max(n, 1)), np.float64) if want_d2 else None
+        words = np.zeros((max(n, 1), max(W, 1)), np.uint64); deg = np.zeros(max(n, 1), np.int32)
+        self._check(self._lib.scl_pcm_consistency(self._h, *args, float(threshold), None if d2 is None else _ptr(d2, c_double),
+                                                  _ptr(words, c_uint64), _ptr(deg, c_int)), "scl_pcm_consistency")
+        words = words[:n, :W]
+        return PcmConsistency(None if d2 is None else d2[:n, :n], pcm_words_to_bool(words, n), words, deg[:n])
+
+    def pcm_max_clique(self, adj):
+        """the greedy maximum clique of the contract on a graph from the host -- an n x n bool matrix, or n x W uint64 words --:
+        (members ascending, seed); ((), -1) for an empty graph"""
+        a = np.asarray(adj)
+        words = np.ascontiguousarray(a, dtype=np.uint64) if a.dtype == np.uint64 else pcm_bool_to_words(a)
+        n = words.shape[0]
+        mem = np.zeros(max(n, 1), np.int32); m = c_int(-7); seed = c_int(-7)
+        self._check(self._lib.scl_pcm_max_clique(self._h, _ptr(words, c_uint64), n, _ptr(mem, c_int), byref(m), byref(seed)), "scl_pcm_max_clique")
+        return mem[:m.value].copy(), seed.value
+
+    def pcm_select(self, poses_a, poses_b, idx_a, idx_b, z, cov, threshold, odom_var=None):
+        """pcm_consistency and pcm_max_clique in one call on the device: (members ascending, seed, degree[n])"""
+        keep, args, n = self._pcm_inputs(poses_a, poses_b, idx_a, idx_b, z, cov, odom_var)
+        mem = np.zeros(max(n, 1), np.int32); deg = np.zeros(max(n, 1), np.int32); m = c_int(-7); seed = c_int(-7)
+        self._check(self._lib.scl_pcm_select(self._h, *args, float(threshold), _ptr(mem, c_int), byref(m), byref(seed), _ptr(deg, c_int)),
+                    "scl_pcm_select")
+        return mem[:m.value].copy(), seed.value, deg[:n]
+
+    def pcm_last_timing(self):
+        """(pairs_ms, clique_ms): device time of the two stages of the last PCM call made under profile_enable(1)"""
+        a, b = c_double(0.0), c_double(0.0)
+        self._check(self._lib.scl_pcm_last_timing(self._h, byref(a), byref(b)), "scl_pcm_last_timing")
+        return a.value, b.value
+
+    @staticmethod
+    def loop_covariance(info, s2):
+        """cov = s2 * info^-1 (6 x 6, by Cholesky): the covariance of a loop from the information matrix of its pairs and the variance
+        of a pair's residual (scl_loop_covariance); needs no engine.  A singular info is refused: regularise it first"""
+        lib = load_library(); _bind(lib)
+        a = np.ascontiguousarray(info, dtype=np.float64).reshape(36)
+        cov = np.empty(36, np.float64)
+        rc = lib.scl_loop_covariance(_ptr(a, c_double), float(s2), _ptr(cov, c_double))
+        if rc != 0:
+            raise SclError(rc, "scl_loop_covariance")
+        return cov.reshape(6, 6)
 
     # -- measurement ------------------------------------------------------------
     def profile_enable(self, on=True):
