@@ -1,5 +1,6 @@
-// engine_internal.hpp -- the engine object behind the C ABI, shared by engine.hip (one database on one GPU)
-// and sharded_front.hip (one database spread over several GPUs, include/scl_engine.h scl_create_sharded).
+// engine_internal.hpp -- the engine object behind the C ABI, shared by engine.hip (one database on one GPU), registration.hip (the
+// registration entry points and the keyframe store) and sharded_front.hip (one database spread over several GPUs, include/scl_engine.h
+// scl_create_sharded).
 #pragma once
 
 #include "scl_engine.h"
@@ -193,6 +194,8 @@ int eng_topk_enqueue(scl_engine *e, int query, int lo, int hi, int k, float eps,
 int eng_topk_finish(scl_engine *e, int k, bool have_dist, int *idx, float *d2, double *dist, int *shift, int *found);
 // wait for everything enqueued on the engine's streams (before another device's arrays may move)
 int eng_sync_streams(scl_engine *e);
+// e->d_points holds at least `bytes` (registration.hip: the batch ICP's source upload).  The one hook that takes NO lock: the caller holds mu
+int eng_ensure_points(scl_engine *e, size_t bytes);
 // true when appending `count` keyframes would move the database arrays
 bool eng_would_regrow(const scl_engine *e, int count);
 int eng_truncate(scl_engine *e, int n_keep);

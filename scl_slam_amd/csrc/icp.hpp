@@ -1,4 +1,4 @@
-// icp.hpp -- geometric verification on the GPU (host-side interface used by engine.hip).
+// icp.hpp -- geometric verification on the GPU (host-side interface used by registration.hip; engine.hip owns the workspaces).
 #pragma once
 
 #include <hip/hip_runtime.h>
