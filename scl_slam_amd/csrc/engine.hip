@@ -526,13 +526,13 @@ static void log_env_overrides_once()
 {
     static std::atomic<bool> done{false};
     if (done.exchange(true)) return;
-    static const char *const names[] = {"SCL_SCREEN", "SCL_SCREEN_FORM", "SCL_SCREEN_V2_MIN", "SCL_SCREEN_PAIR", "SCL_RCCL_LIB",
+    static const char *const names[] = {"SCL_SCREEN", "SCL_SCREEN_FORM", "SCL_SCREEN_V2_MIN", "SCL_SCREEN_PAIR", "SCL_TAIL_PAIR", "SCL_RCCL_LIB",
                                         // experiments: read by a diagnostics build only (kernels.hpp: scl_lab_int)
                                         "SCL_SCREEN_VARIANT", "SCL_SCREEN_PROBE", "SCL_SCREEN_TAIL", "SCL_ALIGN_WGS",
                                         "SCL_ALIGN2_WGS", "SCL_ALIGN_FILTER", "SCL_SC_KERNEL", "SCL_SC_WAVES", "SCL_STAMP", "SCL_ABLATE",
                                         "SCL_ICP_REDUCE", "SCL_MATRIX_PLAIN", "SCL_MATRIX_KERNEL", "SCL_MATRIX_KR", "SCL_WIDE_EXACT", "SCL_STREAM_EXACT", "SCL_SMALL_EXACT_OFF",
                                         "SCL_SELF_ALIGN_OFF", "SCL_CAND_EXACT_OFF"};
-    constexpr int kProduct = 5;
+    constexpr int kProduct = 6;
     int i = 0;
     for (const char *n : names) {
         const char *v = getenv(n);

@@ -9,10 +9,11 @@
 namespace scl {
 
 // ---- switches of experiments ---------------------------------------------------------------------------------------------------
-// A product build (plain `make`) reads four environment variables, all of which select shipped, tested paths: SCL_SCREEN (0: the
+// A product build (plain `make`) reads five environment variables, all of which select shipped, tested paths: SCL_SCREEN (0: the
 // exact kernel on every pair), SCL_SCREEN_FORM (1: the products' first form on every batch), SCL_SCREEN_V2_MIN (smallest batch the
-// second form scores), SCL_SCREEN_PAIR (0: no two-set products launches in the stream form) -- plus SCL_RCCL_LIB (which collective
-// library the sharded front loads).  Every other SCL_* switch selects a
+// second form scores), SCL_SCREEN_PAIR (0: no two-set products launches in the stream form), SCL_TAIL_PAIR (0: a pair's two sets keep
+// a tail launch each instead of one for both; in a diagnostics build 2: the one launch, but each set's keyframes aligned by the
+// one-set role -- an ablation) -- plus SCL_RCCL_LIB (which collective library the sharded front loads).  Every other SCL_* switch selects a
 // measured alternative or an ablation and exists only in a diagnostics build (make EXTRA=-DSCL_DIAGNOSTICS): here it is its default,
 // a constant, and the code it would select is not compiled in.
 #ifdef SCL_DIAGNOSTICS

@@ -38,7 +38,9 @@
 //                                           next batch's alignment
 //   sc_select_kernel                        survivors + ring-key top-k (80 x 180's exact pass; scl_screen_distances)
 //   launch_sc_screen_batch                  the launch group of a batch
-//   launch_sc_screen_pair                   two full batches: one products launch, a tail each
+//   sc_align2_pair_role / _tail_pair_kernel the tail of a PAIR in one launch (64 x 120 stream): both sets' finishing in one grid beside the
+//                                           alignment of the pair behind it, the keyframe's side of that alignment shared by the two sets
+//   launch_sc_screen_pair                   two full batches: one products launch, one tail for both (SCL_TAIL_PAIR=0: a tail each)
 #include <atomic>
 #include <type_traits>
 
@@ -654,6 +656,260 @@ __device__ __forceinline__ void sc_align2_role(const ScreenBatchArgs &ab, const 
         }
     }
     if (lane == 0 && open_pairs && ab.fallbacks) atomicAdd(ab.fallbacks, open_pairs);
+}
+
+// sc_align2_role for the joint tail of a pair (sc_screen2_tail_pair_kernel): the wave aligns its keyframe against the scans of TWO launch
+// groups, abs[0] and abs[1], over the union [u_lo, u_lo + u_n) of both groups' ranges.  Once per keyframe, for both sets: the image's
+// prefetch, the LDS tile, the fragment offsets and the A fragments read from the tile.  Per set: the scans' B registers, the
+// accumulators (the same v_mfma on the same operands as with one set), the tagged top-2 and its exchanges, the range and lead
+// tests, the stage-2 products (run for a set that has an open scan; the image's second part is loaded once if either has), the
+// exact fallback, and the starts / fallbacks / pair_stride of its own argument block.  No sum runs across the sets: every
+// (scan, keyframe) pair goes through the one-set role's instruction sequence, so first shifts and fallback counts are its, bit for bit.
+template <int S, int W>
+__device__ __forceinline__ void sc_align2_pair_role(const ScreenBatchArgs *abs, const unsigned char *halign, int u_lo, int u_n,
+                                                    const int wave_global, const int waves_total, unsigned char *smem_wave)
+{
+    using C = Align2Cfg<S>;
+    constexpr int P = C::P, CP = C::CP, KS = C::KS, NTAU = C::NTAU, NT = C::NT, ND = C::ND, IMG = C::IMG, SK = C::SK, NLD = C::NLD;
+    static_assert(P == 4 || P == 8, "alignment image");
+    static_assert(S % P == 0 && (16 * P) % 32 == 0 && CP >= S + 8 && IMG % 16 == 0 && S <= 256 && NLD >= 1 && NLD <= 2, "tiling of the shifts");
+    constexpr int NS = 2;                                          // scan sets of the wave
+    constexpr int SR = (W - 1) / 2;
+    constexpr int HAB = halign_bytes(S);
+    const int lane = threadIdx.x & (kWave - 1);
+    const int c16 = lane & 15, j4 = lane >> 4;                     // A: row sigma = c16; B / output: scan q = c16
+    // per set and lane, across the wave's keyframes: what every keyframe needs -- the B registers, the scan's norms, its range (n = 0 for
+    // a column past the set's scans) and its buffer set (its row of starts is formed per store: a register less than the pointer).
+    // What only stage 2 and the exact evaluation read (the scan's slot, per-lane addresses) is formed again where it is needed,
+    // behind an opaque copy of the lane's index: hoisted out of the loop those values were five register pairs more than three
+    // waves per SIMD leave, and went to scratch memory.
+    int q_base[NS], q_n[NS], q_buf[NS];
+    h8 bq[NS][KS];
+    float qnorm[NS], qerr[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const ScreenBatchArgs &ab = abs[s];
+        const int cq = c16 < ab.nq ? c16 : 0;                      // columns past the launch's scans shadow scan 0 (never stored)
+        const ScreenQuery sq = ab.q[cq];
+        q_base[s] = sq.base; q_n[s] = c16 < ab.nq ? sq.n : 0;
+        q_buf[s] = sq.buf;
+        // ---- B: this lane's part of scan q's key for every k-step (halfs 32 kk + 8 j .. + 7), both parts, and the scan's norm ----
+        const _Float16 *qk = reinterpret_cast<const _Float16 *>(ab.hkey) + (size_t)sq.slot * (size_t)ab.hkw;
+#pragma unroll
+        for (int kk = 0; kk < KS; ++kk) bq[s][kk] = *reinterpret_cast<const h8 *>(qk + 32 * kk + 8 * j4);
+        qnorm[s] = *reinterpret_cast<const float *>(qk + SK);
+        qerr[s] = *reinterpret_cast<const float *>(qk + SK + 2);               // |q - qh| of the scan's unit key, rounded up (make_sc.hip)
+    }
+    // ---- A: byte offsets of this lane's fragment starts inside a copy: (8 j - P sigma + 32 d) mod S, d = -TSTEP (NTAU - 1) .. KS - 1
+    unsigned int offs[ND];
+    {
+        int base0 = (8 * j4 - P * c16) % S; base0 = base0 < 0 ? base0 + S : base0;
+#pragma unroll
+        for (int d = 0; d < ND; ++d) {
+            int x = (base0 + 32 * (d - C::TSTEP * (NTAU - 1))) % S; x = x < 0 ? x + S : x;
+            offs[d] = (unsigned int)(2 * x);
+        }
+    }
+    const bool use_filter = abs[0].align_filter != 0;              // (one setting per launch: both blocks hold it)
+    const float kNegInf = __int_as_float(0xff800000);
+    unsigned long long open_pairs[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) open_pairs[s] = 0;
+    auto frag = [&](const unsigned char *ap) -> h8 {
+        if constexpr (P == 8) return *reinterpret_cast<const h8 *>(ap);
+        else {
+            const uint2 a0 = *reinterpret_cast<const uint2 *>(ap), a1 = *reinterpret_cast<const uint2 *>(ap + 8);
+            const u32x4 aw = {a0.x, a0.y, a1.x, a1.y};
+            return __builtin_bit_cast(h8, aw);
+        }
+    };
+    // the image's first part (kh) of the wave's next keyframe, requested one keyframe ahead (plain named registers: an array
+    // behind a lambda went to scratch memory, and the prefetch with it)
+    const unsigned int loff0 = (unsigned int)lane * 16u, loff1 = (unsigned int)(kWave + lane) * 16u;
+    const bool ld1 = NLD > 1 && loff1 < (unsigned int)IMG;
+    uint4 pre0 = make_uint4(0, 0, 0, 0), pre1 = make_uint4(0, 0, 0, 0);
+    float knorm_pre = 0.f, kerr_pre = 0.f;
+    auto image_of = [&](int idx) { idx = idx < u_n ? idx : u_n - 1; return halign + (size_t)(u_lo + idx) * (size_t)HAB; };
+    if (wave_global < u_n) {
+        const unsigned char *g = image_of(wave_global);
+        pre0 = *reinterpret_cast<const uint4 *>(g + 16 + loff0);
+        if (NLD > 1) pre1 = *reinterpret_cast<const uint4 *>(g + 16 + (ld1 ? loff1 : 0u));
+        knorm_pre = *reinterpret_cast<const float *>(g);
+        kerr_pre = *reinterpret_cast<const float *>(g + 4);
+    }
+    for (int idx = wave_global; idx < u_n; idx += waves_total) {
+        wave_fence();                                                            // the previous keyframe's fragment reads are done
+        *reinterpret_cast<uint4 *>(smem_wave + loff0) = pre0;
+        if (ld1) *reinterpret_cast<uint4 *>(smem_wave + loff1) = pre1;
+        const float knorm = knorm_pre, kerr = kerr_pre;
+        wave_fence();
+        const unsigned char *g_cur = image_of(idx);
+        {
+            const unsigned char *g = image_of(idx + waves_total);
+            pre0 = *reinterpret_cast<const uint4 *>(g + 16 + loff0);
+            if (NLD > 1) pre1 = *reinterpret_cast<const uint4 *>(g + 16 + (ld1 ? loff1 : 0u));
+            knorm_pre = *reinterpret_cast<const float *>(g);
+            kerr_pre = *reinterpret_cast<const float *>(g + 4);
+        }
+        // ---- stage 1: the correlation tile by tile; the two largest values per scan with the largest's shift ----
+        // (the shift rides in the low 8 mantissa bits of its value: a perturbation of < 3.1e-5, which the margin test allows for;
+        //  pairs of values enter a running (hi, lo) through max3 / med3, two independent chains; the next tile's fragments are
+        //  requested before this tile's products)
+        float hi[NS][2], lo[NS][2];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) { hi[s][0] = hi[s][1] = kNegInf; lo[s][0] = lo[s][1] = kNegInf; }
+        h8 af[2][KS];
+#pragma unroll
+        for (int kk = 0; kk < KS; ++kk) af[0][kk] = frag(smem_wave + offs[kk + C::TSTEP * (NTAU - 1)]);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int rho = t / NTAU, tau = t - rho * NTAU;
+            if (t + 1 < NT) {
+                const int rn = (t + 1) / NTAU, tn = (t + 1) - rn * NTAU;
+#pragma unroll
+                for (int kk = 0; kk < KS; ++kk) af[(t + 1) & 1][kk] = frag(smem_wave + rn * (CP * 2) + offs[kk + C::TSTEP * (NTAU - 1 - tn)]);
+            }
+            const int ch = t & 1;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {                                       // (the sets' chains are independent: the same fragments, their own B)
+                f4v acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int kk = 0; kk < KS; ++kk) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[t & 1][kk], bq[s][kk], acc, 0, 0, 0);
+#pragma unroll
+                for (int i = 0; i < 4; i += 2) {
+                    // lane (q, j) holds rows 4 j + i of the tile: shift P (16 tau + 4 j + i) + rho
+                    const int sg0 = 16 * tau + 4 * j4 + i, sg1 = sg0 + 1;
+                    const float x = sg0 < C::ROWS ? __uint_as_float((__float_as_uint(acc[i]) & ~255u) | (unsigned int)(P * sg0 + rho)) : kNegInf;
+                    const float y = sg1 < C::ROWS ? __uint_as_float((__float_as_uint(acc[i + 1]) & ~255u) | (unsigned int)(P * sg1 + rho)) : kNegInf;
+                    lo[s][ch] = fmaxf(lo[s][ch], __builtin_amdgcn_fmed3f(hi[s][ch], x, y));
+                    hi[s][ch] = fmaxf(fmaxf(hi[s][ch], x), y);
+                }
+            }
+        }
+        auto merge = [](float &h, float &l, float oh, float ol) { l = fmaxf(fmaxf(l, ol), fminf(h, oh)); h = fmaxf(h, oh); };
+        bool in_range[NS], uniq[NS], mine[NS];
+        int a1[NS];
+        unsigned long long amb[NS];
+        bool any_open = false;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            merge(hi[s][0], lo[s][0], hi[s][1], lo[s][1]);
+#pragma unroll
+            for (int off = 16; off <= 32; off <<= 1) merge(hi[s][0], lo[s][0], __shfl_xor(hi[s][0], off, kWave), __shfl_xor(lo[s][0], off, kWave));
+            const float v1 = hi[s][0], v2 = lo[s][0] + 7.0e-5f;                  // (the tags moved either value by < 3.1e-5)
+            a1[s] = (int)(__float_as_uint(hi[s][0]) & 255u);
+            // the same range conditions as sc_align_role's first stage (see there)
+            in_range[s] = qnorm[s] >= 1e-30f && qnorm[s] <= 4.0e6f && knorm >= 1e-30f && knorm <= 4.0e6f &&
+                          qnorm[s] <= 1.0e4f * knorm && knorm <= 1.0e4f * qnorm[s];
+            // the lead the best shift must have: twice the error bound of a value.  |c~ - c| <= |q - qh| |kh| + |q| |k - kh| + the fp32
+            // accumulation of 128 exact products ((n - 1) 2^-24 sum |q k| <= 7.6e-6), with the keys' ACTUAL rounding-error norms as recorded
+            // at ingest (unit keys: |q| = 1, |kh| <= 1 + |k - kh|) -- never more than the worst case the constant stands for
+            const float lead = (qerr[s] > 0.f && kerr > 0.f) ? fminf(kAlign16Margin, 2.0f * (qerr[s] + kerr + qerr[s] * kerr) * 1.0001f + 1.6e-5f) : kAlign16Margin;
+            uniq[s] = use_filter && in_range[s] && (v1 == v1) && (v2 < v1 - lead);
+            const int ci = u_lo + idx - q_base[s];
+            mine[s] = ci >= 0 && ci < q_n[s];                                    // (every lane of column q holds the same numbers)
+            amb[s] = __builtin_amdgcn_ballot_w64(mine[s] && !uniq[s]) & 0xffffull;
+            any_open = any_open || amb[s] != 0;
+        }
+        // ---- stage 2 (some scan of the launch is still open for this keyframe): the split keys ----
+        if (SCL_A2_PROBE != 1 && use_filter && any_open) {
+            // the image's second part (kl) into the second half of the wave's tile
+            int ln = (int)(threadIdx.x & (kWave - 1));
+            asm volatile("" : "+v"(ln));                                         // (opaque: see the per-set state above)
+            const unsigned int lo0 = (unsigned int)ln * 16u, lo1 = (unsigned int)(kWave + ln) * 16u;
+            const bool l1_in = NLD > 1 && lo1 < (unsigned int)IMG;
+            const uint4 l0 = *reinterpret_cast<const uint4 *>(g_cur + 16 + IMG + lo0);
+            uint4 l1 = make_uint4(0, 0, 0, 0);
+            if (NLD > 1) l1 = *reinterpret_cast<const uint4 *>(g_cur + 16 + IMG + (l1_in ? lo1 : 0u));
+            *reinterpret_cast<uint4 *>(smem_wave + IMG + lo0) = l0;
+            if (l1_in) *reinterpret_cast<uint4 *>(smem_wave + IMG + lo1) = l1;
+            const int c16o = ln & 15, j4o = ln >> 4;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                if (!amb[s]) continue;                                               // (wave uniform) a set with no open scan: its products are not needed
+                const _Float16 *qk = reinterpret_cast<const _Float16 *>(abs[s].hkey) + (size_t)abs[s].q[c16o < abs[s].nq ? c16o : 0].slot * (size_t)abs[s].hkw;
+                h8 bql[KS];                                                          // the scans' second parts: needed here only (4 % of the keyframes)
+#pragma unroll
+                for (int kk = 0; kk < KS; ++kk) bql[kk] = *reinterpret_cast<const h8 *>(qk + SK + 8 + 32 * kk + 8 * j4o);
+                wave_fence();
+                float h2 = kNegInf, l2 = kNegInf;
+                int g2 = 0;
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    const int rho = t / NTAU, tau = t - rho * NTAU;
+                    const f4v zero = {0.f, 0.f, 0.f, 0.f};
+                    f4v hh = zero, xx = zero;
+#pragma unroll
+                    for (int kk = 0; kk < KS; ++kk) {
+                        const unsigned char *ap = smem_wave + rho * (CP * 2) + offs[kk + C::TSTEP * (NTAU - 1 - tau)];
+                        const h8 ah = frag(ap), al = frag(ap + IMG);
+                        const f4v one = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bq[s][kk], zero, 0, 0, 0);   // 32 products on a zero accumulator
+                        hh = kk == 0 ? one : hh + one;
+                        xx = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bql[kk], xx, 0, 0, 0);
+                        xx = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bq[s][kk], xx, 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int sg = 16 * tau + 4 * j4 + i;
+                        const float c = sg < C::ROWS ? __builtin_fmaf(xx[i], 0x1p-11f, hh[i]) : kNegInf;     // (2^-11 xx is exact: fma == mul + add)
+                        l2 = fmaxf(l2, fminf(c, h2));
+                        g2 = c > h2 ? P * sg + rho : g2;
+                        h2 = fmaxf(h2, c);
+                    }
+                }
+#pragma unroll
+                for (int off = 16; off <= 32; off <<= 1) {
+                    const float oh = __shfl_xor(h2, off, kWave), ol = __shfl_xor(l2, off, kWave);
+                    const int og = __shfl_xor(g2, off, kWave);
+                    l2 = fmaxf(fmaxf(l2, ol), fminf(h2, oh));
+                    g2 = oh > h2 ? og : g2;
+                    h2 = fmaxf(h2, oh);
+                }
+                if (!uniq[s] && in_range[s] && (h2 == h2) && (l2 < h2 - 2.0f * kAlignSplitEps)) { uniq[s] = true; a1[s] = g2; }
+                amb[s] = __builtin_amdgcn_ballot_w64(mine[s] && !uniq[s]) & 0xffffull;
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const ScreenBatchArgs &ab = abs[s];
+            const int ci = u_lo + idx - q_base[s];
+            int buf = q_buf[s];
+            asm volatile("" : "+v"(buf));                                        // (opaque: the row's address is not to be held across the loop)
+            int *starts_q = ab.starts + (size_t)buf * (size_t)ab.pair_stride;
+            if (mine[s] && j4 == 0 && uniq[s]) starts_q[ci] = wrapS(a1[s] - SR, S);
+            if (SCL_A2_PROBE == 1 && mine[s] && j4 == 0 && !uniq[s]) starts_q[ci] = kAlignUndecided;
+            open_pairs[s] += (unsigned long long)__popcll(amb[s]);
+            // ---- what the filter left open: the reference's own evaluation, one pair at a time ----
+            while (SCL_A2_PROBE != 1 && amb[s]) {
+                const int qn = __ffsll((long long)amb[s]) - 1;
+                amb[s] &= amb[s] - 1;
+                int lane = (int)(threadIdx.x & (kWave - 1));
+                asm volatile("" : "+v"(lane));                                    // (opaque: see the per-set state above)
+                const ScreenQuery oq = ab.q[qn];                                  // (uniform index: scalar loads)
+                const double *vq = ab.vkey + (size_t)oq.slot * S;
+                const double *vkp = ab.vkey + (size_t)(u_lo + idx) * S;
+                double *vk2 = reinterpret_cast<double *>(smem_wave);              // (the image is not needed any more: both sets' products are done)
+                int al;
+                if constexpr (S / 2 <= kWave) {
+                    constexpr int L = S >> 1;
+                    const int ll = lane < L ? lane : L - 1;
+                    const double2 vk = *reinterpret_cast<const double2 *>(vkp + 2 * ll);
+                    al = align_keyframe_exact<S>(vk, lane, vk2, vq);
+                } else {
+                    constexpr int SPL = (S + kWave - 1) / kWave, LA = S / SPL;
+                    const int ll = lane < LA ? lane : LA - 1;
+                    double vk[SPL];
+#pragma unroll
+                    for (int u = 0; u < SPL; ++u) vk[u] = vkp[SPL * ll + u];
+                    al = align_keyframe_wide<S>(vk, lane, vk2, vq);
+                }
+                if (lane == 0) (ab.starts + (size_t)oq.buf * (size_t)ab.pair_stride)[u_lo + idx - oq.base] = wrapS(al - SR, S);
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+        if ((threadIdx.x & (kWave - 1)) == 0 && open_pairs[s] && abs[s].fallbacks) atomicAdd(abs[s].fallbacks, open_pairs[s]);
 }
 
 template <int RG, int S, int W>
@@ -1865,6 +2121,54 @@ __global__ __launch_bounds__(kScreenWaves * kWave, Align2Cfg<S>::OCC) void sc_sc
     sc_screen2_finish_body<RG, S, W, MASKS, D2>(fa, qi, chunk);
 }
 
+// The tail of a PAIR in one launch (64 x 120, the stream form; SCL_TAIL_PAIR=0: a tail per set).  Two tails behind each other were two
+// chains of memory round trips, and the second walked the first one's keyframes again: image, LDS tile and A fragments a second time.
+//   workgroups [0, align_blocks):  the alignment of the group(s) the pair's tails carry -- align_sets = 2: the pair behind this one,
+//     one wave per keyframe of the union of both groups' ranges, the keyframe's side shared (sc_align2_pair_role); 1: a single or
+//     ragged group behind the pair, the one-set role on nb[0]
+//   behind them: the finishing of BOTH sets in one grid.  A workgroup is still one (set, scan, chunk of 256 keyframes) and runs
+//     sc_screen2_finish_body on that set's own Screen2Args: every d~, flag, t_min word and ring-key metric is what two tails write.
+//     finish_block_of over nq[0] + nq[1] scans: the 32 workgroups of a chunk follow each other in one XCD class, so the chunk's ring
+//     keys and masks leave HBM once for both sets.  The grid is sized for the set with more chunks; a workgroup past its own set's
+//     last chunk leaves in front of every barrier.
+// Nothing passes between the workgroups: where they run decides traffic, never a result.
+struct TailPairArgs {
+    Screen2Args fin[2];                            // the two sets whose products the launch in front formed
+    ScreenBatchArgs nb[2];                         // the group(s) to align (nb[1]: align_sets == 2 only)
+    const unsigned char *halign;
+    int u_lo, u_n;                                 // union of the ranges of every scan to align
+    int align_blocks, align_sets;
+    int chunks[2], chunks_max;                     // finishing chunks of each set, and the larger
+};
+static_assert(sizeof(TailPairArgs) <= 2048, "a kernel's arguments end at 4 KB");
+
+template <int RG, int S, int W, bool MASKS, bool D2>
+__global__ __launch_bounds__(kScreenWaves * kWave, 3) void sc_screen2_tail_pair_kernel(TailPairArgs ta)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_tailp[];
+    const int b = (int)blockIdx.x;
+    if (b < ta.align_blocks) {
+        const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        unsigned char *tile = smem_tailp + (size_t)wave * Align2Cfg<S>::LDS_WAVE;
+        const int wg = b * kScreenWaves + wave, wt = ta.align_blocks * kScreenWaves;
+        if (ta.align_sets == 2) sc_align2_pair_role<S, W>(ta.nb, ta.halign, ta.u_lo, ta.u_n, wg, wt, tile);
+#ifdef SCL_DIAGNOSTICS
+        else if (ta.align_sets == -2) {                                          // SCL_TAIL_PAIR=2: the joint launch alone -- each set's keyframes by the one-set role
+            sc_align2_role<S, W>(ta.nb[0], ta.halign, ta.u_lo, ta.u_n, wg, wt, tile);
+            sc_align2_role<S, W>(ta.nb[1], ta.halign, ta.u_lo, ta.u_n, wg, wt, tile);
+        }
+#endif
+        else sc_align2_role<S, W>(ta.nb[0], ta.halign, ta.u_lo, ta.u_n, wg, wt, tile);
+        return;
+    }
+    int qi, chunk;
+    const int nq0 = ta.fin[0].prod.nq;
+    if (!finish_block_of(b - ta.align_blocks, nq0 + ta.fin[1].prod.nq, ta.chunks_max, qi, chunk)) return;
+    const int set = qi < nq0 ? 0 : 1;                                            // (uniform: the set's block is read by scalar loads)
+    if (chunk >= ta.chunks[set]) return;
+    sc_screen2_finish_body<RG, S, W, MASKS, D2>(ta.fin[set], qi - (set ? nq0 : 0), chunk);
+}
+
 static bool screen_second_form()
 {   // SCL_SCREEN_FORM=1 keeps the products' first form (keyframe rows per pair through the L2, alignment riding in the launch)
     static const int form = [] { const char *e = getenv("SCL_SCREEN_FORM"); return e ? atoi(e) : 2; }();
@@ -1874,6 +2178,11 @@ static bool screen_pair_enabled()
 {   // SCL_SCREEN_PAIR=0: every launch group of the stream form streams the database for itself (no two-set products launches)
     static const int on = [] { const char *e = getenv("SCL_SCREEN_PAIR"); return e ? atoi(e) : 1; }();
     return on != 0;
+}
+static int screen_tail_pair()
+{   // SCL_TAIL_PAIR=0: a pair's sets keep a tail each (two launches behind the products instead of one)
+    static const int v = [] { const char *e = getenv("SCL_TAIL_PAIR"); return e ? atoi(e) : 1; }();
+    return v;
 }
 static int screen_v2_min_env()
 {   // SCL_SCREEN_V2_MIN: the smallest batch the second form scores (0 / unset: the grid's own; tests: 1 = always the second form)
@@ -2107,6 +2416,38 @@ static hipError_t launch_screen_grid(const DbView &db, const ScreenBatch &sb, in
             else hipLaunchKernelGGL((sc_align_kernel<RG, S, W>), dim3(ablocks), ablock, lds0, stream, nb);
             return hipGetLastError();
         };
+        if constexpr (kPairGrid) {
+            // ---- a pair: ONE tail for both sets (sc_screen2_tail_pair_kernel) where both need the instance the stream form uses -- no shift
+            // masks, the ring-key metric formed here -- and whatever is to be aligned takes the alignment's second form.  The last pair of
+            // a call (nothing to align; once per call) keeps its two plain finishes.
+            const int tp = screen_tail_pair();
+            const ScreenBatch *n0 = next, *n1 = mate ? mate->next : nullptr;
+            if (mate && tp != 0 && n0 && second_form_for(*n0) && (!n1 || second_form_for(*n1)) &&
+                !sb.smask && !mate->sb->smask && !sb.no_ring_metric && !mate->sb->no_ring_metric) {
+                TailPairArgs ta{};
+                ta.fin[0] = f2; ta.fin[1] = f2_m; ta.halign = db.halign;
+                int lo = 0, hi = 0;
+                const ScreenBatch *nx[2] = {n0, n1};
+                for (int s = 0; s < (n1 ? 2 : 1); ++s) {
+                    if (fill_screen_args(db, *nx[s], align_filter, &ta.nb[s]) < 0) return hipErrorInvalidValue;
+                    ta.nb[s].skip_d2 = 1;
+                    int ulo, un;
+                    union_of(*nx[s], &ulo, &un);
+                    if (s == 0) { lo = ulo; hi = ulo + un; } else { lo = ulo < lo ? ulo : lo; hi = ulo + un > hi ? ulo + un : hi; }
+                }
+                ta.u_lo = lo; ta.u_n = hi - lo;
+                ta.align_sets = n1 ? 2 : 1;
+#ifdef SCL_DIAGNOSTICS
+                if (n1 && tp == 2) ta.align_sets = -2;
+#endif
+                ta.align_blocks = align2_blocks(ta.u_n);
+                ta.chunks[0] = (nmax + 255) / 256; ta.chunks[1] = (nmax_m + 255) / 256;
+                ta.chunks_max = ta.chunks[0] > ta.chunks[1] ? ta.chunks[0] : ta.chunks[1];
+                const dim3 tgrid(ta.align_blocks + finish_blocks(ta.chunks_max, sb.nq + mate->sb->nq));
+                hipLaunchKernelGGL((sc_screen2_tail_pair_kernel<RG, S, W, false, true>), tgrid, dim3(kScreenWaves * kWave), lds_a2, stream, ta);
+                return hipGetLastError();
+            }
+        }
         if ((e = launch_tail(sb, f2, nmax, next)) != hipSuccess || !mate) return e;
         return launch_tail(*mate->sb, f2_m, nmax_m, mate->next);
     }
