@@ -10,12 +10,12 @@ CSRC    := scl_slam_amd/csrc
 LIBDIR  := scl_slam_amd/lib
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math \
             -fhip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-result -Iinclude -I$(CSRC) $(EXTRA)
-SRCS    := $(CSRC)/engine.hip $(CSRC)/registration.hip $(CSRC)/sc_distance.hip $(CSRC)/ringkey_topk.hip $(CSRC)/make_sc.hip $(CSRC)/icp.hip $(CSRC)/voxel.hip $(CSRC)/sharded_front.hip $(CSRC)/sc_screen.hip $(CSRC)/sc_masked.hip $(CSRC)/sc_matrix.hip $(CSRC)/sc_rank.hip $(CSRC)/messages.hip $(CSRC)/iris.hip $(CSRC)/device_sort.hip $(CSRC)/m2dp.hip $(CSRC)/fpfh.hip $(CSRC)/grsd.hip $(CSRC)/pcm.hip
+SRCS    := $(CSRC)/engine.hip $(CSRC)/screen_host.hip $(CSRC)/registration.hip $(CSRC)/sc_distance.hip $(CSRC)/ringkey_topk.hip $(CSRC)/make_sc.hip $(CSRC)/icp.hip $(CSRC)/voxel.hip $(CSRC)/sharded_front.hip $(CSRC)/sc_screen.hip $(CSRC)/sc_masked.hip $(CSRC)/sc_matrix.hip $(CSRC)/sc_rank.hip $(CSRC)/messages.hip $(CSRC)/iris.hip $(CSRC)/device_sort.hip $(CSRC)/m2dp.hip $(CSRC)/fpfh.hip $(CSRC)/grsd.hip $(CSRC)/pcm.hip
 OBJS    := $(SRCS:.hip=.o)
 # the adapter template the M2DP, FPFH and GRSD adapters derive from, and the batch declarations their C headers share
 VP_ADAPTER := include/scl/vector_plugin_hip_descriptor.hpp include/scl_plugin_batch.h
 
-all: $(LIBDIR)/libscl_engine.so oracle tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/grsd_adapter_check tests/cpp/plugin_batch_check tests/cpp/plugin_topk_check tests/cpp/iris_batch_check tests/cpp/iris_search_check tests/cpp/sc_search_check tests/cpp/sc_search_robot_check tests/cpp/nn_plan_check tests/cpp/candidate_windows_check tests/cpp/libfpfh_checker.so tests/cpp/libgrsd_checker.so tests/cpp/libmock_rccl.so
+all: $(LIBDIR)/libscl_engine.so oracle tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/grsd_adapter_check tests/cpp/plugin_batch_check tests/cpp/plugin_topk_check tests/cpp/iris_batch_check tests/cpp/iris_search_check tests/cpp/sc_search_check tests/cpp/sc_search_robot_check tests/cpp/nn_plan_check tests/cpp/candidate_windows_check tests/cpp/screen_plan_check tests/cpp/libfpfh_checker.so tests/cpp/libgrsd_checker.so tests/cpp/libmock_rccl.so
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.hpp) include/scl_engine.h include/scl_m2dp.h include/scl_fpfh.h include/scl_grsd.h include/scl_iris.h include/scl_plugin_batch.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -77,6 +77,11 @@ tests/cpp/nn_plan_check: tests/cpp/nn_plan_check.cpp $(CSRC)/nn_plan.hpp
 tests/cpp/candidate_windows_check: tests/cpp/candidate_windows_check.cpp $(CSRC)/candidate_windows.hpp
 	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -I$(CSRC) -o $@ tests/cpp/candidate_windows_check.cpp
 
+# the launch schedule of a chunk of the screened stream form (screen_plan.hpp, host code only) under ASan + UBSan, a program of its own;
+# runs without a GPU (tests/test_screen_plan.py)
+tests/cpp/screen_plan_check: tests/cpp/screen_plan_check.cpp $(CSRC)/screen_plan.hpp
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -I$(CSRC) -o $@ tests/cpp/screen_plan_check.cpp
+
 # TEST INFRASTRUCTURE: the FPFH CPU checker (tests/fpfh_checker.py loads it); atan2f from oracle/liboracle.so.  No -march, no
 # contraction: every float operation is the one written
 tests/cpp/libfpfh_checker.so: tests/cpp/fpfh_checker.c | oracle
@@ -122,7 +127,7 @@ sanitize: tests/cpp/fuzz_host
 	@cat $(SAN_LOG)
 
 clean:
-	rm -f $(OBJS) $(LIBDIR)/libscl_engine.so tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/grsd_adapter_check tests/cpp/plugin_batch_check tests/cpp/plugin_topk_check tests/cpp/iris_batch_check tests/cpp/iris_search_check tests/cpp/sc_search_check tests/cpp/sc_search_robot_check tests/cpp/nn_plan_check tests/cpp/candidate_windows_check tests/cpp/libfpfh_checker.so tests/cpp/libgrsd_checker.so tests/cpp/libmock_rccl.so
+	rm -f $(OBJS) $(LIBDIR)/libscl_engine.so tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/grsd_adapter_check tests/cpp/plugin_batch_check tests/cpp/plugin_topk_check tests/cpp/iris_batch_check tests/cpp/iris_search_check tests/cpp/sc_search_check tests/cpp/sc_search_robot_check tests/cpp/nn_plan_check tests/cpp/candidate_windows_check tests/cpp/screen_plan_check tests/cpp/libfpfh_checker.so tests/cpp/libgrsd_checker.so tests/cpp/libmock_rccl.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean sanitize

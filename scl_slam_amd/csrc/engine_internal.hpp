@@ -1,13 +1,15 @@
-// engine_internal.hpp -- the engine object behind the C ABI, shared by engine.hip (one database on one GPU), registration.hip (the
-// registration entry points and the keyframe store) and sharded_front.hip (one database spread over several GPUs, include/scl_engine.h
-// scl_create_sharded).
+// engine_internal.hpp -- the engine object behind the C ABI, shared by engine.hip (one database on one GPU), screen_host.hip (the host
+// layer of the screened search), registration.hip (the registration entry points and the keyframe store) and sharded_front.hip (one
+// database spread over several GPUs, include/scl_engine.h scl_create_sharded).
 #pragma once
 
 #include "scl_engine.h"
 
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <climits>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -179,6 +181,70 @@ struct scl_engine {
     int kf_stride = 0;                                     // fixed by the first put
 };
 
+
+// ---- what engine.hip and screen_host.hip share; every function here assumes the caller's locks (the `_locked` convention) -----------
+namespace scl {
+
+// engine.hip: the profile's event pair around what is enqueued on a stream while the object lives; finished pairs folded into e->prof
+struct ProfScope {
+    scl_engine *e; int kind; hipStream_t s; hipEvent_t start = nullptr, stop = nullptr;
+    ProfScope(scl_engine *e_, int kind_, hipStream_t s_ = nullptr);
+    bool active() const { return start && stop; }
+    ~ProfScope();
+};
+void collect_profile(scl_engine *e);
+int sync(scl_engine *e);                                                        // the engine's stream, then collect_profile
+hipError_t wait_event_polled(hipEvent_t ev, std::chrono::microseconds budget, bool relax);
+void drain_keeping_error(scl_engine *e, const hipStream_t *streams, int n);
+inline void drain_keeping_error(scl_engine *e, std::initializer_list<hipStream_t> streams) { drain_keeping_error(e, streams.begin(), (int)streams.size()); }
+DbView db_view(const scl_engine *e);
+int query_view(const scl_engine *e, int query, QueryView *q);
+int ensure_pairs(scl_engine *e, size_t n);
+int ensure_sets(scl_engine *e, size_t n);
+int launch_topk(scl_engine *e, const QueryView &q, int lo, int hi, int k, float eps, hipStream_t on = nullptr);
+
+template <class T> void dev_free(T *&p) { if (p) { (void)hipFree(p); p = nullptr; } }
+
+// Query id -> the slot every kernel addresses it by: a keyframe of the database's first n_db, or staging row j = -1 - query behind the
+// database's slots.  Negative: why not -- the caller has the message and the code
+constexpr int kQueryOutOfRange = -1, kQueryNotStaged = -2;
+inline int query_slot(const scl_engine *e, int query, int n_db)
+{
+    if (query >= 0) return query < n_db ? query : kQueryOutOfRange;
+    const int j = -1 - query;
+    return j < e->stage_rows && e->staged[(size_t)j] ? e->cap + j : kQueryNotStaged;
+}
+
+// [lo, hi) cut down to the database's [0, n_db); returns what is left (<= 0: nothing)
+inline int clamp_range(int &lo, int &hi, int n_db)
+{
+    if (lo < 0) lo = 0;
+    if (hi > n_db) hi = n_db;
+    return hi - lo;
+}
+
+// The group loops of the distance matrix (engine.hip: matrix_plain_locked; screen_host.hip: matrix_screened_locked) hand every group
+// they have enqueued to the caller's consumer
+struct MatrixGroup {
+    int g, h, r0, rows, rb;                  // group, its half, its first row of the call, its rows, rows a half holds
+    size_t cap;                              // entries per row of the halves: row r of the group at (h * rb + r) * cap
+    int lo, n;                               // the group's keyframes [lo, lo + n)
+    hipStream_t ks;                          // the stream the group's exact kernel was enqueued on
+    int set0, sets;                          // the screening's buffer sets the group went through (sets == 0: no screening pass)
+};
+struct MatrixConsumer {
+    virtual int enqueued(const MatrixGroup &m) = 0;   // the group's launches are on m.ks: enqueue what takes its rows out of the half
+    virtual int retire(int g) = 0;                     // the loop is about to move on: group g's half will be written again by group g + 2
+protected:
+    ~MatrixConsumer() = default;
+};
+
+// screen_host.hip
+int matrix_screened_locked(scl_engine *e, const int *slots, int nq, const int *grp_lo, const int *grp_n, MatrixConsumer &out);
+int detect_full_stream_locked(scl_engine *e, std::unique_lock<std::mutex> &lk, const int *queries, const int *lo, const int *hi, int n_queries,
+                              int scans_per_launch, int launches_in_flight, int *nn_idx, int *shift, double *dist);
+
+}  // namespace scl
 
 // ---- hooks for the sharded front (sharded_front.hip); each takes the engine's own lock ---------------------------
 namespace scl {
