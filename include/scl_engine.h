@@ -778,6 +778,100 @@ int  scl_pcm_last_timing(scl_engine *e, double *pairs_ms, double *clique_ms);
  * (adds a prior to its diagonal).  Only the upper triangle of info is read; cov is written symmetric. */
 int  scl_loop_covariance(const double info[36], double s2, double cov[36]);
 
+/*
+ * POSE-GRAPH SOLVE: SE(3) BETWEEN FACTORS AND PRIORS, LEVENBERG-MARQUARDT WITH BLOCK PCG.  The step PCM stands in front of: the reference's
+ * gtsamOpt (DM.h:782-901) -- prior and odometry BetweenFactor<Pose3> (668-699), one loop BetweenFactor<Pose3> per loop_info (798-803) --
+ * and the estimates updatePoses (922-985) copies back into the key poses.  It reuses PCM's conventions, so that one set of arrays serves both.
+ *   * Inputs.  poses: n_poses x 7 doubles, a pose is x, y, z and a quaternion x, y, z, w; the initial estimate, all robots' keyframes in
+ *     one array.  Quaternions are normalised in double before use.  Between factors: f_i[k], f_j[k] index poses; f_z + 7 k = the measured
+ *     X_i^-1 X_j (what scl_loop_pose_between writes, and what an odometry step is); f_cov + 36 k a row-major 6 x 6 covariance of the right
+ *     perturbation Z Exp(xi), rotation first, of which only the upper triangle is read -- the array scl_pcm_* take.  Priors: p_idx[m], p_z
+ *     + 7 m (a pose), p_cov + 36 m.  Factors are numbered between factors first, then priors: factor n_factors + m is prior m.
+ *   * Residuals.  A between factor has E = Z^-1 X_i^-1 X_j, a prior E = Z^-1 X.  r = (Log_SO3(R_E), t_E) by PCM's rule: the quaternion of E
+ *     with w made >= 0, 2 atan2(|v|, w) v / |v|, and 2 v where |v| = 0 (gtsam's default Pose3 chart).  X_i^-1 X_j and Z^-1 X take the
+ *     difference of the two translations first, as PCM does: a trajectory 2 km from its origin costs nothing.
+ *   * Information and cost.  cov = L L^T by Cholesky in double from the upper triangle (the operations of scl_loop_covariance, in its
+ *     order); the whitened residual is y = L^-1 r and Omega = cov^-1 = L^-T L^-1 is never formed.  chi2[k] = y . y = r^T Omega r, between
+ *     factors first and then priors; cost = 1/2 sum chi2.
+ *   * Jacobians, with respect to right perturbations X Exp(xi), exact at xi = 0.  D(E) = blockdiag(Jr^-1(w), R_E) with w = Log_SO3(R_E);
+ *     J_j = D(E); J_i = -D(E) Ad(h^-1) with h = X_i^-1 X_j and Ad(R, t) = [[R, 0], [[t]x R, R]] as in PCM; a prior has J = D(E).
+ *     Jr^-1(w) = I + 1/2 [w]x + c(theta) [w]x^2, c = 1 / theta^2 - (1 + cos theta) / (2 theta sin theta), evaluated by the half angle the
+ *     quaternion already holds: (1 + cos theta) / sin theta = q_w / |v| (no cancellation at theta -> pi).  Below theta < 0.05 the series
+ *     c = 1/12 + theta^2 / 720 + theta^4 / 30240 + theta^6 / 1209600 is used (its next term is below 1e-18 there).
+ *   * Linear system.  With A = L^-1 J the gradient is g = sum A^T y (6 per pose), H = sum A^T A (block sparse), and the damped system is
+ *     (H + lambda diag(H)) delta = -g.  Retraction is gtsam's default: R <- R Exp_SO3(delta_w), t <- t + R delta_v; the quaternion of
+ *     Exp_SO3(w) is (sin(theta / 2) / theta w, cos(theta / 2)), with sin(theta / 2) / theta = 1/2 - theta^2 / 48 below theta < 1e-4; the
+ *     product is normalised again.
+ *   * Levenberg-Marquardt.  lambda starts at lambda_initial.  An iteration is one damped solve at the kept poses and one evaluation of the
+ *     cost at the retracted ones.  A step that lowers the cost (cost_new < cost) is accepted and lambda is divided by lambda_factor; one
+ *     that does not is rejected: the poses are kept and lambda is multiplied by it.  After every iteration the solve stops on the first of
+ *       1 SCL_PGO_STOP_COST        the step was accepted and cost - cost_new <= relative_cost_tolerance * cost
+ *       2 SCL_PGO_STOP_STEP        the step's largest component |delta|_inf <= step_tolerance
+ *       3 SCL_PGO_STOP_ITERATIONS  max_iterations iterations were made (accepted and rejected ones count alike)
+ *       4 SCL_PGO_STOP_LAMBDA      lambda > lambda_max
+ *     The linear solve is conjugate gradients from delta = 0, preconditioned with the 6 x 6 diagonal blocks of the damped matrix, each
+ *     factored by Cholesky; it stops before the iteration at which sqrt(r^T M^-1 r) <= cg_tolerance * its initial value, or after
+ *     cg_max_iterations.
+ *   * Defaults (scl_pgo_default_params).  They are this project's own choice, not the reference's (whose optimiser is not in its tree):
+ *     max_iterations 50, lambda_initial 1e-5, lambda_factor 10, lambda_max 1e10, relative_cost_tolerance 1e-10, step_tolerance 1e-10,
+ *     cg_tolerance 1e-8, cg_max_iterations 500.  Only the two stop tolerances and the CG tolerance influence the answer.
+ *   * Determinism.  The same inputs give the same bits on every run, and after a larger call has grown the workspace.  No floating-point
+ *     atomics.  Every per-pose sum runs over the pose's incident factors in ascending factor number (between factors before priors): one
+ *     after the other for a pose of fewer than 64 incident factors; for a longer row a wave takes it, lane l adds the entries l, l + 64,
+ *     ... of the list in that order and the 64 lanes are summed by a fixed butterfly.  Every dot product is per pose, then a fixed tree
+ *     over blocks of 256 poses, then a fixed tree over the blocks: a shape that depends on n_poses alone.
+ *   * scl_pgo_linearize: cost, gradient (6 n_poses), diag (36 n_poses: the row-major diagonal blocks of H), chi2 (n_factors + n_priors)
+ *     at `poses`; each may be NULL, one must be given.  scl_pgo_hessian_apply: y = (H + lambda diag(H)) x (6 n_poses each; lambda finite,
+ *     >= 0): the operator the solver iterates, exposed so that it can be held to an assembled matrix.  scl_pgo_optimize: poses_out
+ *     (n_poses x 7, unit quaternions with w >= 0; may alias poses), result, chi2 at poses_out (may be NULL; params == NULL: the defaults).
+ *     scl_pgo_result: iterations, accepted, rejected, cg_iterations (the total), stop_reason, initial_cost, final_cost, final_lambda,
+ *     gradient_max = |g|_inf at poses_out.
+ *   * Errors, all SCL_ERR_INVALID_ARG, checked on the host before anything runs, nothing written: a NULL engine; a negative count; n_poses
+ *     = 0 or > 1 048 576; n_factors > 4 194 304; n_priors > n_poses; a required pointer NULL with a positive count; no output given; an
+ *     index out of range; f_i == f_j; a non-finite input; a quaternion with squared norm outside [0.25, 4]; a covariance whose
+ *     factorisation meets a pivot that is not above 2^-43 of its diagonal entry (scl_loop_covariance's rule); a params field that is not
+ *     finite and positive, or lambda_factor <= 1; a connected component of the graph without a prior (a union-find over the factors; the
+ *     reference's disconnectedGraph test, DM.h:826-864, is the same idea) -- its answer would have a free gauge.
+ *   * How it runs.  One thread per factor linearises (whitened residual, A_i^T y, A_j^T y, A_i^T A_i, A_j^T A_j and the one off-diagonal
+ *     block W = A_i^T A_j, which pose i's row reads as it is and pose j's row transposed); one gather per pose over its list of incident
+ *     (factor, side) entries -- built on the host by a stable counting sort -- assembles g, the diagonal block and the cost; PCG is two
+ *     launches per iteration with alpha and beta formed on the device from per-block partial sums that every workgroup reduces again in the
+ *     same order, and a device flag that turns the launches queued behind convergence into returns; the host reads one record per LM
+ *     iteration and the flag once per 32 queued CG iterations.  Memory: a grow-only workspace; every word a call reads it wrote first.  On
+ *     a scl_create_sharded engine the calls run on the primary shard, as the PCM calls do.  See DESIGN.md section 4, PGO.
+ */
+typedef struct scl_pgo_params {
+    int    max_iterations;
+    double lambda_initial, lambda_factor, lambda_max;
+    double relative_cost_tolerance, step_tolerance;
+    double cg_tolerance;
+    int    cg_max_iterations;
+} scl_pgo_params;
+enum { SCL_PGO_STOP_COST = 1, SCL_PGO_STOP_STEP = 2, SCL_PGO_STOP_ITERATIONS = 3, SCL_PGO_STOP_LAMBDA = 4 };
+typedef struct scl_pgo_result {
+    int    iterations, accepted, rejected, cg_iterations, stop_reason;
+    double initial_cost, final_cost, final_lambda, gradient_max;
+} scl_pgo_result;
+#define SCL_PGO_MAX_POSES   1048576
+#define SCL_PGO_MAX_FACTORS 4194304
+int  scl_pgo_default_params(scl_pgo_params *p);
+int  scl_pgo_linearize(scl_engine *e, const double *poses, int n_poses,
+                       const int *f_i, const int *f_j, const double *f_z, const double *f_cov, int n_factors,
+                       const int *p_idx, const double *p_z, const double *p_cov, int n_priors,
+                       double *cost, double *gradient, double *diag, double *chi2);
+int  scl_pgo_hessian_apply(scl_engine *e, const double *poses, int n_poses,
+                           const int *f_i, const int *f_j, const double *f_z, const double *f_cov, int n_factors,
+                           const int *p_idx, const double *p_z, const double *p_cov, int n_priors,
+                           double lambda, const double *x, double *y);
+int  scl_pgo_optimize(scl_engine *e, const double *poses, int n_poses,
+                      const int *f_i, const int *f_j, const double *f_z, const double *f_cov, int n_factors,
+                      const int *p_idx, const double *p_z, const double *p_cov, int n_priors,
+                      const scl_pgo_params *params, double *poses_out, scl_pgo_result *result, double *chi2);
+/* Device time of the last of the three calls above made while scl_profile_enable(e, 1) was in force, HIP events on the engine's stream:
+ * linearize_ms = every linearisation and assembly of the call, solve_ms = every PCG solve and retraction; 0 for a stage that call did not
+ * run.  Either pointer may be NULL. */
+int  scl_pgo_last_timing(scl_engine *e, double *linearize_ms, double *solve_ms);
+
 /* ---- measurement ----------------------------------------------------------- */
 int  scl_profile_enable(scl_engine *e, int on);   /* 0 off, 1 every kernel family, 2 SC distance only,
                                                      3 SC distance only, sampled: one launch in thirteen -- in the stream form one

@@ -531,7 +531,7 @@ const char *scl_status_string(int status)
 
 const char *scl_last_error(const scl_engine *e) { return e ? e->last_error.c_str() : "null engine"; }
 
-int scl_abi_version(void) { return 12; }
+int scl_abi_version(void) { return 13; }
 
 int scl_default_config(scl_config *c)
 {
@@ -686,6 +686,7 @@ int scl_destroy(scl_engine *e)
     for (int i = 0; i < scl_engine::kIcpLanes; ++i) icp_workspace_free(&e->vox_lane_ws[i]);
     icp_workspace_free(&e->icp_batch_ctl);
     pcm_workspace_free(&e->pcm_ws);
+    pgo_workspace_free(&e->pgo_ws);
     for (int i = 0; i < scl_engine::kIcpLanes; ++i) {
         if (e->ev_lane[i]) (void)hipEventDestroy(e->ev_lane[i]);
         icp_workspace_free(&e->icp_lane_ws[i]);
@@ -2146,6 +2147,95 @@ int scl_loop_covariance(const double info[36], double s2, double cov[36])
         }
     for (int k = 0; k < 36; ++k) if (!std::isfinite(out[k])) return SCL_ERR_INVALID_ARG;
     std::memcpy(cov, out, sizeof out);
+    return SCL_OK;
+}
+
+/* ---- pose-graph solve: SE(3) between factors and priors, LM with block PCG (pgo.hip) ------ */
+
+namespace {
+
+// what = 0 scl_pgo_linearize (a, b, c, d = cost, gradient, diag, chi2), 1 scl_pgo_hessian_apply (a = x, b = y), 2 scl_pgo_optimize
+// (b = poses_out, d = chi2)
+int pgo_call(scl_engine *e, const PgoInputs &in, int what, double lambda, const scl_pgo_params *params, scl_pgo_result *result,
+             const double *a_in, double *a, double *b, double *c, double *d)
+{
+    if (!e) return SCL_ERR_INVALID_ARG;
+    if (e->front) {                                        // the primary shard does the work; its message goes to the handle the caller holds
+        scl_engine *front = e;
+        const int rc = pgo_call(front_primary(e), in, what, lambda, params, result, a_in, a, b, c, d);
+        if (rc) front->last_error = scl_last_error(front_primary(front));
+        return rc;
+    }
+    std::lock_guard<std::mutex> lk(e->mu);
+    const std::string name = what == 0 ? "pgo_linearize: " : (what == 1 ? "pgo_hessian_apply: " : "pgo_optimize: ");
+    if (const char *bad = pgo_inputs_bad(in)) return fail(e, SCL_ERR_INVALID_ARG, (name + bad).c_str());
+    scl_pgo_params prm;
+    pgo_default_params(&prm);
+    if (what == 0 && !a && !b && !c && !d) return fail(e, SCL_ERR_INVALID_ARG, (name + "no output given").c_str());
+    if (what == 1) {
+        if (!a_in || !b) return fail(e, SCL_ERR_INVALID_ARG, (name + "x or y is NULL").c_str());
+        if (!std::isfinite(lambda) || lambda < 0.0) return fail(e, SCL_ERR_INVALID_ARG, (name + "lambda non-finite or negative").c_str());
+        for (size_t k = 0; k < 6 * (size_t)in.n_poses; ++k)
+            if (!std::isfinite(a_in[k])) return fail(e, SCL_ERR_INVALID_ARG, (name + "a non-finite x").c_str());
+    }
+    if (what == 2) {
+        if (!b || !result) return fail(e, SCL_ERR_INVALID_ARG, (name + "poses_out or result is NULL").c_str());
+        if (params) prm = *params;
+        if (const char *bad = pgo_params_bad(prm)) return fail(e, SCL_ERR_INVALID_ARG, (name + bad).c_str());
+    }
+    (void)hipSetDevice(e->device);
+    std::string err;
+    const bool timing = e->prof_on == 1;
+    const int rc = what == 0 ? pgo_linearize(&e->pgo_ws, e->stream, in, a, b, c, d, timing, &err)
+                 : what == 1 ? pgo_hessian_apply(&e->pgo_ws, e->stream, in, lambda, a_in, b, timing, &err)
+                             : pgo_optimize(&e->pgo_ws, e->stream, in, prm, b, result, d, timing, &err);
+    if (rc) e->last_error = err;
+    return rc;
+}
+
+}  // namespace
+
+int scl_pgo_default_params(scl_pgo_params *p)
+{
+    if (!p) return SCL_ERR_INVALID_ARG;
+    pgo_default_params(p);
+    return SCL_OK;
+}
+
+int scl_pgo_linearize(scl_engine *e, const double *poses, int n_poses,
+                      const int *f_i, const int *f_j, const double *f_z, const double *f_cov, int n_factors,
+                      const int *p_idx, const double *p_z, const double *p_cov, int n_priors,
+                      double *cost, double *gradient, double *diag, double *chi2)
+{
+    const PgoInputs in = {poses, n_poses, f_i, f_j, f_z, f_cov, n_factors, p_idx, p_z, p_cov, n_priors};
+    return pgo_call(e, in, 0, 0.0, nullptr, nullptr, nullptr, cost, gradient, diag, chi2);
+}
+
+int scl_pgo_hessian_apply(scl_engine *e, const double *poses, int n_poses,
+                          const int *f_i, const int *f_j, const double *f_z, const double *f_cov, int n_factors,
+                          const int *p_idx, const double *p_z, const double *p_cov, int n_priors,
+                          double lambda, const double *x, double *y)
+{
+    const PgoInputs in = {poses, n_poses, f_i, f_j, f_z, f_cov, n_factors, p_idx, p_z, p_cov, n_priors};
+    return pgo_call(e, in, 1, lambda, nullptr, nullptr, x, nullptr, y, nullptr, nullptr);
+}
+
+int scl_pgo_optimize(scl_engine *e, const double *poses, int n_poses,
+                     const int *f_i, const int *f_j, const double *f_z, const double *f_cov, int n_factors,
+                     const int *p_idx, const double *p_z, const double *p_cov, int n_priors,
+                     const scl_pgo_params *params, double *poses_out, scl_pgo_result *result, double *chi2)
+{
+    const PgoInputs in = {poses, n_poses, f_i, f_j, f_z, f_cov, n_factors, p_idx, p_z, p_cov, n_priors};
+    return pgo_call(e, in, 2, 0.0, params, result, nullptr, nullptr, poses_out, nullptr, chi2);
+}
+
+int scl_pgo_last_timing(scl_engine *e, double *linearize_ms, double *solve_ms)
+{
+    if (!e) return SCL_ERR_INVALID_ARG;
+    if (e->front) e = front_primary(e);
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (linearize_ms) *linearize_ms = e->pgo_ws.linearize_ms;
+    if (solve_ms) *solve_ms = e->pgo_ws.solve_ms;
     return SCL_OK;
 }
 

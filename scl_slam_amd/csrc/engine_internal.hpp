@@ -17,6 +17,7 @@
 #include "icp.hpp"
 #include "kernels.hpp"
 #include "pcm.hpp"
+#include "pgo.hpp"
 
 namespace scl {
 
@@ -172,6 +173,7 @@ struct scl_engine {
     hipEvent_t ev_lane[kIcpLanes] = {nullptr};
     hipStream_t icp_lane_stream[kIcpLanes] = {nullptr};
     scl::PcmWorkspace pcm_ws;                              // pairwise consistency of loop closures (pcm.hip)
+    scl::PgoWorkspace pgo_ws;                              // pose-graph solve (pgo.hip)
 
     // on-device keyframe store (robots[id].keyFrameArray, DM.h:86): clouds live in slabs of HBM, bump allocated
     struct StoredCloud { unsigned char *d = nullptr; int n = -1; size_t cap_bytes = 0; };

@@ -12,6 +12,7 @@
 // No floating-point atomics and no atomics on the graph at all; the one integer atomic is the size of the largest clique found so far,
 // which lets a seed that could not even tie leave at once (the answer does not depend on when it is read: see the kernel).
 #include "pcm.hpp"
+#include "se3_device.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -22,70 +23,17 @@ namespace scl {
 
 namespace {
 
-constexpr int kPoseStride = 8;     // q (x, y, z, w) normalised, t, one pad
+using namespace se3;               // the quaternion, composition and adjoint helpers shared with pgo.hip; a pose is kPoseStride doubles
+
 constexpr int kLoopStride = 56;    // q, t of Z (7); q, t of Z^-1 (7); Ad(Z) Sigma Ad(Z)^T upper triangle (21); Sigma upper triangle (21)
 constexpr int kLoopZinv = 7, kLoopS = 14, kLoopRaw = 35;
-
-// index of (a, b), a <= b, in the row-by-row upper triangle of a 6 x 6
-__host__ __device__ constexpr int tri(int a, int b) { return a * 6 - a * (a - 1) / 2 + (b - a); }
-
-// Hamilton product of (x, y, z, w) quaternions: R(a * b) = R(a) R(b)
-__device__ inline void qmul(const double *a, const double *b, double *o)
-{
-    o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    o[1] = a[3] * b[1] - a[0] * b[2] + a[1] * b[3] + a[2] * b[0];
-    o[2] = a[3] * b[2] + a[0] * b[1] - a[1] * b[0] + a[2] * b[3];
-    o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-}
-
-__device__ inline void qconj(const double *a, double *o) { o[0] = -a[0]; o[1] = -a[1]; o[2] = -a[2]; o[3] = a[3]; }
-
-// R(q) v for a unit q: v + w c + u x c with c = 2 u x v
-__device__ inline void qrot(const double *q, const double *v, double *o)
-{
-    const double cx = 2.0 * (q[1] * v[2] - q[2] * v[1]), cy = 2.0 * (q[2] * v[0] - q[0] * v[2]), cz = 2.0 * (q[0] * v[1] - q[1] * v[0]);
-    o[0] = v[0] + q[3] * cx + (q[1] * cz - q[2] * cy);
-    o[1] = v[1] + q[3] * cy + (q[2] * cx - q[0] * cz);
-    o[2] = v[2] + q[3] * cz + (q[0] * cy - q[1] * cx);
-}
-
-// the rotation matrix of a unit q, row major
-__device__ inline void qmat(const double *q, double *R)
-{
-    const double x = q[0], y = q[1], z = q[2], w = q[3];
-    R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - z * w);       R[2] = 2.0 * (x * z + y * w);
-    R[3] = 2.0 * (x * y + z * w);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - x * w);
-    R[6] = 2.0 * (x * z - y * w);       R[7] = 2.0 * (y * z + x * w);       R[8] = 1.0 - 2.0 * (x * x + y * y);
-}
-
-__device__ inline void mm(const double *A, const double *B, double *C)        // C = A B
-{
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) C[3 * r + c] = A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c] + A[3 * r + 2] * B[6 + c];
-}
-
-__device__ inline void mmt(const double *A, const double *B, double *C)       // C = A B^T
-{
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) C[3 * r + c] = A[3 * r] * B[3 * c] + A[3 * r + 1] * B[3 * c + 1] + A[3 * r + 2] * B[3 * c + 2];
-}
 
 // out = upper triangle of Ad(q, t) S Ad(q, t)^T for Ad = [[R, 0], [B, R]], B = [t]x R, and S = [[P, Q], [Q^T, U]] given by its upper
 // triangle: TL = (R P) R^T, TR = (R P) B^T + (R Q) R^T, BR = (B P + R Q^T) B^T + (B Q + R U) R^T
 __device__ inline void adjoint_cov(const double *q, const double *t, const double *S, double *out)
 {
     double R[9], B[9], P[9], Q[9], U[9];
-    qmat(q, R);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        B[c]     = t[1] * R[6 + c] - t[2] * R[3 + c];
-        B[3 + c] = t[2] * R[c] - t[0] * R[6 + c];
-        B[6 + c] = t[0] * R[3 + c] - t[1] * R[c];
-    }
+    adjoint_blocks(q, t, R, B);
 #pragma unroll
     for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -119,13 +67,6 @@ __device__ inline void adjoint_cov(const double *q, const double *t, const doubl
         for (int c = r; c < 3; ++c) out[tri(3 + r, 3 + c)] = X[3 * r + c] + Y[3 * r + c];
 }
 
-__device__ inline void normalise_pose(const double *in, double *out)
-{
-    const double s = sqrt(in[3] * in[3] + in[4] * in[4] + in[5] * in[5] + in[6] * in[6]);
-    out[0] = in[3] / s; out[1] = in[4] / s; out[2] = in[5] / s; out[3] = in[6] / s;
-    out[4] = in[0]; out[5] = in[1]; out[6] = in[2];
-}
-
 __global__ __launch_bounds__(256) void pcm_prep_kernel(const double *poses_a, int n_a, const double *poses_b, int n_b,
                                                         const double *z, const double *cov, int n,
                                                         double *prep_a, double *prep_b, double *loops)
@@ -153,26 +94,6 @@ __global__ __launch_bounds__(256) void pcm_prep_kernel(const double *poses_a, in
     for (int k = 0; k < 21; ++k) { o[kLoopS + k] = A[k]; o[kLoopRaw + k] = S[k]; }
 }
 
-// (X_from)^-1 X_to of two prepared poses: q = conj(q_from) q_to, t = R(q_from)^T (t_to - t_from) -- the difference first, so that a
-// trajectory far from its origin costs nothing
-__device__ inline void relative_pose(const double *from, const double *to, double *q, double *t)
-{
-    double c[4];
-    qconj(from, c);
-    qmul(c, to, q);
-    const double d[3] = {to[4] - from[4], to[5] - from[5], to[6] - from[6]};
-    qrot(c, d, t);
-}
-
-// (q1, t1) (q2, t2)
-__device__ inline void compose(const double *q1, const double *t1, const double *q2, const double *t2, double *q, double *t)
-{
-    double r[3];
-    qmul(q1, q2, q);
-    qrot(q1, t2, r);
-    t[0] = t1[0] + r[0]; t[1] = t1[1] + r[1]; t[2] = t1[2] + r[2];
-}
-
 __device__ double pair_d2(const double *prep_a, const double *prep_b, const int *idx_a, const int *idx_b, const double *loops,
                           const double *odom, int i, int j)
 {
@@ -192,11 +113,8 @@ __device__ double pair_d2(const double *prep_a, const double *prep_b, const int 
     // r = (Log_SO3, t)
     double r[6];
     {
-        const double sg = qE[3] < 0.0 ? -1.0 : 1.0;
-        const double x = sg * qE[0], y = sg * qE[1], zc = sg * qE[2], w = sg * qE[3];
-        const double nv = sqrt(x * x + y * y + zc * zc);
-        const double k = nv == 0.0 ? 2.0 : 2.0 * atan2(nv, w) / nv;
-        r[0] = k * x; r[1] = k * y; r[2] = k * zc;
+        double qp[4], nv;
+        qlog(qE, r, qp, &nv);
         r[3] = tE[0]; r[4] = tE[1]; r[5] = tE[2];
     }
     // Sigma

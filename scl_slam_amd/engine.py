@@ -36,6 +36,36 @@ class IcpParams(ctypes.Structure):
     ]
 
 
+class PgoParams(ctypes.Structure):
+    """scl_pgo_params; PgoParams.defaults() = scl_pgo_default_params (the project's own choice: scl_engine.h POSE-GRAPH SOLVE)."""
+    _fields_ = [
+        ("max_iterations", c_int), ("lambda_initial", c_double), ("lambda_factor", c_double), ("lambda_max", c_double),
+        ("relative_cost_tolerance", c_double), ("step_tolerance", c_double), ("cg_tolerance", c_double), ("cg_max_iterations", c_int),
+    ]
+
+    @classmethod
+    def defaults(cls, **overrides):
+        lib = load_library(); _bind(lib)
+        p = cls()
+        rc = lib.scl_pgo_default_params(byref(p))
+        if rc != 0:
+            raise SclError(rc, "scl_pgo_default_params")
+        for k, v in overrides.items():
+            if k not in dict(cls._fields_):
+                raise TypeError(f"scl_pgo_params has no field {k}")
+            setattr(p, k, v)
+        return p
+
+
+class PgoResult(ctypes.Structure):
+    """scl_pgo_result; stop_reason: 1 cost, 2 step, 3 iterations, 4 lambda"""
+    _fields_ = [
+        ("iterations", c_int), ("accepted", c_int), ("rejected", c_int), ("cg_iterations", c_int), ("stop_reason", c_int),
+        ("initial_cost", c_double), ("final_cost", c_double), ("final_lambda", c_double), ("gradient_max", c_double),
+    ]
+    STOP_COST, STOP_STEP, STOP_ITERATIONS, STOP_LAMBDA = 1, 2, 3, 4
+
+
 class SclProfile(ctypes.Structure):
     _fields_ = [
         ("sc_distance_ms", c_double), ("sc_distance_launches", c_uint64), ("sc_distance_pairs", c_uint64),
@@ -162,6 +192,11 @@ def _bind(lib):
         "scl_pcm_select": (c_int, [P, dp, c_int, dp, c_int, ip, ip, dp, dp, c_int, dp, c_double, ip, ip, ip, ip]),
         "scl_pcm_last_timing": (c_int, [P, dp, dp]),
         "scl_loop_covariance": (c_int, [dp, c_double, dp]),
+        "scl_pgo_default_params": (c_int, [POINTER(PgoParams)]),
+        "scl_pgo_linearize": (c_int, [P, dp, c_int, ip, ip, dp, dp, c_int, ip, dp, dp, c_int, dp, dp, dp, dp]),
+        "scl_pgo_hessian_apply": (c_int, [P, dp, c_int, ip, ip, dp, dp, c_int, ip, dp, dp, c_int, c_double, dp, dp]),
+        "scl_pgo_optimize": (c_int, [P, dp, c_int, ip, ip, dp, dp, c_int, ip, dp, dp, c_int, POINTER(PgoParams), dp, POINTER(PgoResult), dp]),
+        "scl_pgo_last_timing": (c_int, [P, dp, dp]),
         "scl_profile_enable": (c_int, [P, c_int]),
         "scl_profile_reset": (c_int, [P]),
         "scl_profile_get": (c_int, [P, POINTER(SclProfile)]),
@@ -1254,6 +1289,54 @@ class ScanContextEngine:
         if rc != 0:
             raise SclError(rc, "scl_loop_covariance")
         return cov.reshape(6, 6)
+
+    # -- pose-graph solve (scl_engine.h: POSE-GRAPH SOLVE) -------------------------------------------------------------
+    @staticmethod
+    def _pgo_inputs(poses, f_i, f_j, f_z, f_cov, p_idx, p_z, p_cov):
+        x = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7)
+        fi = np.ascontiguousarray(f_i, dtype=np.int32).reshape(-1); fj = np.ascontiguousarray(f_j, dtype=np.int32).reshape(-1)
+        pi = np.ascontiguousarray(p_idx, dtype=np.int32).reshape(-1)
+        nf, npr = fi.size, pi.size
+        if fj.size != nf:
+            raise ValueError("f_i and f_j must have one entry per factor")
+        fz = np.ascontiguousarray(f_z, dtype=np.float64).reshape(nf, 7); fc = np.ascontiguousarray(f_cov, dtype=np.float64).reshape(nf, 36)
+        pz = np.ascontiguousarray(p_z, dtype=np.float64).reshape(npr, 7); pc = np.ascontiguousarray(p_cov, dtype=np.float64).reshape(npr, 36)
+        keep = (x, fi, fj, fz, fc, pi, pz, pc)
+        opt = lambda a, t: _ptr(a, t) if a.size else None
+        args = (_ptr(x, c_double), x.shape[0], opt(fi, c_int), opt(fj, c_int), opt(fz, c_double), opt(fc, c_double), nf,
+                opt(pi, c_int), opt(pz, c_double), opt(pc, c_double), npr)
+        return keep, args, x.shape[0], nf + npr
+
+    def pgo_linearize(self, poses, f_i, f_j, f_z, f_cov, p_idx, p_z, p_cov):
+        """the pose graph linearised at `poses` ((n,7): x, y, z, qx, qy, qz, qw): (cost, gradient[n,6], diag[n,6,6], chi2[n_factors +
+        n_priors]) for between factors (f_i, f_j, f_z[.,7], f_cov[.,6,6]) and priors (p_idx, p_z, p_cov)"""
+        keep, args, n, m = self._pgo_inputs(poses, f_i, f_j, f_z, f_cov, p_idx, p_z, p_cov)
+        cost = c_double(0.0); g = np.zeros((max(n, 1), 6)); d = np.zeros((max(n, 1), 6, 6)); chi2 = np.zeros(max(m, 1))
+        self._check(self._lib.scl_pgo_linearize(self._h, *args, byref(cost), _ptr(g, c_double), _ptr(d, c_double), _ptr(chi2, c_double)),
+                    "scl_pgo_linearize")
+        return cost.value, g[:n], d[:n], chi2[:m]
+
+    def pgo_hessian_apply(self, poses, f_i, f_j, f_z, f_cov, p_idx, p_z, p_cov, lam, x):
+        """y[n,6] = (H + lam diag(H)) x for the Gauss-Newton matrix H of the graph at `poses`: the operator pgo_optimize iterates"""
+        keep, args, n, m = self._pgo_inputs(poses, f_i, f_j, f_z, f_cov, p_idx, p_z, p_cov)
+        xx = np.ascontiguousarray(x, dtype=np.float64).reshape(n, 6); y = np.zeros((max(n, 1), 6))
+        self._check(self._lib.scl_pgo_hessian_apply(self._h, *args, float(lam), _ptr(xx, c_double), _ptr(y, c_double)), "scl_pgo_hessian_apply")
+        return y[:n]
+
+    def pgo_optimize(self, poses, f_i, f_j, f_z, f_cov, p_idx, p_z, p_cov, params=None, want_chi2=True):
+        """Levenberg-Marquardt over the graph from `poses`: (poses_out[n,7] with unit quaternions and w >= 0, PgoResult, chi2 at poses_out
+        or None); params: a PgoParams (None: the defaults)"""
+        keep, args, n, m = self._pgo_inputs(poses, f_i, f_j, f_z, f_cov, p_idx, p_z, p_cov)
+        out = np.zeros((max(n, 1), 7)); res = PgoResult(); chi2 = np.zeros(max(m, 1)) if want_chi2 else None
+        self._check(self._lib.scl_pgo_optimize(self._h, *args, None if params is None else byref(params), _ptr(out, c_double), byref(res),
+                                               None if chi2 is None else _ptr(chi2, c_double)), "scl_pgo_optimize")
+        return out[:n], res, None if chi2 is None else chi2[:m]
+
+    def pgo_last_timing(self):
+        """(linearize_ms, solve_ms): device time of the two stages of the last PGO call made under profile_enable(1)"""
+        a, b = c_double(0.0), c_double(0.0)
+        self._check(self._lib.scl_pgo_last_timing(self._h, byref(a), byref(b)), "scl_pgo_last_timing")
+        return a.value, b.value
 
     # -- measurement ------------------------------------------------------------
     def profile_enable(self, on=True):
