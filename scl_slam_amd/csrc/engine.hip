@@ -4,8 +4,10 @@
 // 1721-1755), whose float-narrowing comparison order is part of the contract.
 // (The registration entry points -- ICP, verification, scoring, submaps, the keyframe store -- are registration.hip's; the host layer of
 // the screened search -- the full-database detection in its blocking, ticket and stream forms, the screened distance matrix's loop,
-// scl_screen_distances* -- is screen_host.hip's.  Here: the database, ingest, the ring-key and candidate searches, the matrix's plain
-// loop and its consumers, the points pipelines, the selftests, PCM, the profile and the hooks.)
+// scl_screen_distances* -- is screen_host.hip's; what fills the database -- its arrays' allocation and growth, the append paths, the
+// points pipelines, the pinned buffers, dump and load, the front's hooks into them -- is ingest_host.hip's.  Here: the engine's creation
+// and destruction, the views of the database, the ring-key and candidate searches, the readers of single keyframes, the matrix's plain
+// loop and its consumers, the ranked searches, the selftests, PCM, the pose-graph solve, the profile and the remaining hooks.)
 #include "scl_engine.h"
 
 #include <hip/hip_runtime.h>
@@ -25,7 +27,6 @@
 #include <thread>
 #include <vector>
 
-#include "db_file.hpp"
 #include "engine_internal.hpp"
 #include "device_sort.hpp"
 #include "plugin_host.hpp"
@@ -139,11 +140,22 @@ void drain_keeping_error(scl_engine *e, const hipStream_t *streams, int n)
 
 DbView db_view(const scl_engine *e)
 {
+    const DbArrays &a = e->db;
     DbView v;
-    v.desc = e->d_desc; v.vkey = e->d_vkey; v.norm = e->d_norm; v.rkey = e->d_rkey; v.rkey4 = e->d_rkey4;
-    v.hdesc = e->d_hdesc; v.kmask = e->d_kmask; v.hkey = e->d_hkey; v.hstride = e->hstride; v.halign = e->d_halign;
+    v.desc = a.d_desc; v.vkey = a.d_vkey; v.norm = a.d_norm; v.rkey = a.d_rkey; v.rkey4 = a.d_rkey4;
+    v.hdesc = a.d_hdesc; v.kmask = a.d_kmask; v.hkey = a.d_hkey; v.hstride = e->hstride; v.halign = a.d_halign;
     v.cap = e->cap; v.R = e->R; v.S = e->S; v.RG = e->RG;
     return v;
+}
+
+// What an ingest launch writes: every array of the slots from first_slot on, out of wire descriptors (`values`) or out of the batch
+// scatter's tiles (then vals_out receives their wire form).  stage_row: first_slot is a staging row, which has no tiled ring key and
+// no alignment image
+IngestArgs ingest_args(const scl_engine *e, int first_slot, const float *values, int *tiles, float *vals_out, bool stage_row)
+{
+    const DbArrays &a = e->db;
+    return IngestArgs{values, first_slot, a.d_desc, a.d_vkey, a.d_norm, a.d_rkey, stage_row ? nullptr : a.d_rkey4, a.d_hdesc, a.d_kmask, a.d_hkey,
+                      e->hstride, e->cap, e->R, e->S, stage_row ? nullptr : a.d_halign, tiles, vals_out};
 }
 
 int query_view(const scl_engine *e, int query, QueryView *q)
@@ -151,12 +163,12 @@ int query_view(const scl_engine *e, int query, QueryView *q)
     query = query_slot(e, query, e->n);
     if (query == kQueryNotStaged) return fail(e, SCL_ERR_INVALID_ARG, "no staged query (call scl_stage_query first)");
     if (query == kQueryOutOfRange) return fail(e, SCL_ERR_OUT_OF_RANGE, "query slot out of range");
-    q->desc = e->d_desc + (size_t)query * e->RG * e->S;
-    q->vkey = e->d_vkey + (size_t)query * e->S;
-    q->norm = e->d_norm + (size_t)query * e->S;
-    q->rkey = e->d_rkey + (size_t)query * e->R4;
-    q->hdesc = e->d_hdesc + (size_t)query * e->hstride;
-    q->kmask = e->d_kmask + (size_t)query * 8;
+    q->desc = e->db.d_desc + (size_t)query * e->RG * e->S;
+    q->vkey = e->db.d_vkey + (size_t)query * e->S;
+    q->norm = e->db.d_norm + (size_t)query * e->S;
+    q->rkey = e->db.d_rkey + (size_t)query * e->R4;
+    q->hdesc = e->db.d_hdesc + (size_t)query * e->hstride;
+    q->kmask = e->db.d_kmask + (size_t)query * 8;
     return SCL_OK;
 }
 
@@ -211,10 +223,6 @@ int launch_topk(scl_engine *e, const QueryView &q, int lo, int hi, int k, float 
     return SCL_OK;
 }
 
-}  // namespace scl
-
-namespace {
-
 // The end of a SHORT blocking call (tens of microseconds of device time): an event behind its last launch, polled for up to 300 us,
 // then a sleep in the runtime -- hipStreamSynchronize wakes up tens of microseconds late, a fifth of such a call.
 int sync_short(scl_engine *e)
@@ -227,83 +235,9 @@ int sync_short(scl_engine *e)
     return SCL_OK;
 }
 
-// grow the database to hold at least `need` slots (geometric growth, D2D copies)
-int ensure_capacity(scl_engine *e, int need)
-{
-    if (need <= e->cap) return SCL_OK;
-    int ncap = e->cap > 0 ? e->cap : (e->cfg.initial_capacity > 0 ? e->cfg.initial_capacity : 4096);
-    while (ncap < need) ncap *= 2;
-    const size_t tile = (size_t)e->RG * e->S;
-    float4 *nd = nullptr; double *nv = nullptr; double *nn = nullptr; float *nr = nullptr; float4 *nr4 = nullptr;
-    uint2 *nh = nullptr; unsigned int *nk = nullptr; unsigned short *nhk = nullptr; unsigned char *nha = nullptr;
-    const size_t hab = (size_t)halign_bytes(e->S);            // alignment images: database slots only
-    int rc;
-    const size_t nst = (size_t)ncap + (size_t)e->stage_rows;  // database slots + the staging (and mirror) rows behind them
-    if ((rc = dev_alloc(e, &nd, tile * nst))) return rc;
-    if ((rc = dev_alloc(e, &nv, (size_t)e->S * nst))) return rc;
-    if ((rc = dev_alloc(e, &nn, (size_t)e->S * nst))) return rc;
-    if ((rc = dev_alloc(e, &nr, (size_t)e->R4 * nst))) return rc;
-    if ((rc = dev_alloc(e, &nh, (size_t)e->hstride * nst))) return rc;
-    if ((rc = dev_alloc(e, &nk, (size_t)8 * nst))) return rc;
-    if ((rc = dev_alloc(e, &nhk, (size_t)e->hkw * nst))) return rc;
-    if (hab && (rc = dev_alloc(e, &nha, hab * (size_t)ncap))) return rc;
-    if ((rc = dev_alloc(e, &nr4, (size_t)e->RG * ncap))) return rc;
-    SCL_HIP(e, hipMemsetAsync(nr4, 0, sizeof(float4) * (size_t)e->RG * ncap, e->stream));
-    if (e->n > 0) {
-        SCL_HIP(e, hipMemcpyAsync(nd, e->d_desc, sizeof(float4) * tile * e->n, hipMemcpyDeviceToDevice, e->stream));
-        SCL_HIP(e, hipMemcpyAsync(nv, e->d_vkey, sizeof(double) * (size_t)e->S * e->n, hipMemcpyDeviceToDevice, e->stream));
-        SCL_HIP(e, hipMemcpyAsync(nn, e->d_norm, sizeof(double) * (size_t)e->S * e->n, hipMemcpyDeviceToDevice, e->stream));
-        SCL_HIP(e, hipMemcpyAsync(nr, e->d_rkey, sizeof(float) * (size_t)e->R4 * e->n, hipMemcpyDeviceToDevice, e->stream));
-        SCL_HIP(e, hipMemcpyAsync(nh, e->d_hdesc, sizeof(uint2) * (size_t)e->hstride * e->n, hipMemcpyDeviceToDevice, e->stream));
-        SCL_HIP(e, hipMemcpyAsync(nk, e->d_kmask, sizeof(unsigned int) * (size_t)8 * e->n, hipMemcpyDeviceToDevice, e->stream));
-        SCL_HIP(e, hipMemcpyAsync(nhk, e->d_hkey, sizeof(unsigned short) * (size_t)e->hkw * e->n, hipMemcpyDeviceToDevice, e->stream));
-        if (hab) SCL_HIP(e, hipMemcpyAsync(nha, e->d_halign, hab * (size_t)e->n, hipMemcpyDeviceToDevice, e->stream));
-        SCL_HIP(e, hipMemcpy2DAsync(nr4, sizeof(float4) * ncap, e->d_rkey4, sizeof(float4) * e->cap,
-                                    sizeof(float4) * e->n, e->RG, hipMemcpyDeviceToDevice, e->stream));
-    }
-    if (e->cap > 0) {                                      // staged queries move with the arrays
-        const size_t k = (size_t)e->stage_rows;
-        SCL_HIP(e, hipMemcpyAsync(nd + tile * ncap, e->d_desc + tile * e->cap, sizeof(float4) * tile * k, hipMemcpyDeviceToDevice, e->stream));
-        SCL_HIP(e, hipMemcpyAsync(nv + (size_t)e->S * ncap, e->d_vkey + (size_t)e->S * e->cap, sizeof(double) * e->S * k, hipMemcpyDeviceToDevice, e->stream));
-        SCL_HIP(e, hipMemcpyAsync(nn + (size_t)e->S * ncap, e->d_norm + (size_t)e->S * e->cap, sizeof(double) * e->S * k, hipMemcpyDeviceToDevice, e->stream));
-        SCL_HIP(e, hipMemcpyAsync(nr + (size_t)e->R4 * ncap, e->d_rkey + (size_t)e->R4 * e->cap, sizeof(float) * e->R4 * k, hipMemcpyDeviceToDevice, e->stream));
-        SCL_HIP(e, hipMemcpyAsync(nh + (size_t)e->hstride * ncap, e->d_hdesc + (size_t)e->hstride * e->cap, sizeof(uint2) * e->hstride * k, hipMemcpyDeviceToDevice, e->stream));
-        SCL_HIP(e, hipMemcpyAsync(nk + (size_t)8 * ncap, e->d_kmask + (size_t)8 * e->cap, sizeof(unsigned int) * 8 * k, hipMemcpyDeviceToDevice, e->stream));
-        SCL_HIP(e, hipMemcpyAsync(nhk + (size_t)e->hkw * ncap, e->d_hkey + (size_t)e->hkw * e->cap, sizeof(unsigned short) * e->hkw * k, hipMemcpyDeviceToDevice, e->stream));
-    }
-    SCL_HIP(e, hipStreamSynchronize(e->stream));
-    // passes still reading the old arrays: the exact pass of a stream's chunk on the side stream, the ring-key scan, the alternate lane
-    // (an append may now run between the chunks of a stream call: stream_screened_locked)
-    for (hipStream_t s2 : {e->stream_alt, e->stream_surv, e->stream2})
-        if (s2) SCL_HIP(e, hipStreamSynchronize(s2));
-    dev_free(e->d_desc); dev_free(e->d_vkey); dev_free(e->d_norm); dev_free(e->d_rkey); dev_free(e->d_rkey4);
-    dev_free(e->d_hdesc); dev_free(e->d_kmask); dev_free(e->d_hkey); dev_free(e->d_halign);
-    e->d_desc = nd; e->d_vkey = nv; e->d_norm = nn; e->d_rkey = nr; e->d_rkey4 = nr4;
-    e->d_hdesc = nh; e->d_kmask = nk; e->d_hkey = nhk; e->d_halign = nha;
-    e->cap = ncap;
-    return SCL_OK;
-}
+}  // namespace scl
 
-int ensure_vals(scl_engine *e, size_t floats)
-{
-    if (floats <= e->vals_cap) return SCL_OK;
-    dev_free(e->d_vals);
-    int rc = dev_alloc(e, &e->d_vals, floats);
-    if (rc) { e->vals_cap = 0; return rc; }
-    e->vals_cap = floats;
-    return SCL_OK;
-}
-
-int ensure_points(scl_engine *e, size_t bytes)
-{
-    if (bytes <= e->points_cap) return SCL_OK;
-    dev_free(e->d_points);
-    size_t nb = bytes + bytes / 4 + 4096;
-    int rc = dev_alloc(e, &e->d_points, nb);
-    if (rc) { e->points_cap = 0; return rc; }
-    e->points_cap = nb;
-    return SCL_OK;
-}
+namespace {
 
 int ensure_pinned(scl_engine *e, size_t bytes)
 {
@@ -313,101 +247,6 @@ int ensure_pinned(scl_engine *e, size_t bytes)
     memset(e->h_pinned, 0, bytes);                          // (a polled sequence word must never start out as somebody's old number)
     e->pinned_cap = bytes;
     return SCL_OK;
-}
-
-// ingest `count` wire descriptors already in e->d_vals into slots [first, first+count)
-int ingest_from_vals(scl_engine *e, int count, int first_slot)
-{
-    ProfScope ps(e, P_INGEST);
-    SCL_HIP(e, launch_ingest(e->d_vals, count, first_slot, e->d_desc, e->d_vkey, e->d_norm, e->d_rkey,
-                             e->d_rkey4, e->d_hdesc, e->d_kmask, e->d_hkey, e->hstride, e->cap, e->R, e->S, e->stream, e->d_halign));
-    e->db_version++;                                       // the second lane (stream_alt) orders itself behind this write
-    return SCL_OK;
-}
-
-int append_meta(scl_engine *e, int8_t robot, int index)
-{
-    e->robots.push_back(robot);
-    e->indexs.push_back(index);
-    e->n++;
-    return SCL_OK;
-}
-
-// the batch scatter's tiles (make_sc.hip): kMaxScBatch polar images in their initial state between calls
-int ensure_tiles(scl_engine *e, hipStream_t s)
-{
-    int rc;
-    if (!e->d_tiles) {
-        if ((rc = dev_alloc(e, &e->d_tiles, (size_t)2 * kMaxScBatch * e->R * e->S))) return rc;   // two sets: the resident path scatters group g + 1 beside the ingest of group g
-        e->tiles_clean = false;
-    }
-    if (!e->tiles_clean) {                                   // first use, or a call that failed between scatter and consumer
-        SCL_HIP(e, launch_make_sc_tiles_init(e->d_tiles, 2 * kMaxScBatch, e->R, e->S, s));
-        e->tiles_clean = true;
-    }
-    return SCL_OK;
-}
-
-int check_cloud(scl_engine *e, const void *points, int n_points, int stride_bytes)
-{
-    if (n_points < 0 || stride_bytes < 12 || (stride_bytes & 3)) return fail(e, SCL_ERR_INVALID_ARG, "bad point layout");
-    if (n_points > 0 && !points) return fail(e, SCL_ERR_INVALID_ARG, "null points");
-    return SCL_OK;
-}
-
-// K3 for up to kMaxScBatch clouds ALREADY ON THE DEVICE (dptr[i], n[i] points of `stride` bytes): one scatter launch over all of
-// them into the tiles.  What consumes the tiles follows: group_ingest (append) or group_values (descriptor only).
-int group_scatter(scl_engine *e, const unsigned char *const *dptr, const int *n, int count, int stride, hipStream_t s)
-{
-    int rc;
-    if (count < 1 || count > kMaxScBatch) return fail(e, SCL_ERR_INVALID_ARG, "batch of 1..16 scans");
-    if ((rc = ensure_tiles(e, s))) return rc;
-    if ((rc = ensure_vals(e, (size_t)e->R * e->S * (size_t)kMaxScBatch))) return rc;
-    ScanBatch b{};
-    b.count = count;
-    uint64_t pts = 0;
-    for (int i = 0; i < count; ++i) { b.points[i] = dptr[i]; b.n[i] = n[i]; pts += (uint64_t)n[i]; }
-    e->tiles_clean = false;
-    ProfScope ps(e, P_MAKESC, s);
-    // points of a cloud per workgroup: a workgroup's private tile is merged with up to R*S atomics, so the slice grows with the grid
-    // (measured, 16 clouds: 64x120 best at 4 096 of 3 072..16 384; 80x180 at 8 192: 47 us against 60 at 4 096)
-    const int slice = e->R * e->S > 10000 ? 2 * kScPointsPerWorkgroup : kScPointsPerWorkgroup;
-    SCL_HIP(e, launch_make_sc_batch(b, stride, e->R, e->S, e->cfg.lidar_height, e->cfg.max_radius, e->d_tiles,
-                                    scl_lab_int("SCL_SC_SLICE", slice), e->num_cu, s));
-    e->prof.make_sc_points += e->prof_on ? pts : 0;
-    return SCL_OK;
-}
-
-// ... tiles -> database slots [first_slot, first_slot + count) (every array of the slot) + wire-format values in e->d_vals; the tiles
-// are initial again afterwards
-int group_ingest(scl_engine *e, int count, int first_slot, hipStream_t s)
-{
-    ProfScope ps(e, P_INGEST, s);
-    SCL_HIP(e, launch_ingest(nullptr, count, first_slot, e->d_desc, e->d_vkey, e->d_norm, e->d_rkey, e->d_rkey4, e->d_hdesc, e->d_kmask,
-                             e->d_hkey, e->hstride, e->cap, e->R, e->S, s, e->d_halign, e->d_tiles, e->d_vals));
-    e->tiles_clean = true;
-    e->db_version++;                                       // the second lane (stream_alt) orders itself behind this write
-    return SCL_OK;
-}
-
-// ... tiles -> wire-format values in e->d_vals only (nothing is stored)
-int group_values(scl_engine *e, int count, hipStream_t s)
-{
-    SCL_HIP(e, launch_make_sc_finalize(e->d_tiles, count, e->R, e->S, e->d_vals, s));
-    e->tiles_clean = true;
-    return SCL_OK;
-}
-
-// one cloud from the host into e->d_points, then the scatter
-int scatter_host_cloud(scl_engine *e, const void *points, int n_points, int stride_bytes)
-{
-    int rc;
-    if ((rc = check_cloud(e, points, n_points, stride_bytes))) return rc;
-    const size_t bytes = (size_t)n_points * (size_t)stride_bytes;
-    if ((rc = ensure_points(e, bytes + 16))) return rc;
-    if (bytes) SCL_HIP(e, hipMemcpyAsync(e->d_points, points, bytes, hipMemcpyHostToDevice, e->stream));
-    const unsigned char *dp = e->d_points;
-    return group_scatter(e, &dp, &n_points, 1, stride_bytes, e->stream);
 }
 
 int launch_distance(scl_engine *e, const QueryView &q, const int *d_cand, int slot_base, int n)
@@ -692,8 +531,7 @@ int scl_destroy(scl_engine *e)
         icp_workspace_free(&e->icp_lane_ws[i]);
         if (e->icp_lane_stream[i]) (void)hipStreamDestroy(e->icp_lane_stream[i]);
     }
-    dev_free(e->d_desc); dev_free(e->d_vkey); dev_free(e->d_norm); dev_free(e->d_rkey); dev_free(e->d_rkey4);
-    dev_free(e->d_hdesc); dev_free(e->d_kmask); dev_free(e->d_hkey); dev_free(e->d_halign);
+    db_arrays_free(e->db);
     dev_free(e->d_vals); dev_free(e->d_points); dev_free(e->d_tiles);
     for (int b = 0; b < 3; ++b) {
         dev_free(e->d_pbuf[b]);
@@ -745,118 +583,6 @@ int scl_destroy(scl_engine *e)
 }
 
 /* ---- the six virtuals ------------------------------------------------------ */
-
-int scl_make_and_save(scl_engine *e, const void *points, int n_points, int stride_bytes,
-                      int8_t robot, int index, float *out_values)
-{
-    if (!e) return SCL_ERR_INVALID_ARG;
-    if (e->front) return front_make_and_save(e, points, n_points, stride_bytes, robot, index, out_values, false, 0.f, nullptr);
-    std::lock_guard<std::mutex> lk(e->mu);
-    (void)hipSetDevice(e->device);
-    int rc;
-    if ((rc = ensure_capacity(e, e->n + 1))) return rc;
-    if ((rc = scatter_host_cloud(e, points, n_points, stride_bytes))) return rc;
-    if ((rc = group_ingest(e, 1, e->n, e->stream))) return rc;
-    if (out_values)
-        SCL_HIP(e, hipMemcpyAsync(out_values, e->d_vals, sizeof(float) * (size_t)e->R * e->S,
-                                  hipMemcpyDeviceToHost, e->stream));
-    if ((rc = sync_short(e))) return rc;                    // (tens of microseconds of device time: polled, not slept on)
-    return append_meta(e, robot, index);
-}
-
-int scl_make_and_save_filtered(scl_engine *e, const void *points, int n_points, int stride_bytes, float leaf,
-                               int8_t robot, int index, float *out_values, int *n_filtered)
-{
-    if (!e) return SCL_ERR_INVALID_ARG;
-    if (e->front) return front_make_and_save(e, points, n_points, stride_bytes, robot, index, out_values, true, leaf, n_filtered);
-    std::lock_guard<std::mutex> lk(e->mu);
-    (void)hipSetDevice(e->device);
-    int rc;
-    if ((rc = check_cloud(e, points, n_points, stride_bytes))) return rc;
-    if ((rc = ensure_capacity(e, e->n + 1))) return rc;
-    // makeDescriptors, DM.h:996-1002: VoxelGrid(descriptLeafSize) then makeAndSaveDescriptorAndKey -- the filtered cloud
-    // never leaves the device
-    std::string err;
-    const void *d_cloud = nullptr;
-    int m = 0;
-    if ((rc = voxel_grid_to_device(&e->vox_ws, e->stream, points, n_points, stride_bytes, leaf, &d_cloud, &m, &err))) { e->last_error = err; return rc; }
-    const unsigned char *dp = static_cast<const unsigned char *>(d_cloud);
-    if ((rc = group_scatter(e, &dp, &m, 1, stride_bytes, e->stream))) return rc;
-    if ((rc = group_ingest(e, 1, e->n, e->stream))) return rc;
-    if (out_values)
-        SCL_HIP(e, hipMemcpyAsync(out_values, e->d_vals, sizeof(float) * (size_t)e->R * e->S,
-                                  hipMemcpyDeviceToHost, e->stream));
-    if ((rc = sync(e))) return rc;
-    if (n_filtered) *n_filtered = m;
-    return append_meta(e, robot, index);
-}
-
-int scl_make_descriptor(scl_engine *e, const void *points, int n_points, int stride_bytes, float *out_values)
-{
-    if (!e || !out_values) return SCL_ERR_INVALID_ARG;
-    if (e->front) e = front_primary(e);
-    std::lock_guard<std::mutex> lk(e->mu);
-    (void)hipSetDevice(e->device);
-    int rc;
-    if ((rc = scatter_host_cloud(e, points, n_points, stride_bytes))) return rc;
-    if ((rc = group_values(e, 1, e->stream))) return rc;
-    SCL_HIP(e, hipMemcpyAsync(out_values, e->d_vals, sizeof(float) * (size_t)e->R * e->S,
-                              hipMemcpyDeviceToHost, e->stream));
-    return sync(e);
-}
-
-int scl_save_from_wire(scl_engine *e, const float *values, int8_t robot, int index)
-{
-    return scl_save_bulk(e, values, 1, &robot, &index);
-}
-
-int scl_save_bulk(scl_engine *e, const float *values, int count, const int8_t *robots, const int *indexs)
-{
-    if (!e || count < 0 || (count > 0 && !values)) return SCL_ERR_INVALID_ARG;
-    if (e->front) return front_save_bulk(e, values, count, robots, indexs);
-    std::lock_guard<std::mutex> lk(e->mu);
-    (void)hipSetDevice(e->device);
-    int rc;
-    if ((rc = ensure_capacity(e, e->n + count))) return rc;
-    const size_t cells = (size_t)e->R * e->S;
-    const int chunk = 2048;
-    if ((rc = ensure_vals(e, cells * (size_t)(count < chunk ? count : chunk)))) return rc;
-    for (int done = 0; done < count; done += chunk) {
-        const int c = count - done < chunk ? count - done : chunk;
-        SCL_HIP(e, hipMemcpyAsync(e->d_vals, values + (size_t)done * cells, sizeof(float) * cells * c,
-                                  hipMemcpyHostToDevice, e->stream));
-        if ((rc = ingest_from_vals(e, c, e->n + done))) return rc;
-        if ((rc = sync(e))) return rc;     // d_vals is reused by the next chunk
-    }
-    for (int i = 0; i < count; ++i) {
-        e->robots.push_back(robots ? robots[i] : (int8_t)0);
-        e->indexs.push_back(indexs ? indexs[i] : e->n + i);
-    }
-    e->n += count;
-    return SCL_OK;
-}
-
-int scl_stage_query(scl_engine *e, const float *values)
-{
-    if (!e || !values) return SCL_ERR_INVALID_ARG;
-    if (e->front) return front_stage_query(e, values);
-    std::lock_guard<std::mutex> pk(e->pass_mu);
-    std::lock_guard<std::mutex> lk(e->mu);
-    (void)hipSetDevice(e->device);
-    int rc;
-    const size_t cells = (size_t)e->R * e->S;
-    if ((rc = ensure_vals(e, cells))) return rc;
-    SCL_HIP(e, hipMemcpyAsync(e->d_vals, values, sizeof(float) * cells, hipMemcpyHostToDevice, e->stream));
-    {
-        ProfScope ps(e, P_INGEST);
-        // staging slot 0 = database index cap; no tiled ring key for staged queries (rkey4 == nullptr)
-        SCL_HIP(e, launch_ingest(e->d_vals, 1, e->cap, e->d_desc, e->d_vkey, e->d_norm, e->d_rkey, nullptr, e->d_hdesc, e->d_kmask, e->d_hkey, e->hstride,
-                                 e->cap, e->R, e->S, e->stream));
-    }
-    if ((rc = sync(e))) return rc;
-    e->staged[0] = true;
-    return SCL_OK;
-}
 
 int scl_detect_intra(scl_engine *e, int cur, int *loop_id, float *shift, double *dist)
 {
@@ -976,7 +702,7 @@ int scl_get_descriptor(const scl_engine *ce, int key, float *values)
     int rc;
     const size_t cells = (size_t)e->R * e->S;
     if ((rc = ensure_vals(e, cells))) return rc;
-    SCL_HIP(e, launch_untile(e->d_desc + (size_t)key * e->RG * e->S, e->R, e->S, e->d_vals, e->stream));
+    SCL_HIP(e, launch_untile(e->db.d_desc + (size_t)key * e->RG * e->S, e->R, e->S, e->d_vals, e->stream));
     SCL_HIP(e, hipMemcpyAsync(values, e->d_vals, sizeof(float) * cells, hipMemcpyDeviceToHost, e->stream));
     return sync(e);
 }
@@ -989,7 +715,7 @@ int scl_get_ringkey(const scl_engine *ce, int key, float *ringkey)
     std::lock_guard<std::mutex> lk(e->mu);
     (void)hipSetDevice(e->device);
     if (key < 0 || key >= e->n) return fail(e, SCL_ERR_OUT_OF_RANGE, "key out of range");
-    SCL_HIP(e, hipMemcpyAsync(ringkey, e->d_rkey + (size_t)key * e->R4, sizeof(float) * e->R,
+    SCL_HIP(e, hipMemcpyAsync(ringkey, e->db.d_rkey + (size_t)key * e->R4, sizeof(float) * e->R,
                               hipMemcpyDeviceToHost, e->stream));
     return sync(e);
 }
@@ -1002,7 +728,7 @@ int scl_get_sectorkey(const scl_engine *ce, int key, double *sectorkey)
     std::lock_guard<std::mutex> lk(e->mu);
     (void)hipSetDevice(e->device);
     if (key < 0 || key >= e->n) return fail(e, SCL_ERR_OUT_OF_RANGE, "key out of range");
-    SCL_HIP(e, hipMemcpyAsync(sectorkey, e->d_vkey + (size_t)key * e->S, sizeof(double) * e->S,
+    SCL_HIP(e, hipMemcpyAsync(sectorkey, e->db.d_vkey + (size_t)key * e->S, sizeof(double) * e->S,
                               hipMemcpyDeviceToHost, e->stream));
     return sync(e);
 }
@@ -1346,8 +1072,7 @@ int scl_sc_search(scl_engine *e, const int *curs, int count, int k, int *cand_id
     std::vector<int> lo((size_t)count, 0), hi((size_t)count, 0);
     for (int i = 0; i < count; ++i) {
         if (curs[i] < 0) return SCL_ERR_OUT_OF_RANGE;                      // (a staged query has no place in the database: scl_sc_search_range)
-        const int h = curs[i] - e->cfg.num_exclude_recent;                 /* D.h:1627 */
-        hi[(size_t)i] = h > 0 ? h : 0;
+        hi[(size_t)i] = detect_range_hi(e, curs[i]);
     }
     return scl_sc_search_range(e, curs, lo.data(), hi.data(), count, k, cand_ids, cand_shifts, cand_dists, n_found);
 }
@@ -1393,360 +1118,6 @@ int scl_sc_search_inter(scl_engine *e, const int *curs, int count, int robot_pre
     if (count == 0) return SCL_OK;
     if (e->front) return front_sc_search_inter(e, curs, count, robot_pre, k, cand_ids, cand_shifts, cand_dists, n_found);
     return sc_search_robot(e, curs, count, true, robot_pre, k, cand_ids, cand_shifts, cand_dists, n_found);
-}
-
-namespace {
-
-constexpr int kDefaultCopyStreams = 2;
-
-// The per-incoming-scan pipeline from raw points (DM.h:988-1025 makeDescriptors once per keyframe, then DM.h:1078 detection):
-// the scans go through in GROUPS of up to kMaxScBatch.  A group's clouds are copied into one of three device buffers on the copy
-// stream -- by DMA when the caller's buffers are pinned (scl_host_alloc / scl_host_register) -- while the group before is binned (one
-// scatter launch), ingested (one launch: every array of its database slots), and, `detect`, searched for over the whole database
-// ([0, key - NUM_EXCLUDE_RECENT), D.h:1627) by the stream form's launch group.  PCIe is the floor of this path (n x stride bytes per
-// scan against ~10 us of kernels), so the only thing that matters is that the copy engine never waits: group g + 1's copy is
-// enqueued before group g's kernels, and the host blocks only on group g's results.
-// pass_mu (detect) and `db` = e->mu are held by the caller; the database lock is given up while a group's detection waits.
-int points_pipeline_locked(scl_engine *e, std::unique_lock<std::mutex> &db, const void *const *clouds, const int *n_points, int n_scans,
-                           int stride_bytes, const int8_t *robots, const int *indexs, float *out_values,
-                           bool detect, int *nn_idx, int *shift, double *dist)
-{
-    int rc;
-    for (int i = 0; i < n_scans; ++i)
-        if ((rc = check_cloud(e, clouds[i], n_points[i], stride_bytes))) return rc;
-    if (n_scans == 0) return SCL_OK;
-    constexpr int G = kMaxScBatch;
-    const int ng = (n_scans + G - 1) / G;
-    const size_t cells = (size_t)e->R * e->S;
-    // every group's clouds at 256-byte aligned offsets of one buffer: the largest group sizes the three buffers
-    // ... unless the group's clouds lie one behind the other in ONE host allocation (a ring of incoming scans, an arena the host
-    // assembles its clouds in): ascending addresses, 16-byte aligned distances, gaps of at most a page.  Such a group travels as ONE copy
-    // of its whole span -- at the link's rate for large copies (56.8 GB/s) instead of sixteen start-ups (44.8 GB/s on one stream) -- and
-    // lies on the device as it lay on the host (*merged; off = the clouds' distances from the first).
-    auto group_bytes = [&](int g, size_t *off, bool *merged_out = nullptr) {
-        const int i0 = g * G, i1 = (g + 1) * G < n_scans ? (g + 1) * G : n_scans;
-        bool merged = i1 - i0 >= 2;
-        const unsigned char *base = static_cast<const unsigned char *>(clouds[i0]), *end = base;
-        for (int i = i0; merged && i < i1; ++i) {
-            const unsigned char *c = static_cast<const unsigned char *>(clouds[i]);
-            const size_t bytes = (size_t)n_points[i] * (size_t)stride_bytes;
-            if (!c || bytes == 0 || c < end || (size_t)(c - end) >= 4096 || ((size_t)(c - base) & 15)) merged = false;   // (a gap below a page lies in pages the clouds themselves touch)
-            else end = c + bytes;
-        }
-        if (merged_out) *merged_out = merged;
-        if (merged) {
-            for (int i = i0; off && i < i1; ++i) off[i - i0] = (size_t)(static_cast<const unsigned char *>(clouds[i]) - base);
-            return (size_t)(end - base) + 16;
-        }
-        size_t at = 0;
-        for (int i = i0; i < i1; ++i) {
-            if (off) off[i - i0] = at;
-            at += (((size_t)n_points[i] * (size_t)stride_bytes + 16) + 255) & ~(size_t)255;
-        }
-        return at;
-    };
-    size_t need = 0;
-    for (int g = 0; g < ng; ++g) { const size_t b = group_bytes(g, nullptr); need = b > need ? b : need; }
-    const int nbuf = ng < 3 ? ng : 3;
-    if (!e->stream_copy) SCL_HIP(e, hipStreamCreateWithFlags(&e->stream_copy, hipStreamNonBlocking));
-    // several copy streams: a cloud is one copy of a megabyte or two, and the copies of ONE stream run strictly one after the other,
-    // each with its own start-up (17 us: 44.8 GB/s for cloud-sized copies against 56.8 for one large copy); with the clouds of a group
-    // dealt over several streams another copy is in flight while one is being set up
-    const int ncs = std::min(std::max(scl_lab_int("SCL_COPY_STREAMS", kDefaultCopyStreams), 1), (int)scl_engine::kCopyStreams);
-    auto cstream = [&](int c) { return c == 0 ? e->stream_copy : e->stream_copy_x[c - 1]; };
-    for (int c = 1; c < ncs; ++c)
-        if (!e->stream_copy_x[c - 1]) SCL_HIP(e, hipStreamCreateWithFlags(&e->stream_copy_x[c - 1], hipStreamNonBlocking));
-    for (int b = 0; b < 3; ++b) {
-        for (int c = 0; c < ncs; ++c)
-            if (!e->ev_copied[c][b]) SCL_HIP(e, hipEventCreateWithFlags(&e->ev_copied[c][b], hipEventDisableTiming));
-        if (!e->ev_consumed[b]) SCL_HIP(e, hipEventCreateWithFlags(&e->ev_consumed[b], hipEventDisableTiming));
-    }
-    if (need > e->pbuf_cap || !e->d_pbuf[nbuf - 1]) {      // (nothing of an earlier call is in flight: every call ends with its last group consumed)
-        const size_t nb = need > e->pbuf_cap ? need + need / 4 + 4096 : e->pbuf_cap;
-        for (int b = 0; b < 3; ++b) {
-            if (need > e->pbuf_cap) { dev_free(e->d_pbuf[b]); e->d_pbuf[b] = nullptr; }
-            if (b < nbuf && !e->d_pbuf[b] && (rc = dev_alloc(e, &e->d_pbuf[b], nb))) { e->pbuf_cap = 0; return rc; }
-        }
-        e->pbuf_cap = nb;
-    }
-    if ((rc = ensure_capacity(e, e->n + n_scans))) return rc;     // the slots of every scan of the call: no regrow between groups
-
-    auto enqueue_copy = [&](int g) -> int {
-        const int b = g % 3;
-        size_t off[G];
-        bool merged = false;
-        const size_t span = group_bytes(g, off, &merged);
-        if (g >= 3)                                          // the group that was binned out of this buffer
-            for (int c = 0; c < ncs; ++c) SCL_HIP(e, hipStreamWaitEvent(cstream(c), e->ev_consumed[b], 0));
-        if (merged) SCL_HIP(e, hipMemcpyAsync(e->d_pbuf[b], clouds[g * G], span - 16, hipMemcpyHostToDevice, cstream(0)));
-        else for (int i = g * G; i < n_scans && i < (g + 1) * G; ++i) {
-            const size_t bytes = (size_t)n_points[i] * (size_t)stride_bytes;
-            if (bytes) SCL_HIP(e, hipMemcpyAsync(e->d_pbuf[b] + off[i - g * G], clouds[i], bytes, hipMemcpyHostToDevice, cstream(i % ncs)));
-        }
-        for (int c = 0; c < ncs; ++c) SCL_HIP(e, hipEventRecord(e->ev_copied[c][b], cstream(c)));
-        return SCL_OK;
-    };
-    // error path: nothing may still read the caller's buffers or write the point buffers when the call returns
-    auto bail = [&](int code) {
-        hipStream_t busy[scl_engine::kCopyStreams + 1];
-        for (int c = 0; c < ncs; ++c) busy[c] = cstream(c);
-        busy[ncs] = e->stream;
-        drain_keeping_error(e, busy, ncs + 1);
-        return code;
-    };
-
-    if ((rc = enqueue_copy(0))) return bail(rc);
-    const int excl = e->cfg.num_exclude_recent;
-    for (int g = 0; g < ng; ++g) {
-        if (g + 1 < ng && (rc = enqueue_copy(g + 1))) return bail(rc);
-        const int b = g % 3, i0 = g * G, m = n_scans - i0 < G ? n_scans - i0 : G;
-        size_t off[G];
-        group_bytes(g, off);
-        const unsigned char *dptr[G];
-        for (int j = 0; j < m; ++j) dptr[j] = e->d_pbuf[b] + off[j];
-        for (int c = 0; c < ncs; ++c)
-            if (hipStreamWaitEvent(e->stream, e->ev_copied[c][b], 0) != hipSuccess) return bail(fail(e, SCL_ERR_HIP, "hipStreamWaitEvent(copied)"));
-        if ((rc = group_scatter(e, dptr, n_points + i0, m, stride_bytes, e->stream))) return bail(rc);
-        if (hipEventRecord(e->ev_consumed[b], e->stream) != hipSuccess) return bail(fail(e, SCL_ERR_HIP, "hipEventRecord(consumed)"));
-        if ((rc = ensure_capacity(e, e->n + m))) return bail(rc);   // (no-op unless another thread appended while a group's detection waited)
-        const int first_slot = e->n;
-        if ((rc = group_ingest(e, m, first_slot, e->stream))) return bail(rc);
-        if (out_values && hipMemcpyAsync(out_values + (size_t)i0 * cells, e->d_vals, sizeof(float) * cells * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess)
-            return bail(fail(e, SCL_ERR_HIP, "descriptor values to the host"));
-        for (int j = 0; j < m; ++j) {
-            e->robots.push_back(robots ? robots[i0 + j] : (int8_t)0);
-            e->indexs.push_back(indexs ? indexs[i0 + j] : first_slot + j);
-        }
-        e->n += m;                                          // (stream order: whatever scores these slots is enqueued behind their ingest)
-        if (detect) {
-            int q[G], lo[G], hi[G];
-            for (int j = 0; j < m; ++j) { q[j] = first_slot + j; lo[j] = 0; hi[j] = first_slot + j - excl; if (hi[j] < 0) hi[j] = 0; }
-            if ((rc = detect_full_stream_locked(e, db, q, lo, hi, m, G, 2, nn_idx + i0, shift + i0, dist + i0))) return bail(rc);
-            if (!db.owns_lock()) db.lock();
-        } else if (g + 1 == ng || out_values) {
-            if ((rc = sync(e))) return bail(rc);            // (d_vals is rewritten by the next group)
-        }
-    }
-    if ((rc = sync(e))) return bail(rc);
-    return SCL_OK;
-}
-
-}  // namespace
-
-namespace {
-
-// The same path for clouds that are ALREADY on the device (the keyframe store): with no copy to hide, the groups' two launches go
-// back to back on the stream (16 scans each), and the detection of all the new keyframes is ONE call of the stream form -- whose
-// launch groups overlap (a group's finishing rides beside the next group's alignment), which separate calls per group of 16 cannot.
-int device_points_pipeline_locked(scl_engine *e, std::unique_lock<std::mutex> &db, const unsigned char *const *d_clouds, const int *n_points,
-                                  int n_scans, int stride_bytes, const int8_t *robots, const int *indexs, float *out_values,
-                                  int *nn_idx, int *shift, double *dist)
-{
-    int rc;
-    if (n_scans == 0) return SCL_OK;
-    constexpr int G = kMaxScBatch;
-    const size_t cells = (size_t)e->R * e->S;
-    if ((rc = ensure_capacity(e, e->n + n_scans))) return rc;
-    const int first_key = e->n;
-    if ((rc = ensure_tiles(e, e->stream))) return rc;
-    if ((rc = ensure_vals(e, cells * (size_t)(2 * G)))) return rc;
-    for (int i = 0; i < n_scans; ++i)
-        if (n_points[i] < 0 || (n_points[i] > 0 && !d_clouds[i])) return fail(e, SCL_ERR_INVALID_ARG, "stored cloud without points");
-    // launch g = [ingest of group g - 1 out of tile set (g - 1) & 1] + [scatter of group g into tile set g & 1]: ng + 1 launches back to back
-    const int ng = (n_scans + G - 1) / G;
-    const int slice = scl_lab_int("SCL_SC_SLICE", e->R * e->S > 10000 ? 2 * kScPointsPerWorkgroup : kScPointsPerWorkgroup);
-    e->tiles_clean = false;
-    for (int g = 0; g <= ng; ++g) {
-        ScanBatch b{};
-        if (g < ng) {
-            const int i0 = g * G;
-            b.count = n_scans - i0 < G ? n_scans - i0 : G;
-            for (int j = 0; j < b.count; ++j) { b.points[j] = d_clouds[i0 + j]; b.n[j] = n_points[i0 + j]; }
-        }
-        IngestArgs ia{};
-        int n_ingest = 0;
-        ia.R = e->R; ia.S = e->S;
-        if (g > 0) {
-            const int i0 = (g - 1) * G;
-            n_ingest = n_scans - i0 < G ? n_scans - i0 : G;
-            ia = IngestArgs{nullptr, first_key + i0, e->d_desc, e->d_vkey, e->d_norm, e->d_rkey, e->d_rkey4, e->d_hdesc, e->d_kmask, e->d_hkey, e->hstride, e->cap,
-                            e->R, e->S, e->d_halign, e->d_tiles + (size_t)((g - 1) & 1) * G * cells, e->d_vals + (size_t)((g - 1) & 1) * G * cells};
-        }
-        {
-            ProfScope ps(e, P_MAKESC);
-            SCL_HIP(e, launch_front_fused(b, stride_bytes, e->cfg.lidar_height, e->cfg.max_radius, e->d_tiles + (size_t)(g & 1) * G * cells, slice, ia, n_ingest, e->stream));
-        }
-        if (g > 0 && out_values) {
-            const int i0 = (g - 1) * G;
-            SCL_HIP(e, hipMemcpyAsync(out_values + (size_t)i0 * cells, e->d_vals + (size_t)((g - 1) & 1) * G * cells, sizeof(float) * cells * (size_t)n_ingest,
-                                      hipMemcpyDeviceToHost, e->stream));
-        }
-    }
-    e->tiles_clean = true;
-    e->db_version++;
-    for (int i = 0; i < n_scans; ++i) {
-        e->robots.push_back(robots ? robots[i] : (int8_t)0);
-        e->indexs.push_back(indexs ? indexs[i] : first_key + i);
-    }
-    e->prof.make_sc_points += e->prof_on ? [&] { uint64_t t = 0; for (int i = 0; i < n_scans; ++i) t += (uint64_t)n_points[i]; return t; }() : 0;
-    e->n += n_scans;
-    std::vector<int> q((size_t)n_scans), lo((size_t)n_scans, 0), hi((size_t)n_scans);
-    const int excl = e->cfg.num_exclude_recent;
-    for (int i = 0; i < n_scans; ++i) { q[(size_t)i] = first_key + i; hi[(size_t)i] = first_key + i - excl < 0 ? 0 : first_key + i - excl; }
-    if ((rc = detect_full_stream_locked(e, db, q.data(), lo.data(), hi.data(), n_scans, G, 2, nn_idx, shift, dist))) return rc;
-    if (!db.owns_lock()) db.lock();
-    return sync(e);
-}
-
-}  // namespace
-
-/* makeDescriptors + full-database detection for keyframes whose clouds are in the on-device keyframe store (scl_keyframe_put) */
-int scl_stream_from_store(scl_engine *e, int robot, int first_index, int count, int *nn_idx, int *shift, double *dist, float *out_values)
-{
-    if (!e || robot < 0 || first_index < 0 || count < 0 || (count > 0 && (!nn_idx || !shift || !dist))) return SCL_ERR_INVALID_ARG;
-    if (e->front) return fail(e, SCL_ERR_UNSUPPORTED, "stream_from_store: the keyframe store lives on one engine; call it on a one-GPU engine");
-    std::lock_guard<std::mutex> pk(e->pass_mu);
-    std::unique_lock<std::mutex> lk(e->mu);
-    (void)hipSetDevice(e->device);
-    if ((size_t)robot >= e->kf.size() || (size_t)first_index + (size_t)count > e->kf[(size_t)robot].size())
-        return fail(e, SCL_ERR_OUT_OF_RANGE, "stream_from_store: keyframes not in the store");
-    std::vector<const unsigned char *> d((size_t)count);
-    std::vector<int> n((size_t)count), idx((size_t)count);
-    std::vector<int8_t> rb((size_t)count, (int8_t)robot);
-    for (int i = 0; i < count; ++i) {
-        const auto &c = e->kf[(size_t)robot][(size_t)(first_index + i)];
-        if (c.n < 0) return fail(e, SCL_ERR_OUT_OF_RANGE, "stream_from_store: a keyframe of the range was never stored");
-        d[(size_t)i] = c.d; n[(size_t)i] = c.n; idx[(size_t)i] = first_index + i;
-    }
-    return device_points_pipeline_locked(e, lk, d.data(), n.data(), count, e->kf_stride, rb.data(), idx.data(), out_values, nn_idx, shift, dist);
-}
-
-/* ---- pinned host buffers ----------------------------------------------------------- */
-
-int scl_host_alloc(scl_engine *e, size_t bytes, void **out)
-{
-    if (!e || !out || bytes == 0) return SCL_ERR_INVALID_ARG;
-    scl_engine *t = e->front ? front_primary(e) : e;
-    std::lock_guard<std::mutex> lk(t->mu);
-    (void)hipSetDevice(t->device);
-    void *p = nullptr;
-    SCL_HIP(e, hipHostMalloc(&p, bytes, hipHostMallocPortable));
-    t->host_allocs.push_back(p);
-    *out = p;
-    return SCL_OK;
-}
-
-int scl_host_free(scl_engine *e, void *p)
-{
-    if (!e) return SCL_ERR_INVALID_ARG;
-    if (!p) return SCL_OK;
-    scl_engine *t = e->front ? front_primary(e) : e;
-    std::lock_guard<std::mutex> lk(t->mu);
-    for (size_t i = 0; i < t->host_allocs.size(); ++i)
-        if (t->host_allocs[i] == p) {
-            t->host_allocs.erase(t->host_allocs.begin() + (long)i);
-            (void)hipSetDevice(t->device);
-            SCL_HIP(e, hipHostFree(p));
-            return SCL_OK;
-        }
-    return fail(e, SCL_ERR_INVALID_ARG, "scl_host_free: not a buffer of scl_host_alloc on this engine");
-}
-
-int scl_host_register(scl_engine *e, void *p, size_t bytes)
-{
-    if (!e || !p || bytes == 0) return SCL_ERR_INVALID_ARG;
-    scl_engine *t = e->front ? front_primary(e) : e;
-    (void)hipSetDevice(t->device);
-    SCL_HIP(e, hipHostRegister(p, bytes, hipHostRegisterPortable));
-    return SCL_OK;
-}
-
-int scl_host_unregister(scl_engine *e, void *p)
-{
-    if (!e || !p) return SCL_ERR_INVALID_ARG;
-    scl_engine *t = e->front ? front_primary(e) : e;
-    (void)hipSetDevice(t->device);
-    SCL_HIP(e, hipHostUnregister(p));
-    return SCL_OK;
-}
-
-/* ---- batches of scans from raw points ------------------------------------------------ */
-
-int scl_make_and_save_many(scl_engine *e, const void *const *clouds, const int *n_points, int count, int stride_bytes,
-                           const int8_t *robots, const int *indexs, float *out_values)
-{
-    if (!e || count < 0 || (count > 0 && (!clouds || !n_points))) return SCL_ERR_INVALID_ARG;
-    if (e->front) {                                        // sharded: keyframe by keyframe through the owners (correct, not tuned)
-        const size_t cells = (size_t)e->R * e->S;
-        for (int i = 0; i < count; ++i) {
-            const int rc = scl_make_and_save(e, clouds[i], n_points[i], stride_bytes, robots ? robots[i] : (int8_t)0,
-                                             indexs ? indexs[i] : scl_get_size(e, -1), out_values ? out_values + (size_t)i * cells : nullptr);
-            if (rc) return rc;
-        }
-        return SCL_OK;
-    }
-    std::unique_lock<std::mutex> lk(e->mu);
-    (void)hipSetDevice(e->device);
-    return points_pipeline_locked(e, lk, clouds, n_points, count, stride_bytes, robots, indexs, out_values, false, nullptr, nullptr, nullptr);
-}
-
-int scl_stream_from_points(scl_engine *e, const void *const *clouds, const int *n_points, int n_scans, int stride_bytes,
-                           const int8_t *robots, const int *indexs, int *nn_idx, int *shift, double *dist, float *out_values)
-{
-    if (!e || n_scans < 0 || (n_scans > 0 && (!clouds || !n_points || !nn_idx || !shift || !dist))) return SCL_ERR_INVALID_ARG;
-    if (e->front) {
-        const size_t cells = (size_t)e->R * e->S;
-        const int excl = e->cfg.num_exclude_recent;
-        for (int i0 = 0; i0 < n_scans; i0 += kMaxScBatch) {
-            const int m = n_scans - i0 < kMaxScBatch ? n_scans - i0 : kMaxScBatch;
-            int q[kMaxScBatch], lo[kMaxScBatch], hi[kMaxScBatch];
-            for (int j = 0; j < m; ++j) {
-                const int key = scl_get_size(e, -1);
-                if (key < 0) return key;
-                const int rc = scl_make_and_save(e, clouds[i0 + j], n_points[i0 + j], stride_bytes, robots ? robots[i0 + j] : (int8_t)0,
-                                                 indexs ? indexs[i0 + j] : key, out_values ? out_values + (size_t)(i0 + j) * cells : nullptr);
-                if (rc) return rc;
-                q[j] = key; lo[j] = 0; hi[j] = key - excl < 0 ? 0 : key - excl;
-            }
-            const int rc = scl_detect_full_stream(e, q, lo, hi, m, kMaxScBatch, 2, nn_idx + i0, shift + i0, dist + i0);
-            if (rc) return rc;
-        }
-        return SCL_OK;
-    }
-    std::lock_guard<std::mutex> pk(e->pass_mu);
-    std::unique_lock<std::mutex> lk(e->mu);
-    (void)hipSetDevice(e->device);
-    return points_pipeline_locked(e, lk, clouds, n_points, n_scans, stride_bytes, robots, indexs, out_values, true, nn_idx, shift, dist);
-}
-
-/* measurement: what ONE large copy from pinned host memory reaches on this box's link (the floor of scl_stream_from_points) */
-int scl_host_copy_rate(scl_engine *e, size_t bytes, int reps, double *gbytes_per_s)
-{
-    if (!e || !gbytes_per_s || bytes == 0 || reps < 1) return SCL_ERR_INVALID_ARG;
-    if (e->front) e = front_primary(e);
-    std::lock_guard<std::mutex> lk(e->mu);
-    (void)hipSetDevice(e->device);
-    void *h = nullptr; unsigned char *d = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t he = hipHostMalloc(&h, bytes, hipHostMallocDefault);
-    if (he == hipSuccess) { memset(h, 1, bytes); he = hipMalloc((void **)&d, bytes); }
-    if (he == hipSuccess) he = hipEventCreate(&e0);
-    if (he == hipSuccess) he = hipEventCreate(&e1);
-    if (!e->stream_copy && he == hipSuccess) he = hipStreamCreateWithFlags(&e->stream_copy, hipStreamNonBlocking);
-    float ms = 0.f;
-    if (he == hipSuccess) he = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, e->stream_copy);       // warm
-    if (he == hipSuccess) he = hipEventRecord(e0, e->stream_copy);
-    for (int i = 0; i < reps && he == hipSuccess; ++i) he = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, e->stream_copy);
-    if (he == hipSuccess) he = hipEventRecord(e1, e->stream_copy);
-    if (he == hipSuccess) he = hipEventSynchronize(e1);
-    if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (d) (void)hipFree(d);
-    if (h) (void)hipHostFree(h);
-    SCL_HIP(e, he);
-    *gbytes_per_s = ms > 0.f ? (double)bytes * reps / (ms * 1e-3) / 1e9 : 0.0;
-    return SCL_OK;
 }
 
 /* test hook: the descriptor scatter's fast binning (device_common.hpp: sc_bin_fast) against the reference's chain (sc_bin_exact,
@@ -1873,32 +1244,7 @@ int scl_get_last_topk(scl_engine *e, int k, int *idx, float *d2)
     return sync(e);
 }
 
-/* ---- database dump / load, index map ----------------------------------------------- */
-
-int scl_get_descriptors(const scl_engine *ce, int first, int count, float *values)
-{
-    scl_engine *e = const_cast<scl_engine *>(ce);
-    if (!e || !values || first < 0 || count < 0) return SCL_ERR_INVALID_ARG;
-    const size_t cells = (size_t)e->R * e->S;
-    if (e->front) {                                         // sharded: keyframe by keyframe through the owners
-        for (int i = 0; i < count; ++i) { const int rc = scl_get_descriptor(e, first + i, values + (size_t)i * cells); if (rc) return rc; }
-        return SCL_OK;
-    }
-    std::lock_guard<std::mutex> lk(e->mu);
-    (void)hipSetDevice(e->device);
-    if (first + count > e->n) return fail(e, SCL_ERR_OUT_OF_RANGE, "get_descriptors: range exceeds the database");
-    const int chunk = 512;
-    int rc;
-    if ((rc = ensure_vals(e, cells * (size_t)(count < chunk ? (count > 0 ? count : 1) : chunk)))) return rc;
-    for (int done = 0; done < count; done += chunk) {
-        const int c = count - done < chunk ? count - done : chunk;
-        for (int i = 0; i < c; ++i)
-            SCL_HIP(e, launch_untile(e->d_desc + (size_t)(first + done + i) * e->RG * e->S, e->R, e->S, e->d_vals + (size_t)i * cells, e->stream));
-        SCL_HIP(e, hipMemcpyAsync(values + (size_t)done * cells, e->d_vals, sizeof(float) * cells * (size_t)c, hipMemcpyDeviceToHost, e->stream));
-        if ((rc = sync(e))) return rc;
-    }
-    return SCL_OK;
-}
+/* ---- index map (dump / load: ingest_host.hip) --------------------------------------- */
 
 int scl_find_key(const scl_engine *e, int8_t robot, int index, int *key)
 {
@@ -1912,67 +1258,6 @@ int scl_find_key(const scl_engine *e, int8_t robot, int index, int *key)
         const int rc = scl_get_index(e, k, &r, &idx);
         if (rc) return rc;
         if (r == robot && idx == index) { *key = k; break; }
-    }
-    return SCL_OK;
-}
-
-int scl_db_dump_file(scl_engine *e, const char *path)
-{
-    if (!e || !path) return SCL_ERR_INVALID_ARG;
-    const int n = scl_get_size(e, -1);
-    if (n < 0) return n;
-    FILE *f = std::fopen(path, "wb");
-    if (!f) return fail(e, SCL_ERR_INVALID_ARG, "db_dump: cannot open the file for writing");
-    DbFileHeader h{};
-    std::memcpy(h.magic, kDbMagic, 8);
-    h.version = 1; h.num_ring = e->R; h.num_sector = e->S; h.count = n;
-    // state of detectInterLoopClosureID's periodic tree (D.h:1691-1703): reserved[0] = 1 marks the two words as present
-    if (!e->front) { std::lock_guard<std::mutex> lk(e->mu); h.reserved[0] = 1; h.reserved[1] = e->tree_counter; h.reserved[2] = e->tree_n; }
-    int rc = SCL_OK;
-    if (std::fwrite(&h, sizeof h, 1, f) != 1) rc = SCL_ERR_INVALID_ARG;
-    const size_t cells = (size_t)e->R * e->S;
-    const int chunk = 512;
-    std::vector<float> buf(cells * (size_t)chunk);
-    for (int done = 0; done < n && !rc; done += chunk) {    // float32[N][R*S], wire order (D.h:1446-1455)
-        const int c = n - done < chunk ? n - done : chunk;
-        rc = scl_get_descriptors(e, done, c, buf.data());
-        if (!rc && std::fwrite(buf.data(), sizeof(float) * cells, (size_t)c, f) != (size_t)c) rc = fail(e, SCL_ERR_INVALID_ARG, "db_dump: short write");
-    }
-    for (int k = 0; k < n && !rc; ++k) {                    // (robot, index) map, D.h:1758-1761
-        int8_t r = 0; int32_t idx = 0;
-        rc = scl_get_index(e, k, &r, &idx);
-        const int32_t rec[2] = {(int32_t)r, idx};
-        if (!rc && std::fwrite(rec, sizeof rec, 1, f) != 1) rc = fail(e, SCL_ERR_INVALID_ARG, "db_dump: short write");
-    }
-    if (std::fclose(f) != 0 && !rc) rc = fail(e, SCL_ERR_INVALID_ARG, "db_dump: close failed");
-    return rc;
-}
-
-int scl_db_load_file(scl_engine *e, const char *path, int *n_loaded)
-{
-    if (!e || !path) return SCL_ERR_INVALID_ARG;
-    if (n_loaded) *n_loaded = 0;
-    FILE *f = std::fopen(path, "rb");
-    if (!f) return fail(e, SCL_ERR_INVALID_ARG, "db_load: cannot open the file");
-    const int n_before = scl_get_size(e, -1);
-    DbFileHeader h{};
-    int sink_rc = 0;
-    // the parser (db_file.hpp: host code, fuzzed under ASan / UBSan by `make sanitize`) proves the file's length against its header before
-    // anything is sized by it, and hands the descriptors over in chunks
-    const int st = db_file_parse(f, e->R, e->S, &h, [&](const float *vals, int c, const int8_t *robots, const int *indexs) {
-        const int rc = scl_save_bulk(e, vals, c, robots, indexs);
-        if (!rc && n_loaded) *n_loaded += c;
-        return rc;
-    }, &sink_rc);
-    std::fclose(f);
-    if (st == DBF_SINK) return sink_rc;                     // (scl_save_bulk left its own message)
-    if (st == DBF_NOMEM) return fail(e, SCL_ERR_NOMEM, db_file_status_string(st));
-    if (st != DBF_OK) return fail(e, SCL_ERR_INVALID_ARG, db_file_status_string(st));
-    // an engine that was empty takes over the dump's inter-robot tree state too (D.h:1691-1703): the next
-    // detectInterLoopClosureID searches the range the dumped engine would have searched
-    if (n_before == 0 && !e->front && h.reserved[0] == 1) {
-        std::lock_guard<std::mutex> lk(e->mu);
-        e->tree_counter = h.reserved[1]; e->tree_n = h.reserved[2];
     }
     return SCL_OK;
 }
@@ -2319,59 +1604,6 @@ int scl_device_name(const scl_engine *e, char *buf, int buflen)
 // ---- hooks for the sharded front (engine_internal.hpp) ---------------------------------------------------------
 namespace scl {
 
-int eng_stage_from_peer(scl_engine *dst, int j, scl_engine *src, int src_slot, int count)
-{
-    if (!dst || !src || count < 1 || j < 0 || j + count > dst->stage_rows) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(dst->mu);
-    if (src_slot < 0 || src_slot + count > src->n) return fail(dst, SCL_ERR_OUT_OF_RANGE, "stage_from_peer: source slot out of range");
-    (void)hipSetDevice(dst->device);
-    const size_t tile = (size_t)dst->RG * dst->S, S = (size_t)dst->S, R4 = (size_t)dst->R4, m = (size_t)count;
-    const size_t d = (size_t)dst->cap + (size_t)j, s = (size_t)src_slot;
-    // consecutive slots are consecutive rows of every array on both sides (the strides agree: same grid): one copy per array
-    if (dst->hstride != src->hstride || dst->hkw != src->hkw) return fail(dst, SCL_ERR_INVALID_ARG, "stage_from_peer: the shards' layouts differ");
-    SCL_HIP(dst, hipMemcpyPeerAsync(dst->d_desc + d * tile, dst->device, src->d_desc + s * tile, src->device, sizeof(float4) * tile * m, dst->stream));
-    SCL_HIP(dst, hipMemcpyPeerAsync(dst->d_vkey + d * S, dst->device, src->d_vkey + s * S, src->device, sizeof(double) * S * m, dst->stream));
-    SCL_HIP(dst, hipMemcpyPeerAsync(dst->d_norm + d * S, dst->device, src->d_norm + s * S, src->device, sizeof(double) * S * m, dst->stream));
-    SCL_HIP(dst, hipMemcpyPeerAsync(dst->d_rkey + d * R4, dst->device, src->d_rkey + s * R4, src->device, sizeof(float) * R4 * m, dst->stream));
-    SCL_HIP(dst, hipMemcpyPeerAsync(dst->d_hdesc + d * dst->hstride, dst->device, src->d_hdesc + s * src->hstride, src->device, sizeof(uint2) * src->hstride * m, dst->stream));
-    SCL_HIP(dst, hipMemcpyPeerAsync(dst->d_kmask + d * 8, dst->device, src->d_kmask + s * 8, src->device, sizeof(unsigned int) * 8 * m, dst->stream));
-    SCL_HIP(dst, hipMemcpyPeerAsync(dst->d_hkey + d * dst->hkw, dst->device, src->d_hkey + s * src->hkw, src->device, sizeof(unsigned short) * src->hkw * m, dst->stream));
-    for (int i = 0; i < count; ++i) dst->staged[j + i] = true;
-    return SCL_OK;
-}
-
-int eng_set_stage_rows(scl_engine *e, int rows)
-{
-    if (!e || rows < scl_engine::kStage) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (e->n > 0) return fail(e, SCL_ERR_INVALID_ARG, "stage rows are fixed once a keyframe is stored");
-    (void)hipSetDevice(e->device);
-    const int old_cap = e->cap;
-    e->stage_rows = rows;
-    e->staged.assign((size_t)rows, 0);
-    e->cap = 0;                                            // empty database: new arrays of the new shape, nothing to copy (the old ones are freed there)
-    return ensure_capacity(e, old_cap > 0 ? old_cap : 1);
-}
-
-int eng_stage_values(scl_engine *e, int j, const float *values)
-{
-    if (!e || !values || j < 0 || j >= e->stage_rows) return SCL_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    (void)hipSetDevice(e->device);
-    int rc;
-    const size_t cells = (size_t)e->R * e->S;
-    if ((rc = ensure_vals(e, cells))) return rc;
-    SCL_HIP(e, hipMemcpyAsync(e->d_vals, values, sizeof(float) * cells, hipMemcpyHostToDevice, e->stream));
-    {
-        ProfScope ps(e, P_INGEST);
-        SCL_HIP(e, launch_ingest(e->d_vals, 1, e->cap + j, e->d_desc, e->d_vkey, e->d_norm, e->d_rkey, nullptr, e->d_hdesc, e->d_kmask, e->d_hkey, e->hstride,
-                                 e->cap, e->R, e->S, e->stream));
-    }
-    if ((rc = sync(e))) return rc;
-    e->staged[j] = true;
-    return SCL_OK;
-}
-
 int eng_topk_enqueue(scl_engine *e, int query, int lo, int hi, int k, float eps, bool want_dist, bool *have_dist)
 {
     std::lock_guard<std::mutex> pk(e->pass_mu);            // pass state (pinned results, slots, buffer sets): pass_mu first, like every scoring entry point
@@ -2398,14 +1630,6 @@ int eng_sync_streams(scl_engine *e)
     return SCL_OK;
 }
 
-int eng_ensure_points(scl_engine *e, size_t bytes) { return ensure_points(e, bytes); }   // (the caller holds mu)
-
-bool eng_would_regrow(const scl_engine *e, int count)
-{
-    std::lock_guard<std::mutex> lk(e->mu);
-    return e->n + count > e->cap;
-}
-
 int eng_sc_search_ruled(scl_engine *e, const int *queries, const int *lo, const int *hi, const ScRankRule *rules, int n_queries, int k,
                         int *cand_ids, int *cand_shifts, double *cand_dists, int *n_found)
 {
@@ -2416,18 +1640,6 @@ int eng_sc_search_ruled(scl_engine *e, const int *queries, const int *lo, const 
     std::lock_guard<std::mutex> lk(e->mu);
     (void)hipSetDevice(e->device);
     return sc_search_locked(e, queries, lo, hi, n_queries, k, cand_ids, cand_shifts, cand_dists, n_found, rules);
-}
-
-// Drop the keyframes from n_keep on (the sharded front undoes a multi-shard append that failed on a later shard; the slots'
-// contents are simply overwritten by the next append).  Passes in flight must have been collected by the caller.
-int eng_truncate(scl_engine *e, int n_keep)
-{
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (n_keep < 0 || n_keep > e->n) return SCL_ERR_INVALID_ARG;
-    e->robots.resize((size_t)n_keep); e->indexs.resize((size_t)n_keep);
-    e->n = n_keep;
-    if (e->meta_n > n_keep) e->meta_n = n_keep;              // the slots from n_keep on will hold other keyframes: uploaded again
-    return SCL_OK;
 }
 
 const double *eng_ticket_record(const scl_engine *e, int ticket, int *slot_lo, bool *empty)

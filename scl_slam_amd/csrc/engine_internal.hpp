@@ -1,6 +1,6 @@
-// engine_internal.hpp -- the engine object behind the C ABI, shared by engine.hip (one database on one GPU), screen_host.hip (the host
-// layer of the screened search), registration.hip (the registration entry points and the keyframe store) and sharded_front.hip (one
-// database spread over several GPUs, include/scl_engine.h scl_create_sharded).
+// engine_internal.hpp -- the engine object behind the C ABI, shared by engine.hip (one database on one GPU), ingest_host.hip (the paths
+// that fill the database), screen_host.hip (the host layer of the screened search), registration.hip (the registration entry points and
+// the keyframe store) and sharded_front.hip (one database spread over several GPUs, include/scl_engine.h scl_create_sharded).
 #pragma once
 
 #include "scl_engine.h"
@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "db_arrays.hpp"
 #include "icp.hpp"
 #include "kernels.hpp"
 #include "pcm.hpp"
@@ -26,6 +27,8 @@ enum ProfKind { P_SC = 0, P_TOPK, P_ARGMIN, P_MAKESC, P_INGEST, P_ICPNN, P_ICPRE
 struct PendingEvent { hipEvent_t start, stop; int kind; int launches = 1; };   // launches: what the pair brackets (a chunk's screening: its launch groups)
 
 struct ShardedFront;                                       // sharded_front.hip
+
+using DbArrays = DbArraysOf<float4, uint2>;
 
 }  // namespace scl
 
@@ -58,11 +61,8 @@ struct scl_engine {
 
     // database (layout: kernels.hpp)
     int n = 0, cap = 0;
-    float4 *d_desc = nullptr; double *d_vkey = nullptr; double *d_norm = nullptr;
-    float *d_rkey = nullptr; float4 *d_rkey4 = nullptr;
-    uint2 *d_hdesc = nullptr; unsigned int *d_kmask = nullptr; int hstride = 0;
-    unsigned char *d_halign = nullptr;                      // alignment images of the database's keyframes (kernels.hpp: halign_bytes(S) each)
-    unsigned short *d_hkey = nullptr; int hkw = 0;          // dense fp16 sector keys (+ norms), hkw halfs per slot   // the screening pass's fp16 copy + sector masks
+    scl::DbArrays db;                                       // the nine per-keyframe arrays (db_arrays.hpp has what a row of each is)
+    int hstride = 0, hkw = 0;                               // elements of a row of hdesc (the screening pass's fp16 copy) and of hkey (dense fp16 sector keys + norms)
     std::vector<int8_t> robots;
     std::vector<int> indexs;
 
@@ -184,7 +184,7 @@ struct scl_engine {
 };
 
 
-// ---- what engine.hip and screen_host.hip share; every function here assumes the caller's locks (the `_locked` convention) -----------
+// ---- what engine.hip, ingest_host.hip and screen_host.hip share; every function here assumes the caller's locks (the `_locked` convention) -----------
 namespace scl {
 
 // engine.hip: the profile's event pair around what is enqueued on a stream while the object lives; finished pairs folded into e->prof
@@ -196,11 +196,13 @@ struct ProfScope {
 };
 void collect_profile(scl_engine *e);
 int sync(scl_engine *e);                                                        // the engine's stream, then collect_profile
+int sync_short(scl_engine *e);                                                  // the end of a short blocking call: an event, polled
 hipError_t wait_event_polled(hipEvent_t ev, std::chrono::microseconds budget, bool relax);
 void drain_keeping_error(scl_engine *e, const hipStream_t *streams, int n);
 inline void drain_keeping_error(scl_engine *e, std::initializer_list<hipStream_t> streams) { drain_keeping_error(e, streams.begin(), (int)streams.size()); }
 DbView db_view(const scl_engine *e);
 int query_view(const scl_engine *e, int query, QueryView *q);
+IngestArgs ingest_args(const scl_engine *e, int first_slot, const float *values, int *tiles, float *vals_out, bool stage_row);
 int ensure_pairs(scl_engine *e, size_t n);
 int ensure_sets(scl_engine *e, size_t n);
 int launch_topk(scl_engine *e, const QueryView &q, int lo, int hi, int k, float eps, hipStream_t on = nullptr);
@@ -240,6 +242,14 @@ struct MatrixConsumer {
 protected:
     ~MatrixConsumer() = default;
 };
+
+// The search set of the reference's detection for keyframe `key`: the slots [0, key - num_exclude_recent) (D.h:1627)
+inline int detect_range_hi(const scl_engine *e, int key) { const int hi = key - e->cfg.num_exclude_recent; return hi > 0 ? hi : 0; }
+
+// ingest_host.hip
+int ensure_capacity(scl_engine *e, int need);               // the database holds at least `need` slots (geometric growth, D2D copies)
+int ensure_vals(scl_engine *e, size_t floats);              // e->d_vals holds at least that many floats
+void db_arrays_free(DbArrays &a);
 
 // screen_host.hip
 int matrix_screened_locked(scl_engine *e, const int *slots, int nq, const int *grp_lo, const int *grp_n, MatrixConsumer &out);

@@ -326,11 +326,11 @@ hipError_t launch_ringkey_topk(const DbView &db, const float *qkey, int lo, int 
                                int *out_idx, float *out_d2, hipStream_t stream);
 
 // ingest: row-major wire descriptors (device) -> DB slots first_slot.. (all derived data)
-hipError_t launch_ingest(const float *values, int count, int first_slot,
-                         float4 *desc, double *vkey, double *norm, float *rkey, float4 *rkey4,
-                         uint2 *hdesc, unsigned int *kmask, unsigned short *hkey, int hstride,
-                         int cap, int R, int S, hipStream_t stream, unsigned char *halign = nullptr,
-                         int *tiles = nullptr, float *vals_out = nullptr);   // tiles: descriptors from the batch scatter's tiles (values may be nullptr)
+struct IngestArgs {
+    const float *values; int first_slot; float4 *desc; double *vkey; double *norm; float *rkey; float4 *rkey4; uint2 *hdesc; unsigned int *kmask;
+    unsigned short *hkey; int hstride, cap, R, S; unsigned char *halign; int *tiles; float *vals_out;   // tiles: descriptors from the batch scatter's tiles (values may be nullptr)
+};
+hipError_t launch_ingest(const IngestArgs &ia, int count, hipStream_t stream);
 // tiled -> row-major wire format (read back)
 hipError_t launch_untile(const float4 *desc_slot, int R, int S, float *values, hipStream_t stream);
 
@@ -342,10 +342,6 @@ struct ScanBatch {
     int n[kMaxScBatch];
     int first_wg[kMaxScBatch + 1];                 // filled by launch_make_sc_batch
     int count;
-};
-struct IngestArgs {
-    const float *values; int first_slot; float4 *desc; double *vkey; double *norm; float *rkey; float4 *rkey4; uint2 *hdesc; unsigned int *kmask;
-    unsigned short *hkey; int hstride, cap, R, S; unsigned char *halign; int *tiles; float *vals_out;
 };
 // ingest of n_ingest scans (ia.tiles: the previous group's tiles) beside the scatter of batch b into gtiles, in ONE launch
 hipError_t launch_front_fused(ScanBatch b, int stride_bytes, double lidar_height, double max_radius, int *gtiles, int points_per_wg,

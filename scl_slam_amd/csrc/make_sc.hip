@@ -557,14 +557,11 @@ hipError_t launch_make_sc_batch(ScanBatch b, int stride_bytes, int R, int S, dou
 
 static size_t ingest_lds_bytes(int R, int S) { return sizeof(float) * ((size_t)R * (S + 1) + S + 2) + sizeof(double) * 3 * (size_t)S; }
 
-hipError_t launch_ingest(const float *values, int count, int first_slot,
-                         float4 *desc, double *vkey, double *norm, float *rkey, float4 *rkey4,
-                         uint2 *hdesc, unsigned int *kmask, unsigned short *hkey, int hstride,
-                         int cap, int R, int S, hipStream_t stream, unsigned char *halign, int *tiles, float *vals_out)
+hipError_t launch_ingest(const IngestArgs &ia, int count, hipStream_t stream)
 {
     if (count <= 0) return hipSuccess;
-    if (S > 224) return hipErrorInvalidValue;              // kmask holds 7 words of sector bits
-    const size_t lds = ingest_lds_bytes(R, S);
+    if (ia.S > 224) return hipErrorInvalidValue;           // kmask holds 7 words of sector bits
+    const size_t lds = ingest_lds_bytes(ia.R, ia.S);
     // (the attribute is raised to what the launch needs, not to the CU's 160 KB: the kernel has a few bytes of static LDS of its own --
     //  __syncthreads_or -- and static + dynamic must fit.  Per device; engines on different threads may race here: setting it twice is harmless)
     static std::atomic<size_t> attr_lds_dev[64];
@@ -575,7 +572,6 @@ hipError_t launch_ingest(const float *values, int count, int first_slot,
         if (e != hipSuccess) return e;
         attr_lds.store(lds, std::memory_order_release);
     }
-    IngestArgs ia{values, first_slot, desc, vkey, norm, rkey, rkey4, hdesc, kmask, hkey, hstride, cap, R, S, halign, tiles, vals_out};
     hipLaunchKernelGGL(ingest_kernel, dim3(count), dim3(256), lds, stream, ia);
     return hipGetLastError();
 }
