@@ -45,7 +45,8 @@ typedef enum scl_status {
     SCL_ERR_HIP          = -3,
     SCL_ERR_OUT_OF_RANGE = -4,
     SCL_ERR_NOMEM        = -5,
-    SCL_ERR_UNSUPPORTED  = -6
+    SCL_ERR_UNSUPPORTED  = -6,
+    SCL_ERR_NUMERIC      = -7     /* a factorisation met a pivot it refuses (scl_pgo_solve_condensed) */
 } scl_status;
 
 /* Constructor arguments of scan_context_descriptor, D.h:1307-1316 (same
@@ -871,6 +872,59 @@ int  scl_pgo_optimize(scl_engine *e, const double *poses, int n_poses,
  * linearize_ms = every linearisation and assembly of the call, solve_ms = every PCG solve and retraction; 0 for a stage that call did not
  * run.  Either pointer may be NULL. */
 int  scl_pgo_last_timing(scl_engine *e, double *linearize_ms, double *solve_ms);
+
+/*
+ * POSE-GRAPH SOLVE, CONDENSED DIRECT STEP.  A second linear solver for the LM loop above, exact up to rounding, for graphs that are
+ * odometry chains plus some hundreds of loops -- where block-Jacobi PCG does not converge within its cap.  The calls above are unchanged.
+ *   * Interior poses and junctions.  Pose k is interior when its list of incident factors holds exactly two entries, both between
+ *     factors, one joining k with k - 1 and one joining k with k + 1 (either in either direction).  Every other pose is a junction: the ends
+ *     of a robot's block, loop endpoints, poses with a prior, with a duplicate odometry factor, or whose odometry skips an index.  A
+ *     segment is a maximal run a..b of interior poses; a - 1 and b + 1 exist and are junctions.  Two junctions may be adjacent.
+ *   * The step solves (H + lambda diag H) delta = -g.  Every segment is eliminated by block cyclic reduction over the path [a - 1, a..b,
+ *     b + 1], whose ends are never eliminated: a level eliminates every second node between the ends of what the level before left (of
+ *     the survivors s_0 .. s_m-1 those at odd positions p < m - 1), so the order depends on the segment's length alone; a path of m
+ *     nodes takes about log2 m levels (one loop-free chain of 100 000 poses: 17).  The 6 x 6 pivot block D of a node is factored by
+ *     Cholesky, D = L L^T; with U_l, U_m the couplings (left neighbour, node) and (node, right neighbour), P = L^-1 U_l^T, Q = L^-1 U_m and
+ *     w = L^-1 b, the left neighbour gets -P^T P and -P^T w, the right one -Q^T Q and -Q^T w, and their new coupling is -P^T Q.  A
+ *     surviving node takes its left contribution, then its right.  What the levels leave on the ends, which start from zero, is the
+ *     segment's Schur contribution: two diagonal updates, one coupling block and two right-hand-side updates.
+ *   * The dense matrix S over the n_J junctions in ascending pose order (lower triangle) is assembled in a fixed order: a block's own
+ *     damped diagonal block and the W blocks of the factors between the two junctions in ascending factor number, then the segments'
+ *     contributions in ascending segment number (segments are numbered by their first pose); the right-hand side likewise.  S, padded
+ *     with the identity to a multiple of 32, is factored by a blocked Cholesky in fp64 (panels of 32 columns: the diagonal block, the
+ *     column below it, the trailing update on v_mfma_f64_16x16x4_f64), delta of the junctions is solved for, and the interior is recovered
+ *     by walking the levels back: x = L^-T (w - P x_left - Q x_right).
+ *   * Determinism.  No floating-point atomics; every sum has a fixed order.  The same inputs give the same bits on every run, and
+ *     after a larger call has grown the workspace.
+ *   * Limits.  At most SCL_PGO_MAX_JUNCTIONS junctions: S is then at most 6144^2 doubles (302 MB) of grow-only workspace.  More:
+ *     SCL_ERR_INVALID_ARG, nothing written -- the caller keeps scl_pgo_optimize.  scl_pgo_count_junctions is host only and takes no
+ *     engine; it answers that before a call (any output may be NULL; SCL_ERR_INVALID_ARG for a negative count, n_poses = 0, a NULL index
+ *     array with a positive count or an index out of range).  longest_segment is in poses.
+ *   * A failed pivot.  scl_loop_covariance's rule: a pivot fails when it is not above 2^-43 of its diagonal entry (of the block as
+ *     factored in a segment; of S as assembled in the dense factorisation).  The failure is written to a word of the record the host
+ *     reads once per LM iteration.  scl_pgo_optimize_condensed makes that iteration a rejected step: the poses are kept, lambda is
+ *     multiplied by lambda_factor, *failed_factorisations (may be NULL) counts it, and of the stops only 3 and 4 are looked at.
+ *     scl_pgo_solve_condensed returns SCL_ERR_NUMERIC with nothing written.
+ *   * scl_pgo_solve_condensed: delta (6 n_poses), one step at `poses`; lambda finite and >= 0.  scl_pgo_optimize_condensed: the LM loop
+ *     above with the same four stops, the same retraction and the trial evaluated by the next linearisation; cg_tolerance and
+ *     cg_max_iterations are checked as above and otherwise ignored, result.cg_iterations is 0.  The errors of scl_pgo_hessian_apply and
+ *     scl_pgo_optimize apply unchanged.  On a scl_create_sharded engine both run on the primary shard.  scl_pgo_last_timing reports the
+ *     condensed solve under solve_ms; scl_pgo_condensed_last_timing splits it for the last timed condensed call: ms[0] elimination, [1]
+ *     assembly of S, [2] factorisation, [3] the triangular solves and the way back, each summed over the call's steps.
+ */
+#define SCL_PGO_MAX_JUNCTIONS 1024
+int  scl_pgo_count_junctions(int n_poses, const int *f_i, const int *f_j, int n_factors, const int *p_idx, int n_priors,
+                             int *n_junctions, int *n_segments, int *longest_segment);
+int  scl_pgo_solve_condensed(scl_engine *e, const double *poses, int n_poses,
+                             const int *f_i, const int *f_j, const double *f_z, const double *f_cov, int n_factors,
+                             const int *p_idx, const double *p_z, const double *p_cov, int n_priors,
+                             double lambda, double *delta);
+int  scl_pgo_optimize_condensed(scl_engine *e, const double *poses, int n_poses,
+                                const int *f_i, const int *f_j, const double *f_z, const double *f_cov, int n_factors,
+                                const int *p_idx, const double *p_z, const double *p_cov, int n_priors,
+                                const scl_pgo_params *params, double *poses_out, scl_pgo_result *result, double *chi2,
+                                int *failed_factorisations);
+int  scl_pgo_condensed_last_timing(scl_engine *e, double ms[4]);
 
 /* ---- measurement ----------------------------------------------------------- */
 int  scl_profile_enable(scl_engine *e, int on);   /* 0 off, 1 every kernel family, 2 SC distance only,

@@ -30,6 +30,7 @@
 #include "engine_internal.hpp"
 #include "device_sort.hpp"
 #include "plugin_host.hpp"
+#include "pgo_condense_plan.hpp"
 
 #ifdef SCL_DIAGNOSTICS
 namespace scl { void ingest_stamps_print(); void cand_stamps_print(); }   // make_sc.hip / sc_masked.hip: phase stamps (SCL_INGEST_STAMPS=1)
@@ -364,13 +365,14 @@ const char *scl_status_string(int status)
     case SCL_ERR_OUT_OF_RANGE: return "index out of range";
     case SCL_ERR_NOMEM: return "out of memory";
     case SCL_ERR_UNSUPPORTED: return "unsupported";
+    case SCL_ERR_NUMERIC: return "a factorisation failed";
     default: return "unknown status";
     }
 }
 
 const char *scl_last_error(const scl_engine *e) { return e ? e->last_error.c_str() : "null engine"; }
 
-int scl_abi_version(void) { return 13; }
+int scl_abi_version(void) { return 14; }
 
 int scl_default_config(scl_config *c)
 {
@@ -1440,19 +1442,20 @@ int scl_loop_covariance(const double info[36], double s2, double cov[36])
 namespace {
 
 // what = 0 scl_pgo_linearize (a, b, c, d = cost, gradient, diag, chi2), 1 scl_pgo_hessian_apply (a = x, b = y), 2 scl_pgo_optimize
-// (b = poses_out, d = chi2)
+// (b = poses_out, d = chi2), 3 scl_pgo_solve_condensed (b = delta), 4 scl_pgo_optimize_condensed (as 2, and failed)
 int pgo_call(scl_engine *e, const PgoInputs &in, int what, double lambda, const scl_pgo_params *params, scl_pgo_result *result,
-             const double *a_in, double *a, double *b, double *c, double *d)
+             const double *a_in, double *a, double *b, double *c, double *d, int *failed = nullptr)
 {
     if (!e) return SCL_ERR_INVALID_ARG;
     if (e->front) {                                        // the primary shard does the work; its message goes to the handle the caller holds
         scl_engine *front = e;
-        const int rc = pgo_call(front_primary(e), in, what, lambda, params, result, a_in, a, b, c, d);
+        const int rc = pgo_call(front_primary(e), in, what, lambda, params, result, a_in, a, b, c, d, failed);
         if (rc) front->last_error = scl_last_error(front_primary(front));
         return rc;
     }
     std::lock_guard<std::mutex> lk(e->mu);
-    const std::string name = what == 0 ? "pgo_linearize: " : (what == 1 ? "pgo_hessian_apply: " : "pgo_optimize: ");
+    static const char *const names[5] = {"pgo_linearize: ", "pgo_hessian_apply: ", "pgo_optimize: ", "pgo_solve_condensed: ", "pgo_optimize_condensed: "};
+    const std::string name = names[what];
     if (const char *bad = pgo_inputs_bad(in)) return fail(e, SCL_ERR_INVALID_ARG, (name + bad).c_str());
     scl_pgo_params prm;
     pgo_default_params(&prm);
@@ -1463,15 +1466,23 @@ int pgo_call(scl_engine *e, const PgoInputs &in, int what, double lambda, const 
         for (size_t k = 0; k < 6 * (size_t)in.n_poses; ++k)
             if (!std::isfinite(a_in[k])) return fail(e, SCL_ERR_INVALID_ARG, (name + "a non-finite x").c_str());
     }
-    if (what == 2) {
+    if (what == 3) {
+        if (!b) return fail(e, SCL_ERR_INVALID_ARG, (name + "delta is NULL").c_str());
+        if (!std::isfinite(lambda) || lambda < 0.0) return fail(e, SCL_ERR_INVALID_ARG, (name + "lambda non-finite or negative").c_str());
+    }
+    if (what == 2 || what == 4) {
         if (!b || !result) return fail(e, SCL_ERR_INVALID_ARG, (name + "poses_out or result is NULL").c_str());
         if (params) prm = *params;
         if (const char *bad = pgo_params_bad(prm)) return fail(e, SCL_ERR_INVALID_ARG, (name + bad).c_str());
     }
+    if (what >= 3)
+        if (const char *bad = pgo_condensed_bad(in)) return fail(e, SCL_ERR_INVALID_ARG, (name + bad).c_str());
     (void)hipSetDevice(e->device);
     std::string err;
     const bool timing = e->prof_on == 1;
-    const int rc = what == 0 ? pgo_linearize(&e->pgo_ws, e->stream, in, a, b, c, d, timing, &err)
+    const int rc = what == 3 ? pgo_solve_condensed(&e->pgo_ws, e->stream, in, lambda, b, timing, &err)
+                 : what == 4 ? pgo_optimize_condensed(&e->pgo_ws, e->stream, in, prm, b, result, d, failed, timing, &err)
+                 : what == 0 ? pgo_linearize(&e->pgo_ws, e->stream, in, a, b, c, d, timing, &err)
                  : what == 1 ? pgo_hessian_apply(&e->pgo_ws, e->stream, in, lambda, a_in, b, timing, &err)
                              : pgo_optimize(&e->pgo_ws, e->stream, in, prm, b, result, d, timing, &err);
     if (rc) e->last_error = err;
@@ -1512,6 +1523,50 @@ int scl_pgo_optimize(scl_engine *e, const double *poses, int n_poses,
 {
     const PgoInputs in = {poses, n_poses, f_i, f_j, f_z, f_cov, n_factors, p_idx, p_z, p_cov, n_priors};
     return pgo_call(e, in, 2, 0.0, params, result, nullptr, nullptr, poses_out, nullptr, chi2);
+}
+
+int scl_pgo_count_junctions(int n_poses, const int *f_i, const int *f_j, int n_factors, const int *p_idx, int n_priors,
+                            int *n_junctions, int *n_segments, int *longest_segment)
+{
+    if (n_poses < 1 || n_factors < 0 || n_priors < 0 || (n_factors > 0 && (!f_i || !f_j)) || (n_priors > 0 && !p_idx)) return SCL_ERR_INVALID_ARG;
+    for (int k = 0; k < n_factors; ++k)
+        if (f_i[k] < 0 || f_i[k] >= n_poses || f_j[k] < 0 || f_j[k] >= n_poses) return SCL_ERR_INVALID_ARG;
+    for (int m = 0; m < n_priors; ++m)
+        if (p_idx[m] < 0 || p_idx[m] >= n_poses) return SCL_ERR_INVALID_ARG;
+    int nj = 0, ns = 0, longest = 0;
+    pgo_count_junctions(n_poses, f_i, f_j, n_factors, p_idx, n_priors, &nj, &ns, &longest);
+    if (n_junctions) *n_junctions = nj;
+    if (n_segments) *n_segments = ns;
+    if (longest_segment) *longest_segment = longest;
+    return SCL_OK;
+}
+
+int scl_pgo_solve_condensed(scl_engine *e, const double *poses, int n_poses,
+                            const int *f_i, const int *f_j, const double *f_z, const double *f_cov, int n_factors,
+                            const int *p_idx, const double *p_z, const double *p_cov, int n_priors,
+                            double lambda, double *delta)
+{
+    const PgoInputs in = {poses, n_poses, f_i, f_j, f_z, f_cov, n_factors, p_idx, p_z, p_cov, n_priors};
+    return pgo_call(e, in, 3, lambda, nullptr, nullptr, nullptr, nullptr, delta, nullptr, nullptr);
+}
+
+int scl_pgo_optimize_condensed(scl_engine *e, const double *poses, int n_poses,
+                               const int *f_i, const int *f_j, const double *f_z, const double *f_cov, int n_factors,
+                               const int *p_idx, const double *p_z, const double *p_cov, int n_priors,
+                               const scl_pgo_params *params, double *poses_out, scl_pgo_result *result, double *chi2,
+                               int *failed_factorisations)
+{
+    const PgoInputs in = {poses, n_poses, f_i, f_j, f_z, f_cov, n_factors, p_idx, p_z, p_cov, n_priors};
+    return pgo_call(e, in, 4, 0.0, params, result, nullptr, nullptr, poses_out, nullptr, chi2, failed_factorisations);
+}
+
+int scl_pgo_condensed_last_timing(scl_engine *e, double ms[4])
+{
+    if (!e || !ms) return SCL_ERR_INVALID_ARG;
+    if (e->front) e = front_primary(e);
+    std::lock_guard<std::mutex> lk(e->mu);
+    for (int k = 0; k < 4; ++k) ms[k] = e->pgo_ws.condensed_ms[k];
+    return SCL_OK;
 }
 
 int scl_pgo_last_timing(scl_engine *e, double *linearize_ms, double *solve_ms)

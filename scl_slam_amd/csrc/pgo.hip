@@ -16,6 +16,7 @@
 // A pose of kPgoLongRow incident factors or more is gathered by the wave of the thread that owns it (gather_rows).  No atomics on floats;
 // the one flag, set at convergence, turns the PCG launches queued behind it into returns.
 #include "pgo.hpp"
+#include "pgo_blocks.hpp"
 #include "pgo_graph.hpp"
 #include "se3_device.hpp"
 
@@ -28,18 +29,17 @@ namespace scl {
 namespace {
 
 using namespace se3;
+using pgo_blocks::chol6;
+using pgo_blocks::forward6;
+using pgo_blocks::backward6;
 
 constexpr int kPrepStride = 28;    // q, t of Z^-1 (a prior: of Z) (7); L, cov = L L^T, L[tri(c, r)] = L_rc for r >= c (21)
 constexpr int kPrepL = 7;
 // the planes of a linearised factor
 constexpr int kFacChi2 = 0, kFacGi = 1, kFacGj = 7, kFacHii = 13, kFacHjj = 34, kFacW = 55, kFacPlanes = 91;
+static_assert(kFacW == pgo_blocks::kFacW, "pgo_condensed.hip reads W from these planes");
 constexpr int kBlock = 256;
 constexpr int kCgBlock = 32;       // PCG iterations queued between two reads of the flag
-
-struct PgoRecord {
-    double cost, gmax, step, rz0;
-    int flag, cg;
-};
 
 // ---- reductions of a fixed shape ----------------------------------------------------------------------------------------------------------
 
@@ -121,52 +121,7 @@ __device__ inline void gather_rows(const int *row_ptr, const int *entries, int p
 
 // ---- 6 x 6 pieces ---------------------------------------------------------------------------------------------------------------------------
 
-// S (upper triangle, 21) = L L^T, column by column (scl_loop_covariance's order); false where a pivot is not > 0
-__device__ inline bool chol6(const double *S, double *L)
-{
-    bool ok = true;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        double s = S[tri(c, c)];
-#pragma unroll
-        for (int k = 0; k < c; ++k) s -= L[tri(k, c)] * L[tri(k, c)];
-        if (!(s > 0.0)) ok = false;
-        const double p = sqrt(s);
-        L[tri(c, c)] = p;
-#pragma unroll
-        for (int rr = c + 1; rr < 6; ++rr) {
-            double v = S[tri(c, rr)];
-#pragma unroll
-            for (int k = 0; k < c; ++k) v -= L[tri(k, rr)] * L[tri(k, c)];
-            L[tri(c, rr)] = v / p;
-        }
-    }
-    return ok;
-}
-
-// v <- L^-1 v
-__device__ inline void forward6(const double *L, double *v)
-{
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-        double s = v[a];
-#pragma unroll
-        for (int k = 0; k < a; ++k) s -= L[tri(k, a)] * v[k];
-        v[a] = s / L[tri(a, a)];
-    }
-}
-
-// v <- L^-T v
-__device__ inline void backward6(const double *L, double *v)
-{
-#pragma unroll
-    for (int a = 5; a >= 0; --a) {
-        double s = v[a];
-#pragma unroll
-        for (int k = a + 1; k < 6; ++k) s -= L[tri(a, k)] * v[k];
-        v[a] = s / L[tri(a, a)];
-    }
-}
+// chol6, forward6, backward6: pgo_blocks.hpp
 
 // out = (D + lambda diag(D)) v for the symmetric D given by its upper triangle
 __device__ inline void damped_times(const double *D, double lambda, const double *v, double *out)
@@ -626,12 +581,7 @@ int covariances_bad(const double *cov, int n)
     return 0;
 }
 
-// what one call keeps between its launches
-struct Graph {
-    int n, M, nb;
-    bool timing;
-    float lin_ms, solve_ms;
-};
+using Graph = PgoGraph;
 
 // inputs to the device, the incidence lists, the prep launch: X0 holds the normalised poses afterwards
 int setup(WS *ws, hipStream_t stream, const PgoInputs &in, bool timing, Graph *gr, std::string *err)
@@ -758,6 +708,7 @@ void pgo_workspace_free(PgoWorkspace *ws)
         ws->buf[k] = nullptr; ws->cap[k] = 0;
     }
     for (hipEvent_t &ev : ws->ev) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
+    for (hipEvent_t &ev : ws->ev_c) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
 }
 
 void pgo_default_params(scl_pgo_params *p)
@@ -846,8 +797,41 @@ int pgo_hessian_apply(PgoWorkspace *ws, hipStream_t stream, const PgoInputs &in,
     return SCL_OK;
 }
 
+int pgo_setup(PgoWorkspace *ws, hipStream_t stream, const PgoInputs &in, bool timing, PgoGraph *gr, std::string *err)
+{
+    return setup(ws, stream, in, timing, gr, err);
+}
+
+int pgo_enqueue_linearise(PgoWorkspace *ws, hipStream_t stream, const PgoGraph &gr, int b, bool with_step, std::string *err)
+{
+    return enqueue_linearise(ws, stream, gr, b, with_step, err);
+}
+
+int pgo_read_record(PgoWorkspace *ws, hipStream_t stream, PgoRecord *rec, std::string *err) { return read_record(ws, stream, rec, err); }
+
+int pgo_add_timing(PgoWorkspace *ws, PgoGraph *gr, bool lin, bool solve, std::string *err) { return add_timing(ws, gr, lin, solve, err); }
+
+int pgo_ensure(PgoWorkspace *ws, int k, size_t bytes, std::string *err) { return ensure(ws, k, bytes, err); }
+
+int pgo_enqueue_retract(PgoWorkspace *ws, hipStream_t stream, const PgoGraph &gr, int b, std::string *err)
+{
+    pgo_retract_kernel<<<dim3((unsigned)gr.nb), dim3(kBlock), 0, stream>>>(at<double>(ws, b ? WS::B_X1 : WS::B_X0), at<double>(ws, WS::B_VX), gr.n,
+                                                                           at<double>(ws, b ? WS::B_X0 : WS::B_X1), at<double>(ws, WS::B_PART_STEP));
+    PGO_HIP(hipGetLastError());
+    return SCL_OK;
+}
+
 int pgo_optimize(PgoWorkspace *ws, hipStream_t stream, const PgoInputs &in, const scl_pgo_params &prm, double *poses_out,
                  scl_pgo_result *result, double *chi2, bool timing, std::string *err)
+{
+    const PgoSolveFn pcg = [&prm](PgoWorkspace *w, hipStream_t st, const PgoGraph &gr, int b, double lambda, std::string *e) {
+        return enqueue_solve(w, st, gr, b, lambda, prm, e);
+    };
+    return pgo_lm(ws, stream, in, prm, pcg, false, poses_out, result, chi2, nullptr, timing, err);
+}
+
+int pgo_lm(PgoWorkspace *ws, hipStream_t stream, const PgoInputs &in, const scl_pgo_params &prm, const PgoSolveFn &solve, bool direct,
+           double *poses_out, scl_pgo_result *result, double *chi2, int *failed_factorisations, bool timing, std::string *err)
 {
     Graph gr;
     int rc;
@@ -857,16 +841,23 @@ int pgo_optimize(PgoWorkspace *ws, hipStream_t stream, const PgoInputs &in, cons
         return rc;
     scl_pgo_result res;
     std::memset(&res, 0, sizeof res);
-    int cur = 0;
+    int cur = 0, failed = 0;
     double cost = rec.cost, gmax = rec.gmax, lambda = prm.lambda_initial;
     res.initial_cost = cost;
     for (;;) {
-        if ((rc = enqueue_solve(ws, stream, gr, cur, lambda, prm, err)) || (rc = enqueue_linearise(ws, stream, gr, 1 - cur, true, err)) ||
+        if ((rc = solve(ws, stream, gr, cur, lambda, err)) || (rc = enqueue_linearise(ws, stream, gr, 1 - cur, true, err)) ||
             (rc = read_record(ws, stream, &rec, err)) || (rc = add_timing(ws, &gr, true, true, err)))
             return rc;
         ++res.iterations;
-        res.cg_iterations += rec.cg;
+        if (!direct) res.cg_iterations += rec.cg;
         bool stop_cost = false;
+        if (direct && rec.fail) {                              // a failed pivot: no step was taken
+            ++res.rejected; ++failed;
+            lambda *= prm.lambda_factor;
+            if (res.iterations >= prm.max_iterations) { res.stop_reason = SCL_PGO_STOP_ITERATIONS; break; }
+            if (lambda > prm.lambda_max) { res.stop_reason = SCL_PGO_STOP_LAMBDA; break; }
+            continue;
+        }
         if (rec.cost < cost) {
             stop_cost = cost - rec.cost <= prm.relative_cost_tolerance * cost;
             cost = rec.cost; gmax = rec.gmax; cur = 1 - cur;
@@ -892,6 +883,7 @@ int pgo_optimize(PgoWorkspace *ws, hipStream_t stream, const PgoInputs &in, cons
     std::memcpy(poses_out, out.data(), sizeof(double) * 7 * nn);
     if (chi2) std::memcpy(chi2, c2.data(), sizeof(double) * (size_t)gr.M);
     *result = res;
+    if (failed_factorisations) *failed_factorisations = failed;
     return SCL_OK;
 }
 

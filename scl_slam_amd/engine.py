@@ -197,6 +197,11 @@ def _bind(lib):
         "scl_pgo_hessian_apply": (c_int, [P, dp, c_int, ip, ip, dp, dp, c_int, ip, dp, dp, c_int, c_double, dp, dp]),
         "scl_pgo_optimize": (c_int, [P, dp, c_int, ip, ip, dp, dp, c_int, ip, dp, dp, c_int, POINTER(PgoParams), dp, POINTER(PgoResult), dp]),
         "scl_pgo_last_timing": (c_int, [P, dp, dp]),
+        "scl_pgo_count_junctions": (c_int, [c_int, ip, ip, c_int, ip, c_int, ip, ip, ip]),
+        "scl_pgo_solve_condensed": (c_int, [P, dp, c_int, ip, ip, dp, dp, c_int, ip, dp, dp, c_int, c_double, dp]),
+        "scl_pgo_optimize_condensed": (c_int, [P, dp, c_int, ip, ip, dp, dp, c_int, ip, dp, dp, c_int, POINTER(PgoParams), dp, POINTER(PgoResult), dp,
+                                               ip]),
+        "scl_pgo_condensed_last_timing": (c_int, [P, dp]),
         "scl_profile_enable": (c_int, [P, c_int]),
         "scl_profile_reset": (c_int, [P]),
         "scl_profile_get": (c_int, [P, POINTER(SclProfile)]),
@@ -1331,6 +1336,46 @@ class ScanContextEngine:
         self._check(self._lib.scl_pgo_optimize(self._h, *args, None if params is None else byref(params), _ptr(out, c_double), byref(res),
                                                None if chi2 is None else _ptr(chi2, c_double)), "scl_pgo_optimize")
         return out[:n], res, None if chi2 is None else chi2[:m]
+
+    @staticmethod
+    def pgo_count_junctions(n_poses, f_i, f_j, p_idx):
+        """(n_junctions, n_segments, longest_segment) of the condensed direct step (scl_engine.h: POSE-GRAPH SOLVE, CONDENSED DIRECT STEP);
+        host only.  More than 1024 junctions: pgo_solve_condensed and pgo_optimize_condensed refuse the graph"""
+        lib = load_library(); _bind(lib)
+        fi = np.ascontiguousarray(f_i, dtype=np.int32).reshape(-1); fj = np.ascontiguousarray(f_j, dtype=np.int32).reshape(-1)
+        pi = np.ascontiguousarray(p_idx, dtype=np.int32).reshape(-1)
+        if fj.size != fi.size:
+            raise ValueError("f_i and f_j must have one entry per factor")
+        opt = lambda a: _ptr(a, c_int) if a.size else None
+        nj, ns, longest = c_int(0), c_int(0), c_int(0)
+        rc = lib.scl_pgo_count_junctions(int(n_poses), opt(fi), opt(fj), fi.size, opt(pi), pi.size, byref(nj), byref(ns), byref(longest))
+        if rc != 0:
+            raise SclError(rc, "scl_pgo_count_junctions")
+        return nj.value, ns.value, longest.value
+
+    def pgo_solve_condensed(self, poses, f_i, f_j, f_z, f_cov, p_idx, p_z, p_cov, lam):
+        """delta[n,6] with (H + lam diag(H)) delta = -g at `poses`, by the condensed direct step: exact up to rounding"""
+        keep, args, n, m = self._pgo_inputs(poses, f_i, f_j, f_z, f_cov, p_idx, p_z, p_cov)
+        delta = np.zeros((max(n, 1), 6))
+        self._check(self._lib.scl_pgo_solve_condensed(self._h, *args, float(lam), _ptr(delta, c_double)), "scl_pgo_solve_condensed")
+        return delta[:n]
+
+    def pgo_optimize_condensed(self, poses, f_i, f_j, f_z, f_cov, p_idx, p_z, p_cov, params=None, want_chi2=True):
+        """pgo_optimize with the condensed direct step in place of PCG: (poses_out, PgoResult, chi2 or None, failed_factorisations)"""
+        keep, args, n, m = self._pgo_inputs(poses, f_i, f_j, f_z, f_cov, p_idx, p_z, p_cov)
+        out = np.zeros((max(n, 1), 7)); res = PgoResult(); chi2 = np.zeros(max(m, 1)) if want_chi2 else None
+        failed = c_int(0)
+        self._check(self._lib.scl_pgo_optimize_condensed(self._h, *args, None if params is None else byref(params), _ptr(out, c_double), byref(res),
+                                                         None if chi2 is None else _ptr(chi2, c_double), byref(failed)),
+                    "scl_pgo_optimize_condensed")
+        return out[:n], res, None if chi2 is None else chi2[:m], failed.value
+
+    def pgo_condensed_last_timing(self):
+        """(elimination, assembly, factorisation, solves and the way back) in ms, summed over the steps of the last condensed call made
+        under profile_enable(1)"""
+        ms = np.zeros(4)
+        self._check(self._lib.scl_pgo_condensed_last_timing(self._h, _ptr(ms, c_double)), "scl_pgo_condensed_last_timing")
+        return tuple(ms.tolist())
 
     def pgo_last_timing(self):
         """(linearize_ms, solve_ms): device time of the two stages of the last PGO call made under profile_enable(1)"""
