@@ -926,6 +926,62 @@ int  scl_pgo_optimize_condensed(scl_engine *e, const double *poses, int n_poses,
                                 int *failed_factorisations);
 int  scl_pgo_condensed_last_timing(scl_engine *e, double ms[4]);
 
+/*
+ * POSE-GRAPH SOLVE, MANY RIGHT-HAND SIDES AND MARGINAL COVARIANCES.  The factorisation the condensed direct step makes -- L, P, Q of
+ * every eliminated node and the blocked Cholesky factor of S -- used for many right-hand sides instead of one, and on top of that the
+ * covariance of a pose and of one pose relative to another under the solved graph: what gtsam's Marginals gives the reference's users
+ * (its optimiser takes useCovariance, DM.h:878-880), what gates a loop candidate by Mahalanobis distance, and the covariance of PCM's
+ * T_A = (X_ai)^-1 X_aj that odom_var stands in for.  The calls above are unchanged: they keep their launches and their bits.
+ *   * scl_pgo_solve_condensed_many solves (H + lambda diag H) x_c = rhs_c for c < n_rhs.  Column c occupies rhs + 6 n_poses c and x + 6
+ *     n_poses c, laid out as delta is; x may alias rhs.  One linearisation at `poses`, one elimination and one factorisation of S per
+ *     call: the kernels of scl_pgo_solve_condensed, fed the call's lambda.  Then every column runs the forward elimination over the
+ *     levels (w = L^-1 b_m, -P^T w to the left neighbour, -Q^T w to the right one; a survivor takes left, then right), the junctions'
+ *     right-hand side in the order of the step's, L Y = B and L^T X = Y on the factor of S, and the way back x = L^-T (w - P x_left - Q
+ *     x_right).
+ *   * The core rule.  A column's arithmetic is one fixed sequence that depends on the graph and on that column alone: not on n_rhs, not
+ *     on the column's position, not on what the other columns hold, not on how columns are grouped into launches.  The same column
+ *     gives the same bits alone, among 1 535 others, on every run, and after a larger call has grown the workspace.  (In the dense
+ *     solves a workgroup owns 16 columns through all panels of 32: the diagonal block is solved per column, c ascending -- descending
+ *     in the transposed sweep --, the rows below or above are updated by v_mfma_f64_16x16x4_f64, eight per panel in ascending k; a
+ *     tile's missing columns are zeros, and no entry of the product reads another column.)  A column equal to -g need NOT reproduce
+ *     scl_pgo_solve_condensed's bits -- the order inside the dense solves differs --, only its accuracy.
+ *   * Column groups.  Columns run in groups whose per-column arrays -- 6 n_poses doubles of the column itself and 18 doubles per path
+ *     node (b / w / x, the two slots) -- stay within 256 MB: group = 256 MB / that, at most 1536, from 16 on rounded down to a multiple
+ *     of 16, never below 6.  One loop-free chain of 100 000 poses: 13 columns per group.  By the core rule the figure changes no bit.
+ *   * scl_pgo_marginals works at lambda = 0, on the Gauss-Newton matrix H at `poses` -- the Laplace approximation gtsam's Marginals
+ *     uses; call it on the optimiser's poses_out.  Sigma = H^-1 in the tangent of the right perturbations X_k Exp(xi_k), rotation first.
+ *     The distinct poses named by q_i and q_j, in ascending order, give six unit columns each (at most SCL_PGO_MAX_MARGINAL_POSES
+ *     distinct poses), solved as above.  blocks + 36 k: the row-major 6 x 6 block Sigma[q_i[k], q_j[k]], read from the rows of pose
+ *     q_i[k] in the columns of pose q_j[k]; where q_i[k] == q_j[k] the upper triangle is read and mirrored, so the block is exactly
+ *     symmetric.  rel + 36 k: the first-order covariance of the right perturbation of h = X_i^-1 X_j.  From h' = Exp(-xi_i) h Exp(xi_j) =
+ *     h Exp(xi_j - Ad(h^-1) xi_i): rel = Sigma_jj - A Sigma_ij - (A Sigma_ij)^T + A Sigma_ii A^T with A = Ad(h^-1), Ad(R, t) = [[R, 0],
+ *     [[t]x R, R]] as in PCM, h^-1 formed as the linearisation forms it (the translations' difference first); the four terms are added in
+ *     the order written, every 6 x 6 product sums in ascending index, the upper triangle is computed and mirrored.  q_i[k] == q_j[k]: 36
+ *     exact zeros.  Either output may be NULL; one must be given.
+ *   * What rel costs in accuracy.  rel is a DIFFERENCE of terms of the size of Sigma_jj.  Each of them carries the solve's error, about
+ *     2^-53 cond(H) relative to |Sigma_jj|, so wherever |Sigma_jj| >> |rel| -- two neighbouring poses at the far end of a long chain, far
+ *     from its prior -- rel's own relative error is that figure times |Sigma_jj| / |rel|, and its smallest eigenvalues may come out
+ *     negative.  Near the prior, or between poses whose marginals differ by as much as they measure, it is as good as blocks.
+ *   * Errors, all SCL_ERR_INVALID_ARG, checked on the host before anything runs, nothing written: everything scl_pgo_solve_condensed
+ *     refuses (more than SCL_PGO_MAX_JUNCTIONS junctions included); n_rhs < 1 or > SCL_PGO_MAX_RHS; n_queries < 1 or >
+ *     SCL_PGO_MAX_MARGINAL_QUERIES; more than SCL_PGO_MAX_MARGINAL_POSES distinct query poses; a query index out of range; a NULL rhs,
+ *     x, q_i or q_j; both outputs NULL; a non-finite rhs entry.  A failed pivot: SCL_ERR_NUMERIC, nothing written, as in the single step.
+ *   * On a scl_create_sharded engine both calls run on the primary shard.  scl_pgo_condensed_last_timing reports them too: ms[0..2]
+ *     keep their meaning, ms[3] spans the forward eliminations, triangular solves and ways back of all columns (in
+ *     scl_pgo_solve_condensed_many the copies of the groups lie between them and count).  See DESIGN.md section 4, PGO marginals.
+ */
+#define SCL_PGO_MAX_RHS            1536   /* 6 x SCL_PGO_MAX_MARGINAL_POSES */
+#define SCL_PGO_MAX_MARGINAL_POSES 256
+#define SCL_PGO_MAX_MARGINAL_QUERIES 4096
+int  scl_pgo_solve_condensed_many(scl_engine *e, const double *poses, int n_poses,
+                                  const int *f_i, const int *f_j, const double *f_z, const double *f_cov, int n_factors,
+                                  const int *p_idx, const double *p_z, const double *p_cov, int n_priors,
+                                  double lambda, const double *rhs, int n_rhs, double *x);
+int  scl_pgo_marginals(scl_engine *e, const double *poses, int n_poses,
+                       const int *f_i, const int *f_j, const double *f_z, const double *f_cov, int n_factors,
+                       const int *p_idx, const double *p_z, const double *p_cov, int n_priors,
+                       const int *q_i, const int *q_j, int n_queries, double *blocks, double *rel);
+
 /* ---- measurement ----------------------------------------------------------- */
 int  scl_profile_enable(scl_engine *e, int on);   /* 0 off, 1 every kernel family, 2 SC distance only,
                                                      3 SC distance only, sampled: one launch in thirteen -- in the stream form one

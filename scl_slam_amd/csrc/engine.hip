@@ -31,6 +31,7 @@
 #include "device_sort.hpp"
 #include "plugin_host.hpp"
 #include "pgo_condense_plan.hpp"
+#include "pgo_marginal_plan.hpp"
 
 #ifdef SCL_DIAGNOSTICS
 namespace scl { void ingest_stamps_print(); void cand_stamps_print(); }   // make_sc.hip / sc_masked.hip: phase stamps (SCL_INGEST_STAMPS=1)
@@ -372,7 +373,7 @@ const char *scl_status_string(int status)
 
 const char *scl_last_error(const scl_engine *e) { return e ? e->last_error.c_str() : "null engine"; }
 
-int scl_abi_version(void) { return 14; }
+int scl_abi_version(void) { return 15; }
 
 int scl_default_config(scl_config *c)
 {
@@ -1442,19 +1443,22 @@ int scl_loop_covariance(const double info[36], double s2, double cov[36])
 namespace {
 
 // what = 0 scl_pgo_linearize (a, b, c, d = cost, gradient, diag, chi2), 1 scl_pgo_hessian_apply (a = x, b = y), 2 scl_pgo_optimize
-// (b = poses_out, d = chi2), 3 scl_pgo_solve_condensed (b = delta), 4 scl_pgo_optimize_condensed (as 2, and failed)
+// (b = poses_out, d = chi2), 3 scl_pgo_solve_condensed (b = delta), 4 scl_pgo_optimize_condensed (as 2, and failed), 5
+// scl_pgo_solve_condensed_many (a_in = rhs, b = x, count = n_rhs), 6 scl_pgo_marginals (q_i, q_j, count = n_queries, a = blocks, b = rel)
 int pgo_call(scl_engine *e, const PgoInputs &in, int what, double lambda, const scl_pgo_params *params, scl_pgo_result *result,
-             const double *a_in, double *a, double *b, double *c, double *d, int *failed = nullptr)
+             const double *a_in, double *a, double *b, double *c, double *d, int *failed = nullptr, int count = 0, const int *q_i = nullptr,
+             const int *q_j = nullptr)
 {
     if (!e) return SCL_ERR_INVALID_ARG;
     if (e->front) {                                        // the primary shard does the work; its message goes to the handle the caller holds
         scl_engine *front = e;
-        const int rc = pgo_call(front_primary(e), in, what, lambda, params, result, a_in, a, b, c, d, failed);
+        const int rc = pgo_call(front_primary(e), in, what, lambda, params, result, a_in, a, b, c, d, failed, count, q_i, q_j);
         if (rc) front->last_error = scl_last_error(front_primary(front));
         return rc;
     }
     std::lock_guard<std::mutex> lk(e->mu);
-    static const char *const names[5] = {"pgo_linearize: ", "pgo_hessian_apply: ", "pgo_optimize: ", "pgo_solve_condensed: ", "pgo_optimize_condensed: "};
+    static const char *const names[7] = {"pgo_linearize: ", "pgo_hessian_apply: ", "pgo_optimize: ", "pgo_solve_condensed: ", "pgo_optimize_condensed: ",
+                                         "pgo_solve_condensed_many: ", "pgo_marginals: "};
     const std::string name = names[what];
     if (const char *bad = pgo_inputs_bad(in)) return fail(e, SCL_ERR_INVALID_ARG, (name + bad).c_str());
     scl_pgo_params prm;
@@ -1475,12 +1479,27 @@ int pgo_call(scl_engine *e, const PgoInputs &in, int what, double lambda, const 
         if (params) prm = *params;
         if (const char *bad = pgo_params_bad(prm)) return fail(e, SCL_ERR_INVALID_ARG, (name + bad).c_str());
     }
+    if (what == 5) {
+        if (!a_in || !b) return fail(e, SCL_ERR_INVALID_ARG, (name + "rhs or x is NULL").c_str());
+        if (!std::isfinite(lambda) || lambda < 0.0) return fail(e, SCL_ERR_INVALID_ARG, (name + "lambda non-finite or negative").c_str());
+        if (count < 1 || count > SCL_PGO_MAX_RHS) return fail(e, SCL_ERR_INVALID_ARG, (name + "n_rhs < 1 or > 1536").c_str());
+        for (size_t k = 0; k < 6 * (size_t)in.n_poses * (size_t)count; ++k)
+            if (!std::isfinite(a_in[k])) return fail(e, SCL_ERR_INVALID_ARG, (name + "a non-finite rhs").c_str());
+    }
+    if (what == 6) {
+        if (!a && !b) return fail(e, SCL_ERR_INVALID_ARG, (name + "no output given").c_str());
+        if (count < 1 || count > SCL_PGO_MAX_MARGINAL_QUERIES) return fail(e, SCL_ERR_INVALID_ARG, (name + "n_queries < 1 or > 4096").c_str());
+        std::vector<int> sel, ui, uj;
+        if (const char *bad = pgo_marginal_select(q_i, q_j, count, in.n_poses, &sel, &ui, &uj)) return fail(e, SCL_ERR_INVALID_ARG, (name + bad).c_str());
+    }
     if (what >= 3)
         if (const char *bad = pgo_condensed_bad(in)) return fail(e, SCL_ERR_INVALID_ARG, (name + bad).c_str());
     (void)hipSetDevice(e->device);
     std::string err;
     const bool timing = e->prof_on == 1;
-    const int rc = what == 3 ? pgo_solve_condensed(&e->pgo_ws, e->stream, in, lambda, b, timing, &err)
+    const int rc = what == 5 ? pgo_solve_condensed_many(&e->pgo_ws, e->stream, in, lambda, a_in, count, b, timing, &err)
+                 : what == 6 ? pgo_marginals(&e->pgo_ws, e->stream, in, q_i, q_j, count, a, b, timing, &err)
+                 : what == 3 ? pgo_solve_condensed(&e->pgo_ws, e->stream, in, lambda, b, timing, &err)
                  : what == 4 ? pgo_optimize_condensed(&e->pgo_ws, e->stream, in, prm, b, result, d, failed, timing, &err)
                  : what == 0 ? pgo_linearize(&e->pgo_ws, e->stream, in, a, b, c, d, timing, &err)
                  : what == 1 ? pgo_hessian_apply(&e->pgo_ws, e->stream, in, lambda, a_in, b, timing, &err)
@@ -1558,6 +1577,24 @@ int scl_pgo_optimize_condensed(scl_engine *e, const double *poses, int n_poses,
 {
     const PgoInputs in = {poses, n_poses, f_i, f_j, f_z, f_cov, n_factors, p_idx, p_z, p_cov, n_priors};
     return pgo_call(e, in, 4, 0.0, params, result, nullptr, nullptr, poses_out, nullptr, chi2, failed_factorisations);
+}
+
+int scl_pgo_solve_condensed_many(scl_engine *e, const double *poses, int n_poses,
+                                 const int *f_i, const int *f_j, const double *f_z, const double *f_cov, int n_factors,
+                                 const int *p_idx, const double *p_z, const double *p_cov, int n_priors,
+                                 double lambda, const double *rhs, int n_rhs, double *x)
+{
+    const PgoInputs in = {poses, n_poses, f_i, f_j, f_z, f_cov, n_factors, p_idx, p_z, p_cov, n_priors};
+    return pgo_call(e, in, 5, lambda, nullptr, nullptr, rhs, nullptr, x, nullptr, nullptr, nullptr, n_rhs);
+}
+
+int scl_pgo_marginals(scl_engine *e, const double *poses, int n_poses,
+                      const int *f_i, const int *f_j, const double *f_z, const double *f_cov, int n_factors,
+                      const int *p_idx, const double *p_z, const double *p_cov, int n_priors,
+                      const int *q_i, const int *q_j, int n_queries, double *blocks, double *rel)
+{
+    const PgoInputs in = {poses, n_poses, f_i, f_j, f_z, f_cov, n_factors, p_idx, p_z, p_cov, n_priors};
+    return pgo_call(e, in, 6, 0.0, nullptr, nullptr, nullptr, blocks, rel, nullptr, nullptr, nullptr, n_queries, q_i, q_j);
 }
 
 int scl_pgo_condensed_last_timing(scl_engine *e, double ms[4])

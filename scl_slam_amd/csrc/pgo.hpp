@@ -5,6 +5,7 @@
 
 #include <functional>
 #include <string>
+#include <vector>
 
 #include "scl_engine.h"
 
@@ -21,6 +22,9 @@ struct PgoWorkspace {
            // the condensed direct step (pgo_condensed.hip): the plan's arrays, the paths' nodes, the dense system
            B_C_NODE_POSE, B_C_NODE_COUPLING, B_C_ELIM, B_C_ABSORB, B_C_BLOCK_PTR, B_C_BLOCK_RC, B_C_SRC, B_C_RHS_PTR, B_C_RHS_SRC, B_C_JPOSE,
            B_C_ND, B_C_NB, B_C_NU, B_C_NP, B_C_NCL, B_C_NCR, B_C_NX, B_C_S, B_C_LDIAG, B_C_DIAG0, B_C_RHS,
+           // the many-column solve on the kept factor (pgo_marginals.hip): a group's columns, its node arrays, its tiles of the dense
+           // right-hand sides; the marginals' query arrays, kept rows and outputs
+           B_M_X, B_M_NB, B_M_NL, B_M_NR, B_M_TILES, B_M_SEL, B_M_QUERY, B_M_KEPT, B_M_BLOCKS, B_M_REL,
            B_COUNT };
     void *buf[B_COUNT] = {nullptr};
     size_t cap[B_COUNT] = {0};
@@ -85,11 +89,35 @@ int pgo_ensure(PgoWorkspace *ws, int k, size_t bytes, std::string *err);
 
 // ---- pgo_condensed.hip ----------------------------------------------------------------------------------------------------------------
 
+// the plan's shape, kept on the host between the launches of a call
+struct PgoCondensed {
+    int n_nodes = 0, n_junctions = 0, n_blocks = 0, n_levels = 0, n_rows = 0, ld = 0;
+    std::vector<int> level_ptr, absorb_ptr;
+    double ms[4] = {0.0, 0.0, 0.0, 0.0};
+    bool pending = false;                                  // a timed step whose events have not been read
+};
+
 // nullptr, or why the condensed step refuses the graph (more than SCL_PGO_MAX_JUNCTIONS junctions); the indices are in range
 const char *pgo_condensed_bad(const PgoInputs &in);
 // one exact step (H + lambda diag H) delta = -g at in.poses; SCL_ERR_NUMERIC on a failed pivot, nothing written
 int pgo_solve_condensed(PgoWorkspace *ws, hipStream_t stream, const PgoInputs &in, double lambda, double *delta, bool timing, std::string *err);
 int pgo_optimize_condensed(PgoWorkspace *ws, hipStream_t stream, const PgoInputs &in, const scl_pgo_params &params, double *poses_out,
                            scl_pgo_result *result, double *chi2, int *failed_factorisations, bool timing, std::string *err);
+// What pgo_marginals.hip takes from the step.  pgo_condensed_factor: setup, plan, one linearisation at in.poses, the elimination,
+// the assembly and the factorisation of S at lambda -- the step's own launches up to the event ev_c[3]; L, P, Q of every node and the
+// factor of S stay in the workspace.  pgo_condensed_finish: behind the caller's launches, the events ev_c[4] and ev[3], a wait for the
+// stream, the call's timing.
+int pgo_condensed_factor(PgoWorkspace *ws, hipStream_t stream, const PgoInputs &in, double lambda, bool timing, PgoGraph *gr, PgoCondensed *C,
+                         std::string *err);
+int pgo_condensed_finish(PgoWorkspace *ws, hipStream_t stream, PgoGraph *gr, PgoCondensed *C, std::string *err);
+
+// ---- pgo_marginals.hip ----------------------------------------------------------------------------------------------------------------
+
+// (H + lambda diag H) x_c = rhs_c for n_rhs columns of 6 n_poses on one factorisation; x may alias rhs
+int pgo_solve_condensed_many(PgoWorkspace *ws, hipStream_t stream, const PgoInputs &in, double lambda, const double *rhs, int n_rhs, double *x,
+                             bool timing, std::string *err);
+// the blocks of H^-1 and the relative-pose covariances of n_queries pairs; the queries are checked by the caller (pgo_marginal_plan.hpp)
+int pgo_marginals(PgoWorkspace *ws, hipStream_t stream, const PgoInputs &in, const int *q_i, const int *q_j, int n_queries, double *blocks,
+                  double *rel, bool timing, std::string *err);
 
 }  // namespace scl

@@ -18,6 +18,8 @@
 //   cond_tri_solve_kernel     L y = b and L^T x = y, one workgroup, panel by panel
 //   cond_scatter_kernel       delta of the junctions; the paths' ends take theirs
 //   cond_back_kernel          one level back: x_m = L^-T (w - P x_l - Q x_r)
+// What the first three stages leave -- L, P, Q of every node, the factor of S -- is also what pgo_marginals.hip solves many columns on
+// (pgo_condensed_factor: the same launches up to the factorisation).
 #include "pgo.hpp"
 #include "pgo_blocks.hpp"
 #include "pgo_condense_plan.hpp"
@@ -373,13 +375,7 @@ __global__ __launch_bounds__(kNodeBlock) void cond_back_kernel(const int *elim, 
 using WS = PgoWorkspace;
 template <class T> T *at(WS *ws, int k) { return static_cast<T *>(ws->buf[k]); }
 
-// the plan's shape, kept on the host between the launches of a call
-struct Condensed {
-    int n_nodes = 0, n_junctions = 0, n_blocks = 0, n_levels = 0, n_rows = 0, ld = 0;
-    std::vector<int> level_ptr, absorb_ptr;
-    double ms[4] = {0.0, 0.0, 0.0, 0.0};
-    bool pending = false;                                  // a timed step whose events have not been read
-};
+using Condensed = PgoCondensed;
 
 int upload(WS *ws, hipStream_t stream, int k, const std::vector<int> &v, std::string *err)
 {
@@ -445,8 +441,8 @@ int collect(WS *ws, Condensed *C, std::string *err)
 
 inline unsigned blocks_for(int count, int block) { return (unsigned)((count > 0 ? count : 1) + block - 1) / (unsigned)block; }
 
-// the damped system of side b solved into B_VX
-int enqueue_step(WS *ws, hipStream_t stream, const PgoGraph &gr, Condensed *C, int b, double lambda, std::string *err)
+// the first three stages of a step on side b: elimination, assembly of S, factorisation
+int enqueue_factor(WS *ws, hipStream_t stream, const PgoGraph &gr, Condensed *C, int b, double lambda, std::string *err)
 {
     int rc;
     if ((rc = collect(ws, C, err))) return rc;
@@ -455,9 +451,8 @@ int enqueue_step(WS *ws, hipStream_t stream, const PgoGraph &gr, Condensed *C, i
     PgoRecord *rec = at<PgoRecord>(ws, WS::B_REC);
     const int *node_kind = at<int>(ws, WS::B_C_NODE_POSE), *elim = at<int>(ws, WS::B_C_ELIM), *absorb = at<int>(ws, WS::B_C_ABSORB);
     double *ND = at<double>(ws, WS::B_C_ND), *NBv = at<double>(ws, WS::B_C_NB), *NU = at<double>(ws, WS::B_C_NU), *NP = at<double>(ws, WS::B_C_NP);
-    double *NCL = at<double>(ws, WS::B_C_NCL), *NCR = at<double>(ws, WS::B_C_NCR), *NX = at<double>(ws, WS::B_C_NX);
+    double *NCL = at<double>(ws, WS::B_C_NCL), *NCR = at<double>(ws, WS::B_C_NCR);
     double *S = at<double>(ws, WS::B_C_S), *Ldiag = at<double>(ws, WS::B_C_LDIAG), *diag0 = at<double>(ws, WS::B_C_DIAG0), *rhs = at<double>(ws, WS::B_C_RHS);
-    double *delta = at<double>(ws, WS::B_VX);
     const int ld = C->ld, T = ld / kNB;
     if (gr.timing) PGO_HIP(hipEventRecord(ws->ev_c[0], stream));
     cond_setup_kernel<<<dim3(blocks_for(C->n_nodes, kNodeBlock)), dim3(kNodeBlock), 0, stream>>>(
@@ -484,7 +479,18 @@ int enqueue_step(WS *ws, hipStream_t stream, const PgoGraph &gr, Condensed *C, i
     }
     PGO_HIP(hipGetLastError());
     if (gr.timing) PGO_HIP(hipEventRecord(ws->ev_c[3], stream));
-    cond_tri_solve_kernel<<<dim3(1), dim3(kSolveThreads), 0, stream>>>(S, ld, Ldiag, rhs);
+    return SCL_OK;
+}
+
+// the damped system of side b solved into B_VX
+int enqueue_step(WS *ws, hipStream_t stream, const PgoGraph &gr, Condensed *C, int b, double lambda, std::string *err)
+{
+    int rc;
+    if ((rc = enqueue_factor(ws, stream, gr, C, b, lambda, err))) return rc;
+    const int *node_kind = at<int>(ws, WS::B_C_NODE_POSE), *elim = at<int>(ws, WS::B_C_ELIM);
+    const double *ND = at<double>(ws, WS::B_C_ND), *NBv = at<double>(ws, WS::B_C_NB), *NU = at<double>(ws, WS::B_C_NU), *NP = at<double>(ws, WS::B_C_NP);
+    double *NX = at<double>(ws, WS::B_C_NX), *rhs = at<double>(ws, WS::B_C_RHS), *delta = at<double>(ws, WS::B_VX);
+    cond_tri_solve_kernel<<<dim3(1), dim3(kSolveThreads), 0, stream>>>(at<double>(ws, WS::B_C_S), C->ld, at<double>(ws, WS::B_C_LDIAG), rhs);
     cond_scatter_kernel<<<dim3(blocks_for(C->n_junctions + C->n_nodes, 256)), dim3(256), 0, stream>>>(C->n_junctions, at<int>(ws, WS::B_C_JPOSE), C->n_nodes,
                                                                                                      node_kind, rhs, delta, NX);
     for (int l = C->n_levels - 1; l >= 0; --l) {
@@ -527,6 +533,30 @@ int pgo_solve_condensed(PgoWorkspace *ws, hipStream_t stream, const PgoInputs &i
     }
     std::memcpy(delta, out.data(), sizeof(double) * 6 * nn);
     return SCL_OK;
+}
+
+int pgo_condensed_factor(PgoWorkspace *ws, hipStream_t stream, const PgoInputs &in, double lambda, bool timing, PgoGraph *gr, PgoCondensed *C,
+                         std::string *err)
+{
+    int rc;
+    if ((rc = pgo_setup(ws, stream, in, timing, gr, err)) || (rc = prepare(ws, stream, in, timing, C, err)) ||
+        (rc = pgo_enqueue_linearise(ws, stream, *gr, 0, false, err)))
+        return rc;
+    if (gr->timing) PGO_HIP(hipEventRecord(ws->ev[2], stream));
+    return enqueue_factor(ws, stream, *gr, C, 0, lambda, err);
+}
+
+int pgo_condensed_finish(PgoWorkspace *ws, hipStream_t stream, PgoGraph *gr, PgoCondensed *C, std::string *err)
+{
+    if (gr->timing) {
+        PGO_HIP(hipEventRecord(ws->ev_c[4], stream));
+        PGO_HIP(hipEventRecord(ws->ev[3], stream));
+        C->pending = true;
+    }
+    PGO_HIP(hipStreamSynchronize(stream));
+    int rc;
+    if ((rc = pgo_add_timing(ws, gr, true, true, err))) return rc;
+    return collect(ws, C, err);
 }
 
 int pgo_optimize_condensed(PgoWorkspace *ws, hipStream_t stream, const PgoInputs &in, const scl_pgo_params &params, double *poses_out,

@@ -202,6 +202,8 @@ def _bind(lib):
         "scl_pgo_optimize_condensed": (c_int, [P, dp, c_int, ip, ip, dp, dp, c_int, ip, dp, dp, c_int, POINTER(PgoParams), dp, POINTER(PgoResult), dp,
                                                ip]),
         "scl_pgo_condensed_last_timing": (c_int, [P, dp]),
+        "scl_pgo_solve_condensed_many": (c_int, [P, dp, c_int, ip, ip, dp, dp, c_int, ip, dp, dp, c_int, c_double, dp, c_int, dp]),
+        "scl_pgo_marginals": (c_int, [P, dp, c_int, ip, ip, dp, dp, c_int, ip, dp, dp, c_int, ip, ip, c_int, dp, dp]),
         "scl_profile_enable": (c_int, [P, c_int]),
         "scl_profile_reset": (c_int, [P]),
         "scl_profile_get": (c_int, [P, POINTER(SclProfile)]),
@@ -1369,6 +1371,33 @@ class ScanContextEngine:
                                                          None if chi2 is None else _ptr(chi2, c_double), byref(failed)),
                     "scl_pgo_optimize_condensed")
         return out[:n], res, None if chi2 is None else chi2[:m], failed.value
+
+    def pgo_solve_condensed_many(self, poses, f_i, f_j, f_z, f_cov, p_idx, p_z, p_cov, lam, rhs):
+        """x[n_rhs,n,6] with (H + lam diag(H)) x_c = rhs_c for the columns rhs[n_rhs,n,6], on one factorisation of the condensed direct
+        step (scl_engine.h: POSE-GRAPH SOLVE, MANY RIGHT-HAND SIDES AND MARGINAL COVARIANCES).  A column's bits depend on the graph and
+        on that column alone"""
+        keep, args, n, m = self._pgo_inputs(poses, f_i, f_j, f_z, f_cov, p_idx, p_z, p_cov)
+        b = np.ascontiguousarray(rhs, dtype=np.float64).reshape(-1, max(n, 1), 6)
+        x = np.zeros(b.shape)
+        self._check(self._lib.scl_pgo_solve_condensed_many(self._h, *args, float(lam), _ptr(b, c_double), b.shape[0], _ptr(x, c_double)),
+                    "scl_pgo_solve_condensed_many")
+        return x
+
+    def pgo_marginals(self, poses, f_i, f_j, f_z, f_cov, p_idx, p_z, p_cov, q_i, q_j, want_blocks=True, want_rel=True):
+        """(blocks[k,6,6] or None, rel[k,6,6] or None) for the queries (q_i[k], q_j[k]): blocks = Sigma[q_i, q_j] of Sigma = H^-1 at `poses`
+        (right perturbations, rotation first), rel = the first-order covariance of X_i^-1 X_j.  At most 256 distinct poses.  rel is a
+        difference of terms of the size of Sigma_jj: see the header for what that costs far from the prior"""
+        keep, args, n, m = self._pgo_inputs(poses, f_i, f_j, f_z, f_cov, p_idx, p_z, p_cov)
+        qi = np.ascontiguousarray(q_i, dtype=np.int32).reshape(-1); qj = np.ascontiguousarray(q_j, dtype=np.int32).reshape(-1)
+        if qj.size != qi.size:
+            raise ValueError("q_i and q_j must have one entry per query")
+        k = qi.size
+        blocks = np.zeros((max(k, 1), 6, 6)) if want_blocks else None
+        rel = np.zeros((max(k, 1), 6, 6)) if want_rel else None
+        opt = lambda a: _ptr(a, c_int) if a.size else None
+        self._check(self._lib.scl_pgo_marginals(self._h, *args, opt(qi), opt(qj), k, None if blocks is None else _ptr(blocks, c_double),
+                                                None if rel is None else _ptr(rel, c_double)), "scl_pgo_marginals")
+        return None if blocks is None else blocks[:k], None if rel is None else rel[:k]
 
     def pgo_condensed_last_timing(self):
         """(elimination, assembly, factorisation, solves and the way back) in ms, summed over the steps of the last condensed call made
