@@ -15,7 +15,7 @@ OBJS    := $(SRCS:.hip=.o)
 # the adapter template the M2DP, FPFH and GRSD adapters derive from, and the batch declarations their C headers share
 VP_ADAPTER := include/scl/vector_plugin_hip_descriptor.hpp include/scl_plugin_batch.h
 
-all: $(LIBDIR)/libscl_engine.so oracle tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/grsd_adapter_check tests/cpp/plugin_batch_check tests/cpp/plugin_topk_check tests/cpp/iris_batch_check tests/cpp/iris_search_check tests/cpp/sc_search_check tests/cpp/sc_search_robot_check tests/cpp/nn_plan_check tests/cpp/candidate_windows_check tests/cpp/screen_plan_check tests/cpp/ingest_plan_check tests/cpp/pgo_graph_check tests/cpp/pgo_condense_plan_check tests/cpp/pgo_marginal_plan_check tests/cpp/libfpfh_checker.so tests/cpp/libgrsd_checker.so tests/cpp/libmock_rccl.so
+all: $(LIBDIR)/libscl_engine.so oracle tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/grsd_adapter_check tests/cpp/plugin_batch_check tests/cpp/plugin_topk_check tests/cpp/iris_batch_check tests/cpp/iris_search_check tests/cpp/sc_search_check tests/cpp/sc_search_robot_check tests/cpp/nn_plan_check tests/cpp/candidate_windows_check tests/cpp/screen_plan_check tests/cpp/ingest_plan_check tests/cpp/grid_limits_check tests/cpp/pgo_graph_check tests/cpp/pgo_condense_plan_check tests/cpp/pgo_marginal_plan_check tests/cpp/libfpfh_checker.so tests/cpp/libgrsd_checker.so tests/cpp/libmock_rccl.so
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.hpp) include/scl_engine.h include/scl_m2dp.h include/scl_fpfh.h include/scl_grsd.h include/scl_iris.h include/scl_plugin_batch.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -87,6 +87,11 @@ tests/cpp/screen_plan_check: tests/cpp/screen_plan_check.cpp $(CSRC)/screen_plan
 tests/cpp/ingest_plan_check: tests/cpp/ingest_plan_check.cpp $(CSRC)/ingest_plan.hpp $(CSRC)/db_arrays.hpp
 	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -I$(CSRC) -o $@ tests/cpp/ingest_plan_check.cpp
 
+# the grid contract (grid_limits.hpp: which num_ring x num_sector scl_create takes, the exact kernels' plans; host code only) under
+# ASan + UBSan, a program of its own; runs without a GPU (tests/test_grid_limits.py)
+tests/cpp/grid_limits_check: tests/cpp/grid_limits_check.cpp $(CSRC)/grid_limits.hpp
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -I$(CSRC) -o $@ tests/cpp/grid_limits_check.cpp
+
 # the connectivity check and the incidence lists of the pose-graph solve (pgo_graph.hpp, host code only) under ASan + UBSan, a program of
 # its own; runs without a GPU (tests/test_pgo_abi.py)
 tests/cpp/pgo_graph_check: tests/cpp/pgo_graph_check.cpp $(CSRC)/pgo_graph.hpp
@@ -147,7 +152,7 @@ sanitize: tests/cpp/fuzz_host
 	@cat $(SAN_LOG)
 
 clean:
-	rm -f $(OBJS) $(LIBDIR)/libscl_engine.so tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/grsd_adapter_check tests/cpp/plugin_batch_check tests/cpp/plugin_topk_check tests/cpp/iris_batch_check tests/cpp/iris_search_check tests/cpp/sc_search_check tests/cpp/sc_search_robot_check tests/cpp/nn_plan_check tests/cpp/candidate_windows_check tests/cpp/screen_plan_check tests/cpp/ingest_plan_check tests/cpp/pgo_graph_check tests/cpp/pgo_condense_plan_check tests/cpp/pgo_marginal_plan_check tests/cpp/libfpfh_checker.so tests/cpp/libgrsd_checker.so tests/cpp/libmock_rccl.so
+	rm -f $(OBJS) $(LIBDIR)/libscl_engine.so tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/grsd_adapter_check tests/cpp/plugin_batch_check tests/cpp/plugin_topk_check tests/cpp/iris_batch_check tests/cpp/iris_search_check tests/cpp/sc_search_check tests/cpp/sc_search_robot_check tests/cpp/nn_plan_check tests/cpp/candidate_windows_check tests/cpp/screen_plan_check tests/cpp/ingest_plan_check tests/cpp/grid_limits_check tests/cpp/pgo_graph_check tests/cpp/pgo_condense_plan_check tests/cpp/pgo_marginal_plan_check tests/cpp/libfpfh_checker.so tests/cpp/libgrsd_checker.so tests/cpp/libmock_rccl.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean sanitize

@@ -52,6 +52,11 @@ typedef enum scl_status {
 /* Constructor arguments of scan_context_descriptor, D.h:1307-1316 (same
  * defaults), plus engine-side knobs. */
 typedef struct scl_config {
+    /* The grid: 1 <= num_ring <= 256, 2 <= num_sector <= 224 (the sector masks hold 224 bits; one sector has no shift to search), and
+     * 900-odd bytes of on-chip memory per ring at 224 sectors: 4 * (num_ring * (num_sector + 1) + num_sector + 2) + 24 * num_sector
+     * + 256 <= 163840 bytes -- 174 rings at 224 sectors, all 256 rings up to 154 sectors.  scl_create answers SCL_ERR_INVALID_ARG
+     * outside 1..256 x 1..1024 and SCL_ERR_UNSUPPORTED for any other grid beyond these limits, before it touches the device; a
+     * grid it accepts is bit-exact against the reference through the descriptor front end and the plain search. */
     int    num_ring;            /* PC_NUM_RING              = 20   */
     int    num_sector;          /* PC_NUM_SECTOR            = 60   */
     int    num_candidates;      /* NUM_CANDIDATES_FROM_TREE = 3    */
@@ -1019,6 +1024,13 @@ int  scl_selftest_atanf_blocks(scl_engine *e, int first_block, int n_blocks, uin
  * generated points of the engine's grid (mode 0: uniform; 1: on ring boundaries; 2: on sector boundaries; 3: zeros, denormals, huge,
  * inf, NaN): *sure = points the fast path answered, *disagreements = those of them where the chain says otherwise (must be 0). */
 int  scl_selftest_bin_paths(scl_engine *e, int mode, uint64_t seed, uint64_t n_points, uint64_t *disagreements, uint64_t *sure);
+/* ... and HOW FAR apart the two ways' quotients are where the fast one answers: the guard bands are four times a derived error on the
+ * engine's grid, and this measures the error.  *disagreements and *sure as above; *max_ring_dev / *max_sector_dev = the largest
+ * |q_fast - q_chain| over the sure points, q_chain = (double)sqrtf(x*x + y*y) / max_radius * num_ring resp. (double)xy2theta(x, y) /
+ * 360 * num_sector as the chain forms them.  mode 0: uniform points; 1: either side of every ring boundary at guard * (1 + u)
+ * quotient units, u in [0, 1) -- the sure points closest to a boundary --; 2: likewise at every sector boundary. */
+int  scl_selftest_bin_margin(scl_engine *e, int mode, uint64_t seed, uint64_t n_points, uint64_t *disagreements, uint64_t *sure,
+                             double *max_ring_dev, double *max_sector_dev);
 
 /* Self test of the verification path's own stable radix sort (csrc/device_sort.hip; it replaced hipCUB's): the n (key, value) pairs
  * sorted on the key bits [0, bits), equal keys in their input order.  key_bytes 4 or 8; n_segments > 1 (8-byte keys): every segment

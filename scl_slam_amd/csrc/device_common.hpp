@@ -99,20 +99,29 @@ __device__ __forceinline__ int ceil_to_int_x86(double v)
 // IEEE sqrtf, xy2theta with glibc's atanf, the double quotients, ceil -- ~220 vector instructions, four IEEE divisions among them: the
 // scatter kernel was bound by them, not by HBM.  sc_bin_fast computes the SAME integers from cheap approximations and says whether it
 // is sure: with q~ an approximation of the exact chain's q = range / max_radius * R (resp. theta / 360 * S) and |q~ - q| <= E,
-// ceil(q~) = ceil(q) whenever q~ is farther than E from every integer; the guards below are four times the E derived here, and a
-// point inside a guard band (2-3 in 10 000) takes the exact chain.  Errors:
+// ceil(q~) = ceil(q) whenever q~ is farther than E from every integer; the guards below are four times the E derived here ON THE
+// ENGINE'S GRID -- E grows with R and with S --, and a point inside a guard band (2-3 in 10 000) takes the exact chain.  Errors:
 //   ring:   s = x*x + y*y is the chain's own float arithmetic; v_sqrt_f32 is within 1 ulp where the chain's sqrtf is correctly
-//           rounded (1.5 ulp apart), the product with fl32(R / max_radius) adds two roundings: |q~ - q| <= 3e-7 q <= 2.4e-5 (R <= 80).
+//           rounded (1.5 ulp apart), the product with fl32(R / max_radius) adds two roundings: |q~ - q| <= 3e-7 q, and q <= R where the
+//           ring matters: E_ring = 3e-7 R -- 2.4e-5 at R = 80, 7.7e-5 at R = 256.
 //   sector: the chain's float angle is within 4e-5 degrees of the true one (atanf < 1 ulp, the quotient's half ulp, and the final
-//           rounding of an angle up to 360: half of 3.05e-5); here: v_rcp_f32 (1 ulp), a degree-17 odd polynomial for atan on [0, 1]
-//           (Abramowitz & Stegun 4.4.49, |error| <= 1.4e-8; 9.3e-8 as evaluated in fp32), the octant placement (pi's rounding, one
-//           rounding at <= 2 pi: 2.9e-7 rad), the product with fl32(S / 2 pi) (two roundings at <= 180: 2.2e-5): together 6e-5 sectors
-//           at S = 180.
+//           rounding of an angle up to 360: half of 3.05e-5), which is 4e-5 S / 360 sectors; here: v_rcp_f32 (1 ulp), a degree-17 odd
+//           polynomial for atan on [0, 1] (Abramowitz & Stegun 4.4.49, |error| <= 1.4e-8; 9.3e-8 as evaluated in fp32), the octant
+//           placement (pi's rounding, one rounding at <= 2 pi: 2.9e-7 rad) -- 4.8e-7 rad = 7.6e-8 S sectors --, the product with
+//           fl32(S / 2 pi) (two roundings at <= S: 1.2e-7 S): every term is proportional to S, together E_sect = 3.3e-7 S -- 6e-5
+//           sectors at S = 180, 7.5e-5 at S = 224.
 //   x or y zero, NaN, or the larger coordinate outside [1e-18, 1e18]: not sure (the chain's quirks live there: y / -0.0, 0 / 0).
-// scl_selftest_bin_paths (tests/test_gpu_make_sc.py) compares the two on 2^30 random, boundary-hugging and special points: no
-// disagreement where the fast path is sure.
+// The guards: 1e-4 (four times E_ring at R = 80) up to 80 rings and 1e-4 R / 80 beyond, 2.5e-4 (four times E_sect at S = 180) up to
+// 180 sectors and 2.5e-4 S / 180 beyond -- on the three baseline grids the constants they always were.  The host forms them once per
+// launch and the scatter takes them as two kernel arguments (formed in the kernel, the division was 1 % of a 4 096-point workgroup's
+// time).  scl_selftest_bin_paths (tests/test_gpu_make_sc.py) compares the two paths on 2^30 random,
+// boundary-hugging and special points: no disagreement where the fast path is sure; scl_selftest_bin_margin
+// (tests/test_gpu_grids.py) MEASURES max |q~ - q| over the sure points of every accepted grid family, at the guard bands' edges
+// too, and holds it to a quarter of the guard (figures: profiles/grids/README.md).
 constexpr float kBinGuardRing = 1.0e-4f;
 constexpr float kBinGuardSect = 2.5e-4f;
+__host__ __device__ __forceinline__ float bin_guard_ring(int R) { return kBinGuardRing * (R > 80 ? (float)R / 80.0f : 1.0f); }
+__host__ __device__ __forceinline__ float bin_guard_sect(int S) { return kBinGuardSect * (S > 180 ? (float)S / 180.0f : 1.0f); }
 
 __device__ __forceinline__ void sc_bin_exact(float px, float py, int R, int S, double max_radius, int &ring, int &sect, bool &drop)
 {
@@ -123,14 +132,16 @@ __device__ __forceinline__ void sc_bin_exact(float px, float py, int R, int S, d
     sect = max(min(S, ceil_to_int_x86(((double)azim_angle / 360.0) * S)), 1);        // D.h:1435
 }
 
-__device__ __forceinline__ bool sc_bin_fast(float x, float y, int R, int S, float c_ring, float c_sect, int &ring, int &sect, bool &drop)
+// (qr, qs: the two approximate quotients themselves, for the margin hook; the scatter drops them)
+__device__ __forceinline__ bool sc_bin_fast_q(float x, float y, int R, int S, float c_ring, float c_sect, float g_ring, float g_sect, int &ring, int &sect, bool &drop,
+                                              float &qr, float &qs)
 {
     const float ax = fabsf(x), ay = fabsf(y);
     const float hi = fmaxf(ax, ay), lo = fminf(ax, ay);
     bool sure = (x == x) & (y == y) & (lo > 0.0f) & (hi >= 1.0e-18f) & (hi <= 1.0e18f);
     const float s = x * x + y * y;                                 // the chain's own operations (no contraction)
-    const float qr = __builtin_amdgcn_sqrtf(s) * c_ring;
-    sure &= fabsf(qr - rintf(qr)) > kBinGuardRing;
+    qr = __builtin_amdgcn_sqrtf(s) * c_ring;
+    sure &= fabsf(qr - rintf(qr)) > g_ring;
     drop = qr > (float)R;
     ring = max(min((int)ceilf(qr), R), 1);
     const float a = lo * __builtin_amdgcn_rcpf(hi);                // in (0, 1]
@@ -147,10 +158,15 @@ __device__ __forceinline__ bool sc_bin_fast(float x, float y, int R, int S, floa
     t = ay > ax ? 1.57079632679f - t : t;
     t = x < 0.0f ? 3.14159265359f - t : t;
     t = y < 0.0f ? 6.28318530718f - t : t;
-    const float qs = t * c_sect;
-    sure &= fabsf(qs - rintf(qs)) > kBinGuardSect;
+    qs = t * c_sect;
+    sure &= fabsf(qs - rintf(qs)) > g_sect;
     sect = max(min((int)ceilf(qs), S), 1);
     return sure;
+}
+__device__ __forceinline__ bool sc_bin_fast(float x, float y, int R, int S, float c_ring, float c_sect, float g_ring, float g_sect, int &ring, int &sect, bool &drop)
+{
+    float qr, qs;
+    return sc_bin_fast_q(x, y, R, S, c_ring, c_sect, g_ring, g_sect, ring, sect, drop, qr, qs);
 }
 
 // ---- wave-level lexicographic arg-min on (double value, int tag) -----------

@@ -29,6 +29,7 @@
 
 #include "engine_internal.hpp"
 #include "device_sort.hpp"
+#include "grid_limits.hpp"
 #include "plugin_host.hpp"
 #include "pgo_condense_plan.hpp"
 #include "pgo_marginal_plan.hpp"
@@ -424,6 +425,12 @@ int scl_create(const scl_config *cfg, scl_engine **out)
         cfg->num_candidates < 1 || cfg->num_candidates > kTopkMaxK || cfg->tree_making_period < 1 ||
         cfg->num_exclude_recent < 0 || !(cfg->max_radius > 0.0) || !(cfg->search_ratio >= 0.0))
         return SCL_ERR_INVALID_ARG;
+    {   // a grid some kernel of the front end or of the search cannot take is refused here, before the device is touched, and not at
+        // its first launch (grid_limits.hpp has every limit and where it comes from)
+        int SR = (int)std::round(0.5 * cfg->search_ratio * (double)cfg->num_sector);   /* D.h:1545 */
+        if (SR < 0) SR = 0;
+        if (!grid_supported(cfg->num_ring, cfg->num_sector, SR)) return SCL_ERR_UNSUPPORTED;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SCL_ERR_NO_DEVICE;
     if (cfg->device < 0 || cfg->device >= ndev) return SCL_ERR_INVALID_ARG;
@@ -1140,6 +1147,28 @@ int scl_selftest_bin_paths(scl_engine *e, int mode, uint64_t seed, uint64_t n_po
     dev_free(d);
     SCL_HIP(e, he);
     *disagreements = h[0]; *sure = h[1];
+    return SCL_OK;
+}
+
+/* test hook: how far the fast binning's quotients are from the chain's on the sure points of n generated points of the engine's grid
+ * (make_sc.hip: bin_margin_selftest_kernel has the modes) */
+int scl_selftest_bin_margin(scl_engine *e, int mode, uint64_t seed, uint64_t n_points, uint64_t *disagreements, uint64_t *sure,
+                            double *max_ring_dev, double *max_sector_dev)
+{
+    if (!e || !disagreements || !sure || !max_ring_dev || !max_sector_dev || mode < 0 || mode > 2) return SCL_ERR_INVALID_ARG;
+    if (e->front) e = front_primary(e);
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    unsigned long long *d = nullptr, h[4] = {0, 0, 0, 0};
+    int rc = dev_alloc(e, &d, (size_t)4);
+    if (rc) return rc;
+    hipError_t he = launch_bin_margin_selftest(mode, seed, n_points, e->R, e->S, e->cfg.max_radius, d, e->stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+    dev_free(d);
+    SCL_HIP(e, he);
+    *disagreements = h[0]; *sure = h[1];
+    memcpy(max_ring_dev, &h[2], sizeof(double)); memcpy(max_sector_dev, &h[3], sizeof(double));
     return SCL_OK;
 }
 

@@ -355,5 +355,7 @@ hipError_t launch_make_sc_batch(ScanBatch b, int stride_bytes, int R, int S, dou
 hipError_t launch_atanf_block_checksums(int first_block, int n_blocks, unsigned long long *d_out, hipStream_t stream);
 // test hook: the scatter's fast binning against the reference's chain on n generated points: d_out2[0] = disagreements where the fast path was sure, [1] = sure
 hipError_t launch_bin_paths_selftest(int mode, unsigned long long seed, unsigned long long n, int R, int S, double max_radius, unsigned long long *d_out2, hipStream_t stream);
+// test hook: how far the fast binning's quotients are from the chain's: d_out4[0], [1] as above, [2] / [3] = bits of the largest ring / sector deviation (doubles) over the sure points
+hipError_t launch_bin_margin_selftest(int mode, unsigned long long seed, unsigned long long n, int R, int S, double max_radius, unsigned long long *d_out4, hipStream_t stream);
 
 }  // namespace scl

@@ -21,6 +21,7 @@
 #include <cstdio>
 
 #include "device_common.hpp"
+#include "grid_limits.hpp"
 #include "kernels.hpp"
 
 namespace scl {
@@ -34,7 +35,8 @@ constexpr int kScThreads = 256;
 // atomicMax per touched cell.  The global tiles are in their initial state when the launch starts and are put back into it by the
 // kernel that consumes them (ingest_kernel), so a batch costs two launches whatever its size.  Four points per thread are in flight.
 __device__ __forceinline__ void scatter_body(const ScanBatch &b, const int wg, int stride, int R, int S,
-                                             double lidar_height, double max_radius, int *gtiles, int lab, int *tile /* R*S ints of LDS */)
+                                             double lidar_height, double max_radius, int *gtiles, int lab, const float g_ring, const float g_sect,
+                                             int *tile /* R*S ints of LDS */)
 {
     const bool exact_only = lab & 1;                       // (diagnostics builds: 1 = the reference's chain for every point, 2 / 4 = ablations)
     const int cells = R * S;
@@ -82,7 +84,7 @@ __device__ __forceinline__ void scatter_body(const ScanBatch &b, const int wg, i
             const float pz = (float)((double)pzr[u] + lidar_height);            // D.h:1422
             int ring, sect; bool drop;
             // the bins from cheap approximations where those are sure of them (device_common.hpp), the reference's chain otherwise
-            const bool sure = !exact_only && sc_bin_fast(px[u], py[u], R, S, c_ring, c_sect, ring, sect, drop);
+            const bool sure = !exact_only && sc_bin_fast(px[u], py[u], R, S, c_ring, c_sect, g_ring, g_sect, ring, sect, drop);
             if (!sure) sc_bin_exact(px[u], py[u], R, S, max_radius, ring, sect, drop);      // D.h:1425-1435
             if (drop) continue;                                                  // D.h:1429
             if (pz != pz) continue;                                              // NaN never passes `<` (D.h:1438)
@@ -99,10 +101,11 @@ __device__ __forceinline__ void scatter_body(const ScanBatch &b, const int wg, i
 }
 
 __global__ __launch_bounds__(kScThreads) void make_sc_batch_scatter_kernel(ScanBatch b, int stride, int R, int S,
-                                                                           double lidar_height, double max_radius, int *gtiles, int lab)
-{
+                                                                           double lidar_height, double max_radius, int *gtiles, int lab,
+                                                                           float g_ring, float g_sect)
+{   // g_ring, g_sect: the fast binning's guards on this grid (device_common.hpp), formed by the host once per launch
     extern __shared__ int tile[];
-    scatter_body(b, (int)blockIdx.x, stride, R, S, lidar_height, max_radius, gtiles, lab, tile);
+    scatter_body(b, (int)blockIdx.x, stride, R, S, lidar_height, max_radius, gtiles, lab, g_ring, g_sect, tile);
 }
 
 __global__ void make_sc_init_kernel(int *gtile, int cells)
@@ -397,7 +400,7 @@ __device__ __forceinline__ void ingest_body(const IngestArgs &ia, const int wg, 
         if (TPC == 2) e2 += __shfl_xor(e2, 1, kWave);                  // (every lane of the workgroup takes part)
         if (c < S && half == 0) svk[c] = sqrt(e2);
     }
-    const bool col = (int)threadIdx.x < S;                             // S <= 224 < blockDim: thread c looks at column c
+    const bool col = (int)threadIdx.x < S;                             // S <= kGridMaxSector (224) < blockDim: thread c looks at column c
     const float ivc = col ? siv[threadIdx.x] : 0.0f;
     const int any_nan = __syncthreads_or(col && ivc != ivc);           // (also the barrier behind the columns' bounds)
     const unsigned long long nzb = __ballot(col && ivc != 0.0f);       // NaN counts as non-zero
@@ -409,7 +412,7 @@ __device__ __forceinline__ void ingest_body(const IngestArgs &ia, const int wg, 
         for (int cc = ln; cc < S; cc += kWave) E = E + svk[cc];
         E = wave_sum_f64(E);
         if (ln == 0) {
-            kmask[(size_t)slot * 8 + 6] = S <= 192 ? (unsigned int)__float_as_int(__double2float_ru(E * (1.0 + 1e-6) + 1e-12)) : (unsigned int)nzb;
+            kmask[(size_t)slot * 8 + 6] = S <= kGridMaskBoundSectors ? (unsigned int)__float_as_int(__double2float_ru(E * (1.0 + 1e-6) + 1e-12)) : (unsigned int)nzb;
             kmask[(size_t)slot * 8 + 7] = any_nan ? 1u : 0u;
         }
     }
@@ -427,11 +430,11 @@ __global__ __launch_bounds__(256) void ingest_kernel(IngestArgs ia)
 // side they cost what the longer one costs.  Workgroups 0 .. n_ingest-1 (dispatched first: the long ones) ingest the previous group's
 // tiles, the others scatter into the other set of tiles.
 __global__ __launch_bounds__(256) void front_fused_kernel(ScanBatch b, int stride, double lidar_height, double max_radius, int *gtiles, int lab,
-                                                          IngestArgs ia, int n_ingest)
+                                                          IngestArgs ia, int n_ingest, float g_ring, float g_sect)
 {
     extern __shared__ float sv_f[];
     if ((int)blockIdx.x < n_ingest) ingest_body(ia, (int)blockIdx.x, sv_f);
-    else scatter_body(b, (int)blockIdx.x - n_ingest, stride, ia.R, ia.S, lidar_height, max_radius, gtiles, lab, reinterpret_cast<int *>(sv_f));
+    else scatter_body(b, (int)blockIdx.x - n_ingest, stride, ia.R, ia.S, lidar_height, max_radius, gtiles, lab, g_ring, g_sect, reinterpret_cast<int *>(sv_f));
 }
 
 // test hook (tests/test_gpu_make_sc.py): the device's atanf_glibc over whole blocks of 2^24 consecutive float bit patterns, reduced to the
@@ -486,7 +489,7 @@ __global__ __launch_bounds__(256) void bin_paths_selftest_kernel(int mode, unsig
             x = tab[(z >> 8) & 15]; y = tab[(z >> 12) & 15];
         }
         int rf, sf, re, se; bool df, de;
-        const bool sure = sc_bin_fast(x, y, R, S, c_ring, c_sect, rf, sf, df);
+        const bool sure = sc_bin_fast(x, y, R, S, c_ring, c_sect, bin_guard_ring(R), bin_guard_sect(S), rf, sf, df);
         sc_bin_exact(x, y, R, S, max_radius, re, se, de);
         if (sure) {
             sure_n++;
@@ -496,6 +499,67 @@ __global__ __launch_bounds__(256) void bin_paths_selftest_kernel(int mode, unsig
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) { bad += __shfl_xor(bad, off, kWave); sure_n += __shfl_xor(sure_n, off, kWave); }
     if ((threadIdx.x & (kWave - 1)) == 0) { atomicAdd(&out[0], bad); atomicAdd(&out[1], sure_n); }
+}
+
+// test hook (tests/test_gpu_grids.py): HOW FAR the fast binning's quotients are from the chain's on the points it is sure of -- the
+// guards are four times a derived error (device_common.hpp), and this measures the error.  out[0] / out[1] as above; out[2] / out[3] =
+// the bits of max |q_ring_fast - q_ring_chain| / max |q_sect_fast - q_sect_chain| over the sure points, the chain's quotients as
+// sc_bin_exact forms them (non-negative doubles: their bit patterns order as unsigned integers).
+//   mode 0: uniform in the square of +-1.125 max_radius; 1: either side of every ring boundary 1 .. R, guard * (1 + u) quotient
+//   units away, u in [0, 1) -- the sure points closest to a boundary --, any angle; 2: likewise either side of every sector boundary
+//   0 .. S - 1, ranges in [0.25, 1.05 max_radius]
+__global__ __launch_bounds__(256) void bin_margin_selftest_kernel(int mode, unsigned long long seed, unsigned long long n, int R, int S, double max_radius,
+                                                                  unsigned long long *out)
+{
+    const float c_ring = (float)((double)R / max_radius), c_sect = (float)((double)S / 6.283185307179586);
+    const float g_ring = bin_guard_ring(R), g_sect = bin_guard_sect(S);
+    unsigned long long bad = 0, sure_n = 0;
+    double dev_r = 0.0, dev_s = 0.0;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * blockDim.x) {
+        unsigned long long z = seed + i * 0x9e3779b97f4a7c15ull;
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull; z = (z ^ (z >> 27)) * 0x94d049bb133111ebull; z ^= z >> 31;
+        unsigned long long w = z + 0x9e3779b97f4a7c15ull;
+        w = (w ^ (w >> 30)) * 0xbf58476d1ce4e5b9ull; w = (w ^ (w >> 27)) * 0x94d049bb133111ebull; w ^= w >> 31;
+        const double u0 = (double)(z >> 40) * (1.0 / 16777216.0), u1 = (double)((z >> 16) & 0xffffffull) * (1.0 / 16777216.0);
+        const double u2 = (double)(w >> 40) * (1.0 / 16777216.0), u3 = (double)((w >> 16) & 0xffffffull) * (1.0 / 16777216.0);
+        const double side = (w & 1ull) ? 1.0 : -1.0;
+        float x, y;
+        if (mode == 0) {
+            x = (float)((2.0 * u0 - 1.0) * 1.125 * max_radius); y = (float)((2.0 * u1 - 1.0) * 1.125 * max_radius);
+        } else if (mode == 1) {
+            const int b = 1 + min((int)(u0 * R), R - 1);
+            const double q = (double)b + side * (double)g_ring * (1.0 + u2);
+            const double r0 = q * max_radius / R, ang = 6.283185307179586 * u1;
+            x = (float)(r0 * cos(ang)); y = (float)(r0 * sin(ang));
+        } else {
+            const int b = min((int)(u0 * S), S - 1);
+            double q = (double)b + side * (double)g_sect * (1.0 + u2);
+            if (q < 0.0) q += (double)S;                                   // below boundary 0 = below boundary S
+            const double ang = q * (6.283185307179586 / S), r0 = 0.25 + u3 * (1.05 * max_radius - 0.25);
+            x = (float)(r0 * cos(ang)); y = (float)(r0 * sin(ang));
+        }
+        int rf, sf, re, se; bool df, de; float qr, qs;
+        const bool sure = sc_bin_fast_q(x, y, R, S, c_ring, c_sect, g_ring, g_sect, rf, sf, df, qr, qs);
+        sc_bin_exact(x, y, R, S, max_radius, re, se, de);
+        if (sure) {
+            sure_n++;
+            if (df != de || (!de && (rf != re || sf != se))) bad++;
+            const double cr = ((double)sqrtf(x * x + y * y) / max_radius) * R, cs = ((double)xy2theta(x, y) / 360.0) * S;
+            const double er = fabs((double)qr - cr), es = fabs((double)qs - cs);
+            dev_r = er > dev_r ? er : dev_r;                               // (a NaN never enters: sure points are finite)
+            dev_s = es > dev_s ? es : dev_s;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        bad += __shfl_xor(bad, off, kWave); sure_n += __shfl_xor(sure_n, off, kWave);
+        dev_r = fmax(dev_r, __shfl_xor(dev_r, off, kWave)); dev_s = fmax(dev_s, __shfl_xor(dev_s, off, kWave));
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        atomicAdd(&out[0], bad); atomicAdd(&out[1], sure_n);
+        atomicMax(&out[2], (unsigned long long)__double_as_longlong(dev_r));
+        atomicMax(&out[3], (unsigned long long)__double_as_longlong(dev_s));
+    }
 }
 
 __global__ void untile_kernel(const float4 *dslot, int R, int S, float *values)
@@ -540,27 +604,36 @@ hipError_t launch_make_sc_batch(ScanBatch b, int stride_bytes, int R, int S, dou
     }
     for (int i = b.count; i <= kMaxScBatch; ++i) b.first_wg[i] = total;
     if (total == 0) return hipSuccess;
-    const size_t lds = sizeof(int) * (size_t)R * S;
+    if (!grid_supported(R, S, 0)) return hipErrorInvalidValue;       // (scl_create refuses such a grid: grid_limits.hpp)
+    const size_t lds = scatter_lds_bytes(R, S);
     static std::atomic<bool> attr_set_dev[64];
     int dev_ = 0; (void)hipGetDevice(&dev_);
     std::atomic<bool> &attr_set = attr_set_dev[dev_ & 63];
     if (!attr_set.load(std::memory_order_acquire) && lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)make_sc_batch_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t e = hipFuncSetAttribute((const void *)make_sc_batch_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerWorkgroup);
         if (e != hipSuccess) return e;
         attr_set.store(true, std::memory_order_release);
     }
     (void)num_cu;
     hipLaunchKernelGGL(make_sc_batch_scatter_kernel, dim3(total), dim3(kScThreads), lds, stream, b, stride_bytes, R, S,
-                       lidar_height, max_radius, tiles, scl_lab_int("SCL_SC_LAB", 0));
+                       lidar_height, max_radius, tiles, scl_lab_int("SCL_SC_LAB", 0), bin_guard_ring(R), bin_guard_sect(S));
     return hipGetLastError();
 }
 
-static size_t ingest_lds_bytes(int R, int S) { return sizeof(float) * ((size_t)R * (S + 1) + S + 2) + sizeof(double) * 3 * (size_t)S; }
+// static + dynamic LDS must fit a workgroup's: grid_limits.hpp counts kIngestStaticLds bytes of static LDS for either kernel.  What the
+// loaded code object reports is compared with it before the dynamic limit is raised (the only launches at which the sum can matter)
+static hipError_t check_static_lds(const void *kernel)
+{
+    hipFuncAttributes fa{};
+    const hipError_t e = hipFuncGetAttributes(&fa, kernel);
+    if (e != hipSuccess) return e;
+    return fa.sharedSizeBytes <= kIngestStaticLds ? hipSuccess : hipErrorInvalidValue;
+}
 
 hipError_t launch_ingest(const IngestArgs &ia, int count, hipStream_t stream)
 {
     if (count <= 0) return hipSuccess;
-    if (ia.S > 224) return hipErrorInvalidValue;           // kmask holds 7 words of sector bits
+    if (!grid_supported(ia.R, ia.S, 0)) return hipErrorInvalidValue;    // grid_limits.hpp: kmask's sector bits, the LDS, the index splits
     const size_t lds = ingest_lds_bytes(ia.R, ia.S);
     // (the attribute is raised to what the launch needs, not to the CU's 160 KB: the kernel has a few bytes of static LDS of its own --
     //  __syncthreads_or -- and static + dynamic must fit.  Per device; engines on different threads may race here: setting it twice is harmless)
@@ -568,7 +641,9 @@ hipError_t launch_ingest(const IngestArgs &ia, int count, hipStream_t stream)
     int dev_ = 0; (void)hipGetDevice(&dev_);
     std::atomic<size_t> &attr_lds = attr_lds_dev[dev_ & 63];
     if (lds > 48 * 1024 && lds > attr_lds.load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute((const void *)ingest_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = check_static_lds((const void *)ingest_kernel);
+        if (e != hipSuccess) return e;
+        e = hipFuncSetAttribute((const void *)ingest_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         attr_lds.store(lds, std::memory_order_release);
     }
@@ -580,7 +655,7 @@ hipError_t launch_ingest(const IngestArgs &ia, int count, hipStream_t stream)
 hipError_t launch_front_fused(ScanBatch b, int stride_bytes, double lidar_height, double max_radius, int *gtiles, int points_per_wg,
                               const IngestArgs &ia, int n_ingest, hipStream_t stream)
 {
-    if (b.count < 0 || b.count > kMaxScBatch || n_ingest < 0 || n_ingest > kMaxScBatch || points_per_wg < 256 || ia.S > 224) return hipErrorInvalidValue;
+    if (b.count < 0 || b.count > kMaxScBatch || n_ingest < 0 || n_ingest > kMaxScBatch || points_per_wg < 256 || !grid_supported(ia.R, ia.S, 0)) return hipErrorInvalidValue;
     int total = 0;
     for (int i = 0; i < b.count; ++i) {
         b.first_wg[i] = total;
@@ -589,18 +664,20 @@ hipError_t launch_front_fused(ScanBatch b, int stride_bytes, double lidar_height
     }
     for (int i = b.count; i <= kMaxScBatch; ++i) b.first_wg[i] = total;
     if (total + n_ingest == 0) return hipSuccess;
-    const size_t lds_i = n_ingest ? ingest_lds_bytes(ia.R, ia.S) : 0, lds_s = sizeof(int) * (size_t)ia.R * ia.S;
+    const size_t lds_i = n_ingest ? ingest_lds_bytes(ia.R, ia.S) : 0, lds_s = scatter_lds_bytes(ia.R, ia.S);
     const size_t lds = lds_i > lds_s ? lds_i : lds_s;
     static std::atomic<size_t> attr_lds_dev[64];
     int dev_ = 0; (void)hipGetDevice(&dev_);
     std::atomic<size_t> &attr_lds = attr_lds_dev[dev_ & 63];
     if (lds > 48 * 1024 && lds > attr_lds.load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute((const void *)front_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = check_static_lds((const void *)front_fused_kernel);
+        if (e != hipSuccess) return e;
+        e = hipFuncSetAttribute((const void *)front_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         attr_lds.store(lds, std::memory_order_release);
     }
     hipLaunchKernelGGL(front_fused_kernel, dim3(total + n_ingest), dim3(256), lds, stream, b, stride_bytes, lidar_height, max_radius, gtiles,
-                       scl_lab_int("SCL_SC_LAB", 0), ia, n_ingest);
+                       scl_lab_int("SCL_SC_LAB", 0), ia, n_ingest, bin_guard_ring(ia.R), bin_guard_sect(ia.S));
     return hipGetLastError();
 }
 
@@ -630,6 +707,14 @@ hipError_t launch_bin_paths_selftest(int mode, unsigned long long seed, unsigned
     hipError_t e = hipMemsetAsync(d_out2, 0, 2 * sizeof(unsigned long long), stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(bin_paths_selftest_kernel, dim3(2048), dim3(256), 0, stream, mode, seed, n, R, S, max_radius, d_out2);
+    return hipGetLastError();
+}
+
+hipError_t launch_bin_margin_selftest(int mode, unsigned long long seed, unsigned long long n, int R, int S, double max_radius, unsigned long long *d_out4, hipStream_t stream)
+{
+    hipError_t e = hipMemsetAsync(d_out4, 0, 4 * sizeof(unsigned long long), stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(bin_margin_selftest_kernel, dim3(2048), dim3(256), 0, stream, mode, seed, n, R, S, max_radius, d_out4);
     return hipGetLastError();
 }
 

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "device_common.hpp"
+#include "grid_limits.hpp"
 #include "kernels.hpp"
 
 namespace scl {
@@ -1315,15 +1316,11 @@ template <int RG, int W, int MAXT>
 hipError_t launch_fast(const ScArgs &args_in, int num_cu, hipStream_t stream)
 {
     ScArgs a = args_in;
-    const int S = a.S;
-    const int QS = S + W - 1;
-    const size_t fixed = (size_t)(RG * 4 * QS + 2 * S) * sizeof(double);
-    const size_t per_group = (size_t)(4 * S + W * S + 8) * sizeof(double);
-    const size_t lds_cap = 160 * 1024;
-    int G = (int)((lds_cap - fixed) / per_group);
-    const int max_g_threads = MAXT / (a.NW * kWave);
-    if (G > max_g_threads) G = max_g_threads;
-    if (G > 8) G = 8;
+    // (the sizes: grid_limits.hpp, which also decides whether this kernel is taken at all -- launch_sc_distance asks sc_fast_branch, and
+    //  a grid on which not one candidate's staging fits goes to the generic kernel instead of failing here)
+    const ScFastPlan plan = sc_fast_plan(RG, W, MAXT, a.S);
+    const size_t fixed = plan.fixed, per_group = plan.per_group, lds_cap = kLdsPerWorkgroup;
+    int G = plan.G;
     if (G < 1) return hipErrorInvalidValue;
     while (G > 1 && a.n < num_cu * G) G >>= 1;   // few candidates: more workgroups, not fuller ones
     a.G = G;
@@ -1406,9 +1403,10 @@ hipError_t launch_sc_distance(const DbView &db, const QueryView &q, const int *c
     if (wave_ok && db.RG == 16 && W == 13 && db.S == 120 && stamp) return launch_wave<16, 13, 4, 120, 512, true>(one, num_cu, stream);
     if (wave_ok && db.RG == 16 && W == 13 && db.S == 120 && occ > 8) return launch_wave<16, 13, 2, 120, 768>(one, num_cu, stream);
     if (wave_ok && db.RG == 16 && W == 13 && db.S == 120) return launch_wave<16, 13, 4, 120, 512>(one, num_cu, stream);
-    if (db.RG == 5 && W == 7 && db.S >= W)   return launch_fast<5, 7, 512>(a, num_cu, stream);
-    if (db.RG == 16 && W == 13 && db.S >= W) return launch_fast<16, 13, 512>(a, num_cu, stream);
-    if (db.RG == 20 && W == 19 && db.S >= W && db.S <= 180) return launch_fast<20, 19, 256>(a, num_cu, stream);
+    const int fast = sc_fast_branch(db.R, db.S, SR);        // 0: no specialised kernel, or its staging does not fit the LDS at this S
+    if (fast == 5)  return launch_fast<5, 7, 512>(a, num_cu, stream);
+    if (fast == 16) return launch_fast<16, 13, 512>(a, num_cu, stream);
+    if (fast == 20) return launch_fast<20, 19, 256>(a, num_cu, stream);
 
     const size_t lds = (size_t)6 * db.S * sizeof(double);
     hipLaunchKernelGGL(sc_distance_generic_kernel, dim3(n), dim3(256), lds, stream, a, db.RG, db.R);

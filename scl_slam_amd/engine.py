@@ -220,6 +220,8 @@ def _bind(lib):
         "scl_selftest_atanf_blocks": (c_int, [P, c_int, c_int, POINTER(ctypes.c_uint64)]),
         "scl_host_copy_rate": (c_int, [P, ctypes.c_size_t, c_int, dp]),
         "scl_selftest_bin_paths": (c_int, [P, c_int, c_uint64, c_uint64, POINTER(ctypes.c_uint64), POINTER(ctypes.c_uint64)]),
+        "scl_selftest_bin_margin": (c_int, [P, c_int, c_uint64, c_uint64, POINTER(ctypes.c_uint64), POINTER(ctypes.c_uint64),
+                                            POINTER(c_double), POINTER(c_double)]),
         "scl_selftest_sort_pairs": (c_int, [P, c_int, c_void_p, POINTER(ctypes.c_uint32), c_int, c_int, POINTER(c_int), c_int, c_void_p, POINTER(ctypes.c_uint32)]),
         "scl_selftest_prefix_sum": (c_int, [P, POINTER(ctypes.c_int32), c_int, c_int, POINTER(ctypes.c_int32)]),
         "scl_selftest_submaps_batch": (c_int, [P, c_int, c_int, ip, ip, fp, c_float, P, c_int, ip]),
@@ -475,6 +477,14 @@ class ScanContextEngine:
         bad, sure = ctypes.c_uint64(), ctypes.c_uint64()
         self._check(self._lib.scl_selftest_bin_paths(self._h, mode, seed, n_points, byref(bad), byref(sure)), "scl_selftest_bin_paths")
         return bad.value, sure.value
+
+    def selftest_bin_margin(self, mode, seed, n_points):
+        """(disagreements, sure, largest ring deviation, largest sector deviation) of the fast binning's quotients from the chain's
+        over the sure points; mode 0 uniform, 1 / 2 at the edges of the ring / sector guard bands"""
+        bad, sure, dr, ds = ctypes.c_uint64(), ctypes.c_uint64(), c_double(), c_double()
+        self._check(self._lib.scl_selftest_bin_margin(self._h, mode, seed, n_points, byref(bad), byref(sure), byref(dr), byref(ds)),
+                    "scl_selftest_bin_margin")
+        return bad.value, sure.value, dr.value, ds.value
 
     def selftest_sort_pairs(self, keys, values, bits, segment_offsets=None):
         """(keys, values) stably sorted on the key bits [0, bits) by csrc/device_sort.hip; keys uint32 or uint64"""
