@@ -10,12 +10,12 @@ CSRC    := scl_slam_amd/csrc
 LIBDIR  := scl_slam_amd/lib
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math \
             -fhip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-result -Iinclude -I$(CSRC) $(EXTRA)
-SRCS    := $(CSRC)/engine.hip $(CSRC)/ingest_host.hip $(CSRC)/screen_host.hip $(CSRC)/registration.hip $(CSRC)/sc_distance.hip $(CSRC)/ringkey_topk.hip $(CSRC)/make_sc.hip $(CSRC)/icp.hip $(CSRC)/voxel.hip $(CSRC)/sharded_front.hip $(CSRC)/sc_screen.hip $(CSRC)/sc_masked.hip $(CSRC)/sc_matrix.hip $(CSRC)/sc_rank.hip $(CSRC)/messages.hip $(CSRC)/iris.hip $(CSRC)/device_sort.hip $(CSRC)/m2dp.hip $(CSRC)/fpfh.hip $(CSRC)/grsd.hip $(CSRC)/pcm.hip $(CSRC)/pgo.hip $(CSRC)/pgo_condensed.hip $(CSRC)/pgo_marginals.hip
+SRCS    := $(CSRC)/engine.hip $(CSRC)/ingest_host.hip $(CSRC)/screen_host.hip $(CSRC)/registration.hip $(CSRC)/sc_distance.hip $(CSRC)/ringkey_topk.hip $(CSRC)/make_sc.hip $(CSRC)/icp.hip $(CSRC)/voxel.hip $(CSRC)/sharded_front.hip $(CSRC)/sc_screen.hip $(CSRC)/sc_masked.hip $(CSRC)/sc_matrix.hip $(CSRC)/sc_rank.hip $(CSRC)/messages.hip $(CSRC)/iris.hip $(CSRC)/device_sort.hip $(CSRC)/m2dp.hip $(CSRC)/fpfh.hip $(CSRC)/grsd.hip $(CSRC)/pcm.hip $(CSRC)/pgo.hip $(CSRC)/pgo_condensed.hip $(CSRC)/pgo_marginals.hip $(CSRC)/global_map.hip
 OBJS    := $(SRCS:.hip=.o)
 # the adapter template the M2DP, FPFH and GRSD adapters derive from, and the batch declarations their C headers share
 VP_ADAPTER := include/scl/vector_plugin_hip_descriptor.hpp include/scl_plugin_batch.h
 
-all: $(LIBDIR)/libscl_engine.so oracle tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/grsd_adapter_check tests/cpp/plugin_batch_check tests/cpp/plugin_topk_check tests/cpp/iris_batch_check tests/cpp/iris_search_check tests/cpp/sc_search_check tests/cpp/sc_search_robot_check tests/cpp/nn_plan_check tests/cpp/candidate_windows_check tests/cpp/screen_plan_check tests/cpp/ingest_plan_check tests/cpp/grid_limits_check tests/cpp/pgo_graph_check tests/cpp/pgo_condense_plan_check tests/cpp/pgo_marginal_plan_check tests/cpp/libfpfh_checker.so tests/cpp/libgrsd_checker.so tests/cpp/libmock_rccl.so
+all: $(LIBDIR)/libscl_engine.so oracle tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/grsd_adapter_check tests/cpp/plugin_batch_check tests/cpp/plugin_topk_check tests/cpp/iris_batch_check tests/cpp/iris_search_check tests/cpp/sc_search_check tests/cpp/sc_search_robot_check tests/cpp/nn_plan_check tests/cpp/candidate_windows_check tests/cpp/screen_plan_check tests/cpp/ingest_plan_check tests/cpp/grid_limits_check tests/cpp/pgo_graph_check tests/cpp/pgo_condense_plan_check tests/cpp/pgo_marginal_plan_check tests/cpp/global_map_plan_check tests/cpp/libfpfh_checker.so tests/cpp/libgrsd_checker.so tests/cpp/libmock_rccl.so
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.hpp) include/scl_engine.h include/scl_m2dp.h include/scl_fpfh.h include/scl_grsd.h include/scl_iris.h include/scl_plugin_batch.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -107,6 +107,11 @@ tests/cpp/pgo_condense_plan_check: tests/cpp/pgo_condense_plan_check.cpp $(CSRC)
 tests/cpp/pgo_marginal_plan_check: tests/cpp/pgo_marginal_plan_check.cpp $(CSRC)/pgo_marginal_plan.hpp
 	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -I$(CSRC) -o $@ tests/cpp/pgo_marginal_plan_check.cpp
 
+# the plan of the global voxel map (global_map_plan.hpp, host code only: capacity rule, hash, the diff of a set call, launch groups) under
+# ASan + UBSan, a program of its own; runs without a GPU (tests/test_global_map_abi.py)
+tests/cpp/global_map_plan_check: tests/cpp/global_map_plan_check.cpp $(CSRC)/global_map_plan.hpp
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -I$(CSRC) -o $@ tests/cpp/global_map_plan_check.cpp
+
 # TEST INFRASTRUCTURE: the FPFH CPU checker (tests/fpfh_checker.py loads it); atan2f from oracle/liboracle.so.  No -march, no
 # contraction: every float operation is the one written
 tests/cpp/libfpfh_checker.so: tests/cpp/fpfh_checker.c | oracle
@@ -152,7 +157,7 @@ sanitize: tests/cpp/fuzz_host
 	@cat $(SAN_LOG)
 
 clean:
-	rm -f $(OBJS) $(LIBDIR)/libscl_engine.so tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/grsd_adapter_check tests/cpp/plugin_batch_check tests/cpp/plugin_topk_check tests/cpp/iris_batch_check tests/cpp/iris_search_check tests/cpp/sc_search_check tests/cpp/sc_search_robot_check tests/cpp/nn_plan_check tests/cpp/candidate_windows_check tests/cpp/screen_plan_check tests/cpp/ingest_plan_check tests/cpp/grid_limits_check tests/cpp/pgo_graph_check tests/cpp/pgo_condense_plan_check tests/cpp/pgo_marginal_plan_check tests/cpp/libfpfh_checker.so tests/cpp/libgrsd_checker.so tests/cpp/libmock_rccl.so
+	rm -f $(OBJS) $(LIBDIR)/libscl_engine.so tests/cpp/adapter_check tests/cpp/m2dp_adapter_check tests/cpp/fpfh_adapter_check tests/cpp/grsd_adapter_check tests/cpp/plugin_batch_check tests/cpp/plugin_topk_check tests/cpp/iris_batch_check tests/cpp/iris_search_check tests/cpp/sc_search_check tests/cpp/sc_search_robot_check tests/cpp/nn_plan_check tests/cpp/candidate_windows_check tests/cpp/screen_plan_check tests/cpp/ingest_plan_check tests/cpp/grid_limits_check tests/cpp/pgo_graph_check tests/cpp/pgo_condense_plan_check tests/cpp/pgo_marginal_plan_check tests/cpp/global_map_plan_check tests/cpp/libfpfh_checker.so tests/cpp/libgrsd_checker.so tests/cpp/libmock_rccl.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean sanitize

@@ -1001,6 +1001,63 @@ int  scl_pgo_marginals(scl_engine *e, const double *poses, int n_poses,
                        const int *p_idx, const double *p_z, const double *p_cov, int n_priors,
                        const int *q_i, const int *q_j, int n_queries, double *blocks, double *rel);
 
+/*
+ * GLOBAL MAP: A PERSISTENT VOXEL MAP OF THE KEYFRAME STORE AT SOLVED POSES.  What the solved poses are for: publishGlobalMap, DM.h:1621-1655,
+ * moves every keyframe cloud of keyFrameArray by its pose, concatenates them and runs a pcl::VoxelGrid of 0.4 m over the lot, again after
+ * every optimisation.  Here the map stays on the device between calls, keyed by 63-bit voxel coordinates in a hash table, filled from the
+ * on-device keyframe store (scl_keyframe_put) at fp64 poses; a keyframe whose pose moved is taken out at the old pose and put in at the new
+ * one, and the map is then bit for bit the one a fresh build gives.  No other call of this header changes.
+ *   * One map per engine; on a scl_create_sharded engine it lives on the primary shard, as the PCM and PGO calls do.
+ *   * Pose: 7 doubles x, y, z, qx, qy, qz, qw -- the layout of poses_out --, normalised in double as the pose-graph kernels do
+ *     (csrc/se3_device.hpp, normalise_pose).
+ *   * World point: p_w = qrot(q, (double)p) + t, qrot's operation sequence (the same header), no contraction.
+ *   * Leaf: a float, finite, > 0; inv = 1.0 / (double)leaf.
+ *   * Voxel of a point, per axis: s = p_w * inv; c = floor(s) as an integer; f = (uint32)floor((s - floor(s)) * 2^20).  Both operations
+ *     of f are exact in fp64 except for -1 < s < 0, where the difference s + 1 is rounded to nearest (by at most 2^-54: f moves only
+ *     where the point lies on a 2^-20 boundary to that precision, and f = 2^20 for -2^-54 <= s < 0: the point counts at the upper face
+ *     of voxel -1).  Either way f is one fixed sequence of IEEE operations.  A point is skipped, and counted in points_skipped, when a
+ *     coordinate is not finite after the move or a c lies outside [-2^20, 2^20).
+ *   * Key = (cz + 2^20) << 42 | (cy + 2^20) << 21 | (cx + 2^20).
+ *   * State per voxel: four unsigned 64-bit integers, the count n and Sx, Sy, Sz = sum of f.  Integration adds, removal subtracts
+ *     (integer atomic adds, of the two's complement for a removal; no floating-point atomics anywhere): the sums are exact, independent
+ *     of order and exactly invertible.  A voxel whose n is back at 0 has zero sums and is not part of the map.
+ *   * Centroid: x = (float)(((double)cx + (double)Sx / ((double)n * 1048576.0)) * (double)leaf), likewise y and z.  Its resolution is
+ *     leaf * 2^-20, and the truncation in f biases it by at most that much towards the voxel's lower corner.  Fields beyond x, y, z are
+ *     not carried: PCL averages intensity, an order-independent integer sum needs a bounded range, and intensity has none.
+ *   * Output: 16-byte records x, y, z (float) and n as uint32, saturated at 2^32 - 1, in ascending key -- PCL's order, x fastest, on the
+ *     global lattice.  The same bits on every run, whatever the table's capacity, growth history and the order of insertion.
+ *   * scl_map_reset creates or empties the map.  scl_map_set_keyframes takes n poses (n x 7 doubles) for n keyframes of the store: one not
+ *     in the map is added; one in the map at bitwise the same 7 doubles is left alone; one in the map at another pose is subtracted
+ *     at the old pose and added at the new one.  scl_map_remove_keyframes subtracts.  scl_map_extract: box NULL or 6 doubles (lo x, y, z,
+ *     hi x, y, z); a voxel is kept when its centroid in double -- before the narrowing -- lies in the closed box; out NULL gives the
+ *     count alone; a capacity too small is an error that writes nothing.  scl_map_stats: see the struct.  scl_map_last_timing: ms[0]
+ *     integrate (reserve and add passes), ms[1] grow, ms[2] extract of the last set / remove / extract made under scl_profile_enable(1).
+ *   * Stale clouds.  The map remembers per integrated keyframe its pose and the generation of the stored cloud; scl_keyframe_put bumps
+ *     the generation.  Setting or removing an integrated keyframe whose cloud was put again since answers SCL_ERR_INVALID_ARG -- its old
+ *     points can no longer be subtracted: reset the map.
+ *   * The table: open addressing, linear probing, 64-bit compare-and-swap on the key, 64 bytes per slot, at most half full; it starts at
+ *     2^20 slots and doubles (the voxels are re-inserted, emptied ones dropped) whenever a launch group's keys do not fit; a group is
+ *     first reserved (keys only: idempotent), then added, so a growth repeats nothing that counts.  At most 2^31 slots.
+ *   * Errors, all SCL_ERR_INVALID_ARG, checked on the host before anything runs, nothing written: NULL engine; n < 0; a NULL pointer with
+ *     n > 0; no map yet; a listed keyframe not in the store; a pose that is not finite; a quaternion's squared norm outside [0.25, 4]; a
+ *     leaf that is not finite or not > 0; a keyframe listed twice in one call; removing a keyframe that is not in the map; a stale
+ *     cloud; a NaN in the box.  See DESIGN.md section 4, Global map.
+ */
+struct scl_map_stats {
+    uint64_t keyframes;         /* keyframes in the map */
+    uint64_t points_added;      /* points in the voxels' counts, net of removals */
+    uint64_t points_skipped;    /* points of the integrated keyframes that were skipped, net of removals */
+    uint64_t occupied_voxels;   /* voxels with n > 0 */
+    uint64_t capacity;          /* slots of the table */
+    uint64_t growths;           /* growths since the reset */
+};
+int  scl_map_reset(scl_engine *e, float leaf);
+int  scl_map_set_keyframes(scl_engine *e, const int *robots, const int *indices, const double *poses, int n);
+int  scl_map_remove_keyframes(scl_engine *e, const int *robots, const int *indices, int n);
+int  scl_map_extract(scl_engine *e, const double *box, void *out, int out_capacity, int *n_out);
+int  scl_map_stats(scl_engine *e, struct scl_map_stats *out);
+int  scl_map_last_timing(scl_engine *e, double ms[3]);
+
 /* ---- measurement ----------------------------------------------------------- */
 int  scl_profile_enable(scl_engine *e, int on);   /* 0 off, 1 every kernel family, 2 SC distance only,
                                                      3 SC distance only, sampled: one launch in thirteen -- in the stream form one
@@ -1060,6 +1117,9 @@ int  scl_selftest_prefix_sum(scl_engine *e, const int32_t *in, int n, int inclus
 int  scl_selftest_submaps_batch(scl_engine *e, int robot, int n_jobs, const int *keys, const int *search_nums,
                                 const float *poses /* the jobs' windows behind each other: sum(2*sn_j+1) matrices */,
                                 float leaf, void *out, int out_capacity /* points, all jobs */, int *n_out /* n_jobs */);
+/* Test hook of the global map: the starting capacity in slots of the NEXT scl_map_reset (rounded up to a power of two, at least 16; 0 =
+ * the default of 2^20), so that growth and long probe chains are reached with a thousand points. */
+int  scl_selftest_map_capacity(scl_engine *e, uint64_t slots);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,7 @@ There is no CPU fallback: importing works anywhere, creating an engine needs a H
 from ._native import load_library, LIB_PATH, NativeLibraryError  # noqa: F401
 from .engine import (  # noqa: F401
     SclConfig, SclError, ScanContextEngine, ScanContextDescriptor, IcpParams, QUERY_STAGED,
-    RegistrationEval, RegistrationPlaneEval, PgoParams, PgoResult,
+    RegistrationEval, RegistrationPlaneEval, PgoParams, PgoResult, MapStats, MAP_RECORD,
 )
 from .m2dp import M2dpConfig, M2dpEngine, M2dpError  # noqa: F401
 from .fpfh import FpfhConfig, FpfhEngine, FpfhError  # noqa: F401
@@ -18,7 +18,7 @@ from .grsd import GrsdConfig, GrsdEngine, GrsdError  # noqa: F401
 __all__ = [
     "load_library", "LIB_PATH", "NativeLibraryError", "SclConfig", "SclError",
     "ScanContextEngine", "ScanContextDescriptor", "IcpParams", "QUERY_STAGED", "RegistrationEval", "RegistrationPlaneEval",
-    "PgoParams", "PgoResult",
+    "PgoParams", "PgoResult", "MapStats", "MAP_RECORD",
     "M2dpConfig", "M2dpEngine", "M2dpError", "FpfhConfig", "FpfhEngine", "FpfhError",
     "GrsdConfig", "GrsdEngine", "GrsdError",
 ]

@@ -374,7 +374,7 @@ const char *scl_status_string(int status)
 
 const char *scl_last_error(const scl_engine *e) { return e ? e->last_error.c_str() : "null engine"; }
 
-int scl_abi_version(void) { return 15; }
+int scl_abi_version(void) { return 16; }
 
 int scl_default_config(scl_config *c)
 {
@@ -536,6 +536,7 @@ int scl_destroy(scl_engine *e)
     icp_workspace_free(&e->icp_batch_ctl);
     pcm_workspace_free(&e->pcm_ws);
     pgo_workspace_free(&e->pgo_ws);
+    map_free(&e->gmap);
     for (int i = 0; i < scl_engine::kIcpLanes; ++i) {
         if (e->ev_lane[i]) (void)hipEventDestroy(e->ev_lane[i]);
         icp_workspace_free(&e->icp_lane_ws[i]);

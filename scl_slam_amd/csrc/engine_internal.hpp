@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "db_arrays.hpp"
+#include "global_map.hpp"
 #include "icp.hpp"
 #include "kernels.hpp"
 #include "pcm.hpp"
@@ -174,9 +175,10 @@ struct scl_engine {
     hipStream_t icp_lane_stream[kIcpLanes] = {nullptr};
     scl::PcmWorkspace pcm_ws;                              // pairwise consistency of loop closures (pcm.hip)
     scl::PgoWorkspace pgo_ws;                              // pose-graph solve (pgo.hip)
+    scl::GlobalMap gmap;                                   // the global voxel map (global_map.hip)
 
     // on-device keyframe store (robots[id].keyFrameArray, DM.h:86): clouds live in slabs of HBM, bump allocated
-    struct StoredCloud { unsigned char *d = nullptr; int n = -1; size_t cap_bytes = 0; };
+    struct StoredCloud { unsigned char *d = nullptr; int n = -1; size_t cap_bytes = 0; uint64_t generation = 0; };   // generation: bumped by every put (the global map tells a replaced cloud by it)
     std::vector<std::vector<StoredCloud>> kf;              // [robot][index]; n < 0: never stored
     std::vector<void *> kf_slabs;
     size_t kf_slab_used = 0, kf_slab_cap = 0;

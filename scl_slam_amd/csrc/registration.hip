@@ -442,6 +442,7 @@ int scl_keyframe_put(scl_engine *e, int robot, int index, const void *points, in
         SCL_HIP(e, hipStreamSynchronize(e->stream));                   // the caller's buffer is free on return
     }
     c.n = n_points;
+    ++c.generation;
     return SCL_OK;
 }
 

@@ -66,6 +66,20 @@ class PgoResult(ctypes.Structure):
     STOP_COST, STOP_STEP, STOP_ITERATIONS, STOP_LAMBDA = 1, 2, 3, 4
 
 
+class MapStats(ctypes.Structure):
+    """struct scl_map_stats (scl_engine.h GLOBAL MAP)"""
+    _fields_ = [
+        ("keyframes", c_uint64), ("points_added", c_uint64), ("points_skipped", c_uint64), ("occupied_voxels", c_uint64),
+        ("capacity", c_uint64), ("growths", c_uint64),
+    ]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+MAP_RECORD = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("n", "<u4")])   # a record of scl_map_extract
+
+
 class SclProfile(ctypes.Structure):
     _fields_ = [
         ("sc_distance_ms", c_double), ("sc_distance_launches", c_uint64), ("sc_distance_pairs", c_uint64),
@@ -204,6 +218,13 @@ def _bind(lib):
         "scl_pgo_condensed_last_timing": (c_int, [P, dp]),
         "scl_pgo_solve_condensed_many": (c_int, [P, dp, c_int, ip, ip, dp, dp, c_int, ip, dp, dp, c_int, c_double, dp, c_int, dp]),
         "scl_pgo_marginals": (c_int, [P, dp, c_int, ip, ip, dp, dp, c_int, ip, dp, dp, c_int, ip, ip, c_int, dp, dp]),
+        "scl_map_reset": (c_int, [P, c_float]),
+        "scl_map_set_keyframes": (c_int, [P, ip, ip, dp, c_int]),
+        "scl_map_remove_keyframes": (c_int, [P, ip, ip, c_int]),
+        "scl_map_extract": (c_int, [P, dp, c_void_p, c_int, ip]),
+        "scl_map_stats": (c_int, [P, POINTER(MapStats)]),
+        "scl_map_last_timing": (c_int, [P, dp]),
+        "scl_selftest_map_capacity": (c_int, [P, c_uint64]),
         "scl_profile_enable": (c_int, [P, c_int]),
         "scl_profile_reset": (c_int, [P]),
         "scl_profile_get": (c_int, [P, POINTER(SclProfile)]),
@@ -1408,6 +1429,61 @@ class ScanContextEngine:
         self._check(self._lib.scl_pgo_marginals(self._h, *args, opt(qi), opt(qj), k, None if blocks is None else _ptr(blocks, c_double),
                                                 None if rel is None else _ptr(rel, c_double)), "scl_pgo_marginals")
         return None if blocks is None else blocks[:k], None if rel is None else rel[:k]
+
+    # ---- the global voxel map (scl_engine.h GLOBAL MAP) ----
+
+    def map_reset(self, leaf):
+        """create or empty the engine's global map with voxels of `leaf` metres"""
+        self._check(self._lib.scl_map_reset(self._h, float(leaf)), "scl_map_reset")
+
+    @staticmethod
+    def _map_ids(robots, indices):
+        r = np.ascontiguousarray(robots, dtype=np.int32).ravel(); x = np.ascontiguousarray(indices, dtype=np.int32).ravel()
+        if r.size != x.size:
+            raise ValueError("robots and indices must have one entry per keyframe")
+        return r, x
+
+    def map_set_keyframes(self, robots, indices, poses):
+        """keyframes of the store placed at poses[n,7] (x, y, z, qx, qy, qz, qw; pgo_optimize's poses_out): added, left alone where
+        the pose is bitwise the one they are in the map at, or subtracted at the old pose and added at the new one"""
+        r, x = self._map_ids(robots, indices)
+        p = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7)
+        if p.shape[0] != r.size:
+            raise ValueError("one pose of 7 doubles per keyframe")
+        opt = lambda a, t: _ptr(a, t) if a.size else None
+        self._check(self._lib.scl_map_set_keyframes(self._h, opt(r, c_int), opt(x, c_int), opt(p, c_double), r.size), "scl_map_set_keyframes")
+
+    def map_remove_keyframes(self, robots, indices):
+        r, x = self._map_ids(robots, indices)
+        opt = lambda a, t: _ptr(a, t) if a.size else None
+        self._check(self._lib.scl_map_remove_keyframes(self._h, opt(r, c_int), opt(x, c_int), r.size), "scl_map_remove_keyframes")
+
+    def map_extract(self, box=None, count_only=False):
+        """the map's voxels in ascending key as MAP_RECORD records (x, y, z, n); box = (lo xyz, hi xyz): those whose centroid lies in the
+        closed box.  count_only: the number alone"""
+        b = None if box is None else np.ascontiguousarray(box, dtype=np.float64).reshape(6)
+        bp = None if b is None else _ptr(b, c_double)
+        n = c_int(-1)
+        self._check(self._lib.scl_map_extract(self._h, bp, None, 0, byref(n)), "scl_map_extract")
+        if count_only:
+            return n.value
+        out = np.zeros(max(n.value, 1), dtype=MAP_RECORD)
+        self._check(self._lib.scl_map_extract(self._h, bp, out.ctypes.data_as(c_void_p), n.value, byref(n)), "scl_map_extract")
+        return out[:n.value].copy()
+
+    def map_stats(self):
+        st = MapStats()
+        self._check(self._lib.scl_map_stats(self._h, byref(st)), "scl_map_stats")
+        return st
+
+    def map_last_timing(self):
+        """(integrate_ms, grow_ms, extract_ms) of the last map calls made under profile_enable(1)"""
+        ms = np.zeros(3, np.float64)
+        self._check(self._lib.scl_map_last_timing(self._h, _ptr(ms, c_double)), "scl_map_last_timing")
+        return tuple(ms.tolist())
+
+    def selftest_map_capacity(self, slots):
+        self._check(self._lib.scl_selftest_map_capacity(self._h, int(slots)), "scl_selftest_map_capacity")
 
     def pgo_condensed_last_timing(self):
         """(elimination, assembly, factorisation, solves and the way back) in ms, summed over the steps of the last condensed call made
